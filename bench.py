@@ -22,7 +22,8 @@ rescaled to 800x800, tracer defaults, fill_holes=False, handle_edges=False, fp32
   N = 1 also reports "predicted_strong_scaling": the 8 tile-shards of the frame run one after the other on this card
           (iron_amd.sharding.render_emulated) -- T(frame) / max_r T(shard r) -- and "f32_core": the same workload on the
           exact-fp32 MFMA core (a child process with IRON_MLP_CORE=f32).
-One JSON line is printed by rank 0.
+One JSON line is printed by rank 0.  `--dump-outputs DIR` also writes the result of the last timed step as DIR/<key>.npy
+(dump_outputs), so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -70,10 +71,19 @@ def parse():
                          "the oracle timed on a bounded sample -- "
                          "c2 = stage-1 NeuS forward, 4096 rays x 128 samples per step; c3 = one stage-2 training step with edge "
                          "sampling at 512x512")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c1: after the timed steps write what the last timed step returned (the render's result dict) as DIR/<key>.npy, "
+                         "float32 (float64 for 64-bit and integer data), at most 64 MB in all: beyond that a fixed, seeded sample of the "
+                         "pixels (the same pixels in every per-pixel array).  N>1: rank 0's assembled result")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="N>1: only join the process group (IRON_BENCH_BACKEND, default nccl), all-reduce the rank count and print the "
                          "line's launch fields -- the launcher's own test (tests/test_bench_launcher.py runs it on CPU over gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload != "c1":
+        ap.error("--dump-outputs covers the c1 workload only")
+    return a
 
 
 _JSON_OUT = None
@@ -372,6 +382,50 @@ def secondary_workload(a):
     print(json.dumps(base))
 
 
+DUMP_BYTES = 60 << 20       # --dump-outputs: budget of all arrays together (under 64 MB with the .npy headers)
+DUMP_SEED = 0               # --dump-outputs: seed of the pixel sample taken when the full arrays exceed the budget
+
+
+def dump_outputs(res, path: str) -> dict:
+    """Writes the tensors of a render's result dict as `path`/<key>.npy: float64 for float64 and integer data, float32 for the
+    rest (masks become 0 / 1).  A list of tensors (per-view edge records) is concatenated.  Arrays whose leading dims are the pixel
+    grid (the shape of `convergent_mask`) are cut to one seeded sample of the pixels, sorted, when everything together would exceed
+    DUMP_BYTES; other arrays are written whole.  Returns what was written, for the JSON line."""
+    import numpy as np
+    arrays = {}
+    for k in sorted(res):
+        v = res[k]
+        if isinstance(v, (list, tuple)):
+            v = [t for t in v if torch.is_tensor(t)]
+            v = torch.cat([t.reshape(1) if t.dim() == 0 else t for t in v]) if v else None
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        wide = v.dtype == torch.float64 or not (v.dtype.is_floating_point or v.dtype == torch.bool)
+        arrays[k] = v.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    grid = tuple(res["convergent_mask"].shape)
+    n_pix = int(np.prod(grid))
+    per_pixel = [k for k, x in arrays.items() if x.shape[:len(grid)] == grid]
+    total = sum(x.nbytes for x in arrays.values())
+    sampled = None
+    if total > DUMP_BYTES:
+        fixed = sum(x.nbytes for k, x in arrays.items() if k not in per_pixel)
+        bytes_per_pixel = sum(arrays[k].nbytes for k in per_pixel) / n_pix
+        sampled = int((DUMP_BYTES - fixed) // bytes_per_pixel)
+        if sampled < 1:
+            raise SystemExit("--dump-outputs: the arrays that are not per pixel alone exceed %d bytes" % DUMP_BYTES)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, sampled, replace=False))
+        for k in per_pixel:
+            x = arrays[k]
+            arrays[k] = np.ascontiguousarray(x.reshape((n_pix,) + x.shape[len(grid):])[idx])
+    os.makedirs(path, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), x)
+    return {"dir": path, "bytes": sum(x.nbytes for x in arrays.values()), "pixel_grid": list(grid),
+            "sampled_pixels": sampled, "sample_seed": DUMP_SEED if sampled is not None else None,
+            "arrays": {k: [str(x.dtype)] + list(x.shape) for k, x in arrays.items()}}
+
+
 def cpu_baseline(scene: str, res: int):
     """The oracle (torch-CPU port of the reference path) timed on this host's cores: config C0 -- the 64x64 crop,
     ul = (224, 224), of the 512x512 fixture camera -- always, plus a bounded full view (`res` x `res`, default 160: ~5 s) of the same
@@ -540,8 +594,12 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
+    last = None
+    for i in range(a.steps):
+        r = step()
+        if a.dump_outputs and i == a.steps - 1:
+            last = r   # the result of the last timed step, kept for --dump-outputs (N>1: None on every rank but 0)
+        del r
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
@@ -549,6 +607,8 @@ def main():
     _lib.profile_enable(False)
     if rank == 0:
         print("[bench] timed region: %.3f s for %d steps" % (dt, a.steps), file=sys.stderr, flush=True)
+    dumped = dump_outputs(last, a.dump_outputs) if last is not None else None
+    last = None
     coll_dev = dev if backend == "nccl" else torch.device("cpu")
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
@@ -673,6 +733,8 @@ def main():
                       "executed_tflops": (FLOP_PER_EVAL * E_hip + FLOP_PER_HIT * H) * a.steps / dt / 1e12},
             "kernels": kernels,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         from iron_amd import build as _build
         man = _build.manifest()
         out["build"] = {"hipcc": man.get("hipcc"), "any_fallback_flags": man.get("any_fallback"),
