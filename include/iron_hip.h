@@ -38,7 +38,8 @@ typedef enum iron_status {
     IRON_ERR_HIP = -3,          /* a HIP runtime call failed; see iron_last_hip_error()        */
     IRON_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
     IRON_ERR_WORKSPACE = -5,    /* workspace too small                                         */
-    IRON_ERR_RANGE = -6         /* IRON_H2_OVERFLOW=error: the previous call on this network left the fp16 range of the h2 core */
+    IRON_ERR_RANGE = -6         /* IRON_H2_OVERFLOW=error: the previous call on this network left the fp16 range of the h2 core;
+                                   iron_mc_count: a vertex or triangle count reaches 2^31 */
 } iron_status;
 
 int iron_version(void);
@@ -149,6 +150,25 @@ int iron_nerf_forward(const iron_net_t* nerf, const float* pts4, const float* vi
 /* extract_fields' lattice (models/renderer.py:9-31): pts [nx*ny*nz,3] = meshgrid(xs, ys, zs) in 'ij' order; the field values
  * are then one iron_sdf_forward (or any other batched query) over pts. */
 int iron_grid_points(const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz, float* pts, void* stream);
+/* Marching cubes over such a lattice (the mcubes.marching_cubes of models/renderer.py:34-42), csrc/mcubes.hip.
+ *   u: fp32 [nx][ny][nz], z fastest (extract_fields' 'ij' order).  Any dim < 2 gives an empty mesh.  A corner is above when
+ *   u > threshold (strict; NaN is below).  Case table: csrc/mc_table.h, generated by iron_amd/mc_table.py; on a face with two
+ *   diagonal above corners the above corners are separated, so the mesh is watertight; it stays open where it leaves the grid.
+ *   Vertices: one per crossed lattice edge, owned by the edge's lower lattice point p and axis a, at p + t e_a in index
+ *   coordinates with t = (threshold - u(p)) / (u(p + e_a) - u(p)) in fp32, clamped to [0, 1]; ordered by (linear index of p, a).
+ *   Triangles: int32 vertex indices, ordered by (cell = its min lattice point, table order); right-hand normals point from
+ *   u > threshold toward u < threshold.  Orders come from prefix sums: the output is bitwise deterministic.
+ * Two calls, as the output sizes depend on the data:
+ *   iron_mc_count  leaves the crossing pattern and the scanned per-block offsets in `workspace` and returns the counts in
+ *                  HOST *n_verts / *n_tris: it synchronises `stream` once (the one entry of this ABI that waits on the device).
+ *                  IRON_ERR_RANGE when either count reaches 2^31.
+ *   iron_mc_emit   writes verts [n_verts,3] and tris [n_tris,3] from that workspace; same u, dims and threshold, nothing else
+ *                  may have touched the workspace in between. */
+int iron_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes);
+int iron_mc_count(const float* u, int32_t nx, int32_t ny, int32_t nz, float threshold, void* workspace, int64_t* n_verts,
+                  int64_t* n_tris, void* stream);
+int iron_mc_emit(const float* u, int32_t nx, int32_t ny, int32_t nz, float threshold, void* workspace, float* verts, int32_t* tris,
+                 void* stream);
 int iron_neus_linspace(const float* near, const float* far, const float* lin, int64_t n, int32_t m, float* z, void* stream);
 int iron_neus_outside_z(const float* far, const float* rev, int64_t n, int32_t m, float offset, float* z, void* stream);
 int iron_neus_points(const float* rays_o, const float* rays_d, const float* z, int64_t n, int32_t m, float* pts, void* stream);

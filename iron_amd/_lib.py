@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libiron_hip.so")
 IRON_OK = 0
 IRON_NET_NERF = 2
 IRON_ERR_UNSUPPORTED = -2
+IRON_ERR_RANGE = -6
 IRON_NET_SDF, IRON_NET_RENDER = 0, 1
 MODES = {"idr": 0, "no_view_dir": 1, "no_normal": 2, "points_only": 3}
 
@@ -99,6 +100,9 @@ SYMBOLS = {
     "iron_composite_colocated": (C.c_int, [C.c_float, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "iron_coloc_head": (C.c_int, [_I32, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "iron_grid_points": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "iron_mc_workspace_bytes": (C.c_int, [_I32, _I32, _I32, C.POINTER(_SZ)]),
+    "iron_mc_count": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, C.POINTER(_I64), C.POINTER(_I64), _P]),
+    "iron_mc_emit": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
     "iron_neus_linspace": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "iron_neus_outside_z": (C.c_int, [_P, _P, _I64, _I32, _F, _P, _P]),
     "iron_neus_points": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),

@@ -37,11 +37,15 @@ def extract_fields(bound_min, bound_max, resolution, query_func, max_points: int
 
 
 def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
-    """models/renderer.py:34-42.  Marching cubes is the third-party `mcubes` there too; it is not part of this build."""
+    """models/renderer.py:34-42.  With PyMCubes (`mcubes`) importable this is the reference's path: the field goes to the host and
+    mcubes triangulates it.  Without it, the field stays on the device and the marching cubes of csrc/mcubes.hip
+    (iron_amd.mesh.extract_geometry_gpu) runs instead; the result is numpy as well (float64 vertices, int64 triangles)."""
     try:
         import mcubes
-    except ImportError as e:  # same dependency as the reference
-        raise ImportError("extract_geometry needs PyMCubes (`mcubes`), as in models/renderer.py:36") from e
+    except ImportError:
+        from .mesh import extract_geometry_gpu
+        vertices, triangles = extract_geometry_gpu(bound_min, bound_max, resolution, threshold, query_func)
+        return vertices.cpu().numpy(), triangles.cpu().numpy()
     u = extract_fields(bound_min, bound_max, resolution, query_func)
     vertices, triangles = mcubes.marching_cubes(u, threshold)
     b_max_np = torch.as_tensor(bound_max).detach().cpu().numpy()
