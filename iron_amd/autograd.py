@@ -70,6 +70,17 @@ def _opt(t: Optional[torch.Tensor], shape=None) -> Optional[torch.Tensor]:
     return t.reshape(shape) if shape is not None else t
 
 
+def _flat3(t: torch.Tensor, lead, name: str) -> torch.Tensor:
+    """A [..., 3] input, or a [..., 1] one broadcast over the channels, as a contiguous [n, 3] CUDA float32 tensor."""
+    return _lib.require_cuda_f32(t.expand(lead + [3]), name).reshape(-1, 3)
+
+
+def _unflat3(g: torch.Tensor, lead, shape) -> torch.Tensor:
+    """The [n, 3] gradient of a _flat3 input in that input's shape (summed over the channels of a broadcast [..., 1])."""
+    g = g.reshape(lead + [3])
+    return (g.sum(dim=-1, keepdim=True) if shape[-1] == 1 else g).reshape(shape)
+
+
 class SDFGetAllFn(torch.autograd.Function):
     """(sdf [n,1], feature [n,d_out-1], gradient [n,3]) = get_all(x); differentiable w.r.t. the network parameters, to
     second order through `gradient` (the tangent sweep of iron_sdf_backward).  x itself gets no gradient: the reference
@@ -210,9 +221,7 @@ class GGXColocatedFn(torch.autograd.Function):
         dev = nrm.device
         sh = list(ctx.shapes[1][:-1])
         dist = _lib.require_cuda_f32(dist, "distance").reshape(-1)
-        vd = _lib.require_cuda_f32(vd, "viewdir").reshape(-1, 3)
-        kd = _lib.require_cuda_f32(kd, "diffuse_albedo").reshape(-1, 3)
-        ks = _lib.require_cuda_f32(ks.expand(sh + [3]), "specular_albedo").reshape(-1, 3)
+        vd, kd, ks = _flat3(vd, sh, "viewdir"), _flat3(kd, sh, "diffuse_albedo"), _flat3(ks, sh, "specular_albedo")
         rough = _lib.require_cuda_f32(rough, "specular_roughness").reshape(-1)
         t1, t2 = ctx.renderer._tables_on(dev)
         g_diff, g_spec, g_rgb = _opt(g_diff, (-1, 3)), _opt(g_spec, (-1, 3)), _opt(g_rgb, (-1, 3))
@@ -227,11 +236,8 @@ class GGXColocatedFn(torch.autograd.Function):
                                                              d_nrm.data_ptr(), d_vd.data_ptr(), d_kd.data_ptr(), d_ks.data_ptr(),
                                                              d_rough.data_ptr(), _lib.stream_ptr(dev)))
         s_dist, s_nrm, s_vd, s_kd, s_ks, s_rough = ctx.shapes
-        d_ks = d_ks.reshape(sh + [3])
-        if s_ks[-1] == 1:  # a [...,1] albedo was broadcast over the channels
-            d_ks = d_ks.sum(dim=-1, keepdim=True)
         return (None, d_light.reshape(ctx.light_shape) if ctx.light_shape is not None else None, d_dist.reshape(s_dist), d_nrm.reshape(s_nrm),
-                d_vd.reshape(s_vd), d_kd.reshape(s_kd), d_ks.reshape(s_ks), d_rough.reshape(s_rough))
+                d_vd.reshape(s_vd), _unflat3(d_kd, sh, s_kd), _unflat3(d_ks, sh, s_ks), d_rough.reshape(s_rough))
 
 
 class CompositeFn(torch.autograd.Function):
@@ -271,15 +277,11 @@ class CompositeFn(torch.autograd.Function):
         dev = nrm.device
         sh = list(ctx.shapes[0][:-1])
 
-        def vec(t, name):
-            t = _lib.require_cuda_f32(t, name)
-            return (t.expand(sh + [3]) if t.shape[-1] != 3 else t).reshape(-1, 3).contiguous()
-
         def sca(t, name):
             return _lib.require_cuda_f32(t, name).reshape(-1)
 
-        vd = vec(vd, "viewdir")
-        kd_f, ks_f = vec(kd, "diffuse_albedo"), vec(ks, "specular_albedo")
+        vd = _flat3(vd, sh, "viewdir")
+        kd_f, ks_f = _flat3(kd, sh, "diffuse_albedo"), _flat3(ks, sh, "specular_albedo")
         maps = [sca(t, k) for t, k in zip((rough, m_eta, m_k, d_eta), CompositeFn.NAMES[2:])]
         last = sca(last, "env_light" if ctx.use_env else "distance")
         t1, t2 = ctx.renderer._tables_on(dev)
@@ -308,11 +310,6 @@ class CompositeFn(torch.autograd.Function):
                                                                    vd.data_ptr(), C.byref(p), t1.data_ptr(), t2.data_ptr(), n, C.byref(gi), C.byref(go),
                                                                    _lib.stream_ptr(dev)))
         s_nrm, s_vd, s_kd, s_ks = ctx.shapes[:4]
-
-        def unvec(g, shape):
-            g = g.reshape(sh + [3])
-            return (g.sum(dim=-1, keepdim=True) if shape[-1] == 1 else g).reshape(shape)
-
         d_light_out = d_light.reshape(ctx.light_shape) if (ctx.light_shape is not None and not ctx.use_env) else None
         d_dist = None
         if not ctx.use_env:
@@ -320,7 +317,7 @@ class CompositeFn(torch.autograd.Function):
         elif ctx.dist_shape is not None:
             d_dist = torch.zeros(ctx.dist_shape, dtype=torch.float32, device=dev)
         d_env = d_last.reshape(ctx.shapes[8]) if ctx.use_env else None
-        return (None, d_light_out, d_dist, d_nrm.reshape(s_nrm), d_vd.reshape(s_vd), unvec(d_kd, s_kd), unvec(d_ks, s_ks)) + tuple(
+        return (None, d_light_out, d_dist, d_nrm.reshape(s_nrm), d_vd.reshape(s_vd), _unflat3(d_kd, sh, s_kd), _unflat3(d_ks, sh, s_ks)) + tuple(
             m.reshape(s) for m, s in zip(d_maps, ctx.shapes[4:8])) + (d_env,)
 
 
@@ -353,9 +350,7 @@ class ColocHeadFn(torch.autograd.Function):
         dev = nrm.device
         sh = list(ctx.shapes[1][:-1])
         dist = _lib.require_cuda_f32(dist, "distance").reshape(-1)
-        vd = _lib.require_cuda_f32(vd, "viewdir").reshape(-1, 3)
-        kd_f = _lib.require_cuda_f32(kd.expand(sh + [3]), "diffuse_albedo").reshape(-1, 3)
-        ks_f = _lib.require_cuda_f32(ks.expand(sh + [3]), "specular_albedo").reshape(-1, 3)
+        vd, kd_f, ks_f = _flat3(vd, sh, "viewdir"), _flat3(kd, sh, "diffuse_albedo"), _flat3(ks, sh, "specular_albedo")
         al = _lib.require_cuda_f32(alpha, "alpha").reshape(-1) if (alpha is not None and head.KIND == 3) else None
         ups = [_opt(g, (-1, 3)) for g in (g_diff, g_spec, g_rgb)]
         with torch.cuda.device(dev):
@@ -368,16 +363,11 @@ class ColocHeadFn(torch.autograd.Function):
                 ks_f.data_ptr(), _lib.ptr(al), n, _lib.ptr(ups[0]), _lib.ptr(ups[1]), _lib.ptr(ups[2]), d_light.data_ptr(), d_dist.data_ptr(),
                 d_nrm.data_ptr(), d_vd.data_ptr(), d_kd.data_ptr(), d_ks.data_ptr(), _lib.ptr(d_al), _lib.stream_ptr(dev)))
         s_dist, s_nrm, s_vd, s_kd, s_ks, s_al = ctx.shapes
-
-        def unvec(g, shape):
-            g = g.reshape(sh + [3])
-            return (g.sum(dim=-1, keepdim=True) if shape[-1] == 1 else g).reshape(shape)
-
         d_alpha = None
         if ctx.has_alpha:
             d_alpha = d_al.reshape(s_al) if d_al is not None else torch.zeros(s_al, dtype=torch.float32, device=dev)
         return (None, d_light.reshape(ctx.light_shape) if ctx.light_shape is not None else None, d_dist.reshape(s_dist), d_nrm.reshape(s_nrm),
-                d_vd.reshape(s_vd), unvec(d_kd, s_kd), unvec(d_ks, s_ks), d_alpha)
+                d_vd.reshape(s_vd), _unflat3(d_kd, sh, s_kd), _unflat3(d_ks, sh, s_ks), d_alpha)
 
 
 class NeRFFn(torch.autograd.Function):

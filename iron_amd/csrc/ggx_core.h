@@ -6,92 +6,133 @@
 
 namespace iron {
 
-struct GgxOut {
-    float diffuse[3];
-    float specular[3];
-    float rgb[3];
+// ---- number types: float, or first-order dual numbers for the backward passes (train.hip) -----------------------------------
+// Dual<N>: a value and its derivatives in N variables.  A float converts to a constant, so one templated formula below serves
+// both; the operators are hidden friends so that conversion applies to `1.0f - c2` and the like.
+template <int N>
+struct Dual {
+    float v, d[N];
+    Dual() = default;
+    __device__ __forceinline__ Dual(float c) : v(c) {
+        for (int i = 0; i < N; ++i) d[i] = 0.f;
+    }
+    __device__ __forceinline__ static Dual var(float x, int k) {
+        Dual r(x);
+        r.d[k] = 1.f;
+        return r;
+    }
+    friend __device__ __forceinline__ Dual operator+(Dual a, Dual b) {
+        Dual r; r.v = a.v + b.v;
+        for (int i = 0; i < N; ++i) r.d[i] = a.d[i] + b.d[i];
+        return r;
+    }
+    friend __device__ __forceinline__ Dual operator-(Dual a, Dual b) {
+        Dual r; r.v = a.v - b.v;
+        for (int i = 0; i < N; ++i) r.d[i] = a.d[i] - b.d[i];
+        return r;
+    }
+    friend __device__ __forceinline__ Dual operator*(Dual a, Dual b) {
+        Dual r; r.v = a.v * b.v;
+        for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i];
+        return r;
+    }
+    friend __device__ __forceinline__ Dual operator/(Dual a, Dual b) {
+        Dual r; r.v = a.v / b.v;
+        const float ib = 1.0f / b.v;
+        for (int i = 0; i < N; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * ib;
+        return r;
+    }
+    friend __device__ __forceinline__ Dual sqrt_t(Dual a) {
+        Dual r; r.v = sqrtf(a.v);
+        const float k = 0.5f / r.v;
+        for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * k;
+        return r;
+    }
+    // hypot(x, 1): the value is hypotf as in the forward, the derivative x / h
+    friend __device__ __forceinline__ Dual hypot1(Dual a) {
+        Dual r; r.v = hypotf(a.v, 1.0f);
+        const float k = a.v / r.v;
+        for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * k;
+        return r;
+    }
 };
+__device__ __forceinline__ float sqrt_t(float x) { return sqrtf(x); }
+__device__ __forceinline__ float hypot1(float x) { return hypotf(x, 1.0f); }
+
+// ---- the reference's constants -------------------------------------------------------------------------------------------------
+constexpr double kEta = 1.48958738;                             // the rough-plastic interior IOR the reference hard-codes
+constexpr float kPi = 3.14159274101257324219f;                  // float32(np.pi)
+constexpr float kInvEta2 = (float)(1.0 / (kEta * kEta));
+constexpr float kEta2 = (float)(kEta * kEta + 1e-10);          // alpha^2 + 1e-10 of the composite NDF (alpha := eta)
+constexpr float kPiEta2 = (float)(3.141592653589793 * kEta * kEta);
+constexpr float kFr = 0.03867f;                                 // GGXColocatedRenderer's specular Fresnel
+constexpr float kThinSpec = (float)(0.04 + 0.96 * 0.96 * 0.04 / (1.0 - 0.04 * 0.04));  // ThinDielectric's specular scale
+
+// ---- BRDF building blocks, T = float or Dual<N> -------------------------------------------------------------------------------
+// intensity of a point light at distance d
+template <class T>
+__device__ __forceinline__ T intensity_at(float light, T d) { return light / (d * d + 1e-10f); }
+
+// GGX NDF at cos theta = c (models/renderer_ggx.py:106-108)
+template <class T>
+__device__ __forceinline__ T ggx_ndf(T c, T alpha) {
+    const T c2 = c * c;
+    const T root = c2 + (1.0f - c2) / (alpha * alpha + 1e-10f);
+    return 1.0f / (kPi * alpha * alpha * root * root + 1e-10f);
+}
+
+// CompositeRenderer's NDF: alpha := eta (renderer_ggx.py:806), pi * alpha^2 folded into one constant
+template <class T>
+__device__ __forceinline__ T composite_ndf(T c) {
+    const T c2 = c * c;
+    const T root = c2 + (1.0f - c2) / kEta2;
+    return 1.0f / (kPiEta2 * root * root + 1e-10f);
+}
 
 // smithG1 (models/renderer_ggx.py:12-16)
-__device__ __forceinline__ float smith_g1(float cos_theta, float alpha) {
-    const float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
-    const float tan_theta = sin_theta / (cos_theta + 1e-10f);
-    const float root = alpha * tan_theta;
-    return 2.0f / (1.0f + hypotf(root, 1.0f));
+template <class T>
+__device__ __forceinline__ T smith_g1(T cos_theta, T alpha) {
+    const T sin_theta = sqrt_t(1.0f - cos_theta * cos_theta);
+    const T tan_theta = sin_theta / (cos_theta + 1e-10f);
+    const T root = alpha * tan_theta;
+    return 2.0f / (1.0f + hypot1(root));
 }
-
-// GGXColocatedRenderer.forward (models/renderer_ggx.py:82-146) for one point.
-// tab_trans: 5000 floats (100 theta x 50 alpha), tab_diff: 50 floats.
-__device__ __forceinline__ void ggx_colocated_point(float light, float distance, const float n[3], const float v[3],
-                                                    const float kd[3], const float ks[3], float rough,
-                                                    const float* __restrict__ tab_trans,
-                                                    const float* __restrict__ tab_diff, GgxOut& o) {
-    const float intensity = light / (distance * distance + 1e-10f);
-    float dot = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
-    dot = fminf(fmaxf(dot, 0.00001f), 0.99999f);
-    const float m_inv_eta2 = (float)(1.0 / (1.48958738 * 1.48958738));
-    const float alpha = fmaxf(rough, 0.0001f);
-    const float pi_f = 3.14159274101257324219f;  // float32(np.pi)
-
-    const float c2 = dot * dot;
-    const float root = c2 + (1.0f - c2) / (alpha * alpha + 1e-10f);
-    const float D = 1.0f / (pi_f * alpha * alpha * root * root + 1e-10f);
-    const float Fr = 0.03867f;
-    const float g1 = smith_g1(dot, alpha);
-    const float G = g1 * g1;
-    const float denom = 4.0f * dot + 1e-10f;
-
-    const float warped_cos = powf(dot, 0.25f);
-    const float warped_alpha = powf(alpha / 4.0f, 0.25f);
-    const long long tx = (long long)floorf(warped_cos * 100.0f);
-    const long long ty = (long long)floorf(warped_alpha * 50.0f);
-    long long ti = ty * 100 + tx;
-    ti = ti < 0 ? 0 : (ti > 4999 ? 4999 : ti);
-    const float T12 = fminf(fmaxf(tab_trans[ti], 0.0f), 1.0f);
-    long long ai = ty < 0 ? 0 : (ty > 49 ? 49 : ty);
-    const float Fdr = fminf(fmaxf(1.0f - tab_diff[ai], 0.0f), 1.0f);
-    const float fd = 1.0f - Fdr + 1e-10f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o.specular[c] = intensity * ks[c] * Fr * D * G / denom;
-        o.diffuse[c] = intensity * (kd[c] / fd / pi_f) * dot * T12 * T12 * m_inv_eta2;
-        o.rgb[c] = o.diffuse[c] + o.specular[c];
-    }
-}
-
-// ---- SURVEY 8 row f-4: the fork's other co-located heads (models/renderer_ggx.py:149-517, 520-858) -----------------
 
 // fresnel_conductor_exact (renderer_ggx.py:419-432 = CompositeRenderer.fresnel_conductor_exact :592-605)
-__device__ __forceinline__ float fresnel_conductor_exact(float cos_i, float eta, float k) {
-    const float c2 = cos_i * cos_i;
-    const float s2 = 1.0f - c2;
-    const float s4 = s2 * s2;
-    const float temp1 = eta * eta - k * k - s2;
-    const float a2pb2 = sqrtf(temp1 * temp1 + 4.0f * k * k * eta * eta);
-    const float a = sqrtf(0.5f * (a2pb2 + temp1));
-    const float term1 = a2pb2 + c2;
-    const float term2 = 2.0f * a * cos_i;
-    const float rs2 = (term1 - term2) / (term1 + term2);
-    const float term3 = a2pb2 * c2 + s4;
-    const float term4 = term2 * s2;
-    const float rp2 = rs2 * (term3 - term4) / (term3 + term4);
+template <class T>
+__device__ __forceinline__ T fresnel_conductor_exact(T cos_i, T eta, T k) {
+    const T c2 = cos_i * cos_i;
+    const T s2 = 1.0f - c2;
+    const T s4 = s2 * s2;
+    const T temp1 = eta * eta - k * k - s2;
+    const T a2pb2 = sqrt_t(temp1 * temp1 + 4.0f * k * k * eta * eta);
+    const T a = sqrt_t(0.5f * (a2pb2 + temp1));
+    const T term1 = a2pb2 + c2;
+    const T term2 = 2.0f * a * cos_i;
+    const T rs2 = (term1 - term2) / (term1 + term2);
+    const T term3 = a2pb2 * c2 + s4;
+    const T term4 = term2 * s2;
+    const T rp2 = rs2 * (term3 - term4) / (term3 + term4);
     return 0.5f * (rp2 + rs2);
 }
 
 // fresnel_dielectric (renderer_ggx.py:398-416) for cos_i > 0 (the callers clamp it to [1e-5, 0.99999])
-__device__ __forceinline__ float fresnel_dielectric_pos(float cos_i, float eta) {
-    const float scale = 1.0f / eta;
-    const float cos_t_sqr = 1.0f - (1.0f - cos_i * cos_i) * (scale * scale);
-    const float cos_t = sqrtf(cos_t_sqr);
-    const float rs = (cos_i - eta * cos_t) / (cos_i + eta * cos_t);
-    const float rp = (eta * cos_i - cos_t) / (eta * cos_i + cos_t);
+template <class T>
+__device__ __forceinline__ T fresnel_dielectric_pos(T cos_i, T eta) {
+    const T scale = 1.0f / eta;
+    const T cos_t_sqr = 1.0f - (1.0f - cos_i * cos_i) * (scale * scale);
+    const T cos_t = sqrt_t(cos_t_sqr);
+    const T rs = (cos_i - eta * cos_t) / (cos_i + eta * cos_t);
+    const T rp = (eta * cos_i - cos_t) / (eta * cos_i + cos_t);
     return 0.5f * (rs * rs + rp * rp);
 }
 
 // the Mitsuba rough-plastic diffuse term through the two tables (CompositeRenderer.diffuse_reflection_ggx :654-681);
-// returns the factor that multiplies intensity * kd: 1 / (1 - Fdr + 1e-10) / pi * cos * T12^2 / eta^2 is applied by the caller
-__device__ __forceinline__ void rtrans_lookup(float cos_theta, float alpha, const float* __restrict__ tab_trans,
-                                              const float* __restrict__ tab_diff, float& T12, float& fd) {
+// returns the factor that multiplies intensity * kd: 1 / (1 - Fdr + 1e-10) / pi * cos * T12^2 / eta^2 is applied by the caller.
+// Piecewise constant: the backward passes take it as a constant.
+// tab_trans: 5000 floats (100 theta x 50 alpha), tab_diff: 50 floats.
+__device__ __forceinline__ void rtrans_lookup(float cos_theta, float alpha, const float* tab_trans, const float* tab_diff,
+                                              float& T12, float& fd) {
     const float warped_cos = powf(cos_theta, 0.25f);
     const float warped_alpha = powf(alpha / 4.0f, 0.25f);
     const long long tx = (long long)floorf(warped_cos * 100.0f);
@@ -103,6 +144,38 @@ __device__ __forceinline__ void rtrans_lookup(float cos_theta, float alpha, cons
     const float Fdr = fminf(fmaxf(1.0f - tab_diff[ai], 0.0f), 1.0f);
     fd = 1.0f - Fdr + 1e-10f;
 }
+
+// ---- the forward heads, one point each ---------------------------------------------------------------------------------------
+struct GgxOut {
+    float diffuse[3];
+    float specular[3];
+    float rgb[3];
+};
+
+// GGXColocatedRenderer.forward (models/renderer_ggx.py:82-146) for one point.
+__device__ __forceinline__ void ggx_colocated_point(float light, float distance, const float n[3], const float v[3],
+                                                    const float kd[3], const float ks[3], float rough,
+                                                    const float* __restrict__ tab_trans,
+                                                    const float* __restrict__ tab_diff, GgxOut& o) {
+    const float intensity = intensity_at(light, distance);
+    float dot = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
+    dot = fminf(fmaxf(dot, 0.00001f), 0.99999f);
+    const float alpha = fmaxf(rough, 0.0001f);
+    const float D = ggx_ndf(dot, alpha);
+    const float g1 = smith_g1(dot, alpha);
+    const float G = g1 * g1;
+    const float denom = 4.0f * dot + 1e-10f;
+    float T12, fd;
+    rtrans_lookup(dot, alpha, tab_trans, tab_diff, T12, fd);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o.specular[c] = intensity * ks[c] * kFr * D * G / denom;
+        o.diffuse[c] = intensity * (kd[c] / fd / kPi) * dot * T12 * T12 * kInvEta2;
+        o.rgb[c] = o.diffuse[c] + o.specular[c];
+    }
+}
+
+// ---- SURVEY 8 row f-4: the fork's other co-located heads (models/renderer_ggx.py:149-517, 520-858) -----------------
 
 struct CompositeOut {
     float specular[3], metallic[3], dielectric[3], rgb[3];
@@ -121,11 +194,7 @@ __device__ __forceinline__ void composite_point(float intensity, const float n[3
     const float m_k = fminf(fmaxf(m_k_in, 0.099999f), 9.999999f);
     float cos_i = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
     cos_i = fminf(fmaxf(cos_i, 0.00001f), 0.99999f);
-    const float eta2 = (float)(1.48958738 * 1.48958738 + 1e-10);
-    const float pi_eta2 = (float)(3.141592653589793 * 1.48958738 * 1.48958738);
-    const float c2 = cos_i * cos_i;
-    const float root = c2 + (1.0f - c2) / eta2;
-    const float D = 1.0f / (pi_eta2 * root * root + 1e-10f);
+    const float D = composite_ndf(cos_i);
     const float g1 = smith_g1(cos_i, rough);
     const float G = g1 * g1;
     const float Fm = fresnel_conductor_exact(cos_i, m_eta, m_k);
@@ -133,8 +202,6 @@ __device__ __forceinline__ void composite_point(float intensity, const float n[3
     const float denom = 4.0f * fabsf(cos_i);
     float T12, fd;
     rtrans_lookup(cos_i, fmaxf(rough, 0.0001f), tab_trans, tab_diff, T12, fd);
-    const float pi_f = 3.14159274101257324219f;
-    const float inv_eta2 = (float)(1.0 / (1.48958738 * 1.48958738));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float ks = fmaxf(ks_in[c], 0.00001f);
@@ -142,7 +209,7 @@ __device__ __forceinline__ void composite_point(float intensity, const float n[3
         o.metallic[c] = (ks * Fm) * intensity;
         o.dielectric[c] = (ks * Fd * D * G / denom) * intensity;
         o.specular[c] = o.dielectric[c] + o.metallic[c];
-        const float diffuse = intensity * (kd / fd / pi_f) * cos_i * T12 * T12 * inv_eta2;
+        const float diffuse = intensity * (kd / fd / kPi) * cos_i * T12 * T12 * kInvEta2;
         o.rgb[c] = diffuse + o.specular[c];
     }
 }
@@ -153,23 +220,20 @@ enum { kHeadSmoothDielectric = 0, kHeadThinDielectric = 1, kHeadSmoothConductor 
 __device__ __forceinline__ void coloc_head_point(int kind, float light, float distance, const float n[3], const float v[3],
                                                  const float kd[3], const float ks[3], float rough, float eta, float k,
                                                  GgxOut& o) {
-    const float intensity = light / (distance * distance + 1e-10f);
+    const float intensity = intensity_at(light, distance);
     float dot = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
     dot = fminf(fmaxf(dot, 0.00001f), 0.99999f);
     float spec_scale;  // specular_rgb = intensity * ks * spec_scale  (left-to-right products below keep the reference order)
-    float D = 1.0f, G = 1.0f, denom = 1.0f;
+    float denom = 1.0f, G = 1.0f, D = 1.0f;
     if (kind == kHeadSmoothDielectric) {
         spec_scale = 0.04f;
     } else if (kind == kHeadThinDielectric) {
-        spec_scale = (float)(0.04 + 0.96 * 0.96 * 0.04 / (1.0 - 0.04 * 0.04));
+        spec_scale = kThinSpec;
     } else {
         spec_scale = fresnel_conductor_exact(dot, eta, k);
         if (kind == kHeadRoughConductor) {
             const float alpha = fmaxf(rough, 0.0001f);
-            const float pi_f = 3.14159274101257324219f;
-            const float c2 = dot * dot;
-            const float root = c2 + (1.0f - c2) / (alpha * alpha + 1e-10f);
-            D = 1.0f / (pi_f * alpha * alpha * root * root + 1e-10f);
+            D = ggx_ndf(dot, alpha);
             const float g1 = smith_g1(dot, alpha);
             G = g1 * g1;
             denom = 4.0f * dot + 1e-10f;

@@ -10,6 +10,7 @@
 
 #include "../../include/iron_train.h"
 #include "gemm_h2.h"
+#include "ggx_core.h"
 
 namespace iron_train {
 
@@ -678,26 +679,13 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
     return IRON_OK;
 }
 
-// ---- GGX (models/renderer_ggx.py:82-146): first-order dual numbers in (cos, alpha, distance) -------------------------------------
-struct D3 {
-    float v, d[3];
-};
-__device__ __forceinline__ D3 cst(float c) { return {c, {0.f, 0.f, 0.f}}; }
-__device__ __forceinline__ D3 var(float x, int k) { D3 r = {x, {0.f, 0.f, 0.f}}; r.d[k] = 1.0f; return r; }
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2]}}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2]}}; }
-__device__ __forceinline__ D3 operator*(D3 a, D3 b) {
-    return {a.v * b.v, {a.d[0] * b.v + a.v * b.d[0], a.d[1] * b.v + a.v * b.d[1], a.d[2] * b.v + a.v * b.d[2]}};
-}
-__device__ __forceinline__ D3 operator/(D3 a, D3 b) {
-    const float q = a.v / b.v, ib = 1.0f / b.v;
-    return {q, {(a.d[0] - q * b.d[0]) * ib, (a.d[1] - q * b.d[1]) * ib, (a.d[2] - q * b.d[2]) * ib}};
-}
-__device__ __forceinline__ D3 dsqrt(D3 a) {
-    const float s = sqrtf(a.v), k = 0.5f / s;
-    return {s, {a.d[0] * k, a.d[1] * k, a.d[2] * k}};
-}
+// ---- the co-located BRDFs: the blocks of ggx_core.h instantiated with first-order dual numbers -----------------------------------
+using iron::Dual;
+using iron::kFr;
+using iron::kInvEta2;
+using iron::kPi;
 
+// GGX (models/renderer_ggx.py:82-146): duals in (cos, alpha, distance)
 __global__ void k_ggx_back(float light, const float* __restrict__ dist, const float* __restrict__ nrm, const float* __restrict__ view,
                            const float* __restrict__ kd, const float* __restrict__ ks, const float* __restrict__ rough,
                            const float* __restrict__ tab_trans, const float* __restrict__ tab_diff, int n, const float* __restrict__ g_diff,
@@ -715,29 +703,15 @@ __global__ void k_ggx_back(float light, const float* __restrict__ dist, const fl
         const float r0 = rough[p];
         const float alpha0 = fmaxf(r0, 0.0001f);
         const bool alpha_live = r0 >= 0.0001f;
-        const float pi_f = 3.14159274101257324219f;
-        const float m_inv_eta2 = (float)(1.0 / (1.48958738 * 1.48958738));
-        // piecewise-constant table factors
-        const long long tx = (long long)floorf(powf(cdot, 0.25f) * 100.0f);
-        const long long ty = (long long)floorf(powf(alpha0 / 4.0f, 0.25f) * 50.0f);
-        long long ti = ty * 100 + tx;
-        ti = ti < 0 ? 0 : (ti > 4999 ? 4999 : ti);
-        const float T12 = fminf(fmaxf(tab_trans[ti], 0.0f), 1.0f);
-        const long long ai = ty < 0 ? 0 : (ty > 49 ? 49 : ty);
-        const float Fdr = fminf(fmaxf(1.0f - tab_diff[ai], 0.0f), 1.0f);
-        const float fd = 1.0f - Fdr + 1e-10f;
+        float T12, fd;  // piecewise-constant table factors
+        iron::rtrans_lookup(cdot, alpha0, tab_trans, tab_diff, T12, fd);
 
-        const D3 c = var(cdot, 0), a = var(alpha0, 1), ds = var(dist[p], 2);
-        const D3 unit = cst(1.0f) / (ds * ds + cst(1e-10f));  // intensity per unit light
-        const D3 c2 = c * c;
-        const D3 a2 = a * a;
-        const D3 root = c2 + (cst(1.0f) - c2) / (a2 + cst(1e-10f));
-        const D3 Dm = cst(1.0f) / (cst(pi_f) * a2 * root * root + cst(1e-10f));
-        const D3 tan_t = dsqrt(cst(1.0f) - c2) / (c + cst(1e-10f));
-        const D3 rt = a * tan_t;
-        const D3 g1 = cst(2.0f) / (cst(1.0f) + dsqrt(rt * rt + cst(1.0f)));
-        const D3 Ks = unit * cst(0.03867f) * Dm * (g1 * g1) / (cst(4.0f) * c + cst(1e-10f));  // specular per unit light and albedo
-        const D3 Kd = unit * c * cst(T12 * T12 * m_inv_eta2 / (fd * pi_f));                 // diffuse  per unit light and albedo
+        typedef Dual<3> D3d;
+        const D3d c = D3d::var(cdot, 0), a = D3d::var(alpha0, 1);
+        const D3d unit = iron::intensity_at(1.0f, D3d::var(dist[p], 2));  // intensity per unit light
+        const D3d g1 = iron::smith_g1(c, a);
+        const D3d Ks = unit * kFr * iron::ggx_ndf(c, a) * (g1 * g1) / (4.0f * c + 1e-10f);  // specular per unit light and albedo
+        const D3d Kd = unit * c * (T12 * T12 * kInvEta2 / (fd * kPi));                      // diffuse  per unit light and albedo
         float A = 0.0f, B = 0.0f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -764,28 +738,8 @@ __global__ void k_ggx_back(float light, const float* __restrict__ dist, const fl
     }
 }
 
-// ---- CompositeRenderer (models/renderer_ggx.py:781-858, point-light branch): duals in (cos, roughness, distance, metallic eta,
-// metallic k, dielectric eta); linear in the two albedos and the light.  Same expressions as csrc/ggx_core.h:composite_point.
-template <int N>
-struct Dual {
-    float v, d[N];
-};
-template <int N> __device__ __forceinline__ Dual<N> dc(float c) { Dual<N> r; r.v = c; for (int i = 0; i < N; ++i) r.d[i] = 0.f; return r; }
-template <int N> __device__ __forceinline__ Dual<N> dvar(float x, int k) { Dual<N> r = dc<N>(x); r.d[k] = 1.f; return r; }
-template <int N> __device__ __forceinline__ Dual<N> operator+(Dual<N> a, Dual<N> b) { Dual<N> r; r.v = a.v + b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
-template <int N> __device__ __forceinline__ Dual<N> operator-(Dual<N> a, Dual<N> b) { Dual<N> r; r.v = a.v - b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
-template <int N> __device__ __forceinline__ Dual<N> operator*(Dual<N> a, Dual<N> b) { Dual<N> r; r.v = a.v * b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
-template <int N> __device__ __forceinline__ Dual<N> operator/(Dual<N> a, Dual<N> b) {
-    Dual<N> r; r.v = a.v / b.v; const float ib = 1.0f / b.v;
-    for (int i = 0; i < N; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * ib;
-    return r;
-}
-template <int N> __device__ __forceinline__ Dual<N> dsqrt(Dual<N> a) {
-    Dual<N> r; r.v = sqrtf(a.v); const float k = 0.5f / r.v;
-    for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * k;
-    return r;
-}
-
+// CompositeRenderer (models/renderer_ggx.py:781-858): duals in (cos, roughness, distance or env light, metallic eta, metallic k,
+// dielectric eta); linear in the two albedos and the light.
 struct CompBackArgs {
     const float *dist, *nrm, *view, *kd, *ks, *rough, *m_eta, *m_k, *d_eta, *env, *tab_trans, *tab_diff;
     const float *g_rgb, *g_spec, *g_met, *g_die, *g_env;
@@ -815,57 +769,22 @@ __global__ void k_composite_back(CompBackArgs a) {
                               me_in >= 0.099999f && me_in <= 4.999999f,
                               mk_in >= 0.099999f && mk_in <= 9.999999f, de_in >= 1.000001f && de_in <= 1.999999f};
         // piecewise-constant diffuse tables (alpha := max(rough, 1e-4) as CompositeRenderer.diffuse_reflection_ggx does)
-        const float alpha_t = fmaxf(rough0, 0.0001f);
-        const long long tx = (long long)floorf(powf(cdot, 0.25f) * 100.0f);
-        const long long ty = (long long)floorf(powf(alpha_t / 4.0f, 0.25f) * 50.0f);
-        long long ti = ty * 100 + tx;
-        ti = ti < 0 ? 0 : (ti > 4999 ? 4999 : ti);
-        const float T12 = fminf(fmaxf(a.tab_trans[ti], 0.0f), 1.0f);
-        const long long ai = ty < 0 ? 0 : (ty > 49 ? 49 : ty);
-        const float Fdr = fminf(fmaxf(1.0f - a.tab_diff[ai], 0.0f), 1.0f);
-        const float fd = 1.0f - Fdr + 1e-10f;
-        const float pi_f = 3.14159274101257324219f;
-        const float inv_eta2 = (float)(1.0 / (1.48958738 * 1.48958738));
-        const float eta2 = (float)(1.48958738 * 1.48958738 + 1e-10);
-        const float pi_eta2 = (float)(3.141592653589793 * 1.48958738 * 1.48958738);
+        float T12, fd;
+        iron::rtrans_lookup(cdot, fmaxf(rough0, 0.0001f), a.tab_trans, a.tab_diff, T12, fd);
 
-        const D6 c = dvar<6>(cdot, 0), rg = dvar<6>(rough0, 1), me = dvar<6>(me0, 3), mk = dvar<6>(mk0, 4), de = dvar<6>(de0, 5);
-        const D6 one = dc<6>(1.0f);
+        const D6 c = D6::var(cdot, 0), rg = D6::var(rough0, 1), me = D6::var(me0, 3), mk = D6::var(mk0, 4), de = D6::var(de0, 5);
         D6 U;  // intensity per unit `lightf`: variable 2 is the distance (point light) or the env-light value
         if (use_env) {
-            U = dvar<6>(fminf(fmaxf(env_in, 0.000001f), 20.0f), 2);
+            U = D6::var(fminf(fmaxf(env_in, 0.000001f), 20.0f), 2);
         } else {
-            const D6 ds = dvar<6>(a.dist[p], 2);
-            U = one / (ds * ds + dc<6>(1e-10f));
+            U = iron::intensity_at(1.0f, D6::var(a.dist[p], 2));
         }
         const float lightf = use_env ? 1.0f : a.light;
-        const D6 c2 = c * c, s2 = one - c2;
-        // GGX NDF with alpha := eta (the reference's quirk), Smith G1 with the roughness
-        const D6 root = c2 + s2 / dc<6>(eta2);
-        const D6 Dn = one / (dc<6>(pi_eta2) * root * root + dc<6>(1e-10f));
-        const D6 tan_t = dsqrt(s2) / (c + dc<6>(1e-10f));
-        const D6 rt = rg * tan_t;
-        const D6 g1 = dc<6>(2.0f) / (one + dsqrt(rt * rt + one));
-        // conductor Fresnel
-        const D6 s4 = s2 * s2;
-        const D6 temp1 = me * me - mk * mk - s2;
-        const D6 a2pb2 = dsqrt(temp1 * temp1 + dc<6>(4.0f) * mk * mk * me * me);
-        const D6 aa = dsqrt(dc<6>(0.5f) * (a2pb2 + temp1));
-        const D6 term1 = a2pb2 + c2, term2 = dc<6>(2.0f) * aa * c;
-        const D6 rs2 = (term1 - term2) / (term1 + term2);
-        const D6 term3 = a2pb2 * c2 + s4, term4 = term2 * s2;
-        const D6 rp2 = rs2 * (term3 - term4) / (term3 + term4);
-        const D6 Fm = dc<6>(0.5f) * (rp2 + rs2);
-        // dielectric Fresnel (cos > 0)
-        const D6 sc = one / de;
-        const D6 cos_t = dsqrt(one - s2 * (sc * sc));
-        const D6 rs = (c - de * cos_t) / (c + de * cos_t);
-        const D6 rp = (de * c - cos_t) / (de * c + cos_t);
-        const D6 Fd = dc<6>(0.5f) * (rs * rs + rp * rp);
-
-        const D6 M = Fm * U;                                            // metallic   per unit light and specular albedo
-        const D6 Dl = Fd * Dn * (g1 * g1) / (dc<6>(4.0f) * c) * U;      // dielectric per unit light and specular albedo
-        const D6 Df = U * c * dc<6>(T12 * T12 * inv_eta2 / (fd * pi_f)); // diffuse    per unit light and diffuse albedo
+        const D6 g1 = iron::smith_g1(c, rg);
+        // metallic and dielectric per unit light and specular albedo, diffuse per unit light and diffuse albedo
+        const D6 M = iron::fresnel_conductor_exact(c, me, mk) * U;
+        const D6 Dl = iron::fresnel_dielectric_pos(c, de) * iron::composite_ndf(c) * (g1 * g1) / (4.0f * c) * U;
+        const D6 Df = U * c * (T12 * T12 * kInvEta2 / (fd * kPi));
         float Am = 0.f, Ad = 0.f, Af = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -920,36 +839,22 @@ __global__ void k_coloc_head_back(HeadBackArgs a) {
         const float cdot = fminf(fmaxf(raw_dot, 0.00001f), 0.99999f);
         const bool dot_live = raw_dot >= 0.00001f && raw_dot <= 0.99999f;
         const float r_in = a.rough ? a.rough[p] : 1.0f;
-        const bool rough_live = a.kind == 3 && r_in >= 0.0001f;
-        const D3d c = dvar<3>(cdot, 0), al = dvar<3>(fmaxf(r_in, 0.0001f), 1), ds = dvar<3>(a.dist[p], 2);
-        const D3d one = dc<3>(1.0f);
-        const D3d U = one / (ds * ds + dc<3>(1e-10f));
+        const bool rough_live = a.kind == iron::kHeadRoughConductor && r_in >= 0.0001f;
+        const D3d c = D3d::var(cdot, 0), al = D3d::var(fmaxf(r_in, 0.0001f), 1);
+        const D3d U = iron::intensity_at(1.0f, D3d::var(a.dist[p], 2));
         D3d S;  // specular per unit light and specular albedo
-        if (a.kind == 0) {
-            S = U * dc<3>(0.04f);
-        } else if (a.kind == 1) {
-            S = U * dc<3>((float)(0.04 + 0.96 * 0.96 * 0.04 / (1.0 - 0.04 * 0.04)));
+        if (a.kind == iron::kHeadSmoothDielectric) {
+            S = U * 0.04f;
+        } else if (a.kind == iron::kHeadThinDielectric) {
+            S = U * iron::kThinSpec;
         } else {
-            const D3d c2 = c * c, s2 = one - c2, s4 = s2 * s2;
-            const D3d me = dc<3>(a.eta), mk = dc<3>(a.k);
-            const D3d temp1 = me * me - mk * mk - s2;
-            const D3d a2pb2 = dsqrt(temp1 * temp1 + dc<3>(4.0f) * mk * mk * me * me);
-            const D3d aa = dsqrt(dc<3>(0.5f) * (a2pb2 + temp1));
-            const D3d term1 = a2pb2 + c2, term2 = dc<3>(2.0f) * aa * c;
-            const D3d rs2 = (term1 - term2) / (term1 + term2);
-            const D3d term3 = a2pb2 * c2 + s4, term4 = term2 * s2;
-            const D3d rp2 = rs2 * (term3 - term4) / (term3 + term4);
-            S = U * dc<3>(0.5f) * (rp2 + rs2);
-            if (a.kind == 3) {
-                const D3d a2 = al * al;
-                const D3d root = c2 + s2 / (a2 + dc<3>(1e-10f));
-                const D3d Dn = one / (dc<3>(3.14159274101257324219f) * a2 * root * root + dc<3>(1e-10f));
-                const D3d rt = al * (dsqrt(s2) / (c + dc<3>(1e-10f)));
-                const D3d g1 = dc<3>(2.0f) / (one + dsqrt(rt * rt + one));
-                S = S * Dn * (g1 * g1) / (dc<3>(4.0f) * c + dc<3>(1e-10f));
+            S = U * iron::fresnel_conductor_exact<D3d>(c, a.eta, a.k);
+            if (a.kind == iron::kHeadRoughConductor) {
+                const D3d g1 = iron::smith_g1(c, al);
+                S = S * iron::ggx_ndf(c, al) * (g1 * g1) / (4.0f * c + 1e-10f);
             }
         }
-        const D3d Df = U * dc<3>(0.0001f);  // diffuse per unit light and diffuse albedo
+        const D3d Df = U * 0.0001f;  // diffuse per unit light and diffuse albedo
         float As = 0.f, Ad = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
