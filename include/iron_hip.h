@@ -71,7 +71,7 @@ typedef struct iron_net_desc {
     int32_t kind;          /* IRON_NET_SDF | IRON_NET_RENDER | IRON_NET_NERF                        */
     int32_t n_linear;      /* number of linear layers (= n_layers + 1)                              */
     int32_t d_hidden;      /* hidden width (256)                                                    */
-    int32_t d_out;         /* SDF: 257 (sdf + feature); RENDER: 1..3                                */
+    int32_t d_out;         /* SDF: 1 (sdf only) or 257 (sdf + feature); RENDER: 1..3; NERF: 4        */
     int32_t multires;      /* PE levels on points (SDF: 6)                                          */
     int32_t multires_view; /* RENDER: PE levels on view_dirs (<=0: none)                            */
     int32_t skip_layer;    /* index of the skip-concat layer, -1 if none (SDF: 4)                   */
@@ -83,6 +83,18 @@ typedef struct iron_net_desc {
     float output_scale;
     float scale;           /* SDF: input scale (fields.py:83,98)                                    */
 } iron_net_desc;
+
+/* Accepted shapes (d_hidden = 256 throughout; tests/test_gpu_net_shapes.py computes each family against an fp64 oracle):
+ *   SDF:    n_linear 3..17, multires 6, skip_layer -1 or 2..n_linear-2, d_out 1 or 257, scale > 0, weight_g or NULL.
+ *           n_linear 9 with skip 4 runs on the default (h2) core, every other shape on the exact-fp32 core.
+ *           The backward (include/iron_train.h) covers every accepted shape with scale = 1.
+ *   RENDER: n_linear 2..17, d_feature 256, d_out 1..3, squeeze / bias / scale any, weight_g or NULL; skip_layer -1 or
+ *           1..n_linear-2 (idr, PE 10 points / 4 views only; n_linear 9 with skip 4 on the h2 core).  The (mode, PE) pairs with a
+ *           kernel: idr 0/4, no_view_dir 6, points_only 6 (h2 core at an even number of hidden layers <= 8), idr 10/4 with a skip.
+ *           Any other pair (no_normal among them) is created but refused by the first evaluation (IRON_ERR_UNSUPPORTED).
+ *   NERF:   D = n_linear - 4 in 2..14, skip -1..D-2, PE 10 / 4 (other levels are created but refused by iron_nerf_forward);
+ *           D 8 with skip 4 on the h2 core.
+ * Anything else fails here with IRON_ERR_UNSUPPORTED. */
 
 /* Build a packed network on the current device.  `layers` is a HOST array of n_linear entries
  * whose pointers are DEVICE pointers.  Synchronises `stream` before returning (the source

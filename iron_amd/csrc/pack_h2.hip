@@ -269,6 +269,9 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
 
 int build_h2_sdf(iron_net* net, const iron_linear* L, const float* scale_base, const size_t* soff, hipStream_t st) {
     const iron_net_desc& d = net->desc;
+    // only the shape the h2 SDF kernels are written for (h2_sdf_usable: 8 hidden layers, skip at 4) gets the streams; every other
+    // accepted shape runs on the exact-fp32 core and keeps the fp32 pack only (deeper nets would also exceed the 127-slot table)
+    if (d.n_linear != 9 || d.skip_layer != 4) return IRON_OK;
     { const int rc0 = h2_overflow_reset(st); if (rc0 != IRON_OK) return rc0; }
     H2StreamDev s;
     uint32_t n_trace = 0, n_full = 0;
@@ -319,7 +322,7 @@ int build_h2_render(iron_net* net, const iron_linear* L, const float* scale_base
             add(1);
         }
     const uint32_t n_slots = (uint32_t)(table.size() / 2);
-    if (n_slots > 127 || nl - 1 > 8) return IRON_ERR_UNSUPPORTED;
+    if (n_slots > 127 || nl - 1 > 8) return IRON_OK;   // fp32 pack only: the h2 material kernels take at most 8 hidden layers
     const size_t table_off = (off + 255) & ~(size_t)255;
     const size_t bias_off = table_off + 1024;
     const size_t rows_off = bias_off + kLdsBiasBytes;

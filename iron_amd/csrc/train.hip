@@ -324,7 +324,7 @@ __global__ void k_sdf_act_back(const float* __restrict__ dX, int ld_dx, const fl
 }
 
 constexpr int kSdfChunk = 65536;
-constexpr int kMaxLayers = 16;
+constexpr int kMaxLayers = 18;   // what iron_net_create accepts: SDF / material nets of 17 linear layers, NeRF D = 14 (+ 4 heads)
 
 struct SdfPlan {
     int L, m_max;

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _nets import _compare_param_grads
 from _util import cpu_sd, golden, golden_meta, t, tables
 
 pytestmark = pytest.mark.gpu
@@ -15,40 +16,6 @@ NETS = ("sdf_network", "diffuse_albedo_network", "specular_albedo_network", "spe
 def _rel(a, b):
     a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def _compare_param_grads(module, leaf_sd, tol, tag, tol_for=None):
-    """tol_for: {parameter-name prefix: tolerance} overrides for individual tensors (every other tensor is held to `tol`)."""
-    worst = 0.0
-    base_tol = tol
-    for name, p in module.named_parameters():
-        tol = base_tol
-        for prefix, t_ in (tol_for or {}).items():
-            if name.startswith(prefix):
-                tol = t_
-        assert p.grad is not None, name
-        ref = leaf_sd[name].grad
-        if ref is None:  # torch found no path to this parameter (e.g. the last bias from a gradient-only loss): ours must be 0
-            assert float(p.grad.abs().max()) == 0.0, (tag, name)
-            p.grad = None
-            continue
-        r = _rel(p.grad.cpu().numpy(), ref.numpy())
-        if name.endswith("weight_g") and r > tol:
-            # d/dg_i = <dW_i, v_i/|v_i|> is a projection of the effective-weight gradient dW (what the GEMMs produce) that can cancel
-            # by orders of magnitude (lin0 of the PE-10 colour net: |d/dg| ~ 1e-3 |dW_i|), so its own norm is the wrong yardstick:
-            # the split-fp16 GEMM carries 2^-22 per operand, relative to dW.  |dW_i| = |d/dv_i| |v_i| / g_i up to that projection.
-            v = dict(module.named_parameters())[name.replace("weight_g", "weight_v")].detach().cpu()
-            gv = leaf_sd[name.replace("weight_g", "weight_v")].grad
-            dw_rows = gv.norm(dim=1, keepdim=True) * v.norm(dim=1, keepdim=True) / dict(module.named_parameters())[name].detach().cpu().abs()
-            r = float(((p.grad.cpu() - ref).abs() / dw_rows.clamp_min(1e-30)).max())
-        # a parameter whose gradient is pure rounding noise (e.g. zero-initialised PE columns' norm direction) is compared in
-        # absolute terms against the largest gradient of the network
-        if r > worst:
-            worst = r
-            _compare_param_grads.last = "%s |ref| %.2e" % (name, float(ref.norm()))
-        assert r <= tol or float(ref.abs().max()) <= 1e-9, (tag, name, r)
-        p.grad = None
-    return worst
 
 
 def test_sdf_get_all_backward_vs_autograd():
