@@ -108,8 +108,10 @@ int iron_net_destroy(iron_net_t* net);
  * the exact-fp32 MFMA core for good (IRON_H2_OVERFLOW=error: returns IRON_ERR_RANGE instead).  The reference is plain fp32
  * (models/fields.py:82-98, 203-239), which the exact core reproduces over the whole fp32 range.
  *   iron_net_numeric_status: synchronises `stream`; *status_out = bit 0: an overflow was seen, bit 1: the network runs on the exact
- *                            core, bit 2: a flag is pending (the call just finished overflowed).
- *   iron_net_force_exact:    on != 0 pins the network to the exact core; 0 returns it to the default core and clears the status. */
+ *                            core, bit 2: a flag is pending (the call just finished overflowed),
+ *                            bit 3: the dense sampler's screen guard has turned the screen off for this network (iron_set_sampler_screen).
+ *   iron_net_force_exact:    on != 0 pins the network to the exact core; 0 returns it to the default core and clears the status
+ *                            (bits 0-3). */
 int iron_net_numeric_status(const iron_net_t* net, int32_t* status_out, void* stream);
 int iron_net_force_exact(iron_net_t* net, int32_t on);
 
@@ -463,6 +465,30 @@ int32_t iron_set_cu_limit(int32_t n_cus);
  * default (IRON_TRACE_SPLIT, else 1: measured no faster on MI355X, csrc/trace.hip).  Returns the previous setting.  Process-wide;
  * no counterpart in the reference (RayTracer.forward, models/raytracer.py:45-103, is one sequence of masked torch ops). */
 int32_t iron_set_trace_split(int32_t parts);
+
+/* The dense sampler's screen as a batched call (diagnostics and tests; no reference counterpart): out[i] = the SDF of x[i] computed
+ * with ONE fp16 product per multiply-add (fp16 weights and activations, fp32 accumulation; csrc/mlp_h2.h sdf_hidden_stack_h1).
+ * NOT fp32-accurate: the tracer uses it only to decide signs far from zero (csrc/trace.hip).  IRON_ERR_UNSUPPORTED
+ * unless the network runs on the h2 core (8 x 256, skip 4). */
+int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, float* out, void* stream);
+
+/* The dense sampler's screen (csrc/trace.hip k_sampler_screen; no reference counterpart; results do not depend on it).  On the h2
+ * core the sampler decides sample signs on the screen where they are clear by a calibrated margin and evaluates the rest exactly;
+ * outputs and iron_trace_stats are those of the unscreened sampler.  The margin is empirical: a guard (iron_net_numeric_status
+ * bit 3) turns the screen off for a network whose exactly evaluated samples came within half the margin, for every call that
+ * starts after the call that raised it has completed (the flag is a pinned host word; calls already queued behind it still screen).
+ * The trace workspace (iron_trace_workspace_bytes) holds the screen's lists on every path: ~105 bytes per ray.
+ *   iron_set_sampler_screen:   on = 1 screen, 0 don't, -1 the default (IRON_SAMPLER_SCREEN=0: off, else on).  Process-wide;
+ *                              returns the previous state.
+ *   iron_sampler_screen_debug: test hooks, process-wide.  what 0: value > 0 forces the margin delta (0 restores the calibrated
+ *                              one); what 1: value >= 1 caps the resolve list at that many samples per part (0 restores).
+ *   iron_trace_screen_counts:  synchronises `stream`; from the workspace of the last iron_trace / iron_trace_phase(0) /
+ *                              iron_trace_stage(1) call: out[0] screened evaluations (speculative ones included), out[1] exactly
+ *                              resolved samples, out[2] rays that overflowed the resolve list (marched unscreened), out[3] the
+ *                              largest |f_screen - f_exact| / delta over the resolved samples, out[4] rays decided after the resolve. */
+int32_t iron_set_sampler_screen(int32_t on);
+int iron_sampler_screen_debug(int32_t what, double value);
+int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the

@@ -70,6 +70,7 @@ int envelope_create(iron_net* net) {
     net->flag_host = g_pool_host + (size_t)slot * kSlotInts;
     net->flag_dev = g_pool_dev + (size_t)slot * kSlotInts;
     *(volatile int*)net->flag_host = 0;
+    *(volatile int*)(net->flag_host + 1) = 0;   // word 1: the sampler's screen guard (trace.hip)
     return IRON_OK;
 }
 
@@ -115,6 +116,7 @@ extern "C" int iron_net_numeric_status(const iron_net_t* net, int32_t* status_ou
     if (n->flag_host && *(volatile int*)n->flag_host) { n->overflow_seen = 1; s |= 4; }
     if (n->overflow_seen) s |= 1;
     if (n->h2_disabled) s |= 2;
+    if (n->screen_off || (n->flag_host && *(volatile int*)(n->flag_host + 1))) s |= 8;   // the sampler's screen guard (trace.hip)
     *status_out = s;
     return IRON_OK;
 }
@@ -122,6 +124,10 @@ extern "C" int iron_net_numeric_status(const iron_net_t* net, int32_t* status_ou
 extern "C" int iron_net_force_exact(iron_net_t* net, int32_t on) {
     if (!net) return IRON_ERR_BAD_ARG;
     net->h2_disabled = on ? 1 : 0;
-    if (!on) { net->overflow_seen = 0; if (net->flag_host) *(volatile int*)net->flag_host = 0; }
+    if (!on) {
+        net->overflow_seen = 0;
+        net->screen_off = 0;   // the sampler's screen guard (status bit 3) is part of the status, cleared with it
+        if (net->flag_host) { *(volatile int*)net->flag_host = 0; *(volatile int*)(net->flag_host + 1) = 0; }
+    }
     return IRON_OK;
 }

@@ -42,6 +42,29 @@ __global__ __launch_bounds__(256, 1) void k_sdf_values_h2(H2StreamDev s, H2Meta 
 #endif
 }
 
+// the sampler's screen (sdf_hidden_stack_h1: one product per MAC, fp16 operands) on the same layout: tools/bench_screen.py times it
+// against k_sdf_values_h2, tools/screen_margin.py / tests compare its values
+__global__ __launch_bounds__(256, 1) void k_sdf_values_h1(H2StreamDev s, H2Meta m, const float* __restrict__ x, int64_t n,
+                                                         float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    Ring ring;
+    h2_setup(s, lds, ring);
+    const int64_t n_groups = (n + 127) / 128;
+    for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const int64_t idx = g * 128 + wave * 32 + (lane & 31);
+        const bool ok = idx < n;
+        const int64_t src = ok ? idx : (n - 1);
+        const float px = x[src * 3 + 0], py = x[src * 3 + 1], pz = x[src * 3 + 2];
+        f32x16 hf[kHidTiles];
+        sdf_hidden_stack_h1<kFastActH>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, px, py, pz, lane, hf);
+        const float v = (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
+        if (ok && lane < 32) out[idx] = v;
+    }
+    ring.drain();
+}
+
 #if IRON_H2_STAMP
 extern "C" int iron_debug_h2_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_h2_stamps), sizeof(unsigned long long) * 4 * kStampSteps * 8) == hipSuccess ? 0 : -1;
@@ -75,3 +98,24 @@ int launch_sdf_values_h2(const iron_net* net, const float* x, int64_t n, float* 
 }
 
 }  // namespace iron
+
+using namespace iron;
+
+extern "C" int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, float* out, void* stream) {
+    if (!net || net->desc.kind != IRON_NET_SDF || n < 0 || (n > 0 && (!x || !out))) return IRON_ERR_BAD_ARG;
+    if (!h2_sdf_usable(net)) return IRON_ERR_UNSUPPORTED;
+    if (n == 0) return IRON_OK;
+    static bool attr = false;
+    if (!attr) {
+        IRON_HIP_TRY(hipFuncSetAttribute((const void*)k_sdf_values_h1, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsH2Total));
+        attr = true;
+    }
+    H2Meta m;
+    m.n_hidden_layers = net->sdf.n_hidden_layers; m.skip_layer = net->sdf.skip_layer; m.scale = net->sdf.scale; m.b_last = net->sdf.b_last;
+    const int64_t groups = (n + 127) / 128;
+    const int64_t cus = cu_budget();
+    const unsigned grid = (unsigned)(groups < cus ? groups : cus);
+    hipLaunchKernelGGL(k_sdf_values_h1, dim3(grid), dim3(256), kLdsH2Total, (hipStream_t)stream, net->h2_trace, m, x, n, out);
+    IRON_HIP_TRY(hipGetLastError());
+    return IRON_OK;
+}

@@ -137,6 +137,11 @@ struct iron_net {
     int* flag_dev;
     int overflow_seen;    // a call on the h2 core returned non-finite values
     int h2_disabled;      // the network runs on the exact-fp32 core from now on (iron_net_force_exact, or after an overflow)
+    // the dense sampler's screen (trace.hip): the calibration word (device, allocated at the first screened trace), whether it has
+    // been measured, and the guard's sticky verdict (flag word 1 of the envelope's pinned slot raised it: the unscreened sampler runs)
+    unsigned* screen_calib;
+    int screen_calibrated;
+    int screen_off;
 };
 
 namespace iron {

@@ -807,4 +807,170 @@ __device__ __forceinline__ void sdf_hidden_stack_h2(Ring& ring, const char* lds,
     h2_hidden_layer<FAST, false, true, 0, D, false>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, hf, c_hi, c_lo);
 }
 
+// ---- the screen: one product per MAC -------------------------------------------------------------------
+// sdf_hidden_stack_h1 walks the same ring (same stream, same slot sequence, same refills) as sdf_hidden_stack_h2 but takes every
+// layer as wh * xh only: ONE v_mfma_f32_32x32x16_f16 and one ds_read_b128 (the hi fragment; the lo fragment of the slot is never
+// read) per k-step, and the epilogue rounds the activation to a single fp16 piece.  Weights and activations are therefore fp16
+// (11-bit significands) with fp32 accumulation: the value is NOT fp32-accurate.  The dense sampler (trace.hip) uses it only to
+// decide signs far from zero, with an empirical margin it calibrates per network against this core's exact (h2) value.
+struct Epi1State {
+    float z[16], e[16];
+    u32x4 oh[2];
+};
+
+// the epilogue of one tile as 104 instructions in dependency order (softplus_100 as in epi_gap, then 8 packed conversions), cut
+// into the 16 MFMA gaps of a step: 6-7 per gap.  An instruction's operands come from >= 8 instructions earlier.
+constexpr int kEpi1Ops = 104;
+constexpr int kEpi1OpsF32 = 96;   // last layer: f32 tile, no conversion
+__device__ __forceinline__ constexpr int epi1_first(int g, int n) { return g * n / 16; }
+
+__device__ __forceinline__ void epi1_op(Epi1State& st, int op, const f32x16& p) {
+    constexpr float kC1 = 144.26950408889634f;            // 100 * log2(e)
+    constexpr float kC2 = 0.0069314718055994531f;         // ln(2) / 100
+    if (op < 16) { st.e[op] = __builtin_fabsf(p[op]) * -kC1; pin1(st.e[op]); }
+    else if (op < 32) { const int i = op - 16; st.e[i] = __builtin_amdgcn_exp2f(st.e[i]); pin1(st.e[i]); }
+    else if (op < 48) { const int i = op - 32; st.e[i] = 1.0f + st.e[i]; pin1(st.e[i]); }
+    else if (op < 64) { const int i = op - 48; st.e[i] = __builtin_amdgcn_logf(st.e[i]); pin1(st.e[i]); }
+    else if (op < 80) { const int i = op - 64; st.z[i] = relu_med3(p[i]); pin1(st.z[i]); }
+    else if (op < 96) { const int i = op - 80; st.z[i] = __builtin_fmaf(st.e[i], kC2, st.z[i]); pin1(st.z[i]); }
+    else if (op < 104) {
+        const int q = op - 96;
+        unsigned h = __builtin_bit_cast(unsigned, cvt_pk_rn(st.z[2 * q], st.z[2 * q + 1]));
+        pin1u(h);
+        st.oh[q >> 2][q & 3] = h;
+    }
+}
+
+// f32 tile -> the two k-step B fragments of the next layer, hi pieces only
+__device__ __forceinline__ void hi_tile(const f32x16& v, half8 (&out)[2]) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        u32x4 hh;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hh[i] = __builtin_bit_cast(unsigned, cvt_pk_rn(v[8 * s + 2 * i], v[8 * s + 2 * i + 1]));
+        out[s] = __builtin_bit_cast(half8, hh);
+    }
+}
+
+struct TileH {
+    half8 h[2];
+};
+
+__device__ __forceinline__ void step_head_h1(const char* __restrict__ rd, const char* __restrict__ bias, char* __restrict__ wr,
+                                             const RingSrc& src, bool src_hidden, int wave, int lane, int tile, bool add_bias,
+                                             const HeadFrag& hd, f32x16& acc) {
+    dma_issue(src, wr, src_hidden, wave);
+    if (add_bias) acc = lds_half_tile(bias, tile, lane >> 5);
+#pragma unroll
+    for (int ks = 0; ks < kHeadKSteps; ++ks) acc = mfma_h(lds_frag(rd, 2 * ks, lane), hd.h[ks], acc);
+}
+
+// One ring step on a hidden slot: acc += Wh[tile,:] * in_h (16 MFMAs), the epilogue of the pending tile `p` in their gaps.
+// EPI: 0 = nothing pending, 1 = pending tile -> hi fragments, 2 = pending tile -> f32 tile (last layer).
+template <int EPI>
+__device__ __forceinline__ void step_hidden_h1(const char* __restrict__ rd, const char* __restrict__ bias, char* __restrict__ wr,
+                                               const RingSrc& src, bool src_hidden, int wave, int lane, int tile, bool add_bias,
+                                               const TileH (&in)[kHidTiles], f32x16& acc, const f32x16& p, TileH& out_prev,
+                                               f32x16& hf_prev) {
+    if (add_bias) acc = lds_half_tile(bias, tile, lane >> 5);
+    half8 fr[2];
+    fr[0] = lds_frag(rd, 0, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    dma_issue(src, wr, src_hidden, wave);
+    __builtin_amdgcn_sched_barrier(0);
+    Epi1State es;
+    constexpr int kOps = EPI == 2 ? kEpi1OpsF32 : kEpi1Ops;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        if (ks + 1 < 16) fr[(ks + 1) & 1] = lds_frag(rd, 2 * (ks + 1), lane);
+        acc = mfma_h(fr[ks & 1], in[ks >> 1].h[ks & 1], acc);
+        if constexpr (EPI != 0) {
+            const int o0 = epi1_first(ks, kOps), o1 = epi1_first(ks + 1, kOps);
+#pragma unroll
+            for (int k = 0; k < 7; ++k)
+                if (o0 + k < o1) epi1_op(es, o0 + k, p);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (EPI == 1) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) out_prev.h[s2] = __builtin_bit_cast(half8, es.oh[s2]);
+    }
+    if constexpr (EPI == 2) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) hf_prev[i] = es.z[i];
+    }
+}
+
+// One 256 -> 256 layer of the screen; HEAD: the layer also has a head product (skip layer); LAST: f32 tiles in `hf`.
+// The last tile's epilogue is exposed at the layer boundary.
+template <bool FAST, bool HEAD, bool LAST>
+__device__ __forceinline__ void h1_hidden_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, const TileH (&in)[kHidTiles],
+                                                TileH (&out)[kHidTiles], f32x16 (&hf)[kHidTiles]) {
+    const int wave = ring.wave;
+    f32x16 acc[2];
+    TileH dummy_out;
+    f32x16 dummy_hf;
+#pragma unroll
+    for (int to = 0; to < kHidTiles; ++to) {
+        const int P = to & 1, Q = P ^ 1;
+        acc[P] = zero16();
+        if constexpr (HEAD) {
+            ring.sync();
+            const RingStep sh = ring.step();
+            step_head_h1(sh.rd, bias, sh.wr, sh.src, sh.hidden, wave, lane, to, true, hd, acc[P]);
+        }
+        ring.sync();
+        const RingStep st = ring.step();
+        if (to == 0)
+            step_hidden_h1<0>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], dummy_out, dummy_hf);
+        else if constexpr (LAST)
+            step_hidden_h1<2>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], dummy_out, hf[to > 0 ? to - 1 : 0]);
+        else
+            step_hidden_h1<1>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], out[to > 0 ? to - 1 : 0], dummy_hf);
+    }
+    if constexpr (LAST) hf[kHidTiles - 1] = softplus_tile<FAST>(acc[1]);
+    else hi_tile(softplus_tile<FAST>(acc[1]), out[kHidTiles - 1].h);
+}
+
+// SDFNetwork hidden stack on the screen (one product per MAC).  Same contract as sdf_hidden_stack_h2: all four waves together,
+// the same ring (it consumes exactly the slots sdf_hidden_stack_h2 consumes, so the two may alternate on one ring), hf = the last
+// hidden activation.
+template <bool FAST>
+__device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds, int n_hidden_layers, int skip_layer,
+                                                    float scale, float x, float y, float z, int lane,
+                                                    f32x16 (&hf)[kHidTiles]) {
+    const int half = lane >> 5;
+    const int wave = ring.wave;
+    float pe[kHeadSlots];
+#pragma unroll
+    for (int i = 0; i < kHeadSlots; ++i) pe[i] = 0.0f;
+    head_fill<kSdfPeLevels>(x * scale, y * scale, z * scale, half, pe);
+    HeadFrag hd;
+#pragma unroll
+    for (int s = 0; s < kHeadKSteps; ++s) {
+        u32x4 hh;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hh[i] = __builtin_bit_cast(unsigned, cvt_pk_rn(pe[8 * s + 2 * i], pe[8 * s + 2 * i + 1]));
+        hd.h[s] = __builtin_bit_cast(half8, hh);
+    }
+    TileH X[kHidTiles], Y[kHidTiles];
+#pragma unroll
+    for (int to = 0; to < kHidTiles; ++to) {
+        ring.sync();
+        const RingStep st = ring.step();
+        f32x16 a = zero16();
+        step_head_h1(st.rd, lds + kLdsBias, st.wr, st.src, st.hidden, wave, lane, to, true, hd, a);
+        hi_tile(softplus_tile<FAST>(a), X[to].h);
+    }
+    for (int l = 1; l + 1 < n_hidden_layers - 1; l += 2) {
+        const char* bias_a = lds + kLdsBias + l * 1024;
+        const char* bias_b = bias_a + 1024;
+        h1_hidden_layer<FAST, false, false>(ring, bias_a, hd, lane, X, Y, hf);
+        if (l + 1 == skip_layer) h1_hidden_layer<FAST, true, false>(ring, bias_b, hd, lane, Y, X, hf);
+        else h1_hidden_layer<FAST, false, false>(ring, bias_b, hd, lane, Y, X, hf);
+    }
+    h1_hidden_layer<FAST, false, true>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, hf);
+}
+
 }  // namespace iron

@@ -539,6 +539,7 @@ extern "C" int iron_net_destroy(iron_net_t* net) {
     envelope_destroy(net);
     if (net->h2_scratch) IRON_HIP_TRY(hipFree(net->h2_scratch));
     if (net->w16_blob) IRON_HIP_TRY(hipFree(net->w16_blob));
+    if (net->screen_calib) IRON_HIP_TRY(hipFree(net->screen_calib));
     delete net;
     return IRON_OK;
 }

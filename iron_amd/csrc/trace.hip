@@ -40,20 +40,77 @@ constexpr int kMaxTraceSplits = 4;
 #endif
 constexpr bool kFastActT = IRON_FAST_SOFTPLUS != 0;
 
+struct SamplerQ {       // one dense-sampler work queue
+    int n_list;         // rays listed
+    int head;           // tickets drawn
+    int n_cont;         // continuation items published
+    int n_done;         // listed rays whose sampling has ended
+};
+
 struct TraceCounters {  // zeroed at the start of every call
     int q_head;         // sphere-trace ray queue
-    int n_sampler;      // rays appended for dense sampling
-    int sampler_head;
+    SamplerQ smp;       // the dense sampler's list: n_list = rays appended by k_sphere
     int n_root;         // rays with a sign-change bracket
     int root_head_a;
     int root_head_b;
-    int n_cont;         // k_sampler: continuation items published
-    int n_sampler_done; // k_sampler: listed rays whose sampling has ended
     long long n_evals;
     long long n_sphere_conv;
     long long n_evals_sphere;
     long long sampler_abort;   // k_sampler workgroups that left the queue protocol by the poll bound (0 unless the protocol is broken)
+    // the screened sampler (k_sampler_screen; read through iron_trace_screen_counts, never through iron_trace_stats)
+    SamplerQ ovf;       // rays whose uncertain samples did not fit the resolve list: marched again by the unscreened k_sampler
+    int n_res;          // uncertain samples appended to the resolve list (may exceed its capacity: the excess rays overflowed)
+    int res_head;       // k_screen_resolve's queue
+    int n_pend;         // rays whose outcome waits for the resolve
+    unsigned ratio_bits;   // largest |f_screen - f_h2| / delta over the resolved samples (f32 bits; non-negative floats order as uints)
+    long long n_screen;    // screened evaluations, speculative ones included
+    long long n_resolved;  // exact evaluations of listed samples
+    long long n_ovf;       // rays that overflowed the resolve list
 };
+
+// The screened sampler's state (see k_sampler_screen)
+struct ResolveEntry {   // one uncertain sample: written by k_sampler_screen, f_ex by k_screen_resolve
+    int ray;
+    int s;              // sample index
+    float z;            // its depth
+    float f1;           // screened value
+    float f_prev1;      // screened value of sample s - 1 (the previous item's last sample for s % block == 0; 0 for s == 0)
+    float f_ex;         // exact (h2) value
+    int pad0, pad1;
+};
+struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
+    int first;          // first certainly-negative sample (n_steps: none); atomicMin-ed by the resolve with the negative listed samples
+    float fhi, flo;     // bracket values at `first` (screened, or exact where the sample was listed)
+    float flo_ex;       // exact value of sample first - 1 when it was listed
+    int has_flo_ex;
+    int pad[3];
+};
+struct ScreenWs {
+    const unsigned* calib;   // per network: max |f_screen - f_h2| over the calibration set (f32 bits), device
+    int* flag;               // per network: the guard flag (pinned host word), may be null
+    float delta_override;    // test hook (> 0: this delta)
+    ResolveEntry* ent;       // [cap]
+    int cap;
+    PendRec* rec;            // [rays of the call] by ray id
+    int* pend_list;          // [rays of the part]
+    int* ovf_list;           // [rays of the part]
+    uint8_t* ray_state;      // [rays of the call] by ray id (zeroed at the start of a call): kRayPending | kRayOverflowed
+};
+
+// margin of the screen: delta = max(K * max|f_screen - f_h2| on the calibration set, floor).  EMPIRICAL, not a certified bound:
+// a worst-case elementwise bound grows by about || |W| ||_inf ~ 18 per 256-wide layer and is useless here.  The resolve kernel
+// watches every sample it evaluates exactly; a ratio |f_screen - f_h2| / delta above kScreenGuard turns the screen off for the
+// network for the calls that start after the one that raised it has completed.
+constexpr float kScreenK = 12.0f;
+constexpr float kScreenFloor = 1.0e-3f;
+constexpr float kScreenGuard = 0.5f;
+constexpr int kScreenCalibPoints = 8192;
+constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
+constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
+constexpr uint8_t kRayOverflowed = 1;  // ray_state: the ray's samples did not fit the list; k_sampler marches it again
+__device__ __forceinline__ float screen_delta(const ScreenWs& s) {
+    return s.delta_override > 0.0f ? s.delta_override : fmaxf(kScreenK * __uint_as_float(*s.calib), kScreenFloor);
+}
 
 struct TraceWs {
     TraceCounters* cnt;
@@ -69,6 +126,8 @@ struct TraceWs {
     int n_chunks;
     unsigned long long* cont;  // k_sampler's continuation items, [cont_cap] (zeroed at the start of a call)
     int cont_cap;
+    int ovf_pass;       // k_sampler: 0 = the list k_sphere fills (cnt->smp), 1 = the screen's overflow list (cnt->ovf, sampler_list = it)
+    ScreenWs scr;
 };
 
 struct TraceArgs {
@@ -156,6 +215,12 @@ struct BackendH2T {
     __device__ __forceinline__ float eval(float x, float y, float z) {
         f32x16 hf[kHidTiles];
         sdf_hidden_stack_h2<kFastActT, DEFER_TILES>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
+        return (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
+    }
+    // the screen: one product per MAC on the same ring (sdf_hidden_stack_h1), for sign decisions only
+    __device__ __forceinline__ float eval_screen(float x, float y, float z) {
+        f32x16 hf[kHidTiles];
+        sdf_hidden_stack_h1<kFastActT>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
         return (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
     }
     __device__ __forceinline__ void finish() { ring.drain(); }
@@ -249,7 +314,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sphere(IRON_TRACE_KERNEL_AR
         const unsigned samp = (unsigned)__ballot(to_sampler);
         int sbase = 0;
         if (samp) {
-            if (lane == 0) sbase = atomicAdd(&w.cnt->n_sampler, __popc(samp));
+            if (lane == 0) sbase = atomicAdd(&w.cnt->smp.n_list, __popc(samp));
             sbase = __shfl(sbase, 0, 64);
         }
         if (retire) {
@@ -327,7 +392,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
     const int slot = j / kSamplerBlock, s_in = j % kSamplerBlock;   // this lane's ray slot and its sample within the slot's block
     const int slot_lane0 = slot * kSamplerBlock;
     const unsigned slot_bits = (kSamplerBlock == 32 ? 0xffffffffu : ((1u << kSamplerBlock) - 1u)) << slot_lane0;
-    const int n_list = w.cnt->n_sampler;
+    SamplerQ* const q = w.ovf_pass ? &w.cnt->ovf : &w.cnt->smp;
+    const int n_list = q->n_list;
     const bool dyn = w.cont_cap > 0;
     const long long n_tickets = (long long)n_list + (dyn ? (long long)w.cont_cap : 0ll);
     long long evals = 0;
@@ -350,8 +416,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         }
         if (pub_slots | need_slots) {
             int v = 0;
-            if (lane == 0 && need_slots) v = atomicAdd(&w.cnt->sampler_head, __popc(need_slots));
-            if (lane == 1 && pub_slots) v = atomicAdd(&w.cnt->n_cont, __popc(pub_slots));
+            if (lane == 0 && need_slots) v = atomicAdd(&q->head, __popc(need_slots));
+            if (lane == 1 && pub_slots) v = atomicAdd(&q->n_cont, __popc(pub_slots));
             const int tbase = __shfl(v, 0, 64), pbase = __shfl(v, 1, 64);
             if (publish) {
                 const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
@@ -400,7 +466,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         }
         if (!be.any(__ballot(has_ray) != 0ull)) {
             // no ray in the workgroup: done when no slot holds a ticket that can still be served
-            const bool all_ended = __hip_atomic_load(&w.cnt->n_sampler_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
+            const bool all_ended = __hip_atomic_load(&q->n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
             const bool waiting = __ballot(ticket >= 0 || publish) != 0ull && !all_ended;
             if (!be.any(waiting)) break;
             if (++idle_polls > (1u << 22)) {   // the bound: a few seconds; never reached unless the protocol is broken -- reported in the stats
@@ -458,7 +524,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
                 a.sdf[ray] = 0.f;
                 a.dist[ray] = 0.f;
             }
-            atomicAdd(&w.cnt->n_sampler_done, 1);
+            atomicAdd(&q->n_done, 1);
         }
         prev_z = z_last;
         prev_f = f_last;
@@ -470,6 +536,366 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
     }
     be.finish();
     if (lane == 0) atomicAdd((unsigned long long*)&w.cnt->n_evals, (unsigned long long)evals);
+}
+
+// ---- the screened sampler -------------------------------------------------------------------------------------------------------
+// The sampler consumes only signs: sign(f) < 0 for the first negative sample, f_low > 0 / f_high < 0 for the bracket (the bisection
+// re-evaluates its points exactly).  k_sampler_screen marches the same blocks, work items and continuations as k_sampler, but on the
+// screen (sdf_hidden_stack_h1: one product per MAC, ~0.62 of an h2 evaluation).  A sample is certainly positive if f1 > delta,
+// certainly negative if f1 < -delta, uncertain otherwise (NaN and zeros included).  A ray whose samples before its first certainly-
+// negative one are all certainly positive (or that ends with all of them certainly positive) is decided here, exactly as k_sampler
+// decides it.  Otherwise its uncertain samples before that point go to the resolve list and the ray ends "pending" at its first
+// certainly-negative sample (or its end); k_screen_resolve evaluates the listed samples on the h2 core, 32 per wave from any rays,
+// and k_screen_fin_* give each pending ray the bracket, root-list entry or zeros k_sampler would have written.  A ray whose samples
+// do not fit the list is marched again from its start by k_sampler on a second list.  n_evals still counts what k_sampler evaluates.
+template <class BE>
+__global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_KERNEL_ARGS) {
+    BE be;
+    be.init(net, hs, hm);
+    const int lane = be.lane;
+    const int j = lane & 31;
+    const int slot = j / kSamplerBlock, s_in = j % kSamplerBlock;
+    const int slot_lane0 = slot * kSamplerBlock;
+    const unsigned slot_bits = (kSamplerBlock == 32 ? 0xffffffffu : ((1u << kSamplerBlock) - 1u)) << slot_lane0;
+    SamplerQ* const q = &w.cnt->smp;
+    const int n_list = q->n_list;
+    const bool dyn = w.cont_cap > 0;
+    const long long n_tickets = (long long)n_list + (dyn ? (long long)w.cont_cap : 0ll);
+    const float delta = screen_delta(w.scr);
+    unsigned ev_ref = 0, ev_scr = 0;   // per lane: k_sampler's evaluations of the rays decided here | per wave: screened evaluations
+    bool has_ray = false, retired = false, publish = false, pend = false;
+    int ticket = -1;
+    int ray = 0, blk = 0;
+    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, smin = 0.f, width = 0.f, prev_z = 0.f, prev_f = 0.f;
+    unsigned idle_polls = 0;
+    for (;;) {
+        unsigned pub_slots = 0, need_slots = 0;
+        {
+            const unsigned pub = (unsigned)__ballot(publish), need = (unsigned)__ballot(!has_ray && ticket < 0 && !retired);
+#pragma unroll
+            for (int qq = 0; qq < kSamplerSlots; ++qq) {
+                pub_slots |= ((pub >> (qq * kSamplerBlock)) & 1u) << qq;
+                need_slots |= ((need >> (qq * kSamplerBlock)) & 1u) << qq;
+            }
+        }
+        if (pub_slots | need_slots) {
+            int v = 0;
+            if (lane == 0 && need_slots) v = atomicAdd(&q->head, __popc(need_slots));
+            if (lane == 1 && pub_slots) v = atomicAdd(&q->n_cont, __popc(pub_slots));
+            const int tbase = __shfl(v, 0, 64), pbase = __shfl(v, 1, 64);
+            if (publish) {
+                const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
+                if (lane == slot_lane0 && c < w.cont_cap) {
+                    // a pending ray's state travels in ray_state, published with the item (release here, acquire where it is taken)
+                    if (pend) w.scr.ray_state[ray] = kRayPending;
+                    const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)blk << kContRayBits) |
+                                                    ((unsigned long long)__float_as_uint(prev_f) << 32);
+                    __hip_atomic_store(&w.cont[c], item, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                publish = false;
+            }
+            if (!has_ray && ticket < 0 && !retired) {
+                const long long t = (long long)tbase + __popc(need_slots & ((1u << slot) - 1u));
+                if (t >= n_tickets || tbase < 0) retired = true;
+                else ticket = (int)t;
+            }
+        }
+        if (!has_ray && ticket >= 0) {
+            bool got = false;
+            if (ticket < n_list) {
+                ray = w.sampler_list[ticket];
+                blk = 0;
+                prev_f = 0.f;
+                pend = false;
+                got = true;
+            } else {
+                const unsigned long long item = __hip_atomic_load(&w.cont[ticket - n_list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (item != 0ull) {
+                    // acquire only once the item is there (an acquiring poll invalidates the cache on every pass: +0.5 ms per frame)
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    ray = (int)(item & ((1u << kContRayBits) - 1u)) - 1;
+                    blk = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u));
+                    pend = (w.scr.ray_state[ray] & kRayPending) != 0;
+                    prev_f = __uint_as_float((unsigned)(item >> 32));
+                    got = true;
+                }
+            }
+            if (got) {
+                ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
+                dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
+                const float t = a.dist[ray], s0 = a.sdf[ray];
+                const bool pos = s0 > 0.0f;
+                smin = pos ? t : a.near[ray];
+                const float smax = pos ? a.far[ray] : t;
+                width = smax - smin;
+                prev_z = blk > 0 ? sample_depth(smin, a.lin[blk * kSamplerBlock - 1], width) : 0.f;
+                has_ray = true;
+                ticket = -1;
+            }
+        }
+        if (!be.any(__ballot(has_ray) != 0ull)) {
+            const bool all_ended = __hip_atomic_load(&q->n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
+            const bool waiting = __ballot(ticket >= 0 || publish) != 0ull && !all_ended;
+            if (!be.any(waiting)) break;
+            if (++idle_polls > (1u << 22)) {
+                if (threadIdx.x == 0) atomicAdd((unsigned long long*)&w.cnt->sampler_abort, 1ull);
+                break;
+            }
+            __builtin_amdgcn_s_sleep(16);
+            continue;
+        }
+        const int idx = blk * kSamplerBlock + s_in;
+        const bool in_range = has_ray && idx < a.n_steps;
+        const float z = sample_depth(smin, a.lin[in_range ? idx : a.n_steps - 1], width);
+        const float qx = has_ray ? ox + dx * z : 0.f, qy = has_ray ? oy + dy * z : 0.f, qz = has_ray ? oz + dz * z : 0.f;
+        {
+            const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0);
+            be.park(0, flags); be.park(1, ray); be.park(2, blk); be.park(3, ticket);
+            be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
+            be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
+            be.park(15, (int)ev_ref); be.park(16, (int)ev_scr);
+        }
+        const float f = be.eval_screen(qx, qy, qz);
+        const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0));
+        has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4; pend = flags_back & 16;
+        const bool in_range_b = flags_back & 8;
+        ray = be.unpark(1, ray); blk = be.unpark(2, blk); ticket = be.unpark(3, ticket);
+        ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
+        smin = be.unpark(10, smin); width = be.unpark(11, width); prev_z = be.unpark(12, prev_z); prev_f = be.unpark(13, prev_f);
+        const float zb = be.unpark(14, z);
+        ev_ref = (unsigned)be.unpark(15, (int)ev_ref); ev_scr = (unsigned)be.unpark(16, (int)ev_scr);
+        idle_polls = 0;
+        ev_scr += __popc((unsigned)__ballot(in_range_b));
+        const bool is_neg = in_range_b && f < -delta;                       // certainly negative
+        const bool is_unc = in_range_b && !(f > delta) && !(f < -delta);    // uncertain (NaN included)
+        const unsigned neg = (unsigned)__ballot(is_neg) & slot_bits;
+        const unsigned unc_all = (unsigned)__ballot(is_unc);
+        const int first = neg ? (__ffs(neg) - 1) : slot_lane0;
+        const float z_first = __shfl(zb, first, 64), f_first = __shfl(f, first, 64);
+        const float z_before = __shfl(zb, first > slot_lane0 ? first - 1 : slot_lane0, 64);
+        const float f_before = __shfl(f, first > slot_lane0 ? first - 1 : slot_lane0, 64);
+        const float z_last = __shfl(zb, slot_lane0 + kSamplerBlock - 1, 64), f_last = __shfl(f, slot_lane0 + kSamplerBlock - 1, 64);
+        const float f_up = __shfl(f, lane > 0 ? lane - 1 : 0, 64);
+        const int gidx = blk * kSamplerBlock + (first - slot_lane0);
+        const bool found_neg = has_ray && neg != 0u;
+        const bool done = has_ray && (found_neg || (blk + 1) * kSamplerBlock >= a.n_steps);
+        const float z_lo = first > slot_lane0 ? z_before : prev_z, f_lo = first > slot_lane0 ? f_before : prev_f;
+        // uncertain samples in front of the slot's first certainly-negative one: to the resolve list, one atomicAdd per wave
+        const unsigned before = neg ? (((1u << first) - 1u) & slot_bits) : slot_bits;
+        const unsigned unc = has_ray ? (unc_all & before) : 0u;
+        const unsigned unc_wave = (unsigned)__ballot(j == lane && ((unc >> j) & 1u));   // lanes 0..31 carry one sample each
+        int rbase = 0;
+        if (unc_wave) {
+            if (lane == 0) rbase = atomicAdd(&w.cnt->n_res, __popc(unc_wave));
+            rbase = __shfl(rbase, 0, 64);
+        }
+        bool overflow = false;
+        if (unc) {
+            const int pos_last = rbase + lane_rank(unc_wave, 31 - __clz(unc));
+            overflow = pos_last >= w.scr.cap;
+            const int pos = rbase + lane_rank(unc_wave, j);
+            if (lane < 32 && ((unc >> j) & 1u) && pos < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
+                ResolveEntry e;
+                e.ray = ray; e.s = idx; e.z = zb; e.f1 = f; e.f_prev1 = s_in > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
+                w.scr.ent[pos] = e;
+            }
+        }
+        const bool pend_now = pend || unc != 0u;
+        const bool to_ovf = has_ray && overflow;
+        if (to_ovf) {   // the ray goes to k_sampler's second list, marched from its start
+            if (lane == slot_lane0) {
+                w.scr.ray_state[ray] = kRayOverflowed;
+                const int p = atomicAdd(&w.cnt->ovf.n_list, 1);
+                w.scr.ovf_list[p] = ray;
+                atomicAdd((unsigned long long*)&w.cnt->n_ovf, 1ull);
+                atomicAdd(&q->n_done, 1);
+            }
+        } else if (done && lane == slot_lane0) {
+            if (pend_now) {          // decided by k_screen_fin_* once the listed samples have their exact values
+                PendRec r;
+                r.first = found_neg ? gidx : a.n_steps;
+                r.fhi = f_first; r.flo = f_lo; r.flo_ex = 0.f; r.has_flo_ex = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+                w.scr.rec[ray] = r;
+                const int p = atomicAdd(&w.cnt->n_pend, 1);
+                w.scr.pend_list[p] = ray;
+            } else {                 // exactly what k_sampler writes: every sample before gidx is positive, gidx is negative
+                const int nb = (blk + 1) * kSamplerBlock;
+                ev_ref += (unsigned)(nb < a.n_steps ? nb : a.n_steps);
+                if (found_neg && gidx >= 1) {
+                    const int pos_l = atomicAdd(&w.cnt->n_root, 1);
+                    w.root_list[pos_l] = ray;
+                    w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_first;
+                    w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_first;
+                } else {
+                    a.conv[ray] = 0;
+                    a.points[3 * (size_t)ray] = 0.f; a.points[3 * (size_t)ray + 1] = 0.f; a.points[3 * (size_t)ray + 2] = 0.f;
+                    a.sdf[ray] = 0.f;
+                    a.dist[ray] = 0.f;
+                }
+            }
+            atomicAdd(&q->n_done, 1);
+        }
+        pend = pend_now && !to_ovf;
+        prev_z = z_last;
+        prev_f = f_last;
+        ++blk;
+        const bool hand_over = has_ray && !to_ovf && !done && dyn && (blk % (kSamplerSeg > 0 ? kSamplerSeg : 1)) == 0;
+        publish = hand_over;
+        if (done || hand_over || to_ovf) has_ray = false;
+        if (ev_ref > (1u << 30) || ev_scr > (1u << 30)) {   // flush the 32-bit per-lane counts long before they can wrap
+            unsigned long long r = ev_ref;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off, 64);
+            if (lane == 0) {
+                atomicAdd((unsigned long long*)&w.cnt->n_evals, r);   // (only the slots' first lanes count)
+                atomicAdd((unsigned long long*)&w.cnt->n_screen, (unsigned long long)ev_scr);
+            }
+            ev_ref = 0; ev_scr = 0;
+        }
+    }
+    be.finish();
+    unsigned long long r = ev_ref;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off, 64);
+    if (lane == 0) {
+        atomicAdd((unsigned long long*)&w.cnt->n_evals, r);
+        atomicAdd((unsigned long long*)&w.cnt->n_screen, (unsigned long long)ev_scr);
+    }
+}
+
+// exact (h2) values of the listed samples, 32 per wave from any rays; the first negative one of each ray lowers its `first`
+template <class BE>
+__global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_KERNEL_ARGS) {
+    BE be;
+    be.init(net, hs, hm);
+    const int lane = be.lane;
+    const int j = lane & 31;
+    const int n_res = w.cnt->n_res;
+    const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
+    const float delta = screen_delta(w.scr);
+    long long resolved = 0;
+    float ratio = 0.0f;
+    for (;;) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&w.cnt->res_head, 32);
+        base = __shfl(base, 0, 64);
+        const int li = base + j;
+        const bool valid = li < n_ent;
+        if (!be.any(base < n_ent)) break;
+        float qx = 0.f, qy = 0.f, qz = 0.f;
+        if (valid) {
+            const ResolveEntry& e = w.scr.ent[li];
+            const int ray = e.ray;
+            qx = a.ray_o[3 * (size_t)ray] + a.ray_d[3 * (size_t)ray] * e.z;
+            qy = a.ray_o[3 * (size_t)ray + 1] + a.ray_d[3 * (size_t)ray + 1] * e.z;
+            qz = a.ray_o[3 * (size_t)ray + 2] + a.ray_d[3 * (size_t)ray + 2] * e.z;
+        }
+        be.park(0, valid ? 1 : 0); be.park(1, li); be.park(2, ratio); be.park(3, (int)(unsigned)resolved); be.park(4, (int)(resolved >> 32));
+        const float f = be.eval(qx, qy, qz);
+        const bool v = be.unpark(0, 0) != 0;
+        const int lib = be.unpark(1, 0);
+        ratio = be.unpark(2, 0.0f);
+        resolved = (long long)(((unsigned long long)(unsigned)be.unpark(4, 0) << 32) | (unsigned)be.unpark(3, 0));
+        resolved += __popc((unsigned)__ballot(v));
+        if (v && lane < 32) {
+            ResolveEntry* e = &w.scr.ent[lib];
+            e->f_ex = f;
+            if (f < 0.0f) atomicMin(&w.scr.rec[e->ray].first, e->s);
+            const float f1 = e->f1;
+            float r = fabsf(f1 - f) / delta;
+            if (!(r <= 3.0e38f)) r = ((fabsf(f1) <= 3.0e38f) != (fabsf(f) <= 3.0e38f)) ? 3.0e38f : 0.0f;   // one side non-finite: the screen failed
+            ratio = fmaxf(ratio, r);
+        }
+    }
+    be.finish();
+    float r = ratio;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
+    if (lane == 0) {
+        atomicAdd((unsigned long long*)&w.cnt->n_resolved, (unsigned long long)resolved);
+        atomicMax(&w.cnt->ratio_bits, __float_as_uint(r));
+        if (r > kScreenGuard && w.scr.flag) {   // the guard: the network's next call runs the unscreened sampler
+            *reinterpret_cast<volatile int*>(w.scr.flag) = 1;
+            __threadfence_system();
+        }
+    }
+}
+
+// the exact values at each pending ray's bracket: its first negative sample and the one before it, where those were listed
+__global__ void k_screen_fin_entries(TraceWs w) {
+    const int n_res = w.cnt->n_res;
+    const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_ent; i += gridDim.x * blockDim.x) {
+        const ResolveEntry e = w.scr.ent[i];
+        if (w.scr.ray_state[e.ray] == kRayOverflowed) continue;
+        PendRec* r = &w.scr.rec[e.ray];
+        const int g = r->first;
+        if (e.s == g) { r->fhi = e.f_ex; r->flo = e.f_prev1; }   // (overwritten below when sample g - 1 was listed too)
+        if (e.s == g - 1) { r->flo_ex = e.f_ex; r->has_flo_ex = 1; }
+    }
+}
+
+// each pending ray's outcome, as k_sampler writes it
+__global__ void k_screen_fin_rays(TraceArgs a, TraceWs w) {
+    const int n_pend = w.cnt->n_pend;
+    unsigned long long ev = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pend; i += gridDim.x * blockDim.x) {
+        const int ray = w.scr.pend_list[i];
+        const PendRec r = w.scr.rec[ray];
+        const int g = r.first;
+        const int nb = (g / kSamplerBlock + 1) * kSamplerBlock;
+        ev += (unsigned long long)(g < a.n_steps ? (nb < a.n_steps ? nb : a.n_steps) : a.n_steps);
+        if (g >= 1 && g < a.n_steps) {
+            const float t = a.dist[ray], s0 = a.sdf[ray];
+            const bool pos = s0 > 0.0f;
+            const float smin = pos ? t : a.near[ray];
+            const float smax = pos ? a.far[ray] : t;
+            const float width = smax - smin;
+            const int pos_l = atomicAdd(&w.cnt->n_root, 1);
+            w.root_list[pos_l] = ray;
+            w.root_lo[pos_l] = sample_depth(smin, a.lin[g - 1], width);
+            w.root_hi[pos_l] = sample_depth(smin, a.lin[g], width);
+            w.root_flo[pos_l] = r.has_flo_ex ? r.flo_ex : r.flo;
+            w.root_fhi[pos_l] = r.fhi;
+        } else {
+            a.conv[ray] = 0;
+            a.points[3 * (size_t)ray] = 0.f; a.points[3 * (size_t)ray + 1] = 0.f; a.points[3 * (size_t)ray + 2] = 0.f;
+            a.sdf[ray] = 0.f;
+            a.dist[ray] = 0.f;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ev += __shfl_xor(ev, off, 64);
+    if ((threadIdx.x & 63) == 0 && ev) atomicAdd((unsigned long long*)&w.cnt->n_evals, ev);
+}
+
+// calibration of the margin: max |f_screen - f_h2| over a fixed set of points in the unit ball (a golden-angle spiral of
+// directions, radii from the R2 sequence), once per network handle before its first screened trace
+__global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2StreamDev hs, H2Meta hm, unsigned* calib) {
+    BackendH2 be;
+    be.init(net, hs, hm);
+    const int lane = be.lane;
+    float m = 0.0f;
+    for (int g = blockIdx.x; g < kScreenCalibPoints / 128; g += gridDim.x) {
+        const int i = g * 128 + be.wave * 32 + (lane & 31);
+        const float u = (i + 0.5f) / kScreenCalibPoints;
+        const float cz = 1.0f - 2.0f * u, sz = sqrtf(fmaxf(0.0f, 1.0f - cz * cz));
+        const float phi = 2.39996323f * (float)i;
+        float fr = 0.7548776662f * (float)i;
+        fr -= floorf(fr);
+        const float rad = cbrtf(0.5f / kScreenCalibPoints + fr * (1.0f - 1.0f / kScreenCalibPoints));
+        const float x = rad * sz * cosf(phi), y = rad * sz * sinf(phi), z = rad * cz;
+        const float f1 = be.eval_screen(x, y, z);
+        be.park(0, f1); be.park(1, m);
+        const float f2 = be.eval(x, y, z);
+        const float d = fabsf(be.unpark(0, 0.0f) - f2);
+        m = be.unpark(1, 0.0f);
+        if (d <= 3.0e38f) m = fmaxf(m, d);
+    }
+    be.finish();
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    if (lane == 0) atomicMax(calib, __float_as_uint(m));
 }
 
 __device__ __forceinline__ long long ray_chunk(const TraceArgs& a, int ray) {
@@ -644,7 +1070,7 @@ __global__ void k_trace_stats(TraceWs w, int n_parts, int n_steps, iron_trace_st
         long long n_evals = 0, n_sphere_conv = 0, n_sampler = 0, n_root = 0, n_evals_sphere = 0, n_abort = 0;
         for (int p = 0; p < n_parts; ++p) {
             const TraceCounters* c = (const TraceCounters*)((const char*)w.cnt + (size_t)p * kCntStride);
-            n_evals += c->n_evals; n_sphere_conv += c->n_sphere_conv; n_sampler += c->n_sampler; n_root += c->n_root;
+            n_evals += c->n_evals; n_sphere_conv += c->n_sphere_conv; n_sampler += c->smp.n_list; n_root += c->n_root;
             n_evals_sphere += c->n_evals_sphere;
             n_abort += c->sampler_abort;
         }
@@ -675,7 +1101,7 @@ __global__ void k_stage_sampler_init(TraceArgs a, TraceWs w, const float* __rest
         a.dist[i] = min_dis[i];
         a.sdf[i] = 1.0f;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) w.cnt->n_sampler = a.n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) w.cnt->smp.n_list = a.n;
 }
 
 // rootfind (raytracer.py:199-220) on caller-given brackets
@@ -693,6 +1119,7 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct WsLayout {
     size_t cnt, sampler_list, root_list, lo, hi, flo, fhi, k, chunk_iters, chunk_roots, cont, total;
+    size_t s_rec, s_pend, s_ovf, s_flag, s_ent;   // the screened sampler's arrays
     int64_t n_chunks, cont_cap;
 };
 
@@ -715,11 +1142,17 @@ static WsLayout ws_layout(int64_t n, const iron_trace_params* p) {
     L.k = o; o += align256(sizeof(int) * nn);
     L.cont_cap = sampler_cont_cap(n, p ? p->n_steps : 128);   // k_sampler's continuation items
     L.cont = o; o += align256(sizeof(unsigned long long) * (size_t)(L.cont_cap > 0 ? L.cont_cap : 1));
+    L.s_rec = o; o += align256(sizeof(PendRec) * nn);
+    L.s_pend = o; o += align256(sizeof(int) * nn);
+    L.s_ovf = o; o += align256(sizeof(int) * nn);
+    L.s_flag = o; o += align256(nn);
+    L.s_ent = o; o += align256(sizeof(ResolveEntry) * nn * kResolvePerRay);
     L.total = o;
     return L;
 }
 
-// which: 0 sphere, 1 sampler, 2 bisect_a, 3 bisect_b; `units` = wave-sized work items available
+// which: 0 sphere, 1 sampler, 2 bisect_a, 3 bisect_b; h2 only: 4 screened sampler, 5 resolve, 6 calibration; `units` = wave-sized work
+// items available
 static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t units,
                                 hipStream_t st);
 
@@ -740,6 +1173,9 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
             (void)hipFuncSetAttribute((const void*)k_sampler<BackendH2Sampler>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
             (void)hipFuncSetAttribute((const void*)k_bisect_a<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
             (void)hipFuncSetAttribute((const void*)k_bisect_b<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
+            (void)hipFuncSetAttribute((const void*)k_sampler_screen<BackendH2Sampler>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
+            (void)hipFuncSetAttribute((const void*)k_screen_resolve<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
+            (void)hipFuncSetAttribute((const void*)k_screen_calib, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
             attr = true;
         }
         const int64_t wgs = (units + 3) / 4;
@@ -749,6 +1185,10 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
             case 0: hipLaunchKernelGGL(k_sphere<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             case 1: hipLaunchKernelGGL(k_sampler<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             case 2: hipLaunchKernelGGL(k_bisect_a<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case 4: hipLaunchKernelGGL(k_sampler_screen<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case 5: hipLaunchKernelGGL(k_screen_resolve<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case 6: hipLaunchKernelGGL(k_screen_calib, dim3(cus < kScreenCalibPoints / 128 ? cus : kScreenCalibPoints / 128), block,
+                                       kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, sdf->screen_calib); break;
             default: hipLaunchKernelGGL(k_bisect_b<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
         }
     } else {
@@ -763,9 +1203,102 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
     }
 }
 
+// ---- the screened sampler's host side ----------------------------------------------------------------------------------------
+std::atomic<int> g_screen_switch{-1};           // iron_set_sampler_screen; -1 = the environment's (IRON_SAMPLER_SCREEN=0: off) / default on
+std::atomic<float> g_screen_delta_override{0.0f};   // test hooks (iron_sampler_screen_debug)
+std::atomic<int> g_screen_cap_override{0};
+
+static bool screen_switch() {
+    static int from_env = -1;
+    if (from_env < 0) {
+        const char* e = getenv("IRON_SAMPLER_SCREEN");
+        from_env = (e && e[0] == '0') ? 0 : 1;
+    }
+    const int v = g_screen_switch.load(std::memory_order_relaxed);
+    return v < 0 ? from_env != 0 : v != 0;
+}
+
+// at the start of a call: act on a guard flag an earlier call raised, then decide whether this call screens (h2 core only)
+static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use) {
+    iron_net* net = const_cast<iron_net*>(cnet);
+    *use = false;
+    if (net->flag_host && *(volatile int*)(net->flag_host + 1)) net->screen_off = 1;
+    if (!h2 || !screen_switch() || net->screen_off) return IRON_OK;
+    if (!net->screen_calib) IRON_HIP_TRY(hipMalloc((void**)&net->screen_calib, 256));
+    if (!net->screen_calibrated) {   // once per handle (a re-pack is a new handle): stream-ordered, no synchronisation
+        IRON_HIP_TRY(hipMemsetAsync(net->screen_calib, 0, 256, st));
+        TraceArgs a{};
+        TraceWs w{};
+        launch_trace_kernel(6, true, net, a, w, kScreenCalibPoints / 32, st);
+        net->screen_calibrated = 1;
+    }
+    *use = true;
+    return IRON_OK;
+}
+
+static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk) {
+    w.scr.calib = net->screen_calib;
+    w.scr.flag = net->flag_dev ? net->flag_dev + 1 : nullptr;
+    w.scr.delta_override = g_screen_delta_override.load(std::memory_order_relaxed);
+    w.scr.rec = (PendRec*)(base + L.s_rec);
+    w.scr.ray_state = (uint8_t*)(base + L.s_flag);
+    w.scr.pend_list = (int*)(base + L.s_pend) + b0;
+    w.scr.ovf_list = (int*)(base + L.s_ovf) + b0;
+    w.scr.ent = (ResolveEntry*)(base + L.s_ent) + b0 * kResolvePerRay;
+    int64_t cap = nk * kResolvePerRay;
+    const int ov = g_screen_cap_override.load(std::memory_order_relaxed);
+    if (ov > 0 && ov < cap) cap = ov;
+    w.scr.cap = (int)cap;
+}
+
+// the dense sampler of one part: k_sampler, or (screen) k_sampler_screen + resolve + finalize + k_sampler on the overflow list
+static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t nk, hipStream_t st) {
+    const int64_t units = (nk + kSamplerSlots - 1) / kSamplerSlots;
+    if (!screen) { launch_trace_kernel(1, h2, sdf, a, w, units, st); return; }
+    launch_trace_kernel(4, true, sdf, a, w, units, st);
+    launch_trace_kernel(5, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
+    const int64_t ge = ((int64_t)w.scr.cap + 255) / 256, gr = (nk + 255) / 256;
+    hipLaunchKernelGGL(k_screen_fin_entries, dim3((unsigned)(ge < 1024 ? (ge > 0 ? ge : 1) : 1024)), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(k_screen_fin_rays, dim3((unsigned)(gr < 1024 ? (gr > 0 ? gr : 1) : 1024)), dim3(256), 0, st, a, w);
+    TraceWs w2 = w;   // rays that overflowed the resolve list: k_sampler from their first sample (one slot per ray to the end)
+    w2.ovf_pass = 1;
+    w2.sampler_list = w.scr.ovf_list;
+    w2.cont_cap = 0;
+    launch_trace_kernel(1, true, sdf, a, w2, units, st);
+}
+
 }  // namespace iron
 
 using namespace iron;
+
+extern "C" int32_t iron_set_sampler_screen(int32_t on) {
+    const int prev = screen_switch() ? 1 : 0;
+    g_screen_switch.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return prev;
+}
+
+extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
+    if (what == 0) { g_screen_delta_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
+    if (what == 1) { g_screen_cap_override.store(value >= 1.0 ? (int)value : 0, std::memory_order_relaxed); return IRON_OK; }
+    return IRON_ERR_BAD_ARG;
+}
+
+extern "C" int iron_trace_screen_counts(const void* workspace, double* out, void* stream) {
+    if (!workspace || !out) return IRON_ERR_BAD_ARG;
+    TraceCounters c[kMaxTraceSplits];
+    for (int k = 0; k < kMaxTraceSplits; ++k)
+        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
+                                    (hipStream_t)stream));
+    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    double scr = 0, res = 0, ovf = 0, ratio = 0, pend = 0;
+    for (int k = 0; k < kMaxTraceSplits; ++k) {
+        scr += (double)c[k].n_screen; res += (double)c[k].n_resolved; ovf += (double)c[k].n_ovf; pend += (double)c[k].n_pend;
+        const float r = __builtin_bit_cast(float, c[k].ratio_bits);
+        if (r > ratio) ratio = r;
+    }
+    out[0] = scr; out[1] = res; out[2] = ovf; out[3] = ratio; out[4] = pend;
+    return IRON_OK;
+}
 
 extern "C" size_t iron_trace_workspace_bytes(int64_t n, const iron_trace_params* p) {
     if (n < 0) return 0;
@@ -844,7 +1377,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
     if (chunk_iters && (n_chunks < 1 || n_chunks > 65536)) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)workspace;
-    TraceWs w0;
+    TraceWs w0{};
     w0.cnt = (TraceCounters*)(base + L.cnt);
     w0.sampler_list = (int*)(base + L.sampler_list);
     w0.root_list = (int*)(base + L.root_list);
@@ -870,6 +1403,8 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
     a0.chunk = p->chunk > 0 ? p->chunk : 0;
     if (phase == 0) { const int rce = envelope_begin(sdf); if (rce != IRON_OK) return rce; }
     const bool h2 = h2_sdf_usable(sdf);
+    bool screen = false;
+    if (phase == 0) { const int rcs = screen_begin(sdf, h2, st, &screen); if (rcs != IRON_OK) return rcs; }
 
     // the parts: rays [b_k, b_{k+1}), own counters, own stretch [b_k, ..) of every list (a part lists at most its own rays);
     // both phases of a call see the same n, hence the same split
@@ -894,6 +1429,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
         else IRON_HIP_TRY(hipMemsetAsync(base + L.chunk_iters, 0, align256(sizeof(int) * (size_t)L.n_chunks), st));
         IRON_HIP_TRY(hipMemsetAsync(w0.chunk_roots, 0, sizeof(int) * (size_t)w0.n_chunks, st));
         if (L.cont_cap > 0) IRON_HIP_TRY(hipMemsetAsync(base + L.cont, 0, sizeof(unsigned long long) * (size_t)L.cont_cap, st));
+        if (screen) IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st));
     }
     if (parts > 1) IRON_HIP_TRY(hipEventRecord(S->fork, st));
     // side parts first: their launches are queued before the caller-stream part occupies the chip
@@ -908,6 +1444,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
         w.sampler_list += b0; w.root_list += b0; w.root_lo += b0; w.root_hi += b0; w.root_flo += b0; w.root_fhi += b0; w.root_k += b0;
         a.ray0 = (int)b0; a.n = (int)nk;
         if (L.cont_cap > 0) { const int64_t per_ray = L.cont_cap / n; w.cont += b0 * per_ray; w.cont_cap = (int)(nk * per_ray); }
+        if (screen) screen_ws(w, sdf, base, L, b0, nk);
         const int64_t tiles = (nk + 31) / 32;
         if (phase == 0) {
             {
@@ -916,7 +1453,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
             }
             {
                 ProfScope ps(IRON_PROF_SAMPLER, sk);
-                launch_trace_kernel(1, h2, sdf, a, w, (nk + kSamplerSlots - 1) / kSamplerSlots, sk);
+                run_sampler(h2, screen, sdf, a, w, nk, sk);
             }
             {
                 ProfScope ps(IRON_PROF_BISECT_A, sk);
@@ -955,7 +1492,7 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     { const int rce = envelope_begin(sdf); if (rce != IRON_OK) return rce; }
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)workspace;
-    TraceWs w;
+    TraceWs w{};
     w.cnt = (TraceCounters*)(base + L.cnt);
     w.sampler_list = (int*)(base + L.sampler_list);
     w.root_list = (int*)(base + L.root_list);
@@ -973,6 +1510,12 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     a.ray0 = 0; a.n = (int)n; a.n_steps = p->n_steps; a.iters = p->sphere_tracing_iters; a.thr = p->sdf_threshold; a.chunk = 0;
     a.near = in0; a.far = in1;
     const bool h2 = h2_sdf_usable(sdf);
+    bool screen = false;
+    if (stage == 1) {
+        const int rcs = screen_begin(sdf, h2, st, &screen);
+        if (rcs != IRON_OK) return rcs;
+        if (screen) { IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st)); screen_ws(w, sdf, base, L, 0, n); }
+    }
     IRON_HIP_TRY(hipMemsetAsync(base + L.cnt, 0, kCntStride * kMaxTraceSplits, st));
     IRON_HIP_TRY(hipMemsetAsync(base + L.chunk_iters, 0, align256(sizeof(int)), st));
     IRON_HIP_TRY(hipMemsetAsync(base + L.chunk_roots, 0, align256(sizeof(int)), st));
@@ -982,10 +1525,10 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     if (stage == 0) {            // sphere_tracing (raytracer.py:105-140): in0 = min_dis, in1 = max_dis
         IRON_HIP_TRY(hipMemsetAsync(unfinished_out, 0, (size_t)n, st));
         launch_trace_kernel(0, h2, sdf, a, w, tiles, st);
-        hipLaunchKernelGGL(k_stage_mark_list, dim3(gb), dim3(256), 0, st, w.sampler_list, &w.cnt->n_sampler, unfinished_out);
+        hipLaunchKernelGGL(k_stage_mark_list, dim3(gb), dim3(256), 0, st, w.sampler_list, &w.cnt->smp.n_list, unfinished_out);
     } else if (stage == 1) {     // ray_sampler (:142-197): in0 = min_dis, in1 = max_dis, every ray sampled on its own interval
         hipLaunchKernelGGL(k_stage_sampler_init, dim3(gb), dim3(256), 0, st, a, w, in0);
-        launch_trace_kernel(1, h2, sdf, a, w, (n + kSamplerSlots - 1) / kSamplerSlots, st);
+        run_sampler(h2, screen, sdf, a, w, n, st);
         launch_trace_kernel(2, h2, sdf, a, w, tiles, st);
         launch_trace_kernel(3, h2, sdf, a, w, tiles, st);
     } else {                     // rootfind (:199-220): in0 = f_low, in1 = f_high, in2 = d_low, in3 = d_high
