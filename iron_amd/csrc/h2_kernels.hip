@@ -42,8 +42,8 @@ __global__ __launch_bounds__(256, 1) void k_sdf_values_h2(H2StreamDev s, H2Meta 
 #endif
 }
 
-// the sampler's screen (sdf_hidden_stack_h1: one product per MAC, fp16 operands) on the same layout: tools/bench_screen.py times it
-// against k_sdf_values_h2, tools/screen_margin.py / tests compare its values
+// the sampler's screen (sdf_hidden_stack_h1: one product per MAC, fp16 operands) on the h1 stream (s = the network's h1_trace):
+// tools/bench_screen.py times it against k_sdf_values_h2, tools/screen_margin.py / tests compare its values
 __global__ __launch_bounds__(256, 1) void k_sdf_values_h1(H2StreamDev s, H2Meta m, const float* __restrict__ x, int64_t n,
                                                          float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -103,7 +103,7 @@ using namespace iron;
 
 extern "C" int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, float* out, void* stream) {
     if (!net || net->desc.kind != IRON_NET_SDF || n < 0 || (n > 0 && (!x || !out))) return IRON_ERR_BAD_ARG;
-    if (!h2_sdf_usable(net)) return IRON_ERR_UNSUPPORTED;
+    if (!h2_sdf_usable(net) || !net->h1_trace.base) return IRON_ERR_UNSUPPORTED;
     if (n == 0) return IRON_OK;
     static bool attr = false;
     if (!attr) {
@@ -115,7 +115,7 @@ extern "C" int iron_sdf_screen_forward(const iron_net_t* net, const float* x, in
     const int64_t groups = (n + 127) / 128;
     const int64_t cus = cu_budget();
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
-    hipLaunchKernelGGL(k_sdf_values_h1, dim3(grid), dim3(256), kLdsH2Total, (hipStream_t)stream, net->h2_trace, m, x, n, out);
+    hipLaunchKernelGGL(k_sdf_values_h1, dim3(grid), dim3(256), kLdsH2Total, (hipStream_t)stream, net->h1_trace, m, x, n, out);
     IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
 }

@@ -124,6 +124,7 @@ struct iron_net {
     void* h2_blob;        // h2 (split-fp16) stream, SDF nets
     iron::H2StreamDev h2_trace;  // hidden stack only
     iron::H2StreamDev h2_full;   // + the feature rows of the last layer
+    iron::H2StreamDev h1_trace;  // the sampler's screen (mlp_h2.h: sdf_hidden_stack_h1): hi pieces of h2_trace's fragments, in h2_blob
     void* h2_rev_blob;    // stream of the reverse-mode get_all (getall_rev.hip): h2_full's slots + the transposed layers
     iron::H2StreamDev h2_rev;
     void* h2_scratch;     // material nets with a skip layer on the h2 core: partial sums parked between layer 0 and the skip layer

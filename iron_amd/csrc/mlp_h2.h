@@ -808,21 +808,30 @@ __device__ __forceinline__ void sdf_hidden_stack_h2(Ring& ring, const char* lds,
 }
 
 // ---- the screen: one product per MAC -------------------------------------------------------------------
-// sdf_hidden_stack_h1 walks the same ring (same stream, same slot sequence, same refills) as sdf_hidden_stack_h2 but takes every
-// layer as wh * xh only: ONE v_mfma_f32_32x32x16_f16 and one ds_read_b128 (the hi fragment; the lo fragment of the slot is never
-// read) per k-step, and the epilogue rounds the activation to a single fp16 piece.  Weights and activations are therefore fp16
-// (11-bit significands) with fp32 accumulation: the value is NOT fp32-accurate.  The dense sampler (trace.hip) uses it only to
-// decide signs far from zero, with an empirical margin it calibrates per network against this core's exact (h2) value.
+// sdf_hidden_stack_h1 takes every layer as wh * xh only: ONE v_mfma_f32_32x32x16_f16 and one ds_read_b128 per k-step, and the
+// epilogue rounds the activation to a single fp16 piece.  Weights and activations are therefore fp16 (11-bit significands) with fp32
+// accumulation: the value is NOT fp32-accurate.  The dense sampler (trace.hip) uses it only to decide signs far from zero, with an
+// empirical margin it calibrates per network against the h2 value.
+//
+// It walks a ring of its own on the h1 stream (pack_h2.hip, written by the same pack launches as the h2 stream): the hi pieces of the
+// h2 fragments without the lo pieces, in the same fragment order ([ks][lane][j], 1 KiB per k-step fragment).  Slot sequence (30 slots
+// of 32 KiB, 960 KiB per evaluation, against the 72 slots and 1.92 MB of the h2 stream, whose lo halves it used to refill unread):
+//   layer 0            ONE head slot: the head fragments of all 8 tiles, tile t at fragments 3t .. 3t + 2 (24 KiB + 8 KiB of zeros)
+//   a hidden layer     4 pair slots: tiles 2j, 2j + 1 at fragments 0..15 | 16..31
+//   the skip layer     a head slot of its 8 tiles' head fragments (as layer 0), then its 4 pair slots
+// Every slot is a "hidden" (32 KiB) slot for the ring, so the ordinary Ring / dma_issue walk it (h2_setup on the h1 stream).
+// No epilogue is exposed but the last hidden layer's tile 7 (it feeds the row dot): every tile's epilogue runs
+// in the MFMA gaps of the next tile, across slot and layer boundaries (a layer's tile 7 under the next layer's first tile, as
+// sdf_hidden_stack_h2 does).  Per tile the products and their order are unchanged: bias, [head,] the 16 hidden k-steps.
 struct Epi1State {
     float z[16], e[16];
     u32x4 oh[2];
 };
 
 // the epilogue of one tile as 104 instructions in dependency order (softplus_100 as in epi_gap, then 8 packed conversions), cut
-// into the 16 MFMA gaps of a step: 6-7 per gap.  An instruction's operands come from >= 8 instructions earlier.
+// into the MFMA gaps that carry it.  An instruction's operands come from >= 8 instructions earlier.
 constexpr int kEpi1Ops = 104;
 constexpr int kEpi1OpsF32 = 96;   // last layer: f32 tile, no conversion
-__device__ __forceinline__ constexpr int epi1_first(int g, int n) { return g * n / 16; }
 
 __device__ __forceinline__ void epi1_op(Epi1State& st, int op, const f32x16& p) {
     constexpr float kC1 = 144.26950408889634f;            // 100 * log2(e)
@@ -841,107 +850,136 @@ __device__ __forceinline__ void epi1_op(Epi1State& st, int op, const f32x16& p) 
     }
 }
 
-// f32 tile -> the two k-step B fragments of the next layer, hi pieces only
-__device__ __forceinline__ void hi_tile(const f32x16& v, half8 (&out)[2]) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        u32x4 hh;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) hh[i] = __builtin_bit_cast(unsigned, cvt_pk_rn(v[8 * s + 2 * i], v[8 * s + 2 * i + 1]));
-        out[s] = __builtin_bit_cast(half8, hh);
-    }
-}
-
 struct TileH {
     half8 h[2];
 };
 
-__device__ __forceinline__ void step_head_h1(const char* __restrict__ rd, const char* __restrict__ bias, char* __restrict__ wr,
-                                             const RingSrc& src, bool src_hidden, int wave, int lane, int tile, bool add_bias,
-                                             const HeadFrag& hd, f32x16& acc) {
-    dma_issue(src, wr, src_hidden, wave);
-    if (add_bias) acc = lds_half_tile(bias, tile, lane >> 5);
+__device__ __forceinline__ void tile_from_epi(const Epi1State& es, TileH& t) {
 #pragma unroll
-    for (int ks = 0; ks < kHeadKSteps; ++ks) acc = mfma_h(lds_frag(rd, 2 * ks, lane), hd.h[ks], acc);
+    for (int s = 0; s < 2; ++s) t.h[s] = __builtin_bit_cast(half8, es.oh[s]);
 }
 
-// One ring step on a hidden slot: acc += Wh[tile,:] * in_h (16 MFMAs), the epilogue of the pending tile `p` in their gaps.
-// EPI: 0 = nothing pending, 1 = pending tile -> hi fragments, 2 = pending tile -> f32 tile (last layer).
-template <int EPI>
-__device__ __forceinline__ void step_hidden_h1(const char* __restrict__ rd, const char* __restrict__ bias, char* __restrict__ wr,
-                                               const RingSrc& src, bool src_hidden, int wave, int lane, int tile, bool add_bias,
-                                               const TileH (&in)[kHidTiles], f32x16& acc, const f32x16& p, TileH& out_prev,
-                                               f32x16& hf_prev) {
-    if (add_bias) acc = lds_half_tile(bias, tile, lane >> 5);
-    half8 fr[2];
-    fr[0] = lds_frag(rd, 0, lane);
+// sync, take the next slot, read its first fragment, issue the refill
+__device__ __forceinline__ const char* h1_slot(Ring& ring, half8& fr0, int lane) {
+    ring.sync();
+    // (readfirstlane: in the tracer kernels the ring state travels through code the uniformity analysis gives up on, and Ring::step
+    // pins the slot index in an SGPR)
+    ring.b_take = __builtin_amdgcn_readfirstlane(ring.b_take);
+    const RingStep st = ring.step();
+    fr0 = lds_frag(st.rd, 0, lane);
     __builtin_amdgcn_sched_barrier(0);
-    dma_issue(src, wr, src_hidden, wave);
+    dma_issue(st.src, st.wr, st.hidden, ring.wave);
     __builtin_amdgcn_sched_barrier(0);
-    Epi1State es;
+    return st.rd;
+}
+
+// The MFMAs of one output tile in slot rd: A = fragments fa, fa + 1, ...; B = the head fragments (HEAD: 3 k-steps) or in's 16 k-step
+// fragments.  fr0 holds fragment fa on entry and fragment f_next (if >= 0, same slot) on return, read under the last MFMA.
+// EPI (0 none, 1 -> hi fragments in es.oh, 2 -> f32 tile in es.z): this call carries gaps g0 .. g0 + kM - 1 of the pending tile p's
+// epilogue, which is spread over GD gaps.  CARRY: the pending tile is in[7] itself (the previous layer's last tile), written back
+// behind gap GD - 1, before the k-step that first reads it.
+template <bool HEAD, int EPI, int GD, bool CARRY = false>
+__device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, int f_next, half8& fr0, const HeadFrag& hd,
+                                         TileH (&in)[kHidTiles], f32x16& acc, Epi1State& es, const f32x16& p, int g0, int lane) {
+    constexpr int kM = HEAD ? kHeadKSteps : 16;
     constexpr int kOps = EPI == 2 ? kEpi1OpsF32 : kEpi1Ops;
+    constexpr int kMaxPerGap = (kOps + GD - 1) / GD;
+    half8 fr[2];
+    fr[0] = fr0;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        if (ks + 1 < 16) fr[(ks + 1) & 1] = lds_frag(rd, 2 * (ks + 1), lane);
-        acc = mfma_h(fr[ks & 1], in[ks >> 1].h[ks & 1], acc);
+    for (int m = 0; m < kM; ++m) {
+        if (m + 1 < kM) fr[(m + 1) & 1] = lds_frag(rd, fa + m + 1, lane);
+        else if (f_next >= 0) fr0 = lds_frag(rd, f_next, lane);
+        if constexpr (HEAD) acc = mfma_h(fr[m & 1], hd.h[m], acc);
+        else acc = mfma_h(fr[m & 1], in[m >> 1].h[m & 1], acc);
         if constexpr (EPI != 0) {
-            const int o0 = epi1_first(ks, kOps), o1 = epi1_first(ks + 1, kOps);
+            const int g = g0 + m;
+            if (g < GD) {
+                const int o0 = g * kOps / GD, o1 = (g + 1) * kOps / GD;
 #pragma unroll
-            for (int k = 0; k < 7; ++k)
-                if (o0 + k < o1) epi1_op(es, o0 + k, p);
+                for (int k = 0; k < kMaxPerGap; ++k)
+                    if (o0 + k < o1) epi1_op(es, o0 + k, p);
+                if (CARRY && g == GD - 1) tile_from_epi(es, in[kHidTiles - 1]);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (EPI == 1) {
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) out_prev.h[s2] = __builtin_bit_cast(half8, es.oh[s2]);
-    }
-    if constexpr (EPI == 2) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) hf_prev[i] = es.z[i];
-    }
 }
 
-// One 256 -> 256 layer of the screen; HEAD: the layer also has a head product (skip layer); LAST: f32 tiles in `hf`.
-// The last tile's epilogue is exposed at the layer boundary.
-template <bool FAST, bool HEAD, bool LAST>
-__device__ __forceinline__ void h1_hidden_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, const TileH (&in)[kHidTiles],
-                                                TileH (&out)[kHidTiles], f32x16 (&hf)[kHidTiles]) {
-    const int wave = ring.wave;
-    f32x16 acc[2];
-    TileH dummy_out;
-    f32x16 dummy_hf;
+// One 256 -> 256 layer of the screen on 4 pair slots.  On entry the previous layer's tile 7 is pending in acc[1] (tile t accumulates in
+// acc[t & 1]); tile 0 finishes it into in[7] by k-step 13.  On return this layer's tile 7 is pending in acc[1].  LAST: f32 tiles in hf.
+template <bool LAST>
+__device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, TileH (&in)[kHidTiles],
+                                         TileH (&out)[kHidTiles], f32x16 (&acc)[2], f32x16 (&hf)[kHidTiles]) {
+    const int half = lane >> 5;
 #pragma unroll
-    for (int to = 0; to < kHidTiles; ++to) {
-        const int P = to & 1, Q = P ^ 1;
-        acc[P] = zero16();
-        if constexpr (HEAD) {
-            ring.sync();
-            const RingStep sh = ring.step();
-            step_head_h1(sh.rd, bias, sh.wr, sh.src, sh.hidden, wave, lane, to, true, hd, acc[P]);
+    for (int j = 0; j < kHidTiles / 2; ++j) {
+        half8 fr0;
+        const char* rd = h1_slot(ring, fr0, lane);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int t = 2 * j + u;
+            const int fn = u == 0 ? 16 : -1;
+            acc[u] = lds_half_tile(bias, t, half);
+            Epi1State es;
+            if (t == 0) {
+                h1_mfmas<false, 1, 14, true>(rd, 0, fn, fr0, hd, in, acc[0], es, acc[1], 0, lane);
+            } else if constexpr (LAST) {
+                h1_mfmas<false, 2, 16>(rd, 16 * u, fn, fr0, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) hf[t > 0 ? t - 1 : 0][i] = es.z[i];
+            } else {
+                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, fr0, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
+                tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
+            }
         }
-        ring.sync();
-        const RingStep st = ring.step();
-        if (to == 0)
-            step_hidden_h1<0>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], dummy_out, dummy_hf);
-        else if constexpr (LAST)
-            step_hidden_h1<2>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], dummy_out, hf[to > 0 ? to - 1 : 0]);
-        else
-            step_hidden_h1<1>(st.rd, bias, st.wr, st.src, st.hidden, wave, lane, to, !HEAD, in, acc[P], acc[Q], out[to > 0 ? to - 1 : 0], dummy_hf);
     }
-    if constexpr (LAST) hf[kHidTiles - 1] = softplus_tile<FAST>(acc[1]);
-    else hi_tile(softplus_tile<FAST>(acc[1]), out[kHidTiles - 1].h);
 }
 
-// SDFNetwork hidden stack on the screen (one product per MAC).  Same contract as sdf_hidden_stack_h2: all four waves together,
-// the same ring (it consumes exactly the slots sdf_hidden_stack_h2 consumes, so the two may alternate on one ring), hf = the last
-// hidden activation.
+// The skip layer: its head slot first (all 8 tiles' bias + head product, 24 MFMAs, under which the previous layer's tile 7 is finished
+// into in[7]), then its 4 pair slots add the hidden products.  The 8 partial tiles are held in registers across the layer.
+__device__ __forceinline__ void h1_skip_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, TileH (&in)[kHidTiles],
+                                              TileH (&out)[kHidTiles], f32x16 (&acc)[2]) {
+    const int half = lane >> 5;
+    f32x16 a[kHidTiles];
+    {
+        half8 fr0;
+        const char* rd = h1_slot(ring, fr0, lane);
+        Epi1State es;
+#pragma unroll
+        for (int t = 0; t < kHidTiles; ++t) {
+            a[t] = lds_half_tile(bias, t, half);
+            h1_mfmas<true, 1, kHidTiles * kHeadKSteps, true>(rd, kHeadKSteps * t, t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1, fr0, hd,
+                                                             in, a[t], es, acc[1], kHeadKSteps * t, lane);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kHidTiles / 2; ++j) {
+        half8 fr0;
+        const char* rd = h1_slot(ring, fr0, lane);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int t = 2 * j + u;
+            const int fn = u == 0 ? 16 : -1;
+            Epi1State es;
+            if (t == 0) {
+                h1_mfmas<false, 0, 16>(rd, 0, fn, fr0, hd, in, a[0], es, a[0], 0, lane);
+            } else {
+                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, fr0, hd, in, a[t], es, a[t > 0 ? t - 1 : 0], 0, lane);
+                tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
+            }
+        }
+    }
+    acc[1] = a[kHidTiles - 1];
+}
+
+// SDFNetwork hidden stack on the screen (one product per MAC).  Same contract as sdf_hidden_stack_h2 (all four waves together,
+// hf = the last hidden activation), but on a ring started on the h1 stream.
 template <bool FAST>
 __device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds, int n_hidden_layers, int skip_layer,
                                                     float scale, float x, float y, float z, int lane,
                                                     f32x16 (&hf)[kHidTiles]) {
     const int half = lane >> 5;
-    const int wave = ring.wave;
     float pe[kHeadSlots];
 #pragma unroll
     for (int i = 0; i < kHeadSlots; ++i) pe[i] = 0.0f;
@@ -955,22 +993,33 @@ __device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds,
         hd.h[s] = __builtin_bit_cast(half8, hh);
     }
     TileH X[kHidTiles], Y[kHidTiles];
+    f32x16 acc[2];
+    {   // layer 0: one slot, the 8 head tiles back to back, each tile's epilogue under the next tile's MFMAs
+        half8 fr0;
+        const char* rd = h1_slot(ring, fr0, lane);
 #pragma unroll
-    for (int to = 0; to < kHidTiles; ++to) {
-        ring.sync();
-        const RingStep st = ring.step();
-        f32x16 a = zero16();
-        step_head_h1(st.rd, lds + kLdsBias, st.wr, st.src, st.hidden, wave, lane, to, true, hd, a);
-        hi_tile(softplus_tile<FAST>(a), X[to].h);
+        for (int t = 0; t < kHidTiles; ++t) {
+            acc[t & 1] = lds_half_tile(lds + kLdsBias, t, half);
+            const int fn = t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1;
+            Epi1State es;
+            if (t == 0) {
+                h1_mfmas<true, 0, kHeadKSteps>(rd, 0, fn, fr0, hd, X, acc[0], es, acc[0], 0, lane);
+            } else {
+                h1_mfmas<true, 1, kHeadKSteps>(rd, kHeadKSteps * t, fn, fr0, hd, X, acc[t & 1], es, acc[(t - 1) & 1], 0, lane);
+                tile_from_epi(es, X[t > 0 ? t - 1 : 0]);
+            }
+        }
     }
+    // layers (1,2), (3,4), (5,6): X -> Y -> X, the skip layer second in its pair (the launchers admit 8 hidden layers, skip at 4 only)
     for (int l = 1; l + 1 < n_hidden_layers - 1; l += 2) {
         const char* bias_a = lds + kLdsBias + l * 1024;
         const char* bias_b = bias_a + 1024;
-        h1_hidden_layer<FAST, false, false>(ring, bias_a, hd, lane, X, Y, hf);
-        if (l + 1 == skip_layer) h1_hidden_layer<FAST, true, false>(ring, bias_b, hd, lane, Y, X, hf);
-        else h1_hidden_layer<FAST, false, false>(ring, bias_b, hd, lane, Y, X, hf);
+        h1_layer<false>(ring, bias_a, hd, lane, X, Y, acc, hf);
+        if (l + 1 == skip_layer) h1_skip_layer(ring, bias_b, hd, lane, Y, X, acc);
+        else h1_layer<false>(ring, bias_b, hd, lane, Y, X, acc, hf);
     }
-    h1_hidden_layer<FAST, false, true>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, hf);
+    h1_layer<true>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, acc, hf);
+    hf[kHidTiles - 1] = softplus_tile<FAST>(acc[1]);
 }
 
 }  // namespace iron

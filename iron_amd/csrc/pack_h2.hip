@@ -14,18 +14,23 @@ namespace iron {
 // every kernel runs it on the exact-fp32 core
 __device__ int g_h2_weight_overflow;
 
-__device__ __forceinline__ void store_split(_Float16* dst_hi, _Float16* dst_lo, float w) {
+// dst_h1 (optional): the same hi piece into the screen's h1 stream as well
+__device__ __forceinline__ void store_split(_Float16* dst_hi, _Float16* dst_lo, float w, _Float16* dst_h1 = nullptr) {
     if (!(fabsf(w) < 65504.0f)) atomicOr(&g_h2_weight_overflow, 1);
     const _Float16 hi = (_Float16)w;
     const _Float16 lo = (_Float16)((w - (float)hi) * kLoScale);
     *dst_hi = hi;
     *dst_lo = lo;
+    if (dst_h1) *dst_h1 = hi;
 }
 
 // dst: one hidden slot (32 KiB): fragments [ks 0..15][piece 0..1][lane 64][j 8] of fp16
 // (all slot packers: blockIdx.y = tile offset within a run of equally spaced slots; dst / to are the run's first slot / tile)
-__global__ void k_pack_h2_hidden(_Float16* __restrict__ dst, size_t stride, PackSrc s, int to, int col_off, int cols_valid) {
+// h1 (optional): the tile's 16 hi fragments [ks][lane][j] in the h1 stream, the run's tiles h1_stride bytes apart
+__global__ void k_pack_h2_hidden(_Float16* __restrict__ dst, size_t stride, PackSrc s, int to, int col_off, int cols_valid,
+                                 _Float16* __restrict__ h1, size_t h1_stride) {
     dst = (_Float16*)((char*)dst + blockIdx.y * stride);
+    if (h1) h1 = (_Float16*)((char*)h1 + blockIdx.y * h1_stride);
     to += blockIdx.y;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;  // (ks, lane, j)
     if (e >= 16 * 64 * 8) return;
@@ -36,13 +41,17 @@ __global__ void k_pack_h2_hidden(_Float16* __restrict__ dst, size_t stride, Pack
     float w = 0.0f;
     if (row < s.rows_valid && col < cols_valid)
         w = s.w[(size_t)(s.row_off + row) * s.ld + col_off + col] * s.scale[s.row_off + row] * s.mul;
-    store_split(dst + ((size_t)(2 * ks) * 64 + lane) * 8 + j, dst + ((size_t)(2 * ks + 1) * 64 + lane) * 8 + j, w);
+    store_split(dst + ((size_t)(2 * ks) * 64 + lane) * 8 + j, dst + ((size_t)(2 * ks + 1) * 64 + lane) * 8 + j, w,
+                h1 ? h1 + ((size_t)ks * 64 + lane) * 8 + j : nullptr);
 }
 
 // dst: one head slot (8 KiB): fragments [ks 0..2][piece][lane][j] + 2 KiB of zero padding
 // slot_off: first head slot of this ring slot (a head wider than 24 slots is streamed as two ring slots: 0 and 24)
-__global__ void k_pack_h2_head(_Float16* __restrict__ dst, size_t stride, PackSrc s, HeadSrcs hs, int to, int slot_off) {
+// h1 (optional): the tile's 3 hi fragments [ks][lane][j] in the h1 stream, the run's tiles h1_stride bytes apart
+__global__ void k_pack_h2_head(_Float16* __restrict__ dst, size_t stride, PackSrc s, HeadSrcs hs, int to, int slot_off,
+                               _Float16* __restrict__ h1, size_t h1_stride) {
     dst = (_Float16*)((char*)dst + blockIdx.y * stride);
+    if (h1) h1 = (_Float16*)((char*)h1 + blockIdx.y * h1_stride);
     to += blockIdx.y;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;  // (ks 0..3, lane, j)
     if (e >= 4 * 64 * 8) return;
@@ -61,7 +70,8 @@ __global__ void k_pack_h2_head(_Float16* __restrict__ dst, size_t stride, PackSr
             }
         }
     }
-    store_split(dst + ((size_t)(2 * ks) * 64 + lane) * 8 + j, dst + ((size_t)(2 * ks + 1) * 64 + lane) * 8 + j, w);
+    store_split(dst + ((size_t)(2 * ks) * 64 + lane) * 8 + j, dst + ((size_t)(2 * ks + 1) * 64 + lane) * 8 + j, w,
+                (h1 && ks < kHeadKSteps) ? h1 + ((size_t)ks * 64 + lane) * 8 + j : nullptr);
 }
 
 // Transposed hidden slot (reverse-mode get_all, mlp_h2_rev.h): output row 32*to + i of the slot is ORIGINAL COLUMN col_off + row of the
@@ -155,8 +165,11 @@ static int h2_overflow_check(iron_net* net) {
 //   PE-row slots of W_0.
 // The forward-only streams live in h2_blob (h2_trace / h2_full), the reverse stream is a second blob (h2_rev_blob) holding the
 // same forward slots followed by the transposed ones, so that one ring walks it end to end.
+// h1_out (forward blob only): the screen's h1 stream (mlp_h2.h: sdf_hidden_stack_h1), behind the h2 slots in the same blob and written
+// by the same launches: the hi pieces of the hidden stack's fragments, slots [layer-0 heads] then per layer [skip layer: its heads]
+// + 4 pairs of tiles; it shares the blob's bias / row blocks.
 static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* scale_base, const size_t* soff, bool with_rev, void** blob_out,
-                            H2StreamDev* s_out, uint32_t* n_trace_out, uint32_t* n_full_out, hipStream_t st) {
+                            H2StreamDev* s_out, uint32_t* n_trace_out, uint32_t* n_full_out, H2StreamDev* h1_out, hipStream_t st) {
     const iron_net_desc& d = net->desc;
     const int nl = d.n_linear;
     const int skip = d.skip_layer;
@@ -182,7 +195,20 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
     }
     const uint32_t n_all = (uint32_t)(table.size() / 2);
     if (n_all > 250) return IRON_ERR_UNSUPPORTED;
-    const size_t data_bytes = off;
+    // the h1 stream: 32 KiB slots, a head slot (the 3 head fragments of 8 tiles, zero-padded) or a pair slot (2 tiles x 16 fragments)
+    const size_t h1_off = off;
+    const size_t kH1Tile = 16 * 1024;
+    std::vector<size_t> h1_layer;   // byte offset (from h1_off) of each layer's first slot
+    size_t h1_bytes = 0;
+    if (h1_out) {
+        for (int l = 0; l <= nl - 2; ++l) {
+            h1_layer.push_back(h1_bytes);
+            if (l == 0 || l == skip) h1_bytes += kSlotBytes;
+            if (l > 0) h1_bytes += (size_t)kHidTiles * kH1Tile;
+        }
+        if (h1_bytes / kSlotBytes > 64) return IRON_ERR_UNSUPPORTED;
+    }
+    const size_t data_bytes = off + h1_bytes;
     const size_t table_off = (data_bytes + 255) & ~(size_t)255;
     const size_t bias_off = table_off + 2048;
     const size_t rows_off = bias_off + kLdsBiasBytes;
@@ -200,10 +226,13 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
     hs.n = 1; hs.slot_base[0] = 0; hs.levels[0] = d.multires; hs.col_off[0] = 0;
     size_t q = 0;
     auto slot_ptr = [&](size_t idx) { return (_Float16*)(base + table[2 * idx]); };
+    // h1 destinations: layer l's head fragments (layer 0, skip layer) and its first hidden tile; nullptr without an h1 stream
+    auto h1_head = [&](int l) { return h1_out ? (_Float16*)(base + h1_off + h1_layer[l]) : (_Float16*)nullptr; };
+    auto h1_hid = [&](int l) { return h1_out ? (_Float16*)(base + h1_off + h1_layer[l] + (l == skip ? kSlotBytes : 0)) : (_Float16*)nullptr; };
     // one launch per run of equally spaced slots (blockIdx.y = tile): a training step re-packs every network, and one launch per slot
     // (224 per step at C3) cost ~1 ms per step of 3-4 us launches
     const size_t kHeadB = 8192, kHidB = kSlotBytes;
-    hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB, make_pack_src(L[0], scale_base + soff[0], kHidden, 0, 1.0f), hs, 0, 0);
+    hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB, make_pack_src(L[0], scale_base + soff[0], kHidden, 0, 1.0f), hs, 0, 0, h1_head(0), (size_t)kHeadKSteps * 1024);
     q += kHidTiles;
     for (int l = 1; l <= nl - 2; ++l) {
         const bool is_skip = (l == skip);
@@ -213,17 +242,17 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
         if (is_skip) {   // per tile: [head slot][hidden slot]
             HeadSrcs h2 = hs;
             h2.col_off[0] = kHidden - pe;
-            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB + kHidB, ps, h2, 0, 0);
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + 1), kHeadB + kHidB, ps, 0, 0, cols_valid);
+            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB + kHidB, ps, h2, 0, 0, h1_head(l), (size_t)kHeadKSteps * 1024);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + 1), kHeadB + kHidB, ps, 0, 0, cols_valid, h1_hid(l), kH1Tile);
             q += 2 * kHidTiles;
         } else {
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, 0, cols_valid);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, 0, cols_valid, h1_hid(l), kH1Tile);
             q += kHidTiles;
         }
     }
     const iron_linear& last = L[nl - 1];
     if (has_feat) {
-        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, make_pack_src(last, scale_base + soff[nl - 1], kHidden, 1, 1.0f), 0, 0, kHidden);
+        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, make_pack_src(last, scale_base + soff[nl - 1], kHidden, 1, 1.0f), 0, 0, kHidden, (_Float16*)nullptr, (size_t)0);
         q += kHidTiles;
     }
     if (with_rev) {
@@ -262,6 +291,17 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
         if (table[2 * k + 1]) s.kind_mask[k >> 5] |= 1u << (k & 31);
     }
     *s_out = s;
+    if (h1_out) {
+        H2StreamDev h = s;
+        h.base = base + h1_off;
+        h.table_off = 0;   // (no slot table: the kinds are the whole description)
+        h.n_slots = (uint32_t)(h1_bytes / kSlotBytes);
+        h.bias_off = (uint32_t)(bias_off - h1_off);
+        h.rows_off = (uint32_t)(rows_off - h1_off);
+        for (int i = 0; i < 4; ++i) h.kind_mask[i] = 0;
+        for (uint32_t k = 0; k < h.n_slots; ++k) h.kind_mask[k >> 5] |= 1u << (k & 31);   // all 32 KiB slots
+        *h1_out = h;
+    }
     *n_trace_out = n_trace;
     *n_full_out = n_full;
     return IRON_OK;
@@ -275,8 +315,10 @@ int build_h2_sdf(iron_net* net, const iron_linear* L, const float* scale_base, c
     { const int rc0 = h2_overflow_reset(st); if (rc0 != IRON_OK) return rc0; }
     H2StreamDev s;
     uint32_t n_trace = 0, n_full = 0;
-    int rc = pack_h2_sdf_blob(net, L, scale_base, soff, false, &net->h2_blob, &s, &n_trace, &n_full, st);
+    H2StreamDev h1;
+    int rc = pack_h2_sdf_blob(net, L, scale_base, soff, false, &net->h2_blob, &s, &n_trace, &n_full, &h1, st);
     if (rc != IRON_OK) return rc;
+    net->h1_trace = h1;
     s.n_slots = n_trace;
     net->h2_trace = s;
     s.n_slots = n_full;
@@ -284,11 +326,12 @@ int build_h2_sdf(iron_net* net, const iron_linear* L, const float* scale_base, c
     // the reverse stream: the network shape getall_rev.hip is written for (8 hidden layers of 256, skip at 4, PE-6, feature rows)
     if (d.n_linear == 9 && d.skip_layer == 4 && d.multires == kSdfPeLevels && d.d_out == kHidden + 1) {
         H2StreamDev r;
-        rc = pack_h2_sdf_blob(net, L, scale_base, soff, true, &net->h2_rev_blob, &r, &n_trace, &n_full, st);
+        rc = pack_h2_sdf_blob(net, L, scale_base, soff, true, &net->h2_rev_blob, &r, &n_trace, &n_full, nullptr, st);
         if (rc != IRON_OK) return rc;
         net->h2_rev = r;
     }
     rc = h2_overflow_check(net);
+    if (!net->h2_blob) memset(&net->h1_trace, 0, sizeof(net->h1_trace));   // the h1 stream lived in the dropped blob
     if (rc == IRON_OK && !net->h2_blob && net->h2_rev_blob) { (void)hipFree(net->h2_rev_blob); net->h2_rev_blob = nullptr; }
     return rc;
 }
@@ -337,15 +380,15 @@ int build_h2_render(iron_net* net, const iron_linear* L, const float* scale_base
     const size_t kHeadB = 8192, kHidB = kSlotBytes;
     if (skip != -1) {   // feature columns of the skip layer: [x 256 | head inputs | features 256] / sqrt(2)
         const PackSrc ps = make_pack_src(L[skip], scale_base + soff[skip], kHidden, 0, kInvSqrt2);
-        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, kHidden + head_w, kHidden);
+        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, kHidden + head_w, kHidden, (_Float16*)nullptr, (size_t)0);
         q += kHidTiles;
     }
     {   // layer 0, per tile: [head slot(s)][hidden slot = feature part]
         const PackSrc ps = make_pack_src(L[0], scale_base + soff[0], kHidden, 0, 1.0f);
         const size_t stride = (size_t)n_head * kHeadB + kHidB;
         for (int h = 0; h < n_head; ++h)
-            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q + h), stride, ps, hs, 0, h * kHeadSlots);
-        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + n_head), stride, ps, 0, head_w, kHidden);
+            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q + h), stride, ps, hs, 0, h * kHeadSlots, (_Float16*)nullptr, (size_t)0);
+        hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + n_head), stride, ps, 0, head_w, kHidden, (_Float16*)nullptr, (size_t)0);
         q += (size_t)(n_head + 1) * kHidTiles;
     }
     for (int l = 1; l <= nl - 2; ++l) {
@@ -356,11 +399,11 @@ int build_h2_render(iron_net* net, const iron_linear* L, const float* scale_base
             for (int k = 0; k < hs2.n; ++k) hs2.col_off[k] += kHidden;
             const size_t stride = (size_t)n_head * kHeadB + kHidB;
             for (int h = 0; h < n_head; ++h)
-                hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q + h), stride, ps, hs2, 0, h * kHeadSlots);
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + n_head), stride, ps, 0, 0, kHidden);
+                hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q + h), stride, ps, hs2, 0, h * kHeadSlots, (_Float16*)nullptr, (size_t)0);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + n_head), stride, ps, 0, 0, kHidden, (_Float16*)nullptr, (size_t)0);
             q += (size_t)(n_head + 1) * kHidTiles;
         } else {
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, 0, kHidden);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, 0, kHidden, (_Float16*)nullptr, (size_t)0);
             q += kHidTiles;
         }
     }
@@ -437,14 +480,14 @@ int build_h2_nerf(iron_net* net, const iron_linear* L, const float* scale_base, 
         const PackSrc ps = make_pack_src(L[l], scale_base + soff[l], kHidden, 0, 1.0f);
         for (int to = 0; to < kHidTiles; ++to) {
             if (skip_in) heads4(ps, to);
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, skip_in ? in_p : 0, kHidden);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, skip_in ? in_p : 0, kHidden, (_Float16*)nullptr, (size_t)0);
             ++q;
         }
     }
     {
         const PackSrc ps = make_pack_src(L[D + 1], scale_base + soff[D + 1], kHidden, 0, 1.0f);
         for (int to = 0; to < kHidTiles; ++to, ++q)
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, 0, kHidden);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, 0, kHidden, (_Float16*)nullptr, (size_t)0);
     }
     {
         const PackSrc ps = make_pack_src(L[D + 2], scale_base + soff[D + 2], kHidden / 2, 0, 1.0f);
@@ -452,9 +495,9 @@ int build_h2_nerf(iron_net* net, const iron_linear* L, const float* scale_base, 
         memset(&hv, 0, sizeof(hv));
         hv.n = 1; hv.slot_base[0] = 0; hv.levels[0] = lv; hv.col_off[0] = kHidden;
         for (int to = 0; to < kHidTiles / 2; ++to) {
-            hipLaunchKernelGGL(k_pack_h2_head, dim3(8), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, hv, to, 0);
+            hipLaunchKernelGGL(k_pack_h2_head, dim3(8), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, hv, to, 0, (_Float16*)nullptr, (size_t)0);
             ++q;
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, 0, kHidden);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32), dim3(256), 0, st, slot_ptr(q), (size_t)0, ps, to, 0, kHidden, (_Float16*)nullptr, (size_t)0);
             ++q;
         }
     }

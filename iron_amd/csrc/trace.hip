@@ -105,6 +105,8 @@ constexpr float kScreenK = 12.0f;
 constexpr float kScreenFloor = 1.0e-3f;
 constexpr float kScreenGuard = 0.5f;
 constexpr int kScreenCalibPoints = 8192;
+constexpr int kScreenCalibF1 = 64;   // calibration buffer (32-bit words): [0] the max, [kScreenCalibF1 ..) the screen's values
+constexpr size_t kScreenCalibBytes = (kScreenCalibF1 + kScreenCalibPoints) * 4;
 constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
 constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
 constexpr uint8_t kRayOverflowed = 1;  // ray_state: the ray's samples did not fit the list; k_sampler marches it again
@@ -217,7 +219,7 @@ struct BackendH2T {
         sdf_hidden_stack_h2<kFastActT, DEFER_TILES>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
         return (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
     }
-    // the screen: one product per MAC on the same ring (sdf_hidden_stack_h1), for sign decisions only
+    // the screen: one product per MAC (sdf_hidden_stack_h1) on a ring started on the h1 stream, for sign decisions only
     __device__ __forceinline__ float eval_screen(float x, float y, float z) {
         f32x16 hf[kHidTiles];
         sdf_hidden_stack_h1<kFastActT>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
@@ -551,7 +553,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_KERNEL_ARGS) {
     BE be;
-    be.init(net, hs, hm);
+    be.init(net, hs, hm);   // hs: the h1 stream
     const int lane = be.lane;
     const int j = lane & 31;
     const int slot = j / kSamplerBlock, s_in = j % kSamplerBlock;
@@ -870,25 +872,41 @@ __global__ void k_screen_fin_rays(TraceArgs a, TraceWs w) {
 }
 
 // calibration of the margin: max |f_screen - f_h2| over a fixed set of points in the unit ball (a golden-angle spiral of
-// directions, radii from the R2 sequence), once per network handle before its first screened trace
-__global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2StreamDev hs, H2Meta hm, unsigned* calib) {
+// directions, radii from the R2 sequence), once per network handle before its first screened trace.  Two ring passes over the
+// block's points, one per stream: the screen on the h1 stream (hs1) leaves f1 in calib[kScreenCalibF1 + i] (every lane stores its own
+// point's value and reads back only what it stored), then h2 (hs) compares.
+__device__ __forceinline__ void screen_calib_point(int i, float& x, float& y, float& z) {
+    const float u = (i + 0.5f) / kScreenCalibPoints;
+    const float cz = 1.0f - 2.0f * u, sz = sqrtf(fmaxf(0.0f, 1.0f - cz * cz));
+    const float phi = 2.39996323f * (float)i;
+    float fr = 0.7548776662f * (float)i;
+    fr -= floorf(fr);
+    const float rad = cbrtf(0.5f / kScreenCalibPoints + fr * (1.0f - 1.0f / kScreenCalibPoints));
+    x = rad * sz * cosf(phi); y = rad * sz * sinf(phi); z = rad * cz;
+}
+
+__global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2StreamDev hs, H2StreamDev hs1, H2Meta hm, unsigned* calib) {
     BackendH2 be;
+    float* const f1s = reinterpret_cast<float*>(calib) + kScreenCalibF1;
+    be.init(net, hs1, hm);
+    for (int g = blockIdx.x; g < kScreenCalibPoints / 128; g += gridDim.x) {
+        const int i = g * 128 + be.wave * 32 + (be.lane & 31);
+        float x, y, z;
+        screen_calib_point(i, x, y, z);
+        const float f1 = be.eval_screen(x, y, z);
+        f1s[i] = f1;   // lanes j and j + 32: the same point, the same value
+    }
+    be.finish();
     be.init(net, hs, hm);
     const int lane = be.lane;
     float m = 0.0f;
     for (int g = blockIdx.x; g < kScreenCalibPoints / 128; g += gridDim.x) {
         const int i = g * 128 + be.wave * 32 + (lane & 31);
-        const float u = (i + 0.5f) / kScreenCalibPoints;
-        const float cz = 1.0f - 2.0f * u, sz = sqrtf(fmaxf(0.0f, 1.0f - cz * cz));
-        const float phi = 2.39996323f * (float)i;
-        float fr = 0.7548776662f * (float)i;
-        fr -= floorf(fr);
-        const float rad = cbrtf(0.5f / kScreenCalibPoints + fr * (1.0f - 1.0f / kScreenCalibPoints));
-        const float x = rad * sz * cosf(phi), y = rad * sz * sinf(phi), z = rad * cz;
-        const float f1 = be.eval_screen(x, y, z);
-        be.park(0, f1); be.park(1, m);
+        float x, y, z;
+        screen_calib_point(i, x, y, z);
+        be.park(1, m);
         const float f2 = be.eval(x, y, z);
-        const float d = fabsf(be.unpark(0, 0.0f) - f2);
+        const float d = fabsf(f1s[i] - f2);
         m = be.unpark(1, 0.0f);
         if (d <= 3.0e38f) m = fmaxf(m, d);
     }
@@ -1185,10 +1203,10 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
             case 0: hipLaunchKernelGGL(k_sphere<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             case 1: hipLaunchKernelGGL(k_sampler<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             case 2: hipLaunchKernelGGL(k_bisect_a<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 4: hipLaunchKernelGGL(k_sampler_screen<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case 4: hipLaunchKernelGGL(k_sampler_screen<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h1_trace, m, a, w); break;
             case 5: hipLaunchKernelGGL(k_screen_resolve<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             case 6: hipLaunchKernelGGL(k_screen_calib, dim3(cus < kScreenCalibPoints / 128 ? cus : kScreenCalibPoints / 128), block,
-                                       kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, sdf->screen_calib); break;
+                                       kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, sdf->h1_trace, m, sdf->screen_calib); break;
             default: hipLaunchKernelGGL(k_bisect_b<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
         }
     } else {
@@ -1223,8 +1241,8 @@ static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use
     iron_net* net = const_cast<iron_net*>(cnet);
     *use = false;
     if (net->flag_host && *(volatile int*)(net->flag_host + 1)) net->screen_off = 1;
-    if (!h2 || !screen_switch() || net->screen_off) return IRON_OK;
-    if (!net->screen_calib) IRON_HIP_TRY(hipMalloc((void**)&net->screen_calib, 256));
+    if (!h2 || !screen_switch() || net->screen_off || !net->h1_trace.base) return IRON_OK;
+    if (!net->screen_calib) IRON_HIP_TRY(hipMalloc((void**)&net->screen_calib, kScreenCalibBytes));
     if (!net->screen_calibrated) {   // once per handle (a re-pack is a new handle): stream-ordered, no synchronisation
         IRON_HIP_TRY(hipMemsetAsync(net->screen_calib, 0, 256, st));
         TraceArgs a{};
