@@ -185,6 +185,41 @@ int iron_train_gemm(int32_t op_a, int32_t op_b, int32_t m, int32_t n, int32_t k,
  * range (weight_g up to 137, pre-activations about 10). */
 int iron_train_numeric_status(int32_t reset, void* stream);
 
+/* Stage-2 image losses (models/image_losses.py, used by render_surface.py:597-598), csrc/losses.hip.  Images are [B, C, H, W]
+ * fp32 contiguous.  The loss is written to a DEVICE scalar `loss` [1]; the backward reads the upstream gradient from the DEVICE
+ * scalar `d_loss` [1] and WRITES dx (and dy = d loss / d Y when non-NULL).  Every reduction is a fixed-order sum of per-workgroup
+ * partials (no atomics): loss and gradients are bitwise reproducible.
+ *
+ * Pyramid L2 (PyramidL2Loss): n_planes = B*C planes of h x w, h and w >= 16 (IRON_ERR_UNSUPPORTED below).  `taps` (HOST [49])
+ * is the 7x7 filter, row-major; it must be point symmetric (taps[48 - i] == taps[i]), which the backward relies on.  The
+ * workspace holds the levels d_1..d_4 between the forward and the backward (pass the same one to both) and the backward's
+ * scratch; it is under 2/3 of one input's size. */
+size_t iron_pyramid_l2_workspace_bytes(int64_t n_planes, int32_t h, int32_t w);
+int iron_pyramid_l2_forward(const float* x, const float* y, int64_t n_planes, int32_t h, int32_t w, const float* taps, float* loss,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int iron_pyramid_l2_backward(const float* x, const float* y, int64_t n_planes, int32_t h, int32_t w, const float* taps,
+                             const float* d_loss, void* workspace, size_t workspace_bytes, float* dx, float* dy, void* stream);
+
+/* SSIM loss (ssim_loss_fn): `win` (HOST [win_size], odd, <= 21, else IRON_ERR_UNSUPPORTED) is the 1-D Gaussian applied along every
+ * axis not shorter than win_size (a shorter axis is not smoothed); c1, c2 as the reference's (K1 data_range)^2, (K2 data_range)^2.
+ * mask: NULL, or [B, 1, H, W] with mask_kind 1 (uint8 / bool: kept where non-zero) or 2 (fp32: kept where > 0.5); it is eroded by
+ * a win x win window over the in-image pixels, and a masked call needs both axes >= win_size (IRON_ERR_UNSUPPORTED otherwise).
+ * `state` (state_bytes from iron_ssim_workspace_bytes) carries the eroded mask and |E| from the forward to the backward;
+ * `scratch` (scratch_bytes) is the backward's own. */
+int iron_ssim_workspace_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t win_size, int32_t masked, size_t* state_bytes,
+                              size_t* scratch_bytes);
+int iron_ssim_forward(const float* x, const float* y, int32_t b, int32_t c, int32_t h, int32_t w, const float* win, int32_t win_size,
+                      double c1, double c2, const void* mask, int32_t mask_kind, float* loss, void* state, size_t state_bytes,
+                      void* stream);
+int iron_ssim_backward(const float* x, const float* y, int32_t b, int32_t c, int32_t h, int32_t w, const float* win, int32_t win_size,
+                       double c1, double c2, int32_t masked, const float* d_loss, const void* state, size_t state_bytes, void* scratch,
+                       size_t scratch_bytes, float* dx, float* dy, void* stream);
+
+/* gaussian_filter (inference): the "valid" separable blur with `win` (HOST [win_size]) of n_planes planes of h x w; out is
+ * [n_planes, h', w'], h' = h - win_size + 1 when h >= win_size, else h (that axis is passed through); same for w. */
+int iron_gaussian_filter(const float* x, int64_t n_planes, int32_t h, int32_t w, const float* win, int32_t win_size, float* out,
+                         void* stream);
+
 /* Diagnostics: last hipError_t seen by this library on the calling thread (iron_train_last_blas_status: kept for ABI
  * stability, always 0: the library links no BLAS). */
 int iron_train_last_hip_error(void);

@@ -6,6 +6,7 @@ Module names mirror the reference's `models/` package for this path:
     iron_amd.rendering_func <- models/rendering_func.py
     iron_amd.fields         <- models/fields.py
     iron_amd.embedder       <- models/embedder.py
+    iron_amd.image_losses   <- models/image_losses.py
 `install_as_models()` registers them under those names for `render_surface.py`-style callers.
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ def install_as_models() -> None:
         pkg = types.ModuleType("models")
         pkg.__path__ = []  # mark as package
         sys.modules["models"] = pkg
-    for name in ("raytracer", "renderer_ggx", "rendering_func", "fields", "embedder", "renderer", "network_conf"):
+    for name in ("raytracer", "renderer_ggx", "rendering_func", "fields", "embedder", "renderer", "network_conf", "image_losses"):
         mod = importlib.import_module("iron_amd." + name)
         sys.modules["models." + name] = mod
         setattr(pkg, name, mod)

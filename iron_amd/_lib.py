@@ -202,6 +202,15 @@ TRAIN_SYMBOLS = {
     "iron_train_last_hip_error": (C.c_int, []),
     "iron_train_last_blas_status": (C.c_int, []),
     "iron_train_numeric_status": (C.c_int, [_I32, _P]),
+    "iron_pyramid_l2_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "iron_pyramid_l2_forward": (C.c_int, [_P, _P, _I64, _I32, _I32, C.POINTER(C.c_float), _P, _P, _SZ, _P]),
+    "iron_pyramid_l2_backward": (C.c_int, [_P, _P, _I64, _I32, _I32, C.POINTER(C.c_float), _P, _P, _SZ, _P, _P, _P]),
+    "iron_ssim_workspace_bytes": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "iron_ssim_forward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, C.c_double, C.c_double, _P, _I32, _P,
+                                    _P, _SZ, _P]),
+    "iron_ssim_backward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, C.c_double, C.c_double, _I32, _P, _P,
+                                     _SZ, _P, _SZ, _P, _P, _P]),
+    "iron_gaussian_filter": (C.c_int, [_P, _I64, _I32, _I32, C.POINTER(C.c_float), _I32, _P, _P]),
 }
 
 _lock = threading.Lock()

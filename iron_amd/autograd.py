@@ -7,6 +7,8 @@ libiron_train.so (include/iron_train.h):
     SDFGetAllFn      SDFNetwork.get_all(is_training=True) / .gradient       models/fields.py:106-137 (second order)
     RenderNetFn      RenderingNetwork.forward                               models/fields.py:203-239
     GGXColocatedFn   GGXColocatedRenderer.forward                           models/renderer_ggx.py:82-146
+    PyramidL2Fn      PyramidL2Loss.forward                                  models/image_losses.py:29-48
+    SSIMFn           ssim_loss_fn                                           models/image_losses.py:97-158
 
 so `render_camera(..., is_training=True)`, the reference's `reparam_points`, its `render_fn` closure and its loss code
 run unchanged on top and `loss.backward()` fills `.grad` of weight_g / weight_v / bias / light exactly as there.  There is
@@ -493,6 +495,87 @@ class NeusCompositeFn(torch.autograd.Function):
             _lib.check_train(_lib.load_train().iron_neus_composite_backward(C.byref(a), C.byref(g), _lib.stream_ptr(dev)))
         return (d_sdf.reshape(s_sdf), d_grad.reshape(s_grad), d_col.reshape(s_color), d_inv.reshape(()) if inv_s_is_tensor else None,
                 d_bgd.reshape(s_bgd) if bg else None, d_bgc.reshape(s_bgc) if bg else None, None, None, None, None, None, None)
+
+
+class PyramidL2Fn(torch.autograd.Function):
+    """loss = PyramidL2Loss()(x, y) (models/image_losses.py:29-48); x, y [B, 3, H, W], H, W >= 16.  `taps` is the HOST ctypes
+    float[49] of the 7x7 filter.  The loss is a device scalar; the backward reads its upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, taps):
+        xc, yc = _lib.require_cuda_f32(x, "pred_img"), _lib.require_cuda_f32(y, "trgt_img")
+        b, c, h, w = xc.shape
+        lib = _lib.load_train()
+        dev = xc.device
+        with torch.cuda.device(dev):
+            ws = torch.empty(max(int(lib.iron_pyramid_l2_workspace_bytes(b * c, h, w)), 16), dtype=torch.uint8, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            _lib.check_train(lib.iron_pyramid_l2_forward(xc.data_ptr(), yc.data_ptr(), b * c, h, w, taps, loss.data_ptr(), ws.data_ptr(),
+                                                         ws.numel(), _lib.stream_ptr(dev)))
+        ctx.taps, ctx.ws = taps, ws  # the workspace carries d_1..d_4 to the backward
+        ctx.save_for_backward(xc, yc)
+        return loss
+
+    @staticmethod
+    @once_differentiable  # closed-form first-order backward: differentiating it again raises instead of returning zeros
+    def backward(ctx, g):
+        xc, yc = ctx.saved_tensors
+        b, c, h, w = xc.shape
+        g = _lib.require_cuda_f32(g, "upstream gradient").reshape(1)
+        lib = _lib.load_train()
+        dev = xc.device
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(xc)
+            dy = torch.empty_like(yc) if ctx.needs_input_grad[1] else None
+            _lib.check_train(lib.iron_pyramid_l2_backward(xc.data_ptr(), yc.data_ptr(), b * c, h, w, ctx.taps, g.data_ptr(), ctx.ws.data_ptr(),
+                                                          ctx.ws.numel(), dx.data_ptr(), _lib.ptr(dy), _lib.stream_ptr(dev)))
+        return dx, dy, None
+
+
+class SSIMFn(torch.autograd.Function):
+    """loss = ssim_loss_fn(x, y, mask, ...) (models/image_losses.py:97-158) for [B, C, H, W] x, y.  `win` is the HOST ctypes
+    float[win_size] window, `mask` None or a contiguous [B, 1, H, W] bool / uint8 / float32 CUDA tensor."""
+
+    @staticmethod
+    def forward(ctx, x, y, mask, win, win_size, c1, c2):
+        xc, yc = _lib.require_cuda_f32(x, "X"), _lib.require_cuda_f32(y, "Y")
+        b, c, h, w = xc.shape
+        lib = _lib.load_train()
+        dev = xc.device
+        kind = 0
+        if mask is not None:
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)
+            kind = 1 if mask.dtype == torch.uint8 else 2
+        state_b, scratch_b = C.c_size_t(0), C.c_size_t(0)
+        _lib.check_train(lib.iron_ssim_workspace_bytes(b, c, h, w, win_size, kind != 0, C.byref(state_b), C.byref(scratch_b)))
+        with torch.cuda.device(dev):
+            state = torch.empty(max(state_b.value, 16), dtype=torch.uint8, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            _lib.check_train(lib.iron_ssim_forward(xc.data_ptr(), yc.data_ptr(), b, c, h, w, win, win_size, c1, c2, _lib.ptr(mask), kind,
+                                                   loss.data_ptr(), state.data_ptr(), state.numel(), _lib.stream_ptr(dev)))
+        ctx.args = (win, win_size, c1, c2, kind != 0, scratch_b.value)
+        ctx.state = state  # the eroded mask and |E|
+        ctx.save_for_backward(xc, yc)
+        return loss
+
+    @staticmethod
+    @once_differentiable  # closed-form first-order backward: differentiating it again raises instead of returning zeros
+    def backward(ctx, g):
+        xc, yc = ctx.saved_tensors
+        b, c, h, w = xc.shape
+        win, win_size, c1, c2, masked, scratch_bytes = ctx.args
+        g = _lib.require_cuda_f32(g, "upstream gradient").reshape(1)
+        lib = _lib.load_train()
+        dev = xc.device
+        with torch.cuda.device(dev):
+            scratch = _lib.workspace(scratch_bytes, dev, "ssim_backward")
+            dx = torch.empty_like(xc)
+            dy = torch.empty_like(yc) if ctx.needs_input_grad[1] else None
+            _lib.check_train(lib.iron_ssim_backward(xc.data_ptr(), yc.data_ptr(), b, c, h, w, win, win_size, c1, c2, 1 if masked else 0,
+                                                    g.data_ptr(), ctx.state.data_ptr(), ctx.state.numel(), scratch.data_ptr(), scratch.numel(),
+                                                    dx.data_ptr(), _lib.ptr(dy), _lib.stream_ptr(dev)))
+        return dx, dy, None, None, None, None, None
 
 
 def numeric_status(reset: bool = True, device=None) -> bool:

@@ -1,0 +1,152 @@
+"""The stage-2 image losses (models/image_losses.py) on the GPU: pyramid L2 and (masked) SSIM, forward and closed-form
+backward in HIP (csrc/losses.hip, include/iron_train.h), differentiable through iron_amd.autograd.PyramidL2Fn / SSIMFn.
+
+Same public names and signatures as the reference module, so `from models.image_losses import PyramidL2Loss, ssim_loss_fn`
+(render_surface.py:24, after iron_amd.install_as_models()) resolves here.  Neither scipy (the pyramid filter) nor kornia (the
+erosion of the SSIM mask) is needed: the filter taps are computed in closed form below, the erosion runs in the SSIM kernel.
+Inputs are float32 CUDA tensors; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .autograd import PyramidL2Fn, SSIMFn, refuse_grad
+
+
+def pyramid_taps() -> np.ndarray:
+    """The reference's 7x7 pyramid filter, scipy.ndimage.gaussian_filter(dirac7x7, 1.0) in float32, without scipy: the radius-4
+    Gaussian of sigma 1 normalised in float64, its tails reflect-folded into the 7 taps (p < 0 -> -p-1, p > 6 -> 13-p), then
+    f[i, j] = f32(g[j] * f32(g[i])) -- the two separable passes of scipy, each rounding to float32."""
+    x = np.arange(-4, 5, dtype=np.float64)
+    phi = np.exp(-0.5 / 1.0 * x ** 2)
+    phi = phi / phi.sum()
+    g = np.zeros(7, dtype=np.float64)
+    for p, v in zip(range(-1, 8), phi):
+        g[-p - 1 if p < 0 else (13 - p if p > 6 else p)] += v
+    gi = g.astype(np.float32).astype(np.float64)
+    return (g[None, :] * gi[:, None]).astype(np.float32)
+
+
+class PyramidL2Loss(nn.Module):
+    """sum_k |d_k|^2 / ((h/2^k)(w/2^k)), d_0 = pred - trgt, d_{k+1} = avgpool2(conv7x7(d_k)), k = 0..4."""
+
+    def __init__(self, use_cuda=True):
+        super().__init__()
+        gf = pyramid_taps()
+        f = np.zeros([3, 3, 7, 7], dtype=np.float32)
+        for c in range(3):
+            f[c, c] = gf
+        self.f = torch.from_numpy(f)  # kept for parity with the reference; the kernels take the taps from the host
+        self.use_cuda = use_cuda  # accepted, no effect: the loss always runs on the GPU
+        self._taps = (C.c_float * 49)(*gf.reshape(-1).tolist())
+
+    def forward(self, pred_img, trgt_img):
+        """pred_img, trgt_img: [B, 3, H, W], H, W >= 16."""
+        if pred_img.shape != trgt_img.shape or pred_img.dim() != 4:
+            raise _lib.IronError("PyramidL2Loss: pred_img and trgt_img must both be [B, 3, H, W], got %s and %s"
+                                 % (tuple(pred_img.shape), tuple(trgt_img.shape)))
+        b, c, h, w = pred_img.shape
+        if c != 3:
+            raise _lib.IronError("PyramidL2Loss: the filter is [3, 3, 7, 7], so C must be 3 (got %d)" % c)
+        if h < 16 or w < 16:
+            raise _lib.IronError("PyramidL2Loss: H and W must be >= 16 (the fourth 2x2 pooling would be empty), got %dx%d" % (h, w))
+        _lib.require_cuda_f32(pred_img, "pred_img")
+        _lib.require_cuda_f32(trgt_img, "trgt_img")
+        return PyramidL2Fn.apply(pred_img, trgt_img, self._taps)
+
+
+def _fspecial_gauss_1d(size, sigma):
+    r"""1-D Gaussian kernel [1, 1, size], built in float32 on the host exactly as the reference builds it."""
+    coords = torch.arange(size, dtype=torch.float)
+    coords -= size // 2
+
+    g = torch.exp(-(coords**2) / (2 * sigma**2))
+    g /= g.sum()
+
+    return g.unsqueeze(0).unsqueeze(0)
+
+
+def _host_window(win: torch.Tensor, channels: int):
+    """The 1-D taps of a [C, 1, 1, ws] (or [1, 1, ws]) window as a ctypes float array; every channel must use the same taps."""
+    w = win.detach().to("cpu", torch.float32).reshape(-1, win.shape[-1])
+    if w.shape[0] not in (1, channels) or not bool((w == w[:1]).all()):
+        raise _lib.IronError("gaussian_filter: the window must be one 1-D kernel shared by all %d channels, got %s"
+                             % (channels, tuple(win.shape)))
+    taps = w[0].tolist()
+    return (C.c_float * len(taps))(*taps), len(taps)
+
+
+def _warn_short_axes(shape, ws: int) -> bool:
+    short = False
+    for i, s in enumerate(shape[2:]):
+        if s < ws:
+            short = True
+            warnings.warn(f"Skipping Gaussian Smoothing at dimension 2+{i} for input: {shape} and win size: {ws}")
+    return short
+
+
+def gaussian_filter(input, win):
+    r"""Valid separable blur of a [B, C, H, W] batch with the 1-D kernel `win` ([C, 1, 1, ws]); an axis shorter than the window is
+    not smoothed (with the reference's warning).  Inference only: there is no backward through this entry."""
+    refuse_grad("gaussian_filter", input, win)
+    assert all([ws == 1 for ws in win.shape[1:-1]]), win.shape
+    if input.dim() == 5:
+        raise _lib.IronError("gaussian_filter: 5-D (conv3d) input is not supported by iron_amd")
+    if input.dim() != 4:
+        raise NotImplementedError(input.shape)
+    b, c, h, w = input.shape
+    taps, ws = _host_window(win, c)
+    x = _lib.require_cuda_f32(input, "input")
+    _warn_short_axes(input.shape, ws)
+    ho = h - ws + 1 if h >= ws else h
+    wo = w - ws + 1 if w >= ws else w
+    out = torch.empty((b, c, ho, wo), dtype=torch.float32, device=x.device)
+    lib = _lib.load_train()
+    with torch.cuda.device(x.device):
+        _lib.check_train(lib.iron_gaussian_filter(x.data_ptr(), b * c, h, w, taps, ws, out.data_ptr(), _lib.stream_ptr(x.device)))
+    return out
+
+
+def ssim_loss_fn(X, Y, mask=None, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03)):
+    r"""1 - mean SSIM of X and Y ([B, C, H, W]); with `mask` ([B, 1, H, W], bool / uint8 / float) the valid SSIM map is padded by
+    win_size // 2 with 1.0 and averaged over the pixels kept by the win_size x win_size erosion of the mask."""
+    if not X.shape == Y.shape:
+        raise ValueError("Input images should have the same dimensions.")
+
+    if not X.type() == Y.type():
+        raise ValueError("Input images should have the same dtype.")
+
+    if len(X.shape) != 4:
+        raise ValueError(f"Input images should be 4-d tensors, but got {X.shape}")
+
+    if not (win_size % 2 == 1):
+        raise ValueError("Window size should be odd.")
+
+    _lib.require_cuda_f32(X, "X")
+    _lib.require_cuda_f32(Y, "Y")
+    win = _fspecial_gauss_1d(win_size, win_sigma).reshape(-1).tolist()
+    K1, K2 = K
+    C1 = (K1 * data_range) ** 2
+    C2 = (K2 * data_range) ** 2
+    b, c, h, w = X.shape
+    short = _warn_short_axes(X.shape, win_size)
+    m = None
+    if mask is not None:
+        if short:
+            raise _lib.IronError("ssim_loss_fn: a mask needs both image axes >= win_size (%d), got %dx%d (the reference fails "
+                                 "there with a shape mismatch)" % (win_size, h, w))
+        if tuple(mask.shape) != (b, 1, h, w):
+            raise _lib.IronError("ssim_loss_fn: mask must be [B, 1, H, W] = %s, got %s" % ((b, 1, h, w), tuple(mask.shape)))
+        if not mask.is_cuda or mask.device != X.device:
+            raise _lib.IronError("ssim_loss_fn: mask must be a CUDA tensor on %s" % X.device)
+        m = mask.detach()
+        if m.dtype not in (torch.bool, torch.uint8):
+            m = m.float()
+        m = m.contiguous()
+    return SSIMFn.apply(X, Y, m, (C.c_float * win_size)(*win), win_size, float(C1), float(C2))
