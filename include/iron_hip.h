@@ -39,7 +39,8 @@ typedef enum iron_status {
     IRON_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
     IRON_ERR_WORKSPACE = -5,    /* workspace too small                                         */
     IRON_ERR_RANGE = -6         /* IRON_H2_OVERFLOW=error: the previous call on this network left the fp16 range of the h2 core;
-                                   iron_mc_count: a vertex or triangle count reaches 2^31 */
+                                   iron_mc_count: a vertex or triangle count reaches 2^31;
+                                   iron_bake_*: see that block */
 } iron_status;
 
 int iron_version(void);
@@ -183,6 +184,45 @@ int iron_mc_count(const float* u, int32_t nx, int32_t ny, int32_t nz, float thre
                   int64_t* n_tris, void* stream);
 int iron_mc_emit(const float* u, int32_t nx, int32_t ny, int32_t nz, float threshold, void* workspace, float* verts, int32_t* tris,
                  void* stream);
+/* Material texture baking (models/export_materials.py: sample_surface :13-55, accumulate_splat_material :77-140 and the
+ * normalisation of export_materials :206-207), csrc/texbake.hip.
+ *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3]; uvs fp32 [n_uvs,2], face_uvs int32 [n_faces,3].
+ *   Surface sampling, two calls as the sample total depends on the data:
+ *     iron_bake_count   fp32 areas |cross(v0 - v2, v1 - v2)|, normalised by their sum (fp64, rounded to fp32); per-face count
+ *                       ceil(n_samples * a_f) in fp32; then sum(count) - n_samples draws with replacement among the faces with
+ *                       count > 0, each distinct drawn face losing one sample (numpy's `count[idx] -= 1`).  Draws come from
+ *                       Philox4x32-10 keyed by seed, counter (draw index, round, 0).  Leaves the per-face sample offsets in
+ *                       `workspace` (iron_bake_workspace_bytes(n_faces)), copies the counts before and after the removal to
+ *                       `ceil_counts` and `counts` [n_faces] (device, int32, either may be NULL) and returns the total in
+ *                       HOST *n_total: it synchronises `stream` once.  IRON_ERR_BAD_ARG
+ *                       if a face indexes outside verts or uvs; IRON_ERR_RANGE when n_samples > 2^24 (the count rule is fp32).
+ *     iron_bake_sample  n_total samples ordered by face; r1, r2 from Philox counter (sample index, round, 1), 53-bit uniform;
+ *                       P = (1 - sqrt(r1)) A + sqrt(r1) (1 - r2) B + sqrt(r1) r2 C in fp64, rounded to fp32, for the point
+ *                       [n_total,3] and, with the same weights, the uv [n_total,2]; face_idx [n_total] may be NULL.  Same mesh,
+ *                       seed and round as the count, nothing else may have touched the workspace in between.
+ *   iron_bake_sample_explicit: the same point rule for caller-given face_idx [n] and fp64 r1, r2 [n] (a sample whose face or
+ *                       indices are out of range comes out NaN).
+ *   Splat: acc is int64 [H*W][c_a + c_b + 1] in units of 2^-24, the last channel the weight; zero it before the first call.
+ *     iron_bake_splat   per sample: u = uv_x * W, v = H - uv_y * H (fp32); taps centre, (0,-1), (+1,0), (0,+1), (-1,0) shift
+ *                       (u, v) before floor; label = row * W + col (fp32) is kept iff 0 <= label < H*W (so a tap off the left
+ *                       edge wraps to the row above); weight exp(-((u - col - 1/2)^2 + (v - row - 1/2)^2) / 2) in fp32 from the
+ *                       shifted coordinates.  Adds round(w * value * 2^24) for values_a [n,c_a], values_b [n,c_b] (c_a + c_b
+ *                       <= 16) and round(w * 2^24).  A term above term_bound units, or not finite, is not added and sets
+ *                       *flag (device int32, sticky; zero it with acc).  Bitwise reproducible.  H*W <= 2^24.
+ *     iron_bake_resolve out [H*W][c] = fp32(acc) / (fp32(w) + 1e-10) in fp32, weight [H*W] = fp32(w); synchronises `stream`
+ *                       once and returns IRON_ERR_RANGE if *flag is set. */
+int iron_bake_workspace_bytes(int64_t n_faces, size_t* bytes);
+int iron_bake_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_uvs, const int32_t* face_uvs, int64_t n_faces,
+                    int64_t n_samples, uint64_t seed, uint32_t round, void* workspace, int32_t* ceil_counts, int32_t* counts,
+                    int64_t* n_total, void* stream);
+int iron_bake_sample(const float* verts, const int32_t* faces, const float* uvs, const int32_t* face_uvs, int64_t n_faces, uint64_t seed,
+                     uint32_t round, const void* workspace, int64_t n_total, float* points, float* uv, int32_t* face_idx, void* stream);
+int iron_bake_sample_explicit(const float* verts, int64_t n_verts, const int32_t* faces, const float* uvs, int64_t n_uvs,
+                              const int32_t* face_uvs, int64_t n_faces, const int32_t* face_idx, const double* r1, const double* r2,
+                              int64_t n, float* points, float* uv, void* stream);
+int iron_bake_splat(const float* uv, const float* values_a, int32_t c_a, const float* values_b, int32_t c_b, int64_t n, int32_t H,
+                    int32_t W, int64_t term_bound, int64_t* acc, int32_t* flag, void* stream);
+int iron_bake_resolve(const int64_t* acc, int32_t c, int32_t H, int32_t W, const int32_t* flag, float* out, float* weight, void* stream);
 int iron_neus_linspace(const float* near, const float* far, const float* lin, int64_t n, int32_t m, float* z, void* stream);
 int iron_neus_outside_z(const float* far, const float* rev, int64_t n, int32_t m, float offset, float* z, void* stream);
 int iron_neus_points(const float* rays_o, const float* rays_d, const float* z, int64_t n, int32_t m, float* pts, void* stream);

@@ -103,6 +103,12 @@ SYMBOLS = {
     "iron_mc_workspace_bytes": (C.c_int, [_I32, _I32, _I32, C.POINTER(_SZ)]),
     "iron_mc_count": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, C.POINTER(_I64), C.POINTER(_I64), _P]),
     "iron_mc_emit": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "iron_bake_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_bake_count": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, C.c_uint64, C.c_uint32, _P, _P, _P, C.POINTER(_I64), _P]),
+    "iron_bake_sample": (C.c_int, [_P, _P, _P, _P, _I64, C.c_uint64, C.c_uint32, _P, _I64, _P, _P, _P, _P]),
+    "iron_bake_sample_explicit": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+    "iron_bake_splat": (C.c_int, [_P, _P, _I32, _P, _I32, _I64, _I32, _I32, _I64, _P, _P, _P]),
+    "iron_bake_resolve": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "iron_neus_linspace": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "iron_neus_outside_z": (C.c_int, [_P, _P, _I64, _I32, _F, _P, _P]),
     "iron_neus_points": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
