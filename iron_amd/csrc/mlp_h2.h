@@ -823,6 +823,10 @@ __device__ __forceinline__ void sdf_hidden_stack_h2(Ring& ring, const char* lds,
 // No epilogue is exposed but the last hidden layer's tile 7 (it feeds the row dot): every tile's epilogue runs
 // in the MFMA gaps of the next tile, across slot and layer boundaries (a layer's tile 7 under the next layer's first tile, as
 // sdf_hidden_stack_h2 does).  Per tile the products and their order are unchanged: bias, [head,] the 16 hidden k-steps.
+#ifndef IRON_H1_NO_EPI
+#define IRON_H1_NO_EPI 0    // timing experiment only (results are garbage): the screen's epilogue ops are not issued
+#endif
+
 struct Epi1State {
     float z[16], e[16];
     u32x4 oh[2];
@@ -834,6 +838,9 @@ constexpr int kEpi1Ops = 104;
 constexpr int kEpi1OpsF32 = 96;   // last layer: f32 tile, no conversion
 
 __device__ __forceinline__ void epi1_op(Epi1State& st, int op, const f32x16& p) {
+#if IRON_H1_NO_EPI
+    return;
+#endif
     constexpr float kC1 = 144.26950408889634f;            // 100 * log2(e)
     constexpr float kC2 = 0.0069314718055994531f;         // ln(2) / 100
     if (op < 16) { st.e[op] = __builtin_fabsf(p[op]) * -kC1; pin1(st.e[op]); }
@@ -859,14 +866,27 @@ __device__ __forceinline__ void tile_from_epi(const Epi1State& es, TileH& t) {
     for (int s = 0; s < 2; ++s) t.h[s] = __builtin_bit_cast(half8, es.oh[s]);
 }
 
-// sync, take the next slot, read its first fragment, issue the refill
-__device__ __forceinline__ const char* h1_slot(Ring& ring, half8& fr0, int lane) {
+// Fragments read ahead of their MFMA.  A screen k-step is ONE MFMA: a fragment read one k-step ahead waits out most of the
+// ds_read_b128 latency behind it (tools/micro/mfma_gap_fill_f16.hip: 64 cycles per MFMA with no filler at all, against 32 for the
+// MFMA), so the fragments run two k-steps ahead, across tile boundaries within a slot.
+#ifndef IRON_H1_FRAG_AHEAD
+#define IRON_H1_FRAG_AHEAD 2   // 1 or 2
+#endif
+constexpr int kH1Ahead = IRON_H1_FRAG_AHEAD;
+static_assert(kH1Ahead == 1 || kH1Ahead == 2, "IRON_H1_FRAG_AHEAD: 1 or 2");
+struct H1Pre {
+    half8 f[kH1Ahead];   // the next kH1Ahead fragments of the slot, in order
+};
+
+// sync, take the next slot, read its first fragments, issue the refill
+__device__ __forceinline__ const char* h1_slot(Ring& ring, H1Pre& pre, int lane) {
     ring.sync();
     // (readfirstlane: in the tracer kernels the ring state travels through code the uniformity analysis gives up on, and Ring::step
     // pins the slot index in an SGPR)
     ring.b_take = __builtin_amdgcn_readfirstlane(ring.b_take);
     const RingStep st = ring.step();
-    fr0 = lds_frag(st.rd, 0, lane);
+#pragma unroll
+    for (int i = 0; i < kH1Ahead; ++i) pre.f[i] = lds_frag(st.rd, i, lane);
     __builtin_amdgcn_sched_barrier(0);
     dma_issue(st.src, st.wr, st.hidden, ring.wave);
     __builtin_amdgcn_sched_barrier(0);
@@ -874,24 +894,28 @@ __device__ __forceinline__ const char* h1_slot(Ring& ring, half8& fr0, int lane)
 }
 
 // The MFMAs of one output tile in slot rd: A = fragments fa, fa + 1, ...; B = the head fragments (HEAD: 3 k-steps) or in's 16 k-step
-// fragments.  fr0 holds fragment fa on entry and fragment f_next (if >= 0, same slot) on return, read under the last MFMA.
+// fragments.  pre holds fragments fa .. fa + kH1Ahead - 1 on entry and f_next .. f_next + kH1Ahead - 1 (if f_next >= 0, same slot)
+// on return, read under the last MFMAs.
 // EPI (0 none, 1 -> hi fragments in es.oh, 2 -> f32 tile in es.z): this call carries gaps g0 .. g0 + kM - 1 of the pending tile p's
 // epilogue, which is spread over GD gaps.  CARRY: the pending tile is in[7] itself (the previous layer's last tile), written back
 // behind gap GD - 1, before the k-step that first reads it.
 template <bool HEAD, int EPI, int GD, bool CARRY = false>
-__device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, int f_next, half8& fr0, const HeadFrag& hd,
+__device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, int f_next, H1Pre& pre, const HeadFrag& hd,
                                          TileH (&in)[kHidTiles], f32x16& acc, Epi1State& es, const f32x16& p, int g0, int lane) {
     constexpr int kM = HEAD ? kHeadKSteps : 16;
     constexpr int kOps = EPI == 2 ? kEpi1OpsF32 : kEpi1Ops;
     constexpr int kMaxPerGap = (kOps + GD - 1) / GD;
-    half8 fr[2];
-    fr[0] = fr0;
+    constexpr int kR = kH1Ahead + 1;   // fragment registers in rotation: k-step m reads fr[m % kR]
+    half8 fr[kR];
+#pragma unroll
+    for (int i = 0; i < kH1Ahead; ++i) fr[i] = pre.f[i];
 #pragma unroll
     for (int m = 0; m < kM; ++m) {
-        if (m + 1 < kM) fr[(m + 1) & 1] = lds_frag(rd, fa + m + 1, lane);
-        else if (f_next >= 0) fr0 = lds_frag(rd, f_next, lane);
-        if constexpr (HEAD) acc = mfma_h(fr[m & 1], hd.h[m], acc);
-        else acc = mfma_h(fr[m & 1], in[m >> 1].h[m & 1], acc);
+        const int ahead = m + kH1Ahead;   // the k-step whose fragment is read under this MFMA
+        if (ahead < kM) fr[ahead % kR] = lds_frag(rd, fa + ahead, lane);
+        else if (f_next >= 0) fr[ahead % kR] = lds_frag(rd, f_next + (ahead - kM), lane);
+        if constexpr (HEAD) acc = mfma_h(fr[m % kR], hd.h[m], acc);
+        else acc = mfma_h(fr[m % kR], in[m >> 1].h[m & 1], acc);
         if constexpr (EPI != 0) {
             const int g = g0 + m;
             if (g < GD) {
@@ -904,6 +928,8 @@ __device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, in
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+#pragma unroll
+    for (int i = 0; i < kH1Ahead; ++i) pre.f[i] = fr[(kM + i) % kR];
 }
 
 // One 256 -> 256 layer of the screen on 4 pair slots.  On entry the previous layer's tile 7 is pending in acc[1] (tile t accumulates in
@@ -914,8 +940,8 @@ __device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const Hea
     const int half = lane >> 5;
 #pragma unroll
     for (int j = 0; j < kHidTiles / 2; ++j) {
-        half8 fr0;
-        const char* rd = h1_slot(ring, fr0, lane);
+        H1Pre pre;
+        const char* rd = h1_slot(ring, pre, lane);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int t = 2 * j + u;
@@ -923,13 +949,13 @@ __device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const Hea
             acc[u] = lds_half_tile(bias, t, half);
             Epi1State es;
             if (t == 0) {
-                h1_mfmas<false, 1, 14, true>(rd, 0, fn, fr0, hd, in, acc[0], es, acc[1], 0, lane);
+                h1_mfmas<false, 1, 14, true>(rd, 0, fn, pre, hd, in, acc[0], es, acc[1], 0, lane);
             } else if constexpr (LAST) {
-                h1_mfmas<false, 2, 16>(rd, 16 * u, fn, fr0, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
+                h1_mfmas<false, 2, 16>(rd, 16 * u, fn, pre, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) hf[t > 0 ? t - 1 : 0][i] = es.z[i];
             } else {
-                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, fr0, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
+                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, pre, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
                 tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
             }
         }
@@ -943,29 +969,29 @@ __device__ __forceinline__ void h1_skip_layer(Ring& ring, const char* bias, cons
     const int half = lane >> 5;
     f32x16 a[kHidTiles];
     {
-        half8 fr0;
-        const char* rd = h1_slot(ring, fr0, lane);
+        H1Pre pre;
+        const char* rd = h1_slot(ring, pre, lane);
         Epi1State es;
 #pragma unroll
         for (int t = 0; t < kHidTiles; ++t) {
             a[t] = lds_half_tile(bias, t, half);
-            h1_mfmas<true, 1, kHidTiles * kHeadKSteps, true>(rd, kHeadKSteps * t, t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1, fr0, hd,
+            h1_mfmas<true, 1, kHidTiles * kHeadKSteps, true>(rd, kHeadKSteps * t, t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1, pre, hd,
                                                              in, a[t], es, acc[1], kHeadKSteps * t, lane);
         }
     }
 #pragma unroll
     for (int j = 0; j < kHidTiles / 2; ++j) {
-        half8 fr0;
-        const char* rd = h1_slot(ring, fr0, lane);
+        H1Pre pre;
+        const char* rd = h1_slot(ring, pre, lane);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int t = 2 * j + u;
             const int fn = u == 0 ? 16 : -1;
             Epi1State es;
             if (t == 0) {
-                h1_mfmas<false, 0, 16>(rd, 0, fn, fr0, hd, in, a[0], es, a[0], 0, lane);
+                h1_mfmas<false, 0, 16>(rd, 0, fn, pre, hd, in, a[0], es, a[0], 0, lane);
             } else {
-                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, fr0, hd, in, a[t], es, a[t > 0 ? t - 1 : 0], 0, lane);
+                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, pre, hd, in, a[t], es, a[t > 0 ? t - 1 : 0], 0, lane);
                 tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
             }
         }
@@ -995,17 +1021,17 @@ __device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds,
     TileH X[kHidTiles], Y[kHidTiles];
     f32x16 acc[2];
     {   // layer 0: one slot, the 8 head tiles back to back, each tile's epilogue under the next tile's MFMAs
-        half8 fr0;
-        const char* rd = h1_slot(ring, fr0, lane);
+        H1Pre pre;
+        const char* rd = h1_slot(ring, pre, lane);
 #pragma unroll
         for (int t = 0; t < kHidTiles; ++t) {
             acc[t & 1] = lds_half_tile(lds + kLdsBias, t, half);
             const int fn = t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1;
             Epi1State es;
             if (t == 0) {
-                h1_mfmas<true, 0, kHeadKSteps>(rd, 0, fn, fr0, hd, X, acc[0], es, acc[0], 0, lane);
+                h1_mfmas<true, 0, kHeadKSteps>(rd, 0, fn, pre, hd, X, acc[0], es, acc[0], 0, lane);
             } else {
-                h1_mfmas<true, 1, kHeadKSteps>(rd, kHeadKSteps * t, fn, fr0, hd, X, acc[t & 1], es, acc[(t - 1) & 1], 0, lane);
+                h1_mfmas<true, 1, kHeadKSteps>(rd, kHeadKSteps * t, fn, pre, hd, X, acc[t & 1], es, acc[(t - 1) & 1], 0, lane);
                 tile_from_epi(es, X[t > 0 ? t - 1 : 0]);
             }
         }
