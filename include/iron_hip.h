@@ -33,7 +33,8 @@ extern "C" {
 
 typedef enum iron_status {
     IRON_OK = 0,
-    IRON_ERR_BAD_ARG = -1,      /* null pointer, negative size, misaligned buffer              */
+    IRON_ERR_BAD_ARG = -1,      /* null pointer, negative size, misaligned buffer;
+                                   iron_bvh_boxes: a face indexes outside the vertices or has a non-finite vertex */
     IRON_ERR_UNSUPPORTED = -2,  /* network shape / mode the kernels are not built for          */
     IRON_ERR_HIP = -3,          /* a HIP runtime call failed; see iron_last_hip_error()        */
     IRON_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
@@ -223,6 +224,28 @@ int iron_bake_sample_explicit(const float* verts, int64_t n_verts, const int32_t
 int iron_bake_splat(const float* uv, const float* values_a, int32_t c_a, const float* values_b, int32_t c_b, int64_t n, int32_t H,
                     int32_t W, int64_t term_bound, int64_t* acc, int32_t* flag, void* stream);
 int iron_bake_resolve(const int64_t* acc, int32_t c, int32_t H, int32_t W, const int32_t* flag, float* out, float* weight, void* stream);
+/* Point-to-mesh distance over a linear BVH (evaluation/eval_mesh.py's igl.point_mesh_squared_distance), csrc/meshdist.hip.
+ *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1; vertices no face references are ignored.
+ *   Build, four steps on one stream; `workspace` (iron_bvh_workspace_bytes(n_faces)) then holds the tree and the triangles:
+ *     iron_bvh_keys     zeroes the workspace; box of the face centroids; keys [n_faces] (device uint64) = 30-bit Morton code of
+ *                       the centroid in that box << 32 | face index (all distinct).  A face index outside [0, n_verts) or a
+ *                       non-finite coordinate of a referenced vertex sets a device flag in the workspace.
+ *     (caller)          sorts the keys ascending into sorted_keys (any device sort: the keys are unique).
+ *     iron_bvh_hierarchy  Karras' construction over the sorted keys: n_faces - 1 internal nodes, children and parent links.
+ *     iron_bvh_boxes    the triangles copied in leaf order, the boxes bottom-up (per-node arrival counters, zeroed here; unions
+ *                       are min/max, so the workspace is bitwise reproducible).  Synchronises `stream` once; IRON_ERR_BAD_ARG if
+ *                       the flag is set.
+ *   iron_point_mesh_distance  per point [n_points,3]: the nearest face's squared distance sqr_dist (fp32), index face_idx (int32)
+ *                       and closest point closest [n_points,3] (fp32), in the caller's point order; ties in the fp32 distance go
+ *                       to the smallest face index.  A point equal to a vertex of a face gets sqr_dist 0 and that vertex bitwise.
+ *                       A non-finite point gets NaN, -1, NaN.  Same workspace and n_faces as the build; no host wait. */
+int iron_bvh_workspace_bytes(int64_t n_faces, size_t* bytes);
+int iron_bvh_keys(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* workspace, uint64_t* keys, void* stream);
+int iron_bvh_hierarchy(const uint64_t* sorted_keys, int64_t n_faces, void* workspace, void* stream);
+int iron_bvh_boxes(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const uint64_t* sorted_keys, void* workspace,
+                   void* stream);
+int iron_point_mesh_distance(const void* workspace, int64_t n_faces, const float* points, int64_t n_points, float* sqr_dist,
+                             int32_t* face_idx, float* closest, void* stream);
 int iron_neus_linspace(const float* near, const float* far, const float* lin, int64_t n, int32_t m, float* z, void* stream);
 int iron_neus_outside_z(const float* far, const float* rev, int64_t n, int32_t m, float offset, float* z, void* stream);
 int iron_neus_points(const float* rays_o, const float* rays_d, const float* z, int64_t n, int32_t m, float* pts, void* stream);

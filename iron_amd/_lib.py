@@ -109,6 +109,11 @@ SYMBOLS = {
     "iron_bake_sample_explicit": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
     "iron_bake_splat": (C.c_int, [_P, _P, _I32, _P, _I32, _I64, _I32, _I32, _I64, _P, _P, _P]),
     "iron_bake_resolve": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "iron_bvh_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_bvh_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "iron_bvh_hierarchy": (C.c_int, [_P, _I64, _P, _P]),
+    "iron_bvh_boxes": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "iron_point_mesh_distance": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
     "iron_neus_linspace": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "iron_neus_outside_z": (C.c_int, [_P, _P, _I64, _I32, _F, _P, _P]),
     "iron_neus_points": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),

@@ -140,7 +140,8 @@ extern "C" int iron_last_hip_error(void) { return g_last_hip_error; }
 extern "C" const char* iron_strerror(int status) {
     switch (status) {
         case IRON_OK: return "ok";
-        case IRON_ERR_BAD_ARG: return "bad argument (null pointer, negative size or misaligned buffer)";
+        case IRON_ERR_BAD_ARG: return "bad argument (null pointer, negative size or misaligned buffer; for a mesh: a face index out of "
+                                     "range or a non-finite vertex)";
         case IRON_ERR_UNSUPPORTED: return "unsupported network shape or mode for the gfx950 kernels";
         case IRON_ERR_HIP: return "HIP runtime error (see iron_last_hip_error)";
         case IRON_ERR_NO_DEVICE: return "no gfx950 device visible";
