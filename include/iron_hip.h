@@ -544,7 +544,9 @@ int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, fl
  *   iron_set_sampler_screen:   on = 1 screen, 0 don't, -1 the default (IRON_SAMPLER_SCREEN=0: off, else on).  Process-wide;
  *                              returns the previous state.
  *   iron_sampler_screen_debug: test hooks, process-wide.  what 0: value > 0 forces the margin delta (0 restores the calibrated
- *                              one); what 1: value >= 1 caps the resolve list at that many samples per part (0 restores).
+ *                              one); what 1: value >= 1 caps the resolve list at that many samples per part (0 restores);
+ *                              what 2: value 1 makes iron_sdf_screen_forward evaluate 32 points per wave instead of the
+ *                              sampler's 64 (bit-identical values; 0 restores).
  *   iron_trace_screen_counts:  synchronises `stream`; from the workspace of the last iron_trace / iron_trace_phase(0) /
  *                              iron_trace_stage(1) call: out[0] screened evaluations (speculative ones included), out[1] exactly
  *                              resolved samples, out[2] rays that overflowed the resolve list (marched unscreened), out[3] the

@@ -41,7 +41,11 @@ OPTIONAL_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 # per-source additions.  getall_rev.hip: its ring step carries a longer staged epilogue than mlp_h2.h's; with the default
 # -pragma-unroll-threshold (16 K) LLVM silently leaves the 16-k-step loop of step_hidden_x rolled (runtime stage dispatch, the
 # epilogue state in scratch: 19 630 scratch instructions instead of ~200)
-SOURCE_FLAGS = {"getall_rev.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
+# h2_kernels.hip / trace.hip: likewise the 35-k-step MFMA loop of the skip layer's tile slots in the screen's 64-sample form
+# (mlp_h2.h: h1_mfmas with two point tiles), left rolled otherwise (its register arrays then live in scratch)
+SOURCE_FLAGS = {"getall_rev.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+                "h2_kernels.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+                "trace.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
 
 
 def _hipcc() -> str:

@@ -808,57 +808,78 @@ __device__ __forceinline__ void sdf_hidden_stack_h2(Ring& ring, const char* lds,
 }
 
 // ---- the screen: one product per MAC -------------------------------------------------------------------
-// sdf_hidden_stack_h1 takes every layer as wh * xh only: ONE v_mfma_f32_32x32x16_f16 and one ds_read_b128 per k-step, and the
-// epilogue rounds the activation to a single fp16 piece.  Weights and activations are therefore fp16 (11-bit significands) with fp32
+// sdf_hidden_stack_h1 takes every layer as wh * xh only: ONE v_mfma_f32_32x32x16_f16 per point tile and k-step, and the epilogue
+// rounds the activation to a single fp16 piece.  Weights and activations are therefore fp16 (11-bit significands) with fp32
 // accumulation: the value is NOT fp32-accurate.  The dense sampler (trace.hip) uses it only to decide signs far from zero, with an
 // empirical margin it calibrates per network against the h2 value.
 //
+// NP point tiles of 32 points per wave (NP = 2: 64 samples): every weight fragment read from LDS feeds NP MFMAs, one per point tile,
+// each with its own accumulators, so a slot, its LDS-DMA issue and its barrier serve NP x 32 points.  Per point the products, their
+// order and the epilogue are those of NP = 1: the values are bit-identical (test_gpu_screen_64.py).
+//
 // It walks a ring of its own on the h1 stream (pack_h2.hip, written by the same pack launches as the h2 stream): the hi pieces of the
-// h2 fragments without the lo pieces, in the same fragment order ([ks][lane][j], 1 KiB per k-step fragment).  Slot sequence (30 slots
-// of 32 KiB, 960 KiB per evaluation, against the 72 slots and 1.92 MB of the h2 stream, whose lo halves it used to refill unread):
+// h2 fragments without the lo pieces, in the same fragment order ([ks][lane][j], 1 KiB per k-step fragment).  Slot sequence (33 slots
+// of 32 KiB per evaluation):
 //   layer 0            ONE head slot: the head fragments of all 8 tiles, tile t at fragments 3t .. 3t + 2 (24 KiB + 8 KiB of zeros)
 //   a hidden layer     4 pair slots: tiles 2j, 2j + 1 at fragments 0..15 | 16..31
-//   the skip layer     a head slot of its 8 tiles' head fragments (as layer 0), then its 4 pair slots
+//   the skip layer     8 tile slots: tile t's 3 head fragments at 0..2, its 16 hidden fragments at 3..18 (19 KiB + 13 KiB of zeros),
+//                      so that a tile is finished within its slot (bias, head, hidden) and no partial tiles are held across the layer
 // Every slot is a "hidden" (32 KiB) slot for the ring, so the ordinary Ring / dma_issue walk it (h2_setup on the h1 stream).
-// No epilogue is exposed but the last hidden layer's tile 7 (it feeds the row dot): every tile's epilogue runs
-// in the MFMA gaps of the next tile, across slot and layer boundaries (a layer's tile 7 under the next layer's first tile, as
-// sdf_hidden_stack_h2 does).  Per tile the products and their order are unchanged: bias, [head,] the 16 hidden k-steps.
+// No epilogue is exposed but the last hidden layer's tile 7: every tile's epilogue runs in the MFMA gaps of the next tile, across
+// slot and layer boundaries (a layer's tile 7 under the next layer's first tile, as sdf_hidden_stack_h2 does).  The last layer's
+// tiles go straight into the row dot of the output (in tile order, as row_dot_lds sums them) instead of being held as f32 tiles.
 #ifndef IRON_H1_NO_EPI
-#define IRON_H1_NO_EPI 0    // timing experiment only (results are garbage): the screen's epilogue ops are not issued
+#define IRON_H1_NO_EPI 0    // timing experiment only (results are garbage): of the screen's epilogue only the 8 conversions remain
 #endif
+constexpr int kH1PointTiles = 2;   // point tiles per wave of the sampler's screen and of k_sdf_values_h1
 
 struct Epi1State {
     float z[16], e[16];
     u32x4 oh[2];
 };
 
-// the epilogue of one tile as 104 instructions in dependency order (softplus_100 as in epi_gap, then 8 packed conversions), cut
-// into the MFMA gaps that carry it.  An instruction's operands come from >= 8 instructions earlier.
+// the epilogue of one tile as 104 instructions in dependency order (softplus_100 as in epi_gap, then packed conversions), cut into
+// the MFMA gaps that carry it.  Elements 0..7 first (6 stages of 8, then their 4 conversions), then elements 8..15: an instruction's
+// operands come from >= 8 instructions earlier (the conversions: >= 7), and only half a tile of e / z is live at a time.
 constexpr int kEpi1Ops = 104;
 constexpr int kEpi1OpsF32 = 96;   // last layer: f32 tile, no conversion
 
+template <bool F32>
 __device__ __forceinline__ void epi1_op(Epi1State& st, int op, const f32x16& p) {
-#if IRON_H1_NO_EPI
-    return;
-#endif
     constexpr float kC1 = 144.26950408889634f;            // 100 * log2(e)
     constexpr float kC2 = 0.0069314718055994531f;         // ln(2) / 100
-    if (op < 16) { st.e[op] = __builtin_fabsf(p[op]) * -kC1; pin1(st.e[op]); }
-    else if (op < 32) { const int i = op - 16; st.e[i] = __builtin_amdgcn_exp2f(st.e[i]); pin1(st.e[i]); }
-    else if (op < 48) { const int i = op - 32; st.e[i] = 1.0f + st.e[i]; pin1(st.e[i]); }
-    else if (op < 64) { const int i = op - 48; st.e[i] = __builtin_amdgcn_logf(st.e[i]); pin1(st.e[i]); }
-    else if (op < 80) { const int i = op - 64; st.z[i] = relu_med3(p[i]); pin1(st.z[i]); }
-    else if (op < 96) { const int i = op - 80; st.z[i] = __builtin_fmaf(st.e[i], kC2, st.z[i]); pin1(st.z[i]); }
-    else if (op < 104) {
-        const int q = op - 96;
-        unsigned h = __builtin_bit_cast(unsigned, cvt_pk_rn(st.z[2 * q], st.z[2 * q + 1]));
-        pin1u(h);
-        st.oh[q >> 2][q & 3] = h;
+    constexpr int kHalf = F32 ? 48 : 52;
+    const int h = op / kHalf, lo = op % kHalf;
+#if IRON_H1_NO_EPI   // only the conversions, straight from the accumulators: the next layer's MFMAs keep real operands
+    if (lo >= 48) {
+        const int q = 4 * h + lo - 48;
+        st.oh[q >> 2][q & 3] = __builtin_bit_cast(unsigned, cvt_pk_rn(p[2 * q], p[2 * q + 1]));
     }
+    if (lo >= 40 && lo < 48) st.z[8 * h + lo - 40] = p[8 * h + lo - 40];
+    return;
+#endif
+    if (lo >= 48) {
+        const int q = 4 * h + lo - 48;
+        unsigned u = __builtin_bit_cast(unsigned, cvt_pk_rn(st.z[2 * q], st.z[2 * q + 1]));
+        pin1u(u);
+        st.oh[q >> 2][q & 3] = u;
+        return;
+    }
+    const int stage = lo >> 3, i = 8 * h + (lo & 7);
+    if (stage == 0) { st.e[i] = __builtin_fabsf(p[i]) * -kC1; pin1(st.e[i]); }
+    else if (stage == 1) { st.e[i] = __builtin_amdgcn_exp2f(st.e[i]); pin1(st.e[i]); }
+    else if (stage == 2) { st.e[i] = 1.0f + st.e[i]; pin1(st.e[i]); }
+    else if (stage == 3) { st.e[i] = __builtin_amdgcn_logf(st.e[i]); pin1(st.e[i]); }
+    else if (stage == 4) { st.z[i] = relu_med3(p[i]); pin1(st.z[i]); }
+    else { st.z[i] = __builtin_fmaf(st.e[i], kC2, st.z[i]); pin1(st.z[i]); }
 }
 
 struct TileH {
     half8 h[2];
+};
+
+struct HeadH {
+    half8 h[kHeadKSteps];
 };
 
 __device__ __forceinline__ void tile_from_epi(const Epi1State& es, TileH& t) {
@@ -866,11 +887,19 @@ __device__ __forceinline__ void tile_from_epi(const Epi1State& es, TileH& t) {
     for (int s = 0; s < 2; ++s) t.h[s] = __builtin_bit_cast(half8, es.oh[s]);
 }
 
-// Fragments read ahead of their MFMA.  A screen k-step is ONE MFMA: a fragment read one k-step ahead waits out most of the
-// ds_read_b128 latency behind it (tools/micro/mfma_gap_fill_f16.hip: 64 cycles per MFMA with no filler at all, against 32 for the
-// MFMA), so the fragments run two k-steps ahead, across tile boundaries within a slot.
+// one finished f32 tile of the last hidden layer into the row dot, exactly as row_dot_lds accumulates it
+__device__ __forceinline__ void row_dot_tile(const char* __restrict__ row, int t, int half, const float* z, float& s) {
+    const f32x16 w = lds_half_tile(row, t, half);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s = fmaf(w[r], z[r], s);
+}
+
+// Fragments read ahead of their MFMAs, across tile boundaries within a slot.  With one point tile a fragment read one k-step ahead of
+// its single MFMA waited out most of the ds_read_b128 latency behind it (tools/micro/mfma_gap_fill_f16.hip), so it ran two ahead; with
+// two point tiles a read has two MFMAs (64 cycles) behind it, and the four registers of a second fragment in flight are the ones
+// that keep the 64-sample kernels free of scratch.
 #ifndef IRON_H1_FRAG_AHEAD
-#define IRON_H1_FRAG_AHEAD 2   // 1 or 2
+#define IRON_H1_FRAG_AHEAD 1   // 1 or 2
 #endif
 constexpr int kH1Ahead = IRON_H1_FRAG_AHEAD;
 static_assert(kH1Ahead == 1 || kH1Ahead == 2, "IRON_H1_FRAG_AHEAD: 1 or 2");
@@ -893,16 +922,17 @@ __device__ __forceinline__ const char* h1_slot(Ring& ring, H1Pre& pre, int lane)
     return st.rd;
 }
 
-// The MFMAs of one output tile in slot rd: A = fragments fa, fa + 1, ...; B = the head fragments (HEAD: 3 k-steps) or in's 16 k-step
-// fragments.  pre holds fragments fa .. fa + kH1Ahead - 1 on entry and f_next .. f_next + kH1Ahead - 1 (if f_next >= 0, same slot)
-// on return, read under the last MFMAs.
-// EPI (0 none, 1 -> hi fragments in es.oh, 2 -> f32 tile in es.z): this call carries gaps g0 .. g0 + kM - 1 of the pending tile p's
-// epilogue, which is spread over GD gaps.  CARRY: the pending tile is in[7] itself (the previous layer's last tile), written back
-// behind gap GD - 1, before the k-step that first reads it.
-template <bool HEAD, int EPI, int GD, bool CARRY = false>
-__device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, int f_next, H1Pre& pre, const HeadFrag& hd,
-                                         TileH (&in)[kHidTiles], f32x16& acc, Epi1State& es, const f32x16& p, int g0, int lane) {
-    constexpr int kM = HEAD ? kHeadKSteps : 16;
+// The MFMAs of one output tile in slot rd, for each of the NP point tiles: A = fragments fa, fa + 1, ...; B = KH head k-steps
+// (hd[p]), then KX hidden k-steps (in[p]'s fragments).  pre holds fragments fa .. fa + kH1Ahead - 1 on entry and f_next ..
+// f_next + kH1Ahead - 1 (if f_next >= 0, same slot) on return, read under the last MFMAs.
+// EPI (0 none, 1 -> hi fragments in es[p].oh, 2 -> f32 tile in es[p].z): this call carries gaps g0 .. g0 + kM - 1 of the pending
+// tiles pt[p]'s epilogue, which is spread over GD gaps.  CARRY: the pending tile is in[p][7] itself (the previous layer's last tile),
+// written back behind gap GD - 1, before the k-step that first reads it.
+template <int NP, int KH, int KX, int EPI, int GD, bool CARRY = false>
+__device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, int f_next, H1Pre& pre, const HeadH (&hd)[NP],
+                                         TileH (&in)[NP][kHidTiles], f32x16 (&acc)[NP], Epi1State (&es)[NP],
+                                         const f32x16 (&pt)[NP], int g0, int lane) {
+    constexpr int kM = KH + KX;
     constexpr int kOps = EPI == 2 ? kEpi1OpsF32 : kEpi1Ops;
     constexpr int kMaxPerGap = (kOps + GD - 1) / GD;
     constexpr int kR = kH1Ahead + 1;   // fragment registers in rotation: k-step m reads fr[m % kR]
@@ -914,16 +944,24 @@ __device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, in
         const int ahead = m + kH1Ahead;   // the k-step whose fragment is read under this MFMA
         if (ahead < kM) fr[ahead % kR] = lds_frag(rd, fa + ahead, lane);
         else if (f_next >= 0) fr[ahead % kR] = lds_frag(rd, f_next + (ahead - kM), lane);
-        if constexpr (HEAD) acc = mfma_h(fr[m % kR], hd.h[m], acc);
-        else acc = mfma_h(fr[m % kR], in[m >> 1].h[m & 1], acc);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            if (m < KH) acc[p] = mfma_h(fr[m % kR], hd[p].h[m], acc[p]);
+            else acc[p] = mfma_h(fr[m % kR], in[p][(m - KH) >> 1].h[(m - KH) & 1], acc[p]);
+        }
         if constexpr (EPI != 0) {
             const int g = g0 + m;
             if (g < GD) {
                 const int o0 = g * kOps / GD, o1 = (g + 1) * kOps / GD;
 #pragma unroll
                 for (int k = 0; k < kMaxPerGap; ++k)
-                    if (o0 + k < o1) epi1_op(es, o0 + k, p);
-                if (CARRY && g == GD - 1) tile_from_epi(es, in[kHidTiles - 1]);
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        if (o0 + k < o1) epi1_op<EPI == 2>(es[p], o0 + k, pt[p]);
+                if (CARRY && g == GD - 1) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) tile_from_epi(es[p], in[p][kHidTiles - 1]);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -932,11 +970,32 @@ __device__ __forceinline__ void h1_mfmas(const char* __restrict__ rd, int fa, in
     for (int i = 0; i < kH1Ahead; ++i) pre.f[i] = fr[(kM + i) % kR];
 }
 
-// One 256 -> 256 layer of the screen on 4 pair slots.  On entry the previous layer's tile 7 is pending in acc[1] (tile t accumulates in
-// acc[t & 1]); tile 0 finishes it into in[7] by k-step 13.  On return this layer's tile 7 is pending in acc[1].  LAST: f32 tiles in hf.
-template <bool LAST>
-__device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, TileH (&in)[kHidTiles],
-                                         TileH (&out)[kHidTiles], f32x16 (&acc)[2], f32x16 (&hf)[kHidTiles]) {
+// acc[p][u] for every point tile, from the bias of output tile t
+template <int NP>
+__device__ __forceinline__ void h1_bias(const char* bias, int t, int half, f32x16 (&acc)[NP][2], int u) {
+    const f32x16 b = lds_half_tile(bias, t, half);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p][u] = b;
+}
+
+template <int NP>
+__device__ __forceinline__ void h1_pick(f32x16 (&acc)[NP][2], int u, f32x16 (&a)[NP]) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) a[p] = acc[p][u];
+}
+
+template <int NP>
+__device__ __forceinline__ void h1_put(f32x16 (&acc)[NP][2], int u, const f32x16 (&a)[NP]) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p][u] = a[p];
+}
+
+// One 256 -> 256 layer of the screen on 4 pair slots.  On entry the previous layer's tile 7 is pending in acc[p][1] (tile t
+// accumulates in acc[p][t & 1]); tile 0 finishes it into in[p][7] by k-step 13.  On return this layer's tile 7 is pending in
+// acc[p][1].  LAST: the finished f32 tiles 0..6 go into the row dots s[p] (rows: the last-layer row block).
+template <int NP, bool LAST>
+__device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const HeadH (&hd)[NP], int lane, TileH (&in)[NP][kHidTiles],
+                                         TileH (&out)[NP][kHidTiles], f32x16 (&acc)[NP][2], const char* rows, float (&s)[NP]) {
     const int half = lane >> 5;
 #pragma unroll
     for (int j = 0; j < kHidTiles / 2; ++j) {
@@ -946,106 +1005,164 @@ __device__ __forceinline__ void h1_layer(Ring& ring, const char* bias, const Hea
         for (int u = 0; u < 2; ++u) {
             const int t = 2 * j + u;
             const int fn = u == 0 ? 16 : -1;
-            acc[u] = lds_half_tile(bias, t, half);
-            Epi1State es;
+            h1_bias<NP>(bias, t, half, acc, u);
+            f32x16 a[NP], pt[NP];
+            h1_pick<NP>(acc, u, a);
+            h1_pick<NP>(acc, u ^ 1, pt);
+            Epi1State es[NP];
             if (t == 0) {
-                h1_mfmas<false, 1, 14, true>(rd, 0, fn, pre, hd, in, acc[0], es, acc[1], 0, lane);
+                h1_mfmas<NP, 0, 16, 1, 14, true>(rd, 0, fn, pre, hd, in, a, es, pt, 0, lane);
             } else if constexpr (LAST) {
-                h1_mfmas<false, 2, 16>(rd, 16 * u, fn, pre, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
+                h1_mfmas<NP, 0, 16, 2, 16>(rd, 16 * u, fn, pre, hd, in, a, es, pt, 0, lane);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) hf[t > 0 ? t - 1 : 0][i] = es.z[i];
+                for (int p = 0; p < NP; ++p) row_dot_tile(rows, t - 1, half, es[p].z, s[p]);
             } else {
-                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, pre, hd, in, acc[u], es, acc[u ^ 1], 0, lane);
-                tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
+                h1_mfmas<NP, 0, 16, 1, 16>(rd, 16 * u, fn, pre, hd, in, a, es, pt, 0, lane);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) tile_from_epi(es[p], out[p][t > 0 ? t - 1 : 0]);
             }
+            h1_put<NP>(acc, u, a);
         }
     }
 }
 
-// The skip layer: its head slot first (all 8 tiles' bias + head product, 24 MFMAs, under which the previous layer's tile 7 is finished
-// into in[7]), then its 4 pair slots add the hidden products.  The 8 partial tiles are held in registers across the layer.
-__device__ __forceinline__ void h1_skip_layer(Ring& ring, const char* bias, const HeadFrag& hd, int lane, TileH (&in)[kHidTiles],
-                                              TileH (&out)[kHidTiles], f32x16 (&acc)[2]) {
+// The skip layer on 8 tile slots: tile t's bias, its 3 head k-steps, then its 16 hidden k-steps, all in slot t; the previous tile's
+// epilogue runs under them (the previous layer's tile 7 under tile 0, finished into in[p][7] by k-step 3 + 14).
+template <int NP>
+__device__ __forceinline__ void h1_skip_layer(Ring& ring, const char* bias, const HeadH (&hd)[NP], int lane, TileH (&in)[NP][kHidTiles],
+                                              TileH (&out)[NP][kHidTiles], f32x16 (&acc)[NP][2]) {
     const int half = lane >> 5;
-    f32x16 a[kHidTiles];
-    {
+#pragma unroll
+    for (int t = 0; t < kHidTiles; ++t) {
         H1Pre pre;
         const char* rd = h1_slot(ring, pre, lane);
-        Epi1State es;
+        const int u = t & 1;
+        h1_bias<NP>(bias, t, half, acc, u);
+        f32x16 a[NP], pt[NP];
+        h1_pick<NP>(acc, u, a);
+        h1_pick<NP>(acc, u ^ 1, pt);
+        Epi1State es[NP];
+        if (t == 0) {
+            h1_mfmas<NP, kHeadKSteps, 16, 1, kHeadKSteps + 14, true>(rd, 0, -1, pre, hd, in, a, es, pt, 0, lane);
+        } else {
+            h1_mfmas<NP, kHeadKSteps, 16, 1, kHeadKSteps + 16>(rd, 0, -1, pre, hd, in, a, es, pt, 0, lane);
 #pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            a[t] = lds_half_tile(bias, t, half);
-            h1_mfmas<true, 1, kHidTiles * kHeadKSteps, true>(rd, kHeadKSteps * t, t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1, pre, hd,
-                                                             in, a[t], es, acc[1], kHeadKSteps * t, lane);
+            for (int p = 0; p < NP; ++p) tile_from_epi(es[p], out[p][t - 1]);
         }
+        h1_put<NP>(acc, u, a);
     }
-#pragma unroll
-    for (int j = 0; j < kHidTiles / 2; ++j) {
-        H1Pre pre;
-        const char* rd = h1_slot(ring, pre, lane);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = 2 * j + u;
-            const int fn = u == 0 ? 16 : -1;
-            Epi1State es;
-            if (t == 0) {
-                h1_mfmas<false, 0, 16>(rd, 0, fn, pre, hd, in, a[0], es, a[0], 0, lane);
-            } else {
-                h1_mfmas<false, 1, 16>(rd, 16 * u, fn, pre, hd, in, a[t], es, a[t > 0 ? t - 1 : 0], 0, lane);
-                tile_from_epi(es, out[t > 0 ? t - 1 : 0]);
-            }
-        }
-    }
-    acc[1] = a[kHidTiles - 1];
 }
 
-// SDFNetwork hidden stack on the screen (one product per MAC).  Same contract as sdf_hidden_stack_h2 (all four waves together,
-// hf = the last hidden activation), but on a ring started on the h1 stream.
-template <bool FAST>
-__device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds, int n_hidden_layers, int skip_layer,
-                                                    float scale, float x, float y, float z, int lane,
-                                                    f32x16 (&hf)[kHidTiles]) {
-    const int half = lane >> 5;
-    float pe[kHeadSlots];
+// the fp16 head fragments of the NP point tiles (the positional encoding of this lane half)
+template <int NP>
+__device__ __forceinline__ void h1_head_frags(const float (&x)[NP], const float (&y)[NP], const float (&z)[NP], float scale, int half,
+                                              HeadH (&hd)[NP]) {
 #pragma unroll
-    for (int i = 0; i < kHeadSlots; ++i) pe[i] = 0.0f;
-    head_fill<kSdfPeLevels>(x * scale, y * scale, z * scale, half, pe);
-    HeadFrag hd;
+    for (int p = 0; p < NP; ++p) {
+        float pe[kHeadSlots];
 #pragma unroll
-    for (int s = 0; s < kHeadKSteps; ++s) {
-        u32x4 hh;
+        for (int i = 0; i < kHeadSlots; ++i) pe[i] = 0.0f;
+        head_fill<kSdfPeLevels>(x[p] * scale, y[p] * scale, z[p] * scale, half, pe);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) hh[i] = __builtin_bit_cast(unsigned, cvt_pk_rn(pe[8 * s + 2 * i], pe[8 * s + 2 * i + 1]));
-        hd.h[s] = __builtin_bit_cast(half8, hh);
+        for (int k = 0; k < kHeadKSteps; ++k) {
+            u32x4 hh;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hh[i] = __builtin_bit_cast(unsigned, cvt_pk_rn(pe[8 * k + 2 * i], pe[8 * k + 2 * i + 1]));
+            hd[p].h[k] = __builtin_bit_cast(half8, hh);
+        }
     }
-    TileH X[kHidTiles], Y[kHidTiles];
-    f32x16 acc[2];
+}
+
+// SDFNetwork hidden stack on the screen (one product per MAC), NP x 32 points per wave: point tile p's point on column lane & 31
+// is (x[p], y[p], z[p]) (lanes j and j + 32 hold the same point).  All four waves together, on a ring started on the h1 stream.
+// On return s[p] = this lane half's part of the output row dot (as row_dot_lds before its cross-half sum).
+template <bool FAST, int NP>
+__device__ __forceinline__ void sdf_hidden_stack_h1(Ring& ring, const char* lds, int n_hidden_layers, int skip_layer, float scale,
+                                                    const float (&x)[NP], const float (&y)[NP], const float (&z)[NP], int lane,
+                                                    float (&s)[NP]) {
+    const int half = lane >> 5;
+    HeadH hd[NP];
+    h1_head_frags<NP>(x, y, z, scale, half, hd);
+    TileH X[NP][kHidTiles], Y[NP][kHidTiles];
+    f32x16 acc[NP][2];
     {   // layer 0: one slot, the 8 head tiles back to back, each tile's epilogue under the next tile's MFMAs
         H1Pre pre;
         const char* rd = h1_slot(ring, pre, lane);
 #pragma unroll
         for (int t = 0; t < kHidTiles; ++t) {
-            acc[t & 1] = lds_half_tile(lds + kLdsBias, t, half);
+            const int u = t & 1;
+            h1_bias<NP>(lds + kLdsBias, t, half, acc, u);
+            f32x16 a[NP], pt[NP];
+            h1_pick<NP>(acc, u, a);
+            h1_pick<NP>(acc, u ^ 1, pt);
             const int fn = t + 1 < kHidTiles ? kHeadKSteps * (t + 1) : -1;
-            Epi1State es;
+            Epi1State es[NP];
             if (t == 0) {
-                h1_mfmas<true, 0, kHeadKSteps>(rd, 0, fn, pre, hd, X, acc[0], es, acc[0], 0, lane);
+                h1_mfmas<NP, kHeadKSteps, 0, 0, kHeadKSteps>(rd, 0, fn, pre, hd, X, a, es, pt, 0, lane);
             } else {
-                h1_mfmas<true, 1, kHeadKSteps>(rd, kHeadKSteps * t, fn, pre, hd, X, acc[t & 1], es, acc[(t - 1) & 1], 0, lane);
-                tile_from_epi(es, X[t > 0 ? t - 1 : 0]);
+                h1_mfmas<NP, kHeadKSteps, 0, 1, kHeadKSteps>(rd, kHeadKSteps * t, fn, pre, hd, X, a, es, pt, 0, lane);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) tile_from_epi(es[p], X[p][t - 1]);
             }
+            h1_put<NP>(acc, u, a);
         }
     }
+    const char* rows = lds + kLdsRows;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) s[p] = 0.0f;
     // layers (1,2), (3,4), (5,6): X -> Y -> X, the skip layer second in its pair (the launchers admit 8 hidden layers, skip at 4 only)
     for (int l = 1; l + 1 < n_hidden_layers - 1; l += 2) {
         const char* bias_a = lds + kLdsBias + l * 1024;
         const char* bias_b = bias_a + 1024;
-        h1_layer<false>(ring, bias_a, hd, lane, X, Y, acc, hf);
-        if (l + 1 == skip_layer) h1_skip_layer(ring, bias_b, hd, lane, Y, X, acc);
-        else h1_layer<false>(ring, bias_b, hd, lane, Y, X, acc, hf);
+        h1_layer<NP, false>(ring, bias_a, hd, lane, X, Y, acc, rows, s);
+        if (l + 1 == skip_layer) {
+            // the head fragments again, from the point: cheaper than holding them across the layers between
+            float xs[NP], ys[NP], zs[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                xs[p] = x[p]; ys[p] = y[p]; zs[p] = z[p];
+                asm volatile("" : "+v"(xs[p]), "+v"(ys[p]), "+v"(zs[p]));   // (not CSE'd with layer 0's)
+            }
+            HeadH hs[NP];
+            h1_head_frags<NP>(xs, ys, zs, scale, half, hs);
+            h1_skip_layer<NP>(ring, bias_b, hs, lane, Y, X, acc);
+        }
+        else h1_layer<NP, false>(ring, bias_b, hd, lane, Y, X, acc, rows, s);
     }
-    h1_layer<true>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, acc, hf);
-    hf[kHidTiles - 1] = softplus_tile<FAST>(acc[1]);
+    h1_layer<NP, true>(ring, lds + kLdsBias + (n_hidden_layers - 1) * 1024, hd, lane, X, Y, acc, rows, s);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const f32x16 h7 = softplus_tile<FAST>(acc[p][1]);
+        float z7[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) z7[r] = h7[r];
+        row_dot_tile(rows, kHidTiles - 1, half, z7, s[p]);
+    }
+}
+
+// The screen's SDF value of this lane's point.  NP = 1: lanes j and j + 32 hold point j (32 points per wave, both lanes return its
+// value); NP = 2: every lane holds a point of its own (64 per wave: tile 0 on lanes 0..31, tile 1 on lanes 32..63).
+template <bool FAST, int NP>
+__device__ __forceinline__ float sdf_screen_value(Ring& ring, const char* lds, int n_hidden_layers, int skip_layer, float scale,
+                                                  float b_last, float x, float y, float z, int lane) {
+    // (an opaque lane: in a caller's loop the lane-derived LDS addresses of the stack are then derived per call, not hoisted out of
+    // the loop and held across everything else)
+    asm volatile("" : "+v"(lane));
+    const int j = lane & 31, half = lane >> 5;
+    float px[NP], py[NP], pz[NP], s[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        px[p] = __shfl(x, 32 * p + j, 64); py[p] = __shfl(y, 32 * p + j, 64); pz[p] = __shfl(z, 32 * p + j, 64);
+    }
+    sdf_hidden_stack_h1<FAST, NP>(ring, lds, n_hidden_layers, skip_layer, scale, px, py, pz, lane, s);
+    float v;
+    if constexpr (NP == 1) {
+        v = s[0] + __shfl_xor(s[0], 32, 64);
+    } else {   // lane half h keeps its own part of tile h and hands the other half its part of tile 1 - h (a + b == b + a)
+        const float mine = half ? s[1] : s[0], theirs = half ? s[0] : s[1];
+        v = mine + __shfl_xor(theirs, 32, 64);
+    }
+    return (v + b_last) / scale;
 }
 
 }  // namespace iron

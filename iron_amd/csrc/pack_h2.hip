@@ -166,8 +166,8 @@ static int h2_overflow_check(iron_net* net) {
 // The forward-only streams live in h2_blob (h2_trace / h2_full), the reverse stream is a second blob (h2_rev_blob) holding the
 // same forward slots followed by the transposed ones, so that one ring walks it end to end.
 // h1_out (forward blob only): the screen's h1 stream (mlp_h2.h: sdf_hidden_stack_h1), behind the h2 slots in the same blob and written
-// by the same launches: the hi pieces of the hidden stack's fragments, slots [layer-0 heads] then per layer [skip layer: its heads]
-// + 4 pairs of tiles; it shares the blob's bias / row blocks.
+// by the same launches: the hi pieces of the hidden stack's fragments, slots [layer-0 heads] then per layer 4 pairs of tiles (the skip
+// layer: 8 tile slots, each tile's 3 head fragments then its 16 hidden ones); it shares the blob's bias / row blocks.
 static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* scale_base, const size_t* soff, bool with_rev, void** blob_out,
                             H2StreamDev* s_out, uint32_t* n_trace_out, uint32_t* n_full_out, H2StreamDev* h1_out, hipStream_t st) {
     const iron_net_desc& d = net->desc;
@@ -195,7 +195,8 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
     }
     const uint32_t n_all = (uint32_t)(table.size() / 2);
     if (n_all > 250) return IRON_ERR_UNSUPPORTED;
-    // the h1 stream: 32 KiB slots, a head slot (the 3 head fragments of 8 tiles, zero-padded) or a pair slot (2 tiles x 16 fragments)
+    // the h1 stream: 32 KiB slots, a head slot (the 3 head fragments of 8 tiles, zero-padded), a pair slot (2 tiles x 16 fragments)
+    // or a tile slot of the skip layer (3 head + 16 hidden fragments of one tile, zero-padded)
     const size_t h1_off = off;
     const size_t kH1Tile = 16 * 1024;
     std::vector<size_t> h1_layer;   // byte offset (from h1_off) of each layer's first slot
@@ -203,8 +204,9 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
     if (h1_out) {
         for (int l = 0; l <= nl - 2; ++l) {
             h1_layer.push_back(h1_bytes);
-            if (l == 0 || l == skip) h1_bytes += kSlotBytes;
-            if (l > 0) h1_bytes += (size_t)kHidTiles * kH1Tile;
+            if (l == 0) h1_bytes += kSlotBytes;
+            else if (l == skip) h1_bytes += (size_t)kHidTiles * kSlotBytes;
+            else h1_bytes += (size_t)kHidTiles * kH1Tile;
         }
         if (h1_bytes / kSlotBytes > 64) return IRON_ERR_UNSUPPORTED;
     }
@@ -226,24 +228,25 @@ static int pack_h2_sdf_blob(iron_net* net, const iron_linear* L, const float* sc
     hs.n = 1; hs.slot_base[0] = 0; hs.levels[0] = d.multires; hs.col_off[0] = 0;
     size_t q = 0;
     auto slot_ptr = [&](size_t idx) { return (_Float16*)(base + table[2 * idx]); };
-    // h1 destinations: layer l's head fragments (layer 0, skip layer) and its first hidden tile; nullptr without an h1 stream
+    // h1 destinations: layer l's first head fragments (layer 0, skip layer) and its first hidden tile; nullptr without an h1 stream
+    const size_t kH1Head = (size_t)kHeadKSteps * 1024;
     auto h1_head = [&](int l) { return h1_out ? (_Float16*)(base + h1_off + h1_layer[l]) : (_Float16*)nullptr; };
-    auto h1_hid = [&](int l) { return h1_out ? (_Float16*)(base + h1_off + h1_layer[l] + (l == skip ? kSlotBytes : 0)) : (_Float16*)nullptr; };
+    auto h1_hid = [&](int l) { return h1_out ? (_Float16*)(base + h1_off + h1_layer[l] + (l == skip ? kH1Head : 0)) : (_Float16*)nullptr; };
     // one launch per run of equally spaced slots (blockIdx.y = tile): a training step re-packs every network, and one launch per slot
     // (224 per step at C3) cost ~1 ms per step of 3-4 us launches
     const size_t kHeadB = 8192, kHidB = kSlotBytes;
-    hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB, make_pack_src(L[0], scale_base + soff[0], kHidden, 0, 1.0f), hs, 0, 0, h1_head(0), (size_t)kHeadKSteps * 1024);
+    hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB, make_pack_src(L[0], scale_base + soff[0], kHidden, 0, 1.0f), hs, 0, 0, h1_head(0), kH1Head);
     q += kHidTiles;
     for (int l = 1; l <= nl - 2; ++l) {
         const bool is_skip = (l == skip);
         const float mul = is_skip ? kInvSqrt2 : 1.0f;
         const int cols_valid = is_skip ? kHidden - pe : kHidden;
         const PackSrc ps = make_pack_src(L[l], scale_base + soff[l], L[l].out_dim, 0, mul);
-        if (is_skip) {   // per tile: [head slot][hidden slot]
+        if (is_skip) {   // per tile: [head slot][hidden slot]; h1: one 32 KiB slot per tile
             HeadSrcs h2 = hs;
             h2.col_off[0] = kHidden - pe;
-            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB + kHidB, ps, h2, 0, 0, h1_head(l), (size_t)kHeadKSteps * 1024);
-            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + 1), kHeadB + kHidB, ps, 0, 0, cols_valid, h1_hid(l), kH1Tile);
+            hipLaunchKernelGGL(k_pack_h2_head, dim3(8, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHeadB + kHidB, ps, h2, 0, 0, h1_head(l), kHidB);
+            hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q + 1), kHeadB + kHidB, ps, 0, 0, cols_valid, h1_hid(l), kHidB);
             q += 2 * kHidTiles;
         } else {
             hipLaunchKernelGGL(k_pack_h2_hidden, dim3(32, kHidTiles), dim3(256), 0, st, slot_ptr(q), kHidB, ps, 0, 0, cols_valid, h1_hid(l), kH1Tile);

@@ -153,6 +153,7 @@ struct TraceArgs {
 };
 
 __device__ __forceinline__ int lane_rank(unsigned mask, int j) { return __popc(mask & ((1u << j) - 1u)); }
+__device__ __forceinline__ int lane_rank64(unsigned long long mask, int j) { return __popcll(mask & ((1ull << j) - 1ull)); }
 
 // ---- evaluation back ends ---------------------------------------------------------------------------------
 // The tracer kernels are written once as per-wave state machines around three calls:
@@ -219,11 +220,11 @@ struct BackendH2T {
         sdf_hidden_stack_h2<kFastActT, DEFER_TILES>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
         return (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
     }
-    // the screen: one product per MAC (sdf_hidden_stack_h1) on a ring started on the h1 stream, for sign decisions only
+    // the screen: one product per MAC (sdf_hidden_stack_h1) on a ring started on the h1 stream, for sign decisions only.
+    // NP x 32 points per wave: NP = 1, the point on lane & 31 (as eval); NP = 2, every lane's own point.
+    template <int NP>
     __device__ __forceinline__ float eval_screen(float x, float y, float z) {
-        f32x16 hf[kHidTiles];
-        sdf_hidden_stack_h1<kFastActT>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, x, y, z, lane, hf);
-        return (row_dot_lds(lds + kLdsRows, hf, lane >> 5) + m.b_last) / m.scale;
+        return sdf_screen_value<kFastActT, NP>(ring, lds, m.n_hidden_layers, m.skip_layer, m.scale, m.b_last, x, y, z, lane);
     }
     __device__ __forceinline__ void finish() { ring.drain(); }
     __device__ __forceinline__ void park(int i, float v) { reinterpret_cast<float*>(lds + kLdsPark)[i * 256 + threadIdx.x] = v; }
@@ -369,6 +370,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sphere(IRON_TRACE_KERNEL_AR
 #endif
 constexpr int kSamplerBlock = IRON_SAMPLER_BLOCK;
 constexpr int kSamplerSlots = 32 / kSamplerBlock;
+constexpr int kScreenSlots = 32 * kH1PointTiles / kSamplerBlock;   // k_sampler_screen: every lane a sample of its own (NP = 2: 8 slots)
+static_assert(kScreenSlots <= 32, "screen slots: one bit each in a 32-bit slot mask");
 constexpr int kSamplerSeg = IRON_SAMPLER_SEG;
 static_assert(kSamplerBlock == 4 || kSamplerBlock == 8 || kSamplerBlock == 16 || kSamplerBlock == 32, "sampler block");
 constexpr int kContRayBits = 24, kContBlkBits = 8;   // item word: [ray + 1 : 24][next block : 8][f of the previous sample : 32]
@@ -550,15 +553,15 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // certainly-negative sample (or its end); k_screen_resolve evaluates the listed samples on the h2 core, 32 per wave from any rays,
 // and k_screen_fin_* give each pending ray the bracket, root-list entry or zeros k_sampler would have written.  A ray whose samples
 // do not fit the list is marched again from its start by k_sampler on a second list.  n_evals still counts what k_sampler evaluates.
+// A wave screens 64 samples per pass, 8 ray slots of 8 (k_sampler: 32, 4 slots, lanes j and j + 32 on one point): the screen's
+// weight fragments feed two point tiles each (mlp_h2.h), so that its slots, their LDS-DMA and barriers serve twice the samples.
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_KERNEL_ARGS) {
     BE be;
     be.init(net, hs, hm);   // hs: the h1 stream
-    const int lane = be.lane;
-    const int j = lane & 31;
-    const int slot = j / kSamplerBlock, s_in = j % kSamplerBlock;
+    const int lane = be.lane;   // every lane carries a sample of its own: 64 per wave, kScreenSlots ray slots
+    const int slot = lane / kSamplerBlock, s_in = lane % kSamplerBlock;
     const int slot_lane0 = slot * kSamplerBlock;
-    const unsigned slot_bits = (kSamplerBlock == 32 ? 0xffffffffu : ((1u << kSamplerBlock) - 1u)) << slot_lane0;
     SamplerQ* const q = &w.cnt->smp;
     const int n_list = q->n_list;
     const bool dyn = w.cont_cap > 0;
@@ -573,11 +576,11 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     for (;;) {
         unsigned pub_slots = 0, need_slots = 0;
         {
-            const unsigned pub = (unsigned)__ballot(publish), need = (unsigned)__ballot(!has_ray && ticket < 0 && !retired);
+            const unsigned long long pub = __ballot(publish), need = __ballot(!has_ray && ticket < 0 && !retired);
 #pragma unroll
-            for (int qq = 0; qq < kSamplerSlots; ++qq) {
-                pub_slots |= ((pub >> (qq * kSamplerBlock)) & 1u) << qq;
-                need_slots |= ((need >> (qq * kSamplerBlock)) & 1u) << qq;
+            for (int qq = 0; qq < kScreenSlots; ++qq) {
+                pub_slots |= (unsigned)((pub >> (qq * kSamplerBlock)) & 1ull) << qq;
+                need_slots |= (unsigned)((need >> (qq * kSamplerBlock)) & 1ull) << qq;
             }
         }
         if (pub_slots | need_slots) {
@@ -657,7 +660,13 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
             be.park(15, (int)ev_ref); be.park(16, (int)ev_scr);
         }
-        const float f = be.eval_screen(qx, qy, qz);
+        const float f = be.template eval_screen<kH1PointTiles>(qx, qy, qz);
+        // the lane-derived masks after the evaluation come from an opaque copy of the lane: hoisted out of the loop, they are held
+        // across the evaluation (in scratch, at 64 samples per wave)
+        int me = lane;
+        asm volatile("" : "+v"(me));
+        const int sl0 = (me / kSamplerBlock) * kSamplerBlock, s_in_b = me % kSamplerBlock;
+        const unsigned long long sbits = ((1ull << kSamplerBlock) - 1ull) << sl0;   // the slot's lanes
         const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0));
         has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4; pend = flags_back & 16;
         const bool in_range_b = flags_back & 8;
@@ -667,52 +676,52 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const float zb = be.unpark(14, z);
         ev_ref = (unsigned)be.unpark(15, (int)ev_ref); ev_scr = (unsigned)be.unpark(16, (int)ev_scr);
         idle_polls = 0;
-        ev_scr += __popc((unsigned)__ballot(in_range_b));
+        ev_scr += (unsigned)__popcll(__ballot(in_range_b));
         const bool is_neg = in_range_b && f < -delta;                       // certainly negative
         const bool is_unc = in_range_b && !(f > delta) && !(f < -delta);    // uncertain (NaN included)
-        const unsigned neg = (unsigned)__ballot(is_neg) & slot_bits;
-        const unsigned unc_all = (unsigned)__ballot(is_unc);
-        const int first = neg ? (__ffs(neg) - 1) : slot_lane0;
+        const unsigned long long neg = __ballot(is_neg) & sbits;
+        const unsigned long long unc_all = __ballot(is_unc);
+        const int first = neg ? (__ffsll((long long)neg) - 1) : sl0;
         const float z_first = __shfl(zb, first, 64), f_first = __shfl(f, first, 64);
-        const float z_before = __shfl(zb, first > slot_lane0 ? first - 1 : slot_lane0, 64);
-        const float f_before = __shfl(f, first > slot_lane0 ? first - 1 : slot_lane0, 64);
-        const float z_last = __shfl(zb, slot_lane0 + kSamplerBlock - 1, 64), f_last = __shfl(f, slot_lane0 + kSamplerBlock - 1, 64);
-        const float f_up = __shfl(f, lane > 0 ? lane - 1 : 0, 64);
-        const int gidx = blk * kSamplerBlock + (first - slot_lane0);
+        const float z_before = __shfl(zb, first > sl0 ? first - 1 : sl0, 64);
+        const float f_before = __shfl(f, first > sl0 ? first - 1 : sl0, 64);
+        const float z_last = __shfl(zb, sl0 + kSamplerBlock - 1, 64), f_last = __shfl(f, sl0 + kSamplerBlock - 1, 64);
+        const float f_up = __shfl(f, me > 0 ? me - 1 : 0, 64);
+        const int gidx = blk * kSamplerBlock + (first - sl0);
         const bool found_neg = has_ray && neg != 0u;
         const bool done = has_ray && (found_neg || (blk + 1) * kSamplerBlock >= a.n_steps);
-        const float z_lo = first > slot_lane0 ? z_before : prev_z, f_lo = first > slot_lane0 ? f_before : prev_f;
+        const float z_lo = first > sl0 ? z_before : prev_z, f_lo = first > sl0 ? f_before : prev_f;
         // uncertain samples in front of the slot's first certainly-negative one: to the resolve list, one atomicAdd per wave
-        const unsigned before = neg ? (((1u << first) - 1u) & slot_bits) : slot_bits;
-        const unsigned unc = has_ray ? (unc_all & before) : 0u;
-        const unsigned unc_wave = (unsigned)__ballot(j == lane && ((unc >> j) & 1u));   // lanes 0..31 carry one sample each
+        const unsigned long long before = neg ? (((1ull << first) - 1ull) & sbits) : sbits;
+        const unsigned long long unc = has_ray ? (unc_all & before) : 0ull;
+        const unsigned long long unc_wave = __ballot((unc >> me) & 1ull);   // (each lane sees its own slot's samples in unc)
         int rbase = 0;
         if (unc_wave) {
-            if (lane == 0) rbase = atomicAdd(&w.cnt->n_res, __popc(unc_wave));
+            if (me == 0) rbase = atomicAdd(&w.cnt->n_res, __popcll(unc_wave));
             rbase = __shfl(rbase, 0, 64);
         }
         bool overflow = false;
         if (unc) {
-            const int pos_last = rbase + lane_rank(unc_wave, 31 - __clz(unc));
+            const int pos_last = rbase + lane_rank64(unc_wave, 63 - __clzll((long long)unc));
             overflow = pos_last >= w.scr.cap;
-            const int pos = rbase + lane_rank(unc_wave, j);
-            if (lane < 32 && ((unc >> j) & 1u) && pos < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
+            const int pos = rbase + lane_rank64(unc_wave, me);
+            if (((unc >> me) & 1ull) && pos < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
                 ResolveEntry e;
-                e.ray = ray; e.s = idx; e.z = zb; e.f1 = f; e.f_prev1 = s_in > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
+                e.ray = ray; e.s = idx; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
                 w.scr.ent[pos] = e;
             }
         }
         const bool pend_now = pend || unc != 0u;
         const bool to_ovf = has_ray && overflow;
         if (to_ovf) {   // the ray goes to k_sampler's second list, marched from its start
-            if (lane == slot_lane0) {
+            if (me == sl0) {
                 w.scr.ray_state[ray] = kRayOverflowed;
                 const int p = atomicAdd(&w.cnt->ovf.n_list, 1);
                 w.scr.ovf_list[p] = ray;
                 atomicAdd((unsigned long long*)&w.cnt->n_ovf, 1ull);
                 atomicAdd(&q->n_done, 1);
             }
-        } else if (done && lane == slot_lane0) {
+        } else if (done && me == sl0) {
             if (pend_now) {          // decided by k_screen_fin_* once the listed samples have their exact values
                 PendRec r;
                 r.first = found_neg ? gidx : a.n_steps;
@@ -729,10 +738,12 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                     w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_first;
                     w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_first;
                 } else {
+                    float zero = 0.f;
+                    asm volatile("" : "+v"(zero));   // (else the zeros of these stores are held in registers across the loop)
                     a.conv[ray] = 0;
-                    a.points[3 * (size_t)ray] = 0.f; a.points[3 * (size_t)ray + 1] = 0.f; a.points[3 * (size_t)ray + 2] = 0.f;
-                    a.sdf[ray] = 0.f;
-                    a.dist[ray] = 0.f;
+                    a.points[3 * (size_t)ray] = zero; a.points[3 * (size_t)ray + 1] = zero; a.points[3 * (size_t)ray + 2] = zero;
+                    a.sdf[ray] = zero;
+                    a.dist[ray] = zero;
                 }
             }
             atomicAdd(&q->n_done, 1);
@@ -748,7 +759,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             unsigned long long r = ev_ref;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off, 64);
-            if (lane == 0) {
+            if (me == 0) {
                 atomicAdd((unsigned long long*)&w.cnt->n_evals, r);   // (only the slots' first lanes count)
                 atomicAdd((unsigned long long*)&w.cnt->n_screen, (unsigned long long)ev_scr);
             }
@@ -893,7 +904,7 @@ __global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2Stream
         const int i = g * 128 + be.wave * 32 + (be.lane & 31);
         float x, y, z;
         screen_calib_point(i, x, y, z);
-        const float f1 = be.eval_screen(x, y, z);
+        const float f1 = be.eval_screen<1>(x, y, z);
         f1s[i] = f1;   // lanes j and j + 32: the same point, the same value
     }
     be.finish();
@@ -1225,6 +1236,7 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
 std::atomic<int> g_screen_switch{-1};           // iron_set_sampler_screen; -1 = the environment's (IRON_SAMPLER_SCREEN=0: off) / default on
 std::atomic<float> g_screen_delta_override{0.0f};   // test hooks (iron_sampler_screen_debug)
 std::atomic<int> g_screen_cap_override{0};
+void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
 static bool screen_switch() {
     static int from_env = -1;
@@ -1273,7 +1285,7 @@ static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayou
 static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t nk, hipStream_t st) {
     const int64_t units = (nk + kSamplerSlots - 1) / kSamplerSlots;
     if (!screen) { launch_trace_kernel(1, h2, sdf, a, w, units, st); return; }
-    launch_trace_kernel(4, true, sdf, a, w, units, st);
+    launch_trace_kernel(4, true, sdf, a, w, (nk + kScreenSlots - 1) / kScreenSlots, st);
     launch_trace_kernel(5, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
     const int64_t ge = ((int64_t)w.scr.cap + 255) / 256, gr = (nk + 255) / 256;
     hipLaunchKernelGGL(k_screen_fin_entries, dim3((unsigned)(ge < 1024 ? (ge > 0 ? ge : 1) : 1024)), dim3(256), 0, st, w);
@@ -1298,6 +1310,7 @@ extern "C" int32_t iron_set_sampler_screen(int32_t on) {
 extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 0) { g_screen_delta_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
     if (what == 1) { g_screen_cap_override.store(value >= 1.0 ? (int)value : 0, std::memory_order_relaxed); return IRON_OK; }
+    if (what == 2) { set_screen_forward_tiles(value == 1.0 ? 1 : 0); return IRON_OK; }
     return IRON_ERR_BAD_ARG;
 }
 
