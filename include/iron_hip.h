@@ -34,7 +34,8 @@ extern "C" {
 typedef enum iron_status {
     IRON_OK = 0,
     IRON_ERR_BAD_ARG = -1,      /* null pointer, negative size, misaligned buffer;
-                                   iron_bvh_boxes: a face indexes outside the vertices or has a non-finite vertex */
+                                   iron_bvh_boxes, iron_mesh_components, iron_uv_projections: a face indexes
+                                   outside the vertices or has a non-finite vertex */
     IRON_ERR_UNSUPPORTED = -2,  /* network shape / mode the kernels are not built for          */
     IRON_ERR_HIP = -3,          /* a HIP runtime call failed; see iron_last_hip_error()        */
     IRON_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
@@ -246,6 +247,50 @@ int iron_bvh_boxes(const float* verts, int64_t n_verts, const int32_t* faces, in
                    void* stream);
 int iron_point_mesh_distance(const void* workspace, int64_t n_faces, const float* points, int64_t n_points, float* sqr_dist,
                              int32_t* face_idx, float* closest, void* stream);
+/* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
+ * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
+ *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte
+ *   aligned), zeroed by the caller before the first call of a sequence: it carries an argmin word, the bad-input flag and a round's
+ *   "changed" word.  A face index outside [0, n_verts) or a non-finite coordinate of a referenced vertex sets the flag; the first
+ *   host wait after it (iron_mesh_components or iron_uv_projections) returns IRON_ERR_BAD_ARG.
+ *   iron_mesh_edge_keys   keys [3*n_faces] (device uint64): record 3f+e is edge e = (v_e, v_(e+1)%3) of face f, key min << 32 | max;
+ *                         an edge whose two indices are equal (and every edge of a bad face) gets 2^63 - 1, which sorts last.
+ *   (caller)              sorts the keys ascending into sorted_keys with the permutation perm [3*n_faces] (int64, record index).
+ *   iron_mesh_components  union-find over the faces: faces whose records share a key and whose group [n_faces] (int32; NULL = all 0)
+ *                         is equal are joined, every pair of a longer run included; a degenerate edge joins nothing.  parent
+ *                         [n_faces] (int32) receives each face's component root = its smallest face index.  Rounds of a hook launch
+ *                         (integer atomicMin of the larger root onto the smaller) and a pointer-jumping launch; one host wait per
+ *                         round, *rounds (HOST) counts them; IRON_ERR_RANGE if max_rounds pass without convergence (parent is then
+ *                         not a labelling).  Bitwise deterministic.
+ *   iron_uv_workspace_bytes / iron_uv_projections  per-face unit normals and areas a = |cross(v1 - v0, v2 - v0)| in fp32 (a == 0:
+ *                         degenerate); projection normals P [*n_normals,3] (at most max_normals, else IRON_ERR_RANGE): seed = the
+ *                         largest face (ties: smallest index); tag the untagged non-degenerate faces with n.seed > cos_half, append
+ *                         the normalised sum of their normals (fixed-order reduction); the untagged face with the smallest max_p n.p
+ *                         (ties: smallest index) seeds the next normal unless none is left or that value is >= cos_limit.  One host
+ *                         wait per normal (*n_waits, HOST).  Then group [n_faces] = argmax_p n.p (ties: smallest p), 0 for degenerate
+ *                         faces; normals_out [n_faces,3] (may be NULL) receives the face normals (zeros for degenerate faces).
+ *   iron_uv_project       xy [n_vt,2] = (x.t, x.b) of vertex vt_vertex[i] in the right-handed basis (t, b, p) of p = P[island_group[
+ *                         vt_island[i]]]: t = normalize(e x p), e the axis of the smallest |p_i| (ties: lowest i), b = p x t.
+ *   iron_uv_rotation_search  per island and candidate angle (cs [n_angles,2] = cos, sin, or per_island != 0: [n_islands,n_angles,2]),
+ *                         the box of (x c - y s, x s + y c) over the island's vts: boxes [n_islands,n_angles,4] (uint32) =
+ *                         ord(-min x), ord(-min y), ord(max x), ord(max y), ord the order-preserving encoding of fp32 (x >= 0:
+ *                         bits | 2^31, else ~bits); the caller picks the angle.  vt_island sorted (the wave pre-reduction uses runs).
+ *   iron_uv_apply         uv [n_vt,2]: rotate by params[k] = {cos, sin, min x, min y, max x, max y, offset u, offset v} of island k,
+ *                         subtract the box minimum (swap[k] != 0: first turn by +90 degrees, (x, y) -> (-y, x)), add the offset,
+ *                         multiply by scale, clamp to [0, 1]. */
+int iron_mesh_edge_keys(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, uint64_t* keys, void* state, void* stream);
+int iron_mesh_components(const uint64_t* sorted_keys, const int64_t* perm, int64_t n_records, const int32_t* group, int64_t n_faces,
+                         int32_t* parent, void* state, int32_t max_rounds, int32_t* rounds, void* stream);
+int iron_uv_workspace_bytes(int64_t n_faces, size_t* bytes);
+int iron_uv_projections(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, float cos_half, float cos_limit,
+                        int32_t max_normals, void* workspace, void* state, float* normals_out, float* P, int32_t* group, int32_t* n_normals,
+                        int32_t* n_waits, void* stream);
+int iron_uv_project(const float* verts, const int32_t* vt_vertex, const int32_t* vt_island, int64_t n_vt, const int32_t* island_group,
+                    const float* P, float* xy, void* stream);
+int iron_uv_rotation_search(const float* xy, const int32_t* vt_island, int64_t n_vt, int64_t n_islands, const float* cs, int32_t n_angles,
+                            int32_t per_island, uint32_t* boxes, void* stream);
+int iron_uv_apply(const float* xy, const int32_t* vt_island, int64_t n_vt, const float* params, const int32_t* swap, float scale, float* uv,
+                  void* stream);
 int iron_neus_linspace(const float* near, const float* far, const float* lin, int64_t n, int32_t m, float* z, void* stream);
 int iron_neus_outside_z(const float* far, const float* rev, int64_t n, int32_t m, float offset, float* z, void* stream);
 int iron_neus_points(const float* rays_o, const float* rays_d, const float* z, int64_t n, int32_t m, float* pts, void* stream);

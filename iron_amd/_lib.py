@@ -114,6 +114,13 @@ SYMBOLS = {
     "iron_bvh_hierarchy": (C.c_int, [_P, _I64, _P, _P]),
     "iron_bvh_boxes": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_point_mesh_distance": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
+    "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_uv_projections": (C.c_int, [_P, _I64, _P, _I64, _F, _F, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), C.POINTER(_I32), _P]),
+    "iron_uv_project": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P]),
+    "iron_uv_rotation_search": (C.c_int, [_P, _P, _I64, _I64, _P, _I32, _I32, _P, _P]),
+    "iron_uv_apply": (C.c_int, [_P, _P, _I64, _P, _P, _F, _P, _P]),
     "iron_neus_linspace": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "iron_neus_outside_z": (C.c_int, [_P, _P, _I64, _I32, _F, _P, _P]),
     "iron_neus_points": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
