@@ -291,6 +291,53 @@ int iron_uv_rotation_search(const float* xy, const int32_t* vt_island, int64_t n
                             int32_t per_island, uint32_t* boxes, void* stream);
 int iron_uv_apply(const float* xy, const int32_t* vt_island, int64_t n_vt, const float* params, const int32_t* swap, float scale, float* uv,
                   void* stream);
+/* Image evaluation metrics (evaluation/eval_image_folder.py: PSNR, skimage's uniform-window SSIM, LPIPS-AlexNet), csrc/imgmetrics.hip;
+ * DESIGN.md §14.  Images are [H,W,3], both uint8 (is_f32 = 0) or both fp32 (is_f32 = 1), device memory.  Every entry enqueues on
+ * `stream`, allocates nothing and does not wait; every reduction is a fixed-order sum of fp64 partials kept in the caller's
+ * workspace (no float atomics), so every output is bitwise reproducible.  Bad shapes or null pointers: IRON_ERR_BAD_ARG.
+ *   iron_img_sqerr        out[0] (DEVICE, fp64) = sum over `count` elements of (a - b)^2 in the units of images in [0,1], out[1] =
+ *                         count.  uint8: the integer differences are summed exactly and divided by 255^2 once; fp32: difference and
+ *                         square in fp32 (numpy's (a - b) ** 2), accumulated in fp64.  0 < count < 2^31.
+ *   iron_img_ssim         skimage.metrics.structural_similarity(data_range=1, win_size=11, use_sample_covariance=False) per channel:
+ *                         uniform 11x11 means, C1 = 0.01^2, C2 = 0.03^2, S evaluated where the whole window lies inside the image.
+ *                         sums[3] (DEVICE, fp64) = per channel the sum of S over (H-10) x (W-10); s_map (may be NULL) [3,H-10,W-10]
+ *                         fp64 receives S.  uint8: the five window sums are exact integers (121 * 255^2 < 2^24), S is fp64 of
+ *                         them; fp32: products and window sums in fp64 (the product of two fp32 values is exact there), left
+ *                         to right then top to bottom.  H, W in [11, 16384].
+ *   LPIPS (AlexNet, v0.1), evaluation only.  Activations are NHWC fp32; a convolution weight is [Cout, k, k, Cin] fp32 (the
+ *   checkpoint's [Cout, Cin, k, k] permuted once by the caller).
+ *     iron_lpips_prepare  out [2,H,W,3] = ((2 x - 1) - shift) / scale of pred (image 0) and trgt (image 1); uint8 k is float(k) / 255.
+ *     iron_conv2d_relu    out [B,Ho,Wo,Cout] = relu(conv(in [B,H,W,Cin], weight, stride, zero padding pad) + bias), Ho = (H + 2 pad -
+ *                         ksize) / stride + 1.  An implicit GEMM on the matrix pipe at fp32 accuracy: both operands split into fp16
+ *                         hi / lo pieces, three MFMA products, fp32 accumulation (the split of csrc/gemm_h2.h).  An operand element
+ *                         beyond fp16's range (|x| > 65504, or not finite) has no split: it ORs 1 into *range_flag (DEVICE int32,
+ *                         zeroed by the caller) and the output is then meaningless.  in, weight, out 16-byte aligned.
+ *     iron_maxpool3s2     3x3 max-pool, stride 2, no padding: out [B,(H-3)/2+1,(W-3)/2+1,C].
+ *     iron_lpips_tap      feat [2,H,W,C] (C a multiple of 64, <= 384), lin [C]: per pixel sum_c lin[c] (f0[c] / (|f0| + 1e-10) -
+ *                         f1[c] / (|f1| + 1e-10))^2 in fp64; partials [1024] (DEVICE, fp64) receive fixed per-wave sums over the
+ *                         pixels (their sum / (H W) is the layer's term).
+ *     iron_lpips_forward  the whole metric for one pair: prepare, the five convolutions with their taps, the two pools, the final
+ *                         sum.  out[0] (DEVICE, fp64) = LPIPS, out[1] = 0; if any operand left fp16's range out[0] = NaN and
+ *                         out[1] = 1, which the caller reports as IRON_ERR_RANGE after its own read (this entry does not wait).
+ *                         workspace: iron_lpips_workspace_bytes(H, W), 16-byte aligned.  The stack needs H, W >= 31. */
+typedef struct iron_lpips_weights {
+    const float* conv_weight[5]; /* [64,11,11,3] [192,5,5,64] [384,3,3,192] [256,3,3,384] [256,3,3,256] */
+    const float* conv_bias[5];
+    const float* lin[5];         /* [64] [192] [384] [256] [256] */
+} iron_lpips_weights;
+int iron_img_sqerr_workspace_bytes(int64_t count, size_t* bytes);
+int iron_img_sqerr(const void* a, const void* b, int64_t count, int32_t is_f32, void* workspace, double* out, void* stream);
+int iron_img_ssim_workspace_bytes(int32_t H, int32_t W, size_t* bytes);
+int iron_img_ssim(const void* x, const void* y, int32_t H, int32_t W, int32_t is_f32, void* workspace, double* sums, double* s_map,
+                  void* stream);
+int iron_lpips_prepare(const void* pred, const void* trgt, int32_t H, int32_t W, int32_t is_f32, float* out, void* stream);
+int iron_conv2d_relu(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* weight, const float* bias, int32_t Cout,
+                     int32_t ksize, int32_t stride, int32_t pad, float* out, int32_t* range_flag, void* stream);
+int iron_maxpool3s2(const float* in, int32_t B, int32_t H, int32_t W, int32_t C, float* out, void* stream);
+int iron_lpips_tap(const float* feat, int32_t H, int32_t W, int32_t C, const float* lin, double* partials, void* stream);
+int iron_lpips_workspace_bytes(int32_t H, int32_t W, size_t* bytes);
+int iron_lpips_forward(const void* pred, const void* trgt, int32_t H, int32_t W, int32_t is_f32, const iron_lpips_weights* w,
+                       void* workspace, double* out, void* stream);
 int iron_neus_linspace(const float* near, const float* far, const float* lin, int64_t n, int32_t m, float* z, void* stream);
 int iron_neus_outside_z(const float* far, const float* rev, int64_t n, int32_t m, float offset, float* z, void* stream);
 int iron_neus_points(const float* rays_o, const float* rays_d, const float* z, int64_t n, int32_t m, float* pts, void* stream);

@@ -78,6 +78,10 @@ class iron_shade_out(C.Structure):
                 ("specular_roughness", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class iron_lpips_weights(C.Structure):
+    _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
+
+
 TRACE_STATS_FIELDS = ("n_evals", "n_sphere_conv", "n_sampler", "n_bisect", "n_conv", "n_evals_ref", "n_evals_sphere",
                       "reserved")
 PROF_KINDS = ("sphere", "sampler", "bisect_a", "bisect_b", "sdf_grad", "material", "ggx", "sdf_forward")
@@ -121,6 +125,16 @@ SYMBOLS = {
     "iron_uv_project": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P]),
     "iron_uv_rotation_search": (C.c_int, [_P, _P, _I64, _I64, _P, _I32, _I32, _P, _P]),
     "iron_uv_apply": (C.c_int, [_P, _P, _I64, _P, _P, _F, _P, _P]),
+    "iron_img_sqerr_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_img_sqerr": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
+    "iron_img_ssim_workspace_bytes": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
+    "iron_img_ssim": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "iron_lpips_prepare": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "iron_conv2d_relu": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "iron_maxpool3s2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "iron_lpips_tap": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
+    "iron_lpips_workspace_bytes": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
+    "iron_lpips_forward": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(iron_lpips_weights), _P, _P, _P]),
     "iron_neus_linspace": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "iron_neus_outside_z": (C.c_int, [_P, _P, _I64, _I32, _F, _P, _P]),
     "iron_neus_points": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
