@@ -112,9 +112,10 @@ int iron_net_destroy(iron_net_t* net);
  * (models/fields.py:82-98, 203-239), which the exact core reproduces over the whole fp32 range.
  *   iron_net_numeric_status: synchronises `stream`; *status_out = bit 0: an overflow was seen, bit 1: the network runs on the exact
  *                            core, bit 2: a flag is pending (the call just finished overflowed),
- *                            bit 3: the dense sampler's screen guard has turned the screen off for this network (iron_set_sampler_screen).
+ *                            bit 3: the dense sampler's screen guard has turned the screen off for this network (iron_set_sampler_screen),
+ *                            bit 4: the slope guard has put the screen's adaptive march on stride 1 for this network (iron_set_sampler_stride).
  *   iron_net_force_exact:    on != 0 pins the network to the exact core; 0 returns it to the default core and clears the status
- *                            (bits 0-3). */
+ *                            (bits 0-4). */
 int iron_net_numeric_status(const iron_net_t* net, int32_t* status_out, void* stream);
 int iron_net_force_exact(iron_net_t* net, int32_t on);
 
@@ -646,6 +647,22 @@ int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, fl
 int32_t iron_set_sampler_screen(int32_t on);
 int iron_sampler_screen_debug(int32_t what, double value);
 int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
+
+/* The screen's adaptive march (csrc/trace.hip k_sampler_screen; results do not depend on it).  The screen does not evaluate samples
+ * that an evaluated neighbour proves positive: f1 > delta + L * (distance along the ray), with the slope bound L = 2 x the largest
+ * |grad f| over the screen's calibration points.  L is empirical like the margin: the passes that run at stride 1 watch the slope
+ * between adjacent samples, and one above 0.75 L raises a guard (iron_net_numeric_status bit 4) after which the network's calls
+ * march every sample -- every call that starts after the call that raised it has completed, as for the screen's guard.  Calls with
+ * more than 256 steps, or too large for the sampler's continuation items, march every sample too.
+ *   iron_set_sampler_stride:  on = 1 adaptive, 0 every sample, -1 the default (IRON_SAMPLER_STRIDE=0: off, else on).  Process-wide;
+ *                             returns the previous state.
+ *   iron_sampler_screen_debug what 3: value > 0 forces the slope bound L (0 restores the calibrated one).
+ *   iron_trace_stride_counts: synchronises `stream`; from the workspace of the last traced call: out[0] ray-passes the screen executed
+ *                             (8 samples of one ray), out[1] those at a stride above 1, out[2] the largest watched slope relative
+ *                             to L (after an allowance of delta / 2 for the screen's own error), out[3] 1 if the call marched
+ *                             adaptively, 0 if it ran stride 1 throughout. */
+int32_t iron_set_sampler_stride(int32_t on);
+int iron_trace_stride_counts(const void* workspace, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the

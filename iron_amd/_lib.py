@@ -170,6 +170,8 @@ SYMBOLS = {
     "iron_set_sampler_screen": (_I32, [_I32]),
     "iron_sampler_screen_debug": (C.c_int, [_I32, C.c_double]),
     "iron_trace_screen_counts": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "iron_set_sampler_stride": (_I32, [_I32]),
+    "iron_trace_stride_counts": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),

@@ -71,6 +71,7 @@ int envelope_create(iron_net* net) {
     net->flag_dev = g_pool_dev + (size_t)slot * kSlotInts;
     *(volatile int*)net->flag_host = 0;
     *(volatile int*)(net->flag_host + 1) = 0;   // word 1: the sampler's screen guard (trace.hip)
+    *(volatile int*)(net->flag_host + 2) = 0;   // word 2: the slope guard of the screen's adaptive march (trace.hip)
     return IRON_OK;
 }
 
@@ -117,6 +118,7 @@ extern "C" int iron_net_numeric_status(const iron_net_t* net, int32_t* status_ou
     if (n->overflow_seen) s |= 1;
     if (n->h2_disabled) s |= 2;
     if (n->screen_off || (n->flag_host && *(volatile int*)(n->flag_host + 1))) s |= 8;   // the sampler's screen guard (trace.hip)
+    if (n->stride_off || (n->flag_host && *(volatile int*)(n->flag_host + 2))) s |= 16;   // the adaptive march's slope guard (trace.hip)
     *status_out = s;
     return IRON_OK;
 }
@@ -126,8 +128,9 @@ extern "C" int iron_net_force_exact(iron_net_t* net, int32_t on) {
     net->h2_disabled = on ? 1 : 0;
     if (!on) {
         net->overflow_seen = 0;
-        net->screen_off = 0;   // the sampler's screen guard (status bit 3) is part of the status, cleared with it
-        if (net->flag_host) { *(volatile int*)net->flag_host = 0; *(volatile int*)(net->flag_host + 1) = 0; }
+        net->screen_off = 0;   // the sampler's guards (status bits 3 and 4) are part of the status, cleared with it
+        net->stride_off = 0;
+        if (net->flag_host) { *(volatile int*)net->flag_host = 0; *(volatile int*)(net->flag_host + 1) = 0; *(volatile int*)(net->flag_host + 2) = 0; }
     }
     return IRON_OK;
 }

@@ -143,6 +143,7 @@ struct iron_net {
     unsigned* screen_calib;
     int screen_calibrated;
     int screen_off;
+    int stride_off;       // the slope guard of the screen's adaptive march (flag word 2) was raised: stride 1 from now on
 };
 
 namespace iron {

@@ -66,6 +66,11 @@ struct TraceCounters {  // zeroed at the start of every call
     long long n_screen;    // screened evaluations, speculative ones included
     long long n_resolved;  // exact evaluations of listed samples
     long long n_ovf;       // rays that overflowed the resolve list
+    // the screen's adaptive march (read through iron_trace_stride_counts)
+    long long n_pass;      // slot-passes k_sampler_screen executed (one slot = 8 lanes of one ray)
+    long long n_pass_strided;   // ... of them at a stride above 1
+    unsigned slope_bits;   // the slope guard: largest max(0, |f1(i+1) - f1(i)| - delta / 2) / (dz * L) over the stride-1 passes (f32 bits)
+    int stride_mode;       // 1: the call marched with the slope bound, 0: stride 1 throughout
 };
 
 // The screened sampler's state (see k_sampler_screen)
@@ -89,6 +94,8 @@ struct ScreenWs {
     const unsigned* calib;   // per network: max |f_screen - f_h2| over the calibration set (f32 bits), device
     int* flag;               // per network: the guard flag (pinned host word), may be null
     float delta_override;    // test hook (> 0: this delta)
+    int stride;              // the adaptive march may run (switch on, guard not raised, n_steps <= kStrideMaxSteps, continuation items)
+    float l_override;        // test hook (> 0: this slope bound L)
     ResolveEntry* ent;       // [cap]
     int cap;
     PendRec* rec;            // [rays of the call] by ray id
@@ -107,6 +114,19 @@ constexpr float kScreenGuard = 0.5f;
 constexpr int kScreenCalibPoints = 8192;
 constexpr int kScreenCalibF1 = 64;   // calibration buffer (32-bit words): [0] the max, [kScreenCalibF1 ..) the screen's values
 constexpr size_t kScreenCalibBytes = (kScreenCalibF1 + kScreenCalibPoints) * 4;
+// The adaptive march's slope bound: L = kStrideK * G, G = max |grad f| over the calibration set (central differences of the h2 value
+// at kStrideCalibH, about one sample spacing), stored in calibration word kScreenCalibG.  EMPIRICAL like delta: the stride-1 passes
+// watch the slope between adjacent samples, and a ratio above kStrideGuard (relative to L) puts the network's later calls on stride 1.
+constexpr float kStrideK = 2.0f;
+constexpr float kStrideGuard = 0.75f;
+constexpr float kStrideCalibH = 1.0f / 128.0f;
+constexpr int kScreenCalibG = 1;
+#ifndef IRON_SAMPLER_STRIDE_MAX
+#define IRON_SAMPLER_STRIDE_MAX 16   // 8: 0.2 ms more per C1 frame
+#endif
+constexpr int kStrideMax = IRON_SAMPLER_STRIDE_MAX;
+constexpr int kStrideMaxSteps = 256;   // the continuation word carries a sample index in 8 bits
+static_assert(kStrideMax >= 1 && kStrideMax <= 16, "stride field of the slot's packed position");
 constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
 constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
 constexpr uint8_t kRayOverflowed = 1;  // ray_state: the ray's samples did not fit the list; k_sampler marches it again
@@ -555,6 +575,54 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // do not fit the list is marched again from its start by k_sampler on a second list.  n_evals still counts what k_sampler evaluates.
 // A wave screens 64 samples per pass, 8 ray slots of 8 (k_sampler: 32, 4 slots, lanes j and j + 32 on one point): the screen's
 // weight fragments feed two point tiles each (mlp_h2.h), so that its slots, their LDS-DMA and barriers serve twice the samples.
+//
+// The adaptive march.  Most listed rays have no root: they graze the surface, and behind their closest approach the
+// SDF climbs far above the sample spacing.  A slot therefore holds a start index `pos` and a stride `strd` (one parked int with the
+// item's pass count and first segment) and a pass evaluates samples pos + strd * (0..7).  With ld = L * |width| * lin_step * |d| (L
+// times the ray's sample spacing; a.lin is uniform), an evaluated sample e certifies the next stride_reach(f1(e)) samples behind and in
+// front of it: f1(e) > delta + ld * m.  The block is walked in order: a gap between two evaluated samples is good when every skipped
+// sample in it is certified from one side; a sample that is not certainly positive, or a gap that is not certified, in a block with
+// strd > 1 discards the rest of the block and the slot resumes behind its last good sample at stride 1.  So a ray's first sample that
+// is not certainly positive is always reached at stride 1, next to its evaluated predecessor, and everything that is made of it --
+// brackets, resolve entries, PendRec, overflow -- is the stride-1 code.  After a good block the next one starts 1 + stride_reach(f1(e_7))
+// (at most kStrideMax) behind e_7; a pending ray keeps stride 1.  A work item ends after kSamplerSeg passes once its position has
+// entered a later segment (kSamplerSeg blocks of samples) than the one it started in: at stride 1 exactly the items of k_sampler, and
+// never more than sampler_cont_cap() per ray.  The continuation word carries the next sample index where k_sampler's carries the
+// block, and the taker recomputes the stride from the carried f: that needs the index in 8 bits, so a call with n_steps >
+// kStrideMaxSteps (default 128) or without continuation items runs stride 1, as does a network whose G is zero or non-finite, a ray
+// whose range is empty, reversed or non-finite, and everything after the slope guard was raised (IRON_SAMPLER_STRIDE=0 /
+// iron_set_sampler_stride: off).
+__device__ __forceinline__ int stride_reach(float f, float delta, float ld) {   // skipped samples next to a sample of value f that it certifies
+    int c = 0;
+#pragma unroll
+    for (int m = 1; m < kStrideMax; ++m) c += (f > delta + ld * (float)m) ? 1 : 0;
+    return c;
+}
+// L * the ray's sample spacing; 0: the ray runs stride 1
+__device__ __forceinline__ float stride_ld(float Lg, float lin_step, float width, float dx, float dy, float dz) {
+    const float ld = Lg * fabsf(width) * lin_step * sqrtf(dx * dx + dy * dy + dz * dz);
+    return (width > 0.0f && ld > 0.0f && ld <= 3.0e38f) ? ld : 0.0f;
+}
+constexpr int kPosBits = 13, kStrdBits = 5, kPassBits = 3;   // the slot's parked int: [pos : 13][strd : 5][passes of the item : 3][first segment : 8]
+constexpr int kSegSamples = (kSamplerSeg > 0 ? kSamplerSeg : 1) * kSamplerBlock;
+static_assert(kSamplerSeg < (1 << kPassBits) && kStrideMax < (1 << kStrdBits), "fields of the slot's parked position");
+
+// the per-lane counts of k_sampler_screen, by the lane's place in its slot (see there); ev_scr is the wave's
+__device__ __forceinline__ void screen_flush_counts(TraceCounters* cnt, unsigned ev_ref, unsigned ev_scr, int me) {
+    const int s_in = me % kSamplerBlock;
+    unsigned long long r0 = s_in == 0 ? ev_ref : 0u, r1 = s_in == 1 ? ev_ref : 0u, r2 = s_in == 2 ? ev_ref : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        r0 += __shfl_xor(r0, off, 64); r1 += __shfl_xor(r1, off, 64); r2 += __shfl_xor(r2, off, 64);
+    }
+    if (me == 0) {
+        atomicAdd((unsigned long long*)&cnt->n_evals, r0);
+        atomicAdd((unsigned long long*)&cnt->n_screen, (unsigned long long)ev_scr);
+        atomicAdd((unsigned long long*)&cnt->n_pass, r1);
+        atomicAdd((unsigned long long*)&cnt->n_pass_strided, r2);
+    }
+}
+
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_KERNEL_ARGS) {
     BE be;
@@ -567,10 +635,23 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     const bool dyn = w.cont_cap > 0;
     const long long n_tickets = (long long)n_list + (dyn ? (long long)w.cont_cap : 0ll);
     const float delta = screen_delta(w.scr);
-    unsigned ev_ref = 0, ev_scr = 0;   // per lane: k_sampler's evaluations of the rays decided here | per wave: screened evaluations
+    // the slope bound of the adaptive march (0: stride 1 throughout)
+    float Lg = 0.0f;
+    if (w.scr.stride) {
+        Lg = w.scr.l_override > 0.0f ? w.scr.l_override : kStrideK * __uint_as_float(w.scr.calib[kScreenCalibG]);
+        if (!(Lg > 0.0f && Lg <= 3.0e38f)) Lg = 0.0f;
+    }
+    const bool stride_on = Lg > 0.0f;
+    const float lin_step = a.lin[1] - a.lin[0];
+    const int unit = stride_on ? 1 : kSamplerBlock;   // what the continuation word's position counts: samples | blocks
+    if (stride_on && blockIdx.x == 0 && threadIdx.x == 0) w.cnt->stride_mode = 1;
+    // per lane: s_in 0: k_sampler's evaluations of the rays decided here, s_in 1: the slot's passes, s_in 2: those at a stride above 1
+    unsigned ev_ref = 0;
+    unsigned ev_scr = 0;   // per wave: screened evaluations (parked by lane 0; the other lanes park their `slope` in that field)
+    float slope = 0.0f;    // lanes with a predecessor in their block: the slope guard's ratio
     bool has_ray = false, retired = false, publish = false, pend = false;
     int ticket = -1;
-    int ray = 0, blk = 0;
+    int ray = 0, pos = 0, strd = 1, npass = 0, seg0 = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, smin = 0.f, width = 0.f, prev_z = 0.f, prev_f = 0.f;
     unsigned idle_polls = 0;
     for (;;) {
@@ -593,7 +674,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                 if (lane == slot_lane0 && c < w.cont_cap) {
                     // a pending ray's state travels in ray_state, published with the item (release here, acquire where it is taken)
                     if (pend) w.scr.ray_state[ray] = kRayPending;
-                    const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)blk << kContRayBits) |
+                    const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)(pos / unit) << kContRayBits) |
                                                     ((unsigned long long)__float_as_uint(prev_f) << 32);
                     __hip_atomic_store(&w.cont[c], item, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -609,7 +690,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             bool got = false;
             if (ticket < n_list) {
                 ray = w.sampler_list[ticket];
-                blk = 0;
+                pos = 0;
                 prev_f = 0.f;
                 pend = false;
                 got = true;
@@ -619,7 +700,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                     // acquire only once the item is there (an acquiring poll invalidates the cache on every pass: +0.5 ms per frame)
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                     ray = (int)(item & ((1u << kContRayBits) - 1u)) - 1;
-                    blk = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u));
+                    pos = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u)) * unit;
                     pend = (w.scr.ray_state[ray] & kRayPending) != 0;
                     prev_f = __uint_as_float((unsigned)(item >> 32));
                     got = true;
@@ -629,11 +710,19 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                 ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
                 dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
                 const float t = a.dist[ray], s0 = a.sdf[ray];
-                const bool pos = s0 > 0.0f;
-                smin = pos ? t : a.near[ray];
-                const float smax = pos ? a.far[ray] : t;
+                const bool pos_side = s0 > 0.0f;
+                smin = pos_side ? t : a.near[ray];
+                const float smax = pos_side ? a.far[ray] : t;
                 width = smax - smin;
-                prev_z = blk > 0 ? sample_depth(smin, a.lin[blk * kSamplerBlock - 1], width) : 0.f;
+                // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it
+                strd = 1;
+                if (stride_on && pos > 0 && !pend) {
+                    const float ld = stride_ld(Lg, lin_step, width, dx, dy, dz);
+                    if (ld > 0.0f && prev_f > delta) strd = 1 + stride_reach(prev_f, delta, ld);
+                }
+                prev_z = pos > 0 ? sample_depth(smin, a.lin[pos > strd ? pos - strd : 0], width) : 0.f;   // the sample before the item's first
+                npass = 0;
+                seg0 = pos / kSegSamples;
                 has_ray = true;
                 ticket = -1;
             }
@@ -649,16 +738,17 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             __builtin_amdgcn_s_sleep(16);
             continue;
         }
-        const int idx = blk * kSamplerBlock + s_in;
+        const int idx = pos + strd * s_in;
         const bool in_range = has_ray && idx < a.n_steps;
         const float z = sample_depth(smin, a.lin[in_range ? idx : a.n_steps - 1], width);
         const float qx = has_ray ? ox + dx * z : 0.f, qy = has_ray ? oy + dy * z : 0.f, qz = has_ray ? oz + dz * z : 0.f;
         {
             const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0);
-            be.park(0, flags); be.park(1, ray); be.park(2, blk); be.park(3, ticket);
+            const int ps = pos | (strd << kPosBits) | (npass << (kPosBits + kStrdBits)) | (seg0 << (kPosBits + kStrdBits + kPassBits));
+            be.park(0, flags); be.park(1, ray); be.park(2, ps); be.park(3, ticket);
             be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
             be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
-            be.park(15, (int)ev_ref); be.park(16, (int)ev_scr);
+            be.park(15, (int)ev_ref); be.park(16, lane == 0 ? (int)ev_scr : __float_as_int(slope));
         }
         const float f = be.template eval_screen<kH1PointTiles>(qx, qy, qz);
         // the lane-derived masks after the evaluation come from an opaque copy of the lane: hoisted out of the loop, they are held
@@ -670,15 +760,45 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0));
         has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4; pend = flags_back & 16;
         const bool in_range_b = flags_back & 8;
-        ray = be.unpark(1, ray); blk = be.unpark(2, blk); ticket = be.unpark(3, ticket);
+        ray = be.unpark(1, ray); ticket = be.unpark(3, ticket);
+        {
+            const int ps = be.unpark(2, 0);
+            pos = ps & ((1 << kPosBits) - 1); strd = (ps >> kPosBits) & ((1 << kStrdBits) - 1);
+            npass = (ps >> (kPosBits + kStrdBits)) & ((1 << kPassBits) - 1); seg0 = (int)((unsigned)ps >> (kPosBits + kStrdBits + kPassBits));
+        }
         ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
         smin = be.unpark(10, smin); width = be.unpark(11, width); prev_z = be.unpark(12, prev_z); prev_f = be.unpark(13, prev_f);
         const float zb = be.unpark(14, z);
-        ev_ref = (unsigned)be.unpark(15, (int)ev_ref); ev_scr = (unsigned)be.unpark(16, (int)ev_scr);
+        ev_ref = (unsigned)be.unpark(15, (int)ev_ref);
+        {
+            const int v16 = be.unpark(16, 0);
+            ev_scr = (unsigned)__shfl(v16, 0, 64);
+            slope = me == 0 ? 0.0f : __int_as_float(v16);
+        }
         idle_polls = 0;
         ev_scr += (unsigned)__popcll(__ballot(in_range_b));
-        const bool is_neg = in_range_b && f < -delta;                       // certainly negative
-        const bool is_unc = in_range_b && !(f > delta) && !(f < -delta);    // uncertain (NaN included)
+        const int idx_b = pos + strd * s_in_b;
+        const float ld = stride_on ? stride_ld(Lg, lin_step, width, dx, dy, dz) : 0.0f;
+        const bool good = in_range_b && f > delta;                          // certainly positive
+        const int reach = ld > 0.0f ? stride_reach(f, delta, ld) : 0;
+        const int reach_next = __shfl(reach, me < 63 ? me + 1 : 63, 64);
+        const float f_up = __shfl(f, me > 0 ? me - 1 : 0, 64);
+        // a block at a stride above 1, walked in order: its first sample that is not certainly positive (the last good one is the
+        // sample before it) or its first gap that is not certified from either end (the last good one is the sample in front of it)
+        const bool strided = has_ray && strd > 1;
+        const bool next_in = s_in_b < kSamplerBlock - 1 && idx_b + strd < a.n_steps;
+        const int to_end = a.n_steps - 1 - idx_b;
+        const int gap = s_in_b == kSamplerBlock - 1 ? 0 : (strd - 1 < to_end ? strd - 1 : to_end);   // skipped samples behind this one (the last lane's: the next block's start)
+        const bool gap_ok = reach + (next_in ? reach_next : 0) >= gap;
+        const unsigned long long bad_s = __ballot(strided && in_range_b && !good) & sbits;
+        const unsigned long long bad_g = __ballot(strided && in_range_b && !gap_ok) & sbits;
+        const bool restart = (bad_s | bad_g) != 0ull;
+        const int k_s = bad_s ? (__ffsll((long long)bad_s) - 1 - sl0) : kSamplerBlock, k_g = bad_g ? (__ffsll((long long)bad_g) - 1 - sl0) : kSamplerBlock;
+        const int last_good = k_s - 1 < k_g ? k_s - 1 : k_g;   // -1: the sample before the block
+        const float z_good = __shfl(zb, sl0 + (last_good > 0 ? last_good : 0), 64), f_good = __shfl(f, sl0 + (last_good > 0 ? last_good : 0), 64);
+        const bool counts = in_range_b && !restart;   // (nothing of a discarded block is used; a good strided block has only certainly positive samples)
+        const bool is_neg = counts && f < -delta;                       // certainly negative
+        const bool is_unc = counts && !(f > delta) && !(f < -delta);    // uncertain (NaN included)
         const unsigned long long neg = __ballot(is_neg) & sbits;
         const unsigned long long unc_all = __ballot(is_unc);
         const int first = neg ? (__ffsll((long long)neg) - 1) : sl0;
@@ -686,11 +806,17 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const float z_before = __shfl(zb, first > sl0 ? first - 1 : sl0, 64);
         const float f_before = __shfl(f, first > sl0 ? first - 1 : sl0, 64);
         const float z_last = __shfl(zb, sl0 + kSamplerBlock - 1, 64), f_last = __shfl(f, sl0 + kSamplerBlock - 1, 64);
-        const float f_up = __shfl(f, me > 0 ? me - 1 : 0, 64);
-        const int gidx = blk * kSamplerBlock + (first - sl0);
+        const int reach_last = __shfl(reach, sl0 + kSamplerBlock - 1, 64);
+        const int gidx = pos + strd * (first - sl0);
         const bool found_neg = has_ray && neg != 0u;
-        const bool done = has_ray && (found_neg || (blk + 1) * kSamplerBlock >= a.n_steps);
         const float z_lo = first > sl0 ? z_before : prev_z, f_lo = first > sl0 ? f_before : prev_f;
+        // the slope guard: adjacent samples of a stride-1 block, up to its first one that is not certainly positive
+        {
+            const unsigned long long ngood = __ballot(in_range_b && !good) & sbits;
+            const int first_ng = ngood ? (__ffsll((long long)ngood) - 1) : 64;
+            if (has_ray && strd == 1 && ld > 0.0f && in_range_b && s_in_b > 0 && me <= first_ng)
+                slope = fmaxf(slope, fmaxf(fabsf(f - f_up) - 0.5f * delta, 0.0f) / ld);
+        }
         // uncertain samples in front of the slot's first certainly-negative one: to the resolve list, one atomicAdd per wave
         const unsigned long long before = neg ? (((1ull << first) - 1ull) & sbits) : sbits;
         const unsigned long long unc = has_ray ? (unc_all & before) : 0ull;
@@ -704,15 +830,22 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         if (unc) {
             const int pos_last = rbase + lane_rank64(unc_wave, 63 - __clzll((long long)unc));
             overflow = pos_last >= w.scr.cap;
-            const int pos = rbase + lane_rank64(unc_wave, me);
-            if (((unc >> me) & 1ull) && pos < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
+            const int pos_e = rbase + lane_rank64(unc_wave, me);
+            if (((unc >> me) & 1ull) && pos_e < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
                 ResolveEntry e;
-                e.ray = ray; e.s = idx; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
-                w.scr.ent[pos] = e;
+                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
+                w.scr.ent[pos_e] = e;
             }
         }
         const bool pend_now = pend || unc != 0u;
         const bool to_ovf = has_ray && overflow;
+        // where a good block is followed up: behind its last sample by what that sample certifies (a pending ray: the next sample)
+        const bool last_in = pos + strd * (kSamplerBlock - 1) < a.n_steps;
+        const int next_strd = (ld > 0.0f && !pend_now && last_in && f_last > delta) ? 1 + reach_last : 1;
+        const int next_pos = pos + strd * (kSamplerBlock - 1) + next_strd;
+        const bool done = has_ray && !restart && (found_neg || next_pos >= a.n_steps);
+        if (has_ray && me == sl0 + 1) ++ev_ref;                 // the slot's passes
+        if (strided && me == sl0 + 2) ++ev_ref;                 // ... at a stride above 1
         if (to_ovf) {   // the ray goes to k_sampler's second list, marched from its start
             if (me == sl0) {
                 w.scr.ray_state[ray] = kRayOverflowed;
@@ -730,7 +863,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                 const int p = atomicAdd(&w.cnt->n_pend, 1);
                 w.scr.pend_list[p] = ray;
             } else {                 // exactly what k_sampler writes: every sample before gidx is positive, gidx is negative
-                const int nb = (blk + 1) * kSamplerBlock;
+                const int nb = found_neg ? (gidx / kSamplerBlock + 1) * kSamplerBlock : a.n_steps;   // k_sampler stops behind the block of gidx
                 ev_ref += (unsigned)(nb < a.n_steps ? nb : a.n_steps);
                 if (found_neg && gidx >= 1) {
                     const int pos_l = atomicAdd(&w.cnt->n_root, 1);
@@ -749,30 +882,37 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             atomicAdd(&q->n_done, 1);
         }
         pend = pend_now && !to_ovf;
-        prev_z = z_last;
-        prev_f = f_last;
-        ++blk;
-        const bool hand_over = has_ray && !to_ovf && !done && dyn && (blk % (kSamplerSeg > 0 ? kSamplerSeg : 1)) == 0;
+        if (restart) {   // behind the last good sample, at stride 1 (last_good < 0: the block's predecessor stays the previous sample)
+            if (last_good >= 0) { prev_z = z_good; prev_f = f_good; }
+            pos = pos + strd * last_good + 1;
+            strd = 1;
+        } else {
+            prev_z = z_last;
+            prev_f = f_last;
+            pos = next_pos;
+            strd = next_strd;
+        }
+        if (npass < (1 << kPassBits) - 1) ++npass;
+        // the end of a work item: after kSamplerSeg passes, in a later segment than the item's first (so a ray publishes at most one item per segment)
+        const bool hand_over = has_ray && !to_ovf && !done && !restart && dyn && npass >= kSamplerSeg && pos / kSegSamples > seg0;
         publish = hand_over;
         if (done || hand_over || to_ovf) has_ray = false;
         if (ev_ref > (1u << 30) || ev_scr > (1u << 30)) {   // flush the 32-bit per-lane counts long before they can wrap
-            unsigned long long r = ev_ref;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off, 64);
-            if (me == 0) {
-                atomicAdd((unsigned long long*)&w.cnt->n_evals, r);   // (only the slots' first lanes count)
-                atomicAdd((unsigned long long*)&w.cnt->n_screen, (unsigned long long)ev_scr);
-            }
+            screen_flush_counts(w.cnt, ev_ref, ev_scr, me);
             ev_ref = 0; ev_scr = 0;
         }
     }
     be.finish();
-    unsigned long long r = ev_ref;
+    screen_flush_counts(w.cnt, ev_ref, ev_scr, lane);
+    float r = lane == 0 ? 0.0f : slope;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off, 64);
-    if (lane == 0) {
-        atomicAdd((unsigned long long*)&w.cnt->n_evals, r);
-        atomicAdd((unsigned long long*)&w.cnt->n_screen, (unsigned long long)ev_scr);
+    for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
+    if (lane == 0 && r > 0.0f) {
+        atomicMax(&w.cnt->slope_bits, __float_as_uint(r));
+        if (r > kStrideGuard && w.scr.flag) {   // the slope guard: the network's next call marches at stride 1
+            *reinterpret_cast<volatile int*>(w.scr.flag + 1) = 1;
+            __threadfence_system();
+        }
     }
 }
 
@@ -921,10 +1061,33 @@ __global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2Stream
         m = be.unpark(1, 0.0f);
         if (d <= 3.0e38f) m = fmaxf(m, d);
     }
+    // G = max |grad f| over the same points for the adaptive march's slope bound: central differences of the h2 value at kStrideCalibH
+    // (a non-finite one makes G infinite: the march stays at stride 1)
+    float gm = 0.0f;
+    for (int g = blockIdx.x; g < kScreenCalibPoints / 128; g += gridDim.x) {
+        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+#pragma unroll 1
+        for (int e = 0; e < 6; ++e) {
+            const int i = g * 128 + be.wave * 32 + (lane & 31);
+            float x, y, z;
+            screen_calib_point(i, x, y, z);
+            const float sg = (e & 1) ? -1.0f : 1.0f;
+            const int ax = e >> 1;
+            be.park(1, gm); be.park(2, gx); be.park(3, gy); be.park(4, gz); be.park(5, m);
+            const float fv = be.eval(x + (ax == 0 ? sg * kStrideCalibH : 0.0f), y + (ax == 1 ? sg * kStrideCalibH : 0.0f),
+                                     z + (ax == 2 ? sg * kStrideCalibH : 0.0f));
+            gm = be.unpark(1, 0.0f); gx = be.unpark(2, 0.0f); gy = be.unpark(3, 0.0f); gz = be.unpark(4, 0.0f); m = be.unpark(5, 0.0f);
+            const int axb = e >> 1;
+            const float d = ((e & 1) ? -fv : fv) * (0.5f / kStrideCalibH);
+            gx += axb == 0 ? d : 0.0f; gy += axb == 1 ? d : 0.0f; gz += axb == 2 ? d : 0.0f;
+        }
+        const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
+        gm = gn <= 3.0e38f ? fmaxf(gm, gn) : __uint_as_float(0x7f800000u);
+    }
     be.finish();
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    if (lane == 0) atomicMax(calib, __float_as_uint(m));
+    for (int off = 32; off > 0; off >>= 1) { m = fmaxf(m, __shfl_xor(m, off, 64)); gm = fmaxf(gm, __shfl_xor(gm, off, 64)); }
+    if (lane == 0) { atomicMax(calib, __float_as_uint(m)); atomicMax(calib + kScreenCalibG, __float_as_uint(gm)); }
 }
 
 __device__ __forceinline__ long long ray_chunk(const TraceArgs& a, int ray) {
@@ -1236,6 +1399,8 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
 std::atomic<int> g_screen_switch{-1};           // iron_set_sampler_screen; -1 = the environment's (IRON_SAMPLER_SCREEN=0: off) / default on
 std::atomic<float> g_screen_delta_override{0.0f};   // test hooks (iron_sampler_screen_debug)
 std::atomic<int> g_screen_cap_override{0};
+std::atomic<int> g_stride_switch{-1};           // iron_set_sampler_stride; -1 = the environment's (IRON_SAMPLER_STRIDE=0: off) / default on
+std::atomic<float> g_stride_l_override{0.0f};   // test hook (iron_sampler_screen_debug 3)
 void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
 static bool screen_switch() {
@@ -1248,11 +1413,22 @@ static bool screen_switch() {
     return v < 0 ? from_env != 0 : v != 0;
 }
 
+static bool stride_switch() {
+    static int from_env = -1;
+    if (from_env < 0) {
+        const char* e = getenv("IRON_SAMPLER_STRIDE");
+        from_env = (e && e[0] == '0') ? 0 : 1;
+    }
+    const int v = g_stride_switch.load(std::memory_order_relaxed);
+    return v < 0 ? from_env != 0 : v != 0;
+}
+
 // at the start of a call: act on a guard flag an earlier call raised, then decide whether this call screens (h2 core only)
 static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use) {
     iron_net* net = const_cast<iron_net*>(cnet);
     *use = false;
     if (net->flag_host && *(volatile int*)(net->flag_host + 1)) net->screen_off = 1;
+    if (net->flag_host && *(volatile int*)(net->flag_host + 2)) net->stride_off = 1;   // the slope guard: stride 1 from now on
     if (!h2 || !screen_switch() || net->screen_off || !net->h1_trace.base) return IRON_OK;
     if (!net->screen_calib) IRON_HIP_TRY(hipMalloc((void**)&net->screen_calib, kScreenCalibBytes));
     if (!net->screen_calibrated) {   // once per handle (a re-pack is a new handle): stream-ordered, no synchronisation
@@ -1266,8 +1442,10 @@ static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use
     return IRON_OK;
 }
 
-static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk) {
+static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk, int n_steps) {
     w.scr.calib = net->screen_calib;
+    w.scr.stride = (stride_switch() && !net->stride_off && n_steps <= kStrideMaxSteps && w.cont_cap > 0) ? 1 : 0;
+    w.scr.l_override = g_stride_l_override.load(std::memory_order_relaxed);
     w.scr.flag = net->flag_dev ? net->flag_dev + 1 : nullptr;
     w.scr.delta_override = g_screen_delta_override.load(std::memory_order_relaxed);
     w.scr.rec = (PendRec*)(base + L.s_rec);
@@ -1307,10 +1485,17 @@ extern "C" int32_t iron_set_sampler_screen(int32_t on) {
     return prev;
 }
 
+extern "C" int32_t iron_set_sampler_stride(int32_t on) {
+    const int prev = stride_switch() ? 1 : 0;
+    g_stride_switch.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return prev;
+}
+
 extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 0) { g_screen_delta_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
     if (what == 1) { g_screen_cap_override.store(value >= 1.0 ? (int)value : 0, std::memory_order_relaxed); return IRON_OK; }
     if (what == 2) { set_screen_forward_tiles(value == 1.0 ? 1 : 0); return IRON_OK; }
+    if (what == 3) { g_stride_l_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
     return IRON_ERR_BAD_ARG;
 }
 
@@ -1328,6 +1513,24 @@ extern "C" int iron_trace_screen_counts(const void* workspace, double* out, void
         if (r > ratio) ratio = r;
     }
     out[0] = scr; out[1] = res; out[2] = ovf; out[3] = ratio; out[4] = pend;
+    return IRON_OK;
+}
+
+extern "C" int iron_trace_stride_counts(const void* workspace, double* out, void* stream) {
+    if (!workspace || !out) return IRON_ERR_BAD_ARG;
+    TraceCounters c[kMaxTraceSplits];
+    for (int k = 0; k < kMaxTraceSplits; ++k)
+        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
+                                    (hipStream_t)stream));
+    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    double passes = 0, strided = 0, ratio = 0, mode = 0;
+    for (int k = 0; k < kMaxTraceSplits; ++k) {
+        passes += (double)c[k].n_pass; strided += (double)c[k].n_pass_strided;
+        const float r = __builtin_bit_cast(float, c[k].slope_bits);
+        if (r > ratio) ratio = r;
+        if (c[k].stride_mode) mode = 1;
+    }
+    out[0] = passes; out[1] = strided; out[2] = ratio; out[3] = mode;
     return IRON_OK;
 }
 
@@ -1475,7 +1678,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
         w.sampler_list += b0; w.root_list += b0; w.root_lo += b0; w.root_hi += b0; w.root_flo += b0; w.root_fhi += b0; w.root_k += b0;
         a.ray0 = (int)b0; a.n = (int)nk;
         if (L.cont_cap > 0) { const int64_t per_ray = L.cont_cap / n; w.cont += b0 * per_ray; w.cont_cap = (int)(nk * per_ray); }
-        if (screen) screen_ws(w, sdf, base, L, b0, nk);
+        if (screen) screen_ws(w, sdf, base, L, b0, nk, p->n_steps);
         const int64_t tiles = (nk + 31) / 32;
         if (phase == 0) {
             {
@@ -1545,7 +1748,7 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     if (stage == 1) {
         const int rcs = screen_begin(sdf, h2, st, &screen);
         if (rcs != IRON_OK) return rcs;
-        if (screen) { IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st)); screen_ws(w, sdf, base, L, 0, n); }
+        if (screen) { IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st)); screen_ws(w, sdf, base, L, 0, n, p->n_steps); }
     }
     IRON_HIP_TRY(hipMemsetAsync(base + L.cnt, 0, kCntStride * kMaxTraceSplits, st));
     IRON_HIP_TRY(hipMemsetAsync(base + L.chunk_iters, 0, align256(sizeof(int)), st));

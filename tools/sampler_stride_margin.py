@@ -1,0 +1,193 @@
+"""CPU emulation of the screen's adaptive march (csrc/trace.hip k_sampler_screen).
+
+The screened sampler does not evaluate samples that an evaluated neighbour proves positive: a sample e with screened value f1(e)
+certifies the skipped samples m positions away while f1(e) > delta + L * dz * m, where dz is the ray's sample spacing and
+L = K_STRIDE * G, G = max |grad f| over the screen's calibration points (central differences at CALIB_H, as k_screen_calib takes
+them).  This emulation marches the rays of tools/screen_margin.py's scenes the way the kernel does -- blocks of 8 samples at a
+stride of 1 .. STRIDE_MAX, a gap certified from either end, a restart at stride 1 behind the last good sample when a sample of a
+strided block is not certainly positive or a gap is not certified -- on the emulated screen's values, and reports
+
+  * the lane evaluations (passes x 8: idle lanes are charged) against the stride-1 march's;
+  * the smallest EXACT value of a sample that was skipped, and how many skipped samples are <= 0 (must be none);
+  * the slope guard's ratio as the kernel records it (adjacent samples of stride-1 blocks, delta / 2 allowed for the screen's own
+    error, relative to L), and the same from exact values without the allowance.
+
+A ray's march ends at its first sample with a negative exact value (the kernel marches a pending ray on at stride 1 to its first
+certainly-negative sample; those passes are the same with and without the stride and are not modelled).  L is empirical, not a
+certified bound; tests/test_sampler_stride_margin.py pins the figures.
+
+    python3 tools/sampler_stride_margin.py [--res 200] [--scenes S0,S1,S3] [--gen 2] [--stride-max 16] [--l-scale 1.0]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import screen_margin as SM  # noqa: E402
+from oracle import iron_ref as R  # noqa: E402
+
+# the constants of csrc/trace.hip (kStrideK, kStrideGuard, kStrideCalibH, kStrideMax, kSamplerBlock)
+K_STRIDE = 2.0
+GUARD = 0.75
+CALIB_H = 1.0 / 128.0
+STRIDE_MAX = 16
+BLOCK = SM.BLOCK
+
+
+@torch.no_grad()
+def grad_max(sd, spec):
+    """G of k_screen_calib: the largest central-difference gradient norm of the exact value over the calibration points."""
+    x = SM.calibration_points()
+    g = []
+    for ax in range(3):
+        e = torch.zeros(3)
+        e[ax] = CALIB_H
+        g.append((R.sdf_forward(sd, spec, x + e)[:, 0] - R.sdf_forward(sd, spec, x - e)[:, 0]) * (0.5 / CALIB_H))
+    gn = torch.stack(g, -1).norm(dim=-1)
+    return float(gn.max()) if bool(torch.isfinite(gn).all()) else float("inf")
+
+
+@torch.no_grad()
+def ray_samples(sd, spec, res, prm=R.TracerParams()):
+    """Every sample of the rays the sampler marches on a res x res view of the fixture camera: exact values, screened values [rays, n_steps],
+    the sample spacing along each ray and the width of its range."""
+    from iron_amd import scenes
+    K, W2C = scenes.fixture_camera_matrices(res, res)
+    cam = R.CameraSpec(res, res, K.cpu(), W2C.cpu())
+    ro, rd, _ = cam.get_rays(cam.get_uv())
+    ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
+    hit, near, far = R.intersect_sphere(ro, rd, 1.0)
+    f = lambda p: R.sdf_forward(sd, spec, p)[:, 0]
+    _, unf, _, s, t = R.sphere_tracing(f, ro, rd, near, far, hit, prm)
+    o, d = ro[unf], rd[unf]
+    pos = s[unf] > 0
+    smin = torch.where(pos, t[unf], near[unf])
+    smax = torch.where(pos, far[unf], t[unf])
+    n = prm.n_steps
+    lin = torch.linspace(0, 1, steps=n).float()
+    width = smax - smin
+    z = smin[:, None] + lin[None, :] * width[:, None]
+    p = (o[:, None, :] + d[:, None, :] * z[..., None]).reshape(-1, 3)
+    fe = torch.cat([f(c) for c in p.split(200000)]).reshape(-1, n)
+    f1 = torch.cat([SM.screen_forward(sd, spec, c) for c in p.split(200000)]).reshape(-1, n)
+    dz = width.abs() * float(lin[1] - lin[0]) * d.norm(dim=-1)
+    return fe, f1, dz, width
+
+
+def _reach(v, delta, ld, smax):
+    c = 0
+    for m in range(1, smax):
+        if v > delta + ld * m:
+            c += 1
+    return c
+
+
+def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
+    """The adaptive march over every ray.  Returns passes, strided passes, the stride-1 march's passes, the smallest exact value of a
+    skipped sample, the skipped samples <= 0, and the guard ratio from screened (with allowance) and exact values."""
+    n_rays, n = fe.shape
+    fe_l, f1_l = fe.tolist(), f1.tolist()
+    dz_l, w_l = dz.tolist(), width.tolist()
+    passes = strided = base = nonpos = 0
+    worst = math.inf
+    guard1 = guard_ex = 0.0
+    for r in range(n_rays):
+        a, b = f1_l[r], fe_l[r]
+        ld = L * dz_l[r]
+        if not (w_l[r] > 0.0 and 0.0 < ld < math.inf):
+            ld = 0.0
+        first = next((i for i in range(n) if b[i] < 0), n)
+        base += min(first // BLOCK + 1, (n + BLOCK - 1) // BLOCK)
+        seen = [False] * n
+        pos, s, pend = 0, 1, False
+        while pos < n:
+            idx = [pos + s * k for k in range(BLOCK) if pos + s * k < n]
+            passes += 1
+            strided += s > 1
+            for e in idx:
+                seen[e] = True
+            reach = [_reach(a[e], delta, ld, smax) if ld > 0.0 else 0 for e in idx]
+            if s > 1:
+                last_good = None
+                for k, e in enumerate(idx):
+                    if not a[e] > delta:
+                        last_good = k - 1
+                        break
+                    if k < BLOCK - 1:
+                        gap = min(s - 1, n - 1 - e)
+                        if reach[k] + (reach[k + 1] if k + 1 < len(idx) else 0) < gap:
+                            last_good = k
+                            break
+                if last_good is not None:   # the rest of the block is discarded
+                    for e in idx[last_good + 1:]:
+                        seen[e] = False
+                    pos, s = pos + s * last_good + 1, 1
+                    continue
+            else:
+                ended, watch = False, True
+                for k, e in enumerate(idx):
+                    if k > 0 and watch and ld > 0.0:   # the slope guard: pairs up to the block's first sample that is not certainly positive
+                        guard1 = max(guard1, max(abs(a[e] - a[e - 1]) - 0.5 * delta, 0.0) / ld)
+                        guard_ex = max(guard_ex, abs(b[e] - b[e - 1]) / ld)
+                    if b[e] < 0:
+                        ended = True
+                        break
+                    if not a[e] > delta:   # listed for the resolve: the ray is pending and stays at stride 1
+                        pend, watch = True, False
+                if ended:
+                    break
+            if len(idx) < BLOCK:
+                break
+            last = idx[-1]
+            s = 1 + reach[-1] if (ld > 0.0 and not pend and a[last] > delta) else 1
+            pos = last + s
+        for i in range(first):
+            if not seen[i]:
+                v = b[i]
+                worst = min(worst, v)
+                nonpos += not v > 0
+    return {"passes": passes, "strided_passes": strided, "baseline_passes": base, "min_exact_skipped": worst,
+            "skipped_nonpositive": nonpos, "guard": guard1, "guard_exact": guard_ex}
+
+
+@torch.no_grad()
+def stride_report(sd, spec, res, smax=STRIDE_MAX, l_scale=1.0, samples=None):
+    """The figures of the module docstring for one network; `samples` = ray_samples(sd, spec, res) when the caller has them."""
+    delta = SM.delta_of(sd, spec)
+    G = grad_max(sd, spec)
+    L = K_STRIDE * G * l_scale
+    fe, f1, dz, width = samples if samples is not None else ray_samples(sd, spec, res)
+    out = {"sampled_rays": int(fe.shape[0]), "no_root": int((~(fe < 0).any(1)).sum()), "delta": delta, "G": G, "L": L,
+           "dz_min": float(dz.min()), "dz_median": float(dz.median())}
+    if not (0.0 < L < math.inf):
+        L = 0.0   # the kernel's rule: stride 1
+    m = march(fe, f1, dz, width, delta, L, smax)
+    out.update(m)
+    out["lane_evals"] = m["passes"] * BLOCK
+    out["baseline_lane_evals"] = m["baseline_passes"] * BLOCK
+    out["ratio"] = m["passes"] / max(m["baseline_passes"], 1)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=200)
+    ap.add_argument("--scenes", default="S0,S1,S3")
+    ap.add_argument("--gen", type=int, default=2, help="generalised 8 x 256 nets (tests/_nets.py), seeds 0..gen-1")
+    ap.add_argument("--stride-max", type=int, default=STRIDE_MAX)
+    ap.add_argument("--l-scale", type=float, default=1.0, help="scale the slope bound (0.1: what trips the guard)")
+    a = ap.parse_args()
+    for s in [x for x in a.scenes.split(",") if x]:
+        print(s, json.dumps(stride_report(*SM.scene_net(s), a.res, a.stride_max, a.l_scale)), flush=True)
+    for g in range(a.gen):
+        print("gen%d" % g, json.dumps(stride_report(*SM.generalised_net(g), a.res, a.stride_max, a.l_scale)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
