@@ -650,8 +650,10 @@ int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
 
 /* The screen's adaptive march (csrc/trace.hip k_sampler_screen; results do not depend on it).  The screen does not evaluate samples
  * that an evaluated neighbour proves positive: f1 > delta + L * (distance along the ray), with the slope bound L = 2 x the largest
- * |grad f| over the screen's calibration points.  L is empirical like the margin: the passes that run at stride 1 watch the slope
- * between adjacent samples, and one above 0.75 L raises a guard (iron_net_numeric_status bit 4) after which the network's calls
+ * |grad f| over the screen's calibration points.  L is empirical like the margin, and watched from three sources: the passes that
+ * run at stride 1 see the slope between adjacent screened samples; the resolve sees the exact value of every listed (uncertain)
+ * sample against the screened value of the sample before it, and the exact values of adjacent listed samples.  One above 0.75 L
+ * raises a guard (iron_net_numeric_status bit 4) after which the network's calls
  * march every sample -- every call that starts after the call that raised it has completed, as for the screen's guard.  Calls with
  * more than 256 steps, or too large for the sampler's continuation items, march every sample too.
  *   iron_set_sampler_stride:  on = 1 adaptive, 0 every sample, -1 the default (IRON_SAMPLER_STRIDE=0: off, else on).  Process-wide;
@@ -660,9 +662,17 @@ int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
  *   iron_trace_stride_counts: synchronises `stream`; from the workspace of the last traced call: out[0] ray-passes the screen executed
  *                             (8 samples of one ray), out[1] those at a stride above 1, out[2] the largest watched slope relative
  *                             to L (after an allowance of delta / 2 for the screen's own error), out[3] 1 if the call marched
- *                             adaptively, 0 if it ran stride 1 throughout. */
+ *                             adaptively, 0 if it ran stride 1 throughout.  out[2] is the largest over the guard's three sources.
+ *   iron_sampler_screen_debug what 4: value != 0 keeps rays with listed samples on stride 1 (the march before such rays strode);
+ *                             what 5: value != 0 mutes the guard's stride-1-pass source (tests of the resolve's sources).
+ *   iron_trace_stride_detail: synchronises `stream`; out[9] from the workspace of the last traced call: out[0] stride-1 passes of
+ *                             rays that had already listed samples and whose 8 samples were all certainly positive, out[1]
+ *                             stride-1 passes of rays that had listed none when the pass began, out[2] strided blocks discarded
+ *                             (restarts), out[3..5] slope observations of the guard's sources (stride-1 passes, resolve against
+ *                             the screened predecessor, exact adjacent pairs), out[6..8] the largest ratio each source saw. */
 int32_t iron_set_sampler_stride(int32_t on);
 int iron_trace_stride_counts(const void* workspace, double* out, void* stream);
+int iron_trace_stride_detail(const void* workspace, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the

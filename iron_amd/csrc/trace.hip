@@ -69,8 +69,16 @@ struct TraceCounters {  // zeroed at the start of every call
     // the screen's adaptive march (read through iron_trace_stride_counts)
     long long n_pass;      // slot-passes k_sampler_screen executed (one slot = 8 lanes of one ray)
     long long n_pass_strided;   // ... of them at a stride above 1
-    unsigned slope_bits;   // the slope guard: largest max(0, |f1(i+1) - f1(i)| - delta / 2) / (dz * L) over the stride-1 passes (f32 bits)
+    unsigned slope_bits;   // the slope guard: the largest ratio any of its three sources below saw (f32 bits)
     int stride_mode;       // 1: the call marched with the slope bound, 0: stride 1 throughout
+    // where the stride-1 passes go and what the slope guard sees (read through iron_trace_stride_detail)
+    long long n_pass_behind;   // stride-1 passes of rays already pending whose samples were all certainly positive
+    long long n_pass_fresh;    // stride-1 passes of rays not pending when the pass began
+    long long n_restart;       // strided blocks discarded behind their last good sample
+    long long n_obs_march;     // slope observations: adjacent screened samples of k_sampler_screen's stride-1 passes,
+    long long n_obs_res;       // ... k_screen_resolve's exact value of a listed sample against its screened predecessor,
+    long long n_obs_pair;      // ... k_screen_fin_entries' exact values of two adjacent listed samples
+    unsigned slope_march_bits, slope_res_bits, slope_pair_bits;   // the largest ratio of each source (f32 bits)
 };
 
 // The screened sampler's state (see k_sampler_screen)
@@ -81,7 +89,8 @@ struct ResolveEntry {   // one uncertain sample: written by k_sampler_screen, f_
     float f1;           // screened value
     float f_prev1;      // screened value of sample s - 1 (the previous item's last sample for s % block == 0; 0 for s == 0)
     float f_ex;         // exact (h2) value
-    int pad0, pad1;
+    int pad0;           // f32 bits of the ray's ld (stride_ld; 0: the ray marched without the slope bound), for the resolve's slope guard
+    int pad1;
 };
 struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
     int first;          // first certainly-negative sample (n_steps: none); atomicMin-ed by the resolve with the negative listed samples
@@ -94,7 +103,8 @@ struct ScreenWs {
     const unsigned* calib;   // per network: max |f_screen - f_h2| over the calibration set (f32 bits), device
     int* flag;               // per network: the guard flag (pinned host word), may be null
     float delta_override;    // test hook (> 0: this delta)
-    int stride;              // the adaptive march may run (switch on, guard not raised, n_steps <= kStrideMaxSteps, continuation items)
+    int stride;              // kStrideOn: the adaptive march may run (switch on, guard not raised, n_steps <= kStrideMaxSteps,
+                             // continuation items) | test hooks kStridePendingOff, kStrideMuteMarch
     float l_override;        // test hook (> 0: this slope bound L)
     ResolveEntry* ent;       // [cap]
     int cap;
@@ -116,7 +126,8 @@ constexpr int kScreenCalibF1 = 64;   // calibration buffer (32-bit words): [0] t
 constexpr size_t kScreenCalibBytes = (kScreenCalibF1 + kScreenCalibPoints) * 4;
 // The adaptive march's slope bound: L = kStrideK * G, G = max |grad f| over the calibration set (central differences of the h2 value
 // at kStrideCalibH, about one sample spacing), stored in calibration word kScreenCalibG.  EMPIRICAL like delta: the stride-1 passes
-// watch the slope between adjacent samples, and a ratio above kStrideGuard (relative to L) puts the network's later calls on stride 1.
+// watch the slope between adjacent samples and the resolve that of every listed sample (slope_guard_raise), and a ratio above
+// kStrideGuard (relative to L) puts the network's later calls on stride 1.
 constexpr float kStrideK = 2.0f;
 constexpr float kStrideGuard = 0.75f;
 constexpr float kStrideCalibH = 1.0f / 128.0f;
@@ -126,6 +137,9 @@ constexpr int kScreenCalibG = 1;
 #endif
 constexpr int kStrideMax = IRON_SAMPLER_STRIDE_MAX;
 constexpr int kStrideMaxSteps = 256;   // the continuation word carries a sample index in 8 bits
+constexpr int kStrideOn = 1;           // ScreenWs::stride
+constexpr int kStridePendingOff = 2;   // test hook: a pending ray keeps stride 1 (the march before pending rays strode)
+constexpr int kStrideMuteMarch = 4;    // test hook: k_sampler_screen's stride-1 passes do not feed the slope guard
 static_assert(kStrideMax >= 1 && kStrideMax <= 16, "stride field of the slot's packed position");
 constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
 constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
@@ -585,10 +599,14 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // strd > 1 discards the rest of the block and the slot resumes behind its last good sample at stride 1.  So a ray's first sample that
 // is not certainly positive is always reached at stride 1, next to its evaluated predecessor, and everything that is made of it --
 // brackets, resolve entries, PendRec, overflow -- is the stride-1 code.  After a good block the next one starts 1 + stride_reach(f1(e_7))
-// (at most kStrideMax) behind e_7; a pending ray keeps stride 1.  A work item ends after kSamplerSeg passes once its position has
-// entered a later segment (kSamplerSeg blocks of samples) than the one it started in: at stride 1 exactly the items of k_sampler, and
-// never more than sampler_cont_cap() per ray.  The continuation word carries the next sample index where k_sampler's carries the
-// block, and the taker recomputes the stride from the carried f: that needs the index in 8 bits, so a call with n_steps >
+// (at most kStrideMax) behind e_7.  A pending ray (one that has listed uncertain samples) strides by the same rules: most pending rays
+// graze the surface, list a few samples at their closest approach and then climb far above delta + ld * m, and a strided block only
+// ever accepts certainly positive samples, so every later uncertain or negative sample of the ray is still met at stride 1 and listed
+// or bracketed by the stride-1 code (per C1 frame 288 k of the 551 k stride-1 passes were such rays' passes through certainly
+// positive samples; 43 k are left).  A work item ends after kSamplerSeg passes once its position has entered a later segment
+// (kSamplerSeg blocks of samples) than the one it started in: at stride 1 exactly the items of k_sampler, and never more than
+// sampler_cont_cap() per ray.  The continuation word carries the next sample index where k_sampler's carries the block, and the
+// taker recomputes the stride from the carried f (a pending ray's too: ray_state carries its pending bit): that needs the index in 8 bits, so a call with n_steps >
 // kStrideMaxSteps (default 128) or without continuation items runs stride 1, as does a network whose G is zero or non-finite, a ray
 // whose range is empty, reversed or non-finite, and everything after the slope guard was raised (IRON_SAMPLER_STRIDE=0 /
 // iron_set_sampler_stride: off).
@@ -609,17 +627,28 @@ static_assert(kSamplerSeg < (1 << kPassBits) && kStrideMax < (1 << kStrdBits), "
 
 // the per-lane counts of k_sampler_screen, by the lane's place in its slot (see there); ev_scr is the wave's
 __device__ __forceinline__ void screen_flush_counts(TraceCounters* cnt, unsigned ev_ref, unsigned ev_scr, int me) {
-    const int s_in = me % kSamplerBlock;
-    unsigned long long r0 = s_in == 0 ? ev_ref : 0u, r1 = s_in == 1 ? ev_ref : 0u, r2 = s_in == 2 ? ev_ref : 0u;
+    unsigned long long r = ev_ref;   // summed over the slots: lane k < kSamplerBlock ends with the total of place k
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        r0 += __shfl_xor(r0, off, 64); r1 += __shfl_xor(r1, off, 64); r2 += __shfl_xor(r2, off, 64);
-    }
-    if (me == 0) {
-        atomicAdd((unsigned long long*)&cnt->n_evals, r0);
-        atomicAdd((unsigned long long*)&cnt->n_screen, (unsigned long long)ev_scr);
-        atomicAdd((unsigned long long*)&cnt->n_pass, r1);
-        atomicAdd((unsigned long long*)&cnt->n_pass_strided, r2);
+    for (int off = 32; off >= kSamplerBlock; off >>= 1) r += __shfl_xor(r, off, 64);
+    static_assert(kSamplerBlock >= 7, "places of the per-lane counts");
+    long long* const dst = me == 0 ? &cnt->n_evals : me == 1 ? &cnt->n_pass : me == 2 ? &cnt->n_pass_strided : me == 3 ? &cnt->n_pass_behind
+                         : me == 4 ? &cnt->n_pass_fresh : me == 5 ? &cnt->n_restart : &cnt->n_obs_march;
+    if (me < 7 && r) atomicAdd((unsigned long long*)dst, r);
+    if (me == 0) atomicAdd((unsigned long long*)&cnt->n_screen, (unsigned long long)ev_scr);
+}
+
+// The slope guard (one lane per wave, r = the wave's largest ratio of a slope to L from one of the three sources): k_sampler_screen
+// sees adjacent screened samples of its stride-1 passes (first blocks, restarts, the neighbourhoods of uncertain samples);
+// k_screen_resolve sees the exact value of every listed sample against its screened predecessor, and k_screen_fin_entries the exact
+// values of adjacent listed samples -- both where a ray is closest to the surface, and whatever the march strides over.
+__device__ __forceinline__ void slope_guard_raise(const TraceWs& w, unsigned* source_bits, float r) {
+    if (!(r > 0.0f)) return;
+    // (a plain look first: the maxima only grow, and thousands of waves' atomics on one line would serialise)
+    if (__float_as_uint(r) > *reinterpret_cast<volatile unsigned*>(source_bits)) atomicMax(source_bits, __float_as_uint(r));
+    if (__float_as_uint(r) > *reinterpret_cast<volatile unsigned*>(&w.cnt->slope_bits)) atomicMax(&w.cnt->slope_bits, __float_as_uint(r));
+    if (r > kStrideGuard && w.scr.flag) {   // the network's next call marches at stride 1
+        *reinterpret_cast<volatile int*>(w.scr.flag + 1) = 1;
+        __threadfence_system();
     }
 }
 
@@ -637,15 +666,18 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     const float delta = screen_delta(w.scr);
     // the slope bound of the adaptive march (0: stride 1 throughout)
     float Lg = 0.0f;
-    if (w.scr.stride) {
-        Lg = w.scr.l_override > 0.0f ? w.scr.l_override : kStrideK * __uint_as_float(w.scr.calib[kScreenCalibG]);
+    if (w.scr.stride & kStrideOn) {
+        Lg =w.scr.l_override > 0.0f ? w.scr.l_override : kStrideK * __uint_as_float(w.scr.calib[kScreenCalibG]);
         if (!(Lg > 0.0f && Lg <= 3.0e38f)) Lg = 0.0f;
     }
     const bool stride_on = Lg > 0.0f;
     const float lin_step = a.lin[1] - a.lin[0];
     const int unit = stride_on ? 1 : kSamplerBlock;   // what the continuation word's position counts: samples | blocks
     if (stride_on && blockIdx.x == 0 && threadIdx.x == 0) w.cnt->stride_mode = 1;
-    // per lane: s_in 0: k_sampler's evaluations of the rays decided here, s_in 1: the slot's passes, s_in 2: those at a stride above 1
+    const bool pend_strides = !(w.scr.stride & kStridePendingOff), watch_march = !(w.scr.stride & kStrideMuteMarch);
+    // per lane: s_in 0: k_sampler's evaluations of the rays decided here, s_in 1: the slot's passes, s_in 2: those at a stride above 1,
+    // s_in 3 / 4: the stride-1 passes of a ray already pending whose samples were all certainly positive / of a ray not yet pending,
+    // s_in 5: discarded strided blocks, s_in 6: the slot's slope observations (screen_flush_counts)
     unsigned ev_ref = 0;
     unsigned ev_scr = 0;   // per wave: screened evaluations (parked by lane 0; the other lanes park their `slope` in that field)
     float slope = 0.0f;    // lanes with a predecessor in their block: the slope guard's ratio
@@ -716,7 +748,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                 width = smax - smin;
                 // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it
                 strd = 1;
-                if (stride_on && pos > 0 && !pend) {
+                if (stride_on && pos > 0 && (pend_strides || !pend)) {
                     const float ld = stride_ld(Lg, lin_step, width, dx, dy, dz);
                     if (ld > 0.0f && prev_f > delta) strd = 1 + stride_reach(prev_f, delta, ld);
                 }
@@ -811,11 +843,13 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const bool found_neg = has_ray && neg != 0u;
         const float z_lo = first > sl0 ? z_before : prev_z, f_lo = first > sl0 ? f_before : prev_f;
         // the slope guard: adjacent samples of a stride-1 block, up to its first one that is not certainly positive
+        const unsigned long long ngood = __ballot(in_range_b && !good) & sbits;
         {
-            const unsigned long long ngood = __ballot(in_range_b && !good) & sbits;
             const int first_ng = ngood ? (__ffsll((long long)ngood) - 1) : 64;
-            if (has_ray && strd == 1 && ld > 0.0f && in_range_b && s_in_b > 0 && me <= first_ng)
-                slope = fmaxf(slope, fmaxf(fabsf(f - f_up) - 0.5f * delta, 0.0f) / ld);
+            const bool obs = watch_march && has_ray && strd == 1 && ld > 0.0f && in_range_b && s_in_b > 0 && me <= first_ng;
+            if (obs) slope = fmaxf(slope, fmaxf(fabsf(f - f_up) - 0.5f * delta, 0.0f) / ld);
+            const unsigned long long obs_slot = __ballot(obs) & sbits;
+            if (me == sl0 + 6) ev_ref += (unsigned)__popcll(obs_slot);
         }
         // uncertain samples in front of the slot's first certainly-negative one: to the resolve list, one atomicAdd per wave
         const unsigned long long before = neg ? (((1ull << first) - 1ull) & sbits) : sbits;
@@ -833,19 +867,22 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             const int pos_e = rbase + lane_rank64(unc_wave, me);
             if (((unc >> me) & 1ull) && pos_e < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
                 ResolveEntry e;
-                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = 0; e.pad1 = 0;
+                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = __float_as_int(ld); e.pad1 = 0;
                 w.scr.ent[pos_e] = e;
             }
         }
         const bool pend_now = pend || unc != 0u;
         const bool to_ovf = has_ray && overflow;
-        // where a good block is followed up: behind its last sample by what that sample certifies (a pending ray: the next sample)
+        // where a good block is followed up: behind its last sample by what that sample certifies, for a pending ray too
         const bool last_in = pos + strd * (kSamplerBlock - 1) < a.n_steps;
-        const int next_strd = (ld > 0.0f && !pend_now && last_in && f_last > delta) ? 1 + reach_last : 1;
+        const int next_strd = (ld > 0.0f && (pend_strides || !pend_now) && last_in && f_last > delta) ? 1 + reach_last : 1;
         const int next_pos = pos + strd * (kSamplerBlock - 1) + next_strd;
         const bool done = has_ray && !restart && (found_neg || next_pos >= a.n_steps);
         if (has_ray && me == sl0 + 1) ++ev_ref;                 // the slot's passes
         if (strided && me == sl0 + 2) ++ev_ref;                 // ... at a stride above 1
+        if (has_ray && strd == 1 && pend && ngood == 0ull && me == sl0 + 3) ++ev_ref;   // stride 1, already pending, all certainly positive
+        if (has_ray && strd == 1 && !pend && me == sl0 + 4) ++ev_ref;                   // stride 1, not pending when the pass began
+        if (restart && me == sl0 + 5) ++ev_ref;                 // discarded strided blocks
         if (to_ovf) {   // the ray goes to k_sampler's second list, marched from its start
             if (me == sl0) {
                 w.scr.ray_state[ray] = kRayOverflowed;
@@ -907,13 +944,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     float r = lane == 0 ? 0.0f : slope;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
-    if (lane == 0 && r > 0.0f) {
-        atomicMax(&w.cnt->slope_bits, __float_as_uint(r));
-        if (r > kStrideGuard && w.scr.flag) {   // the slope guard: the network's next call marches at stride 1
-            *reinterpret_cast<volatile int*>(w.scr.flag + 1) = 1;
-            __threadfence_system();
-        }
-    }
+    if (lane == 0) slope_guard_raise(w, &w.cnt->slope_march_bits, r);
 }
 
 // exact (h2) values of the listed samples, 32 per wave from any rays; the first negative one of each ray lowers its `first`
@@ -928,6 +959,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
     const float delta = screen_delta(w.scr);
     long long resolved = 0;
     float ratio = 0.0f;
+    float slope = 0.0f;   // the slope guard: |f_ex(s) - f1(s - 1)|, less delta / 2 for the screened side, relative to the ray's ld
+    int n_obs = 0;
     for (;;) {
         int base = 0;
         if (lane == 0) base = atomicAdd(&w.cnt->res_head, 32);
@@ -944,17 +977,24 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
             qz = a.ray_o[3 * (size_t)ray + 2] + a.ray_d[3 * (size_t)ray + 2] * e.z;
         }
         be.park(0, valid ? 1 : 0); be.park(1, li); be.park(2, ratio); be.park(3, (int)(unsigned)resolved); be.park(4, (int)(resolved >> 32));
+        be.park(5, slope); be.park(6, n_obs);
         const float f = be.eval(qx, qy, qz);
         const bool v = be.unpark(0, 0) != 0;
         const int lib = be.unpark(1, 0);
         ratio = be.unpark(2, 0.0f);
         resolved = (long long)(((unsigned long long)(unsigned)be.unpark(4, 0) << 32) | (unsigned)be.unpark(3, 0));
+        slope = be.unpark(5, 0.0f); n_obs = be.unpark(6, 0);
         resolved += __popc((unsigned)__ballot(v));
         if (v && lane < 32) {
             ResolveEntry* e = &w.scr.ent[lib];
             e->f_ex = f;
             if (f < 0.0f) atomicMin(&w.scr.rec[e->ray].first, e->s);
             const float f1 = e->f1;
+            const float ld = __int_as_float(e->pad0);
+            if (ld > 0.0f && e->s > 0) {   // sample s - 1 was screened at stride 1, next to s
+                slope = fmaxf(slope, fmaxf(fabsf(f - e->f_prev1) - 0.5f * delta, 0.0f) / ld);
+                ++n_obs;
+            }
             float r = fabsf(f1 - f) / delta;
             if (!(r <= 3.0e38f)) r = ((fabsf(f1) <= 3.0e38f) != (fabsf(f) <= 3.0e38f)) ? 3.0e38f : 0.0f;   // one side non-finite: the screen failed
             ratio = fmaxf(ratio, r);
@@ -964,7 +1004,13 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
     float r = ratio;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
+    float sl = lane < 32 ? slope : 0.0f;
+    int obs = lane < 32 ? n_obs : 0;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) { sl = fmaxf(sl, __shfl_xor(sl, off, 64)); obs += __shfl_xor(obs, off, 64); }
     if (lane == 0) {
+        if (obs) atomicAdd((unsigned long long*)&w.cnt->n_obs_res, (unsigned long long)obs);
+        slope_guard_raise(w, &w.cnt->slope_res_bits, sl);
         atomicAdd((unsigned long long*)&w.cnt->n_resolved, (unsigned long long)resolved);
         atomicMax(&w.cnt->ratio_bits, __float_as_uint(r));
         if (r > kScreenGuard && w.scr.flag) {   // the guard: the network's next call runs the unscreened sampler
@@ -978,13 +1024,35 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
 __global__ void k_screen_fin_entries(TraceWs w) {
     const int n_res = w.cnt->n_res;
     const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
+    float slope = 0.0f;   // the slope guard: exact values of adjacent listed samples (a pass lists its samples in order), relative to ld
+    int n_obs = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_ent; i += gridDim.x * blockDim.x) {
         const ResolveEntry e = w.scr.ent[i];
+        const float ld = __int_as_float(e.pad0);
+        if (i > 0 && ld > 0.0f) {
+            const ResolveEntry p = w.scr.ent[i - 1];
+            if (p.ray == e.ray && p.s + 1 == e.s) {
+                slope = fmaxf(slope, fabsf(e.f_ex - p.f_ex) / ld);
+                ++n_obs;
+            }
+        }
         if (w.scr.ray_state[e.ray] == kRayOverflowed) continue;
         PendRec* r = &w.scr.rec[e.ray];
         const int g = r->first;
         if (e.s == g) { r->fhi = e.f_ex; r->flo = e.f_prev1; }   // (overwritten below when sample g - 1 was listed too)
         if (e.s == g - 1) { r->flo_ex = e.f_ex; r->has_flo_ex = 1; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { slope = fmaxf(slope, __shfl_xor(slope, off, 64)); n_obs += __shfl_xor(n_obs, off, 64); }
+    __shared__ float s_slope[16];   // one set of atomics per workgroup (blockDim.x <= 1024)
+    __shared__ int s_obs[16];
+    const int wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) { s_slope[wave] = slope; s_obs[wave] = n_obs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < n_waves; ++k) { slope = fmaxf(slope, s_slope[k]); n_obs += s_obs[k]; }
+        if (n_obs) atomicAdd((unsigned long long*)&w.cnt->n_obs_pair, (unsigned long long)n_obs);
+        slope_guard_raise(w, &w.cnt->slope_pair_bits, slope);
     }
 }
 
@@ -1401,6 +1469,7 @@ std::atomic<float> g_screen_delta_override{0.0f};   // test hooks (iron_sampler_
 std::atomic<int> g_screen_cap_override{0};
 std::atomic<int> g_stride_switch{-1};           // iron_set_sampler_stride; -1 = the environment's (IRON_SAMPLER_STRIDE=0: off) / default on
 std::atomic<float> g_stride_l_override{0.0f};   // test hook (iron_sampler_screen_debug 3)
+std::atomic<int> g_stride_hooks{0};             // test hooks (iron_sampler_screen_debug 4, 5): kStridePendingOff | kStrideMuteMarch
 void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
 static bool screen_switch() {
@@ -1444,7 +1513,8 @@ static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use
 
 static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk, int n_steps) {
     w.scr.calib = net->screen_calib;
-    w.scr.stride = (stride_switch() && !net->stride_off && n_steps <= kStrideMaxSteps && w.cont_cap > 0) ? 1 : 0;
+    w.scr.stride = (stride_switch() && !net->stride_off && n_steps <= kStrideMaxSteps && w.cont_cap > 0)
+                       ? (kStrideOn | g_stride_hooks.load(std::memory_order_relaxed)) : 0;
     w.scr.l_override = g_stride_l_override.load(std::memory_order_relaxed);
     w.scr.flag = net->flag_dev ? net->flag_dev + 1 : nullptr;
     w.scr.delta_override = g_screen_delta_override.load(std::memory_order_relaxed);
@@ -1496,6 +1566,12 @@ extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 1) { g_screen_cap_override.store(value >= 1.0 ? (int)value : 0, std::memory_order_relaxed); return IRON_OK; }
     if (what == 2) { set_screen_forward_tiles(value == 1.0 ? 1 : 0); return IRON_OK; }
     if (what == 3) { g_stride_l_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
+    if (what == 4 || what == 5) {
+        const int bit = what == 4 ? kStridePendingOff : kStrideMuteMarch;
+        if (value != 0.0) g_stride_hooks.fetch_or(bit, std::memory_order_relaxed);
+        else g_stride_hooks.fetch_and(~bit, std::memory_order_relaxed);
+        return IRON_OK;
+    }
     return IRON_ERR_BAD_ARG;
 }
 
@@ -1531,6 +1607,26 @@ extern "C" int iron_trace_stride_counts(const void* workspace, double* out, void
         if (c[k].stride_mode) mode = 1;
     }
     out[0] = passes; out[1] = strided; out[2] = ratio; out[3] = mode;
+    return IRON_OK;
+}
+
+extern "C" int iron_trace_stride_detail(const void* workspace, double* out, void* stream) {
+    if (!workspace || !out) return IRON_ERR_BAD_ARG;
+    TraceCounters c[kMaxTraceSplits];
+    for (int k = 0; k < kMaxTraceSplits; ++k)
+        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
+                                    (hipStream_t)stream));
+    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < 9; ++i) out[i] = 0.0;
+    for (int k = 0; k < kMaxTraceSplits; ++k) {
+        out[0] += (double)c[k].n_pass_behind; out[1] += (double)c[k].n_pass_fresh; out[2] += (double)c[k].n_restart;
+        out[3] += (double)c[k].n_obs_march; out[4] += (double)c[k].n_obs_res; out[5] += (double)c[k].n_obs_pair;
+        const unsigned bits[3] = {c[k].slope_march_bits, c[k].slope_res_bits, c[k].slope_pair_bits};
+        for (int s = 0; s < 3; ++s) {
+            const float r = __builtin_bit_cast(float, bits[s]);
+            if (r > out[6 + s]) out[6 + s] = r;
+        }
+    }
     return IRON_OK;
 }
 

@@ -13,8 +13,12 @@ strided block is not certainly positive or a gap is not certified -- on the emul
     error, relative to L), and the same from exact values without the allowance.
 
 A ray's march ends at its first sample with a negative exact value (the kernel marches a pending ray on at stride 1 to its first
-certainly-negative sample; those passes are the same with and without the stride and are not modelled).  L is empirical, not a
-certified bound; tests/test_sampler_stride_margin.py pins the figures.
+certainly-negative sample; march() does not model those passes).  march_rays() / pending_report() do: they march every ray to its
+first certainly-negative screened sample the way the kernel does, with pending rays striding like the others, and report that the
+samples the stride-1 code classifies as uncertain or negative are those of the all-stride-1 march, what the stride saves on pending
+rays, and the slope guard's ratio and number of observations from each of its three sources (the stride-1 passes, the resolve's
+exact value against the screened predecessor, the exact values of adjacent listed samples).  L is empirical, not a
+certified bound; tests/test_sampler_stride_margin.py and tests/test_sampler_stride_pending.py pin the figures.
 
     python3 tools/sampler_stride_margin.py [--res 200] [--scenes S0,S1,S3] [--gen 2] [--stride-max 16] [--l-scale 1.0]
 """
@@ -156,6 +160,107 @@ def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
             "skipped_nonpositive": nonpos, "guard": guard1, "guard_exact": guard_ex}
 
 
+def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True):
+    """The march of k_sampler_screen ray by ray, to each ray's first certainly-negative screened sample or its end, pending rays
+    (those that have listed an uncertain sample) included: with `pending_stride` they stride by the rules of the others, without
+    it they keep stride 1 (the march before they strode); L = 0 is the all-stride-1 march.  Returns the pass counts, per ray what
+    the stride-1 code classified (the listed uncertain samples and the first certainly-negative one), and the slope guard's three
+    sources as the kernels take them, each with its number of observations:
+      march    adjacent screened samples of stride-1 passes up to the first that is not certainly positive, delta / 2 allowed;
+      resolve  the exact value of a listed sample against the screened value of its predecessor, delta / 2 allowed;
+      pair     the exact values of two adjacent samples listed by one pass, no allowance."""
+    n_rays, n = fe.shape
+    fe_l, f1_l = fe.tolist(), f1.tolist()
+    dz_l, w_l = dz.tolist(), width.tolist()
+    c = {"passes": 0, "strided_passes": 0, "restarts": 0, "stride1_behind": 0, "stride1_fresh": 0,
+         "obs_march": 0, "obs_resolve": 0, "obs_pair": 0, "guard_march": 0.0, "guard_resolve": 0.0, "guard_pair": 0.0, "pending_rays": 0}
+    classified = []
+    for r in range(n_rays):
+        a, b = f1_l[r], fe_l[r]
+        ld = L * dz_l[r]
+        if not (w_l[r] > 0.0 and 0.0 < ld < math.inf):
+            ld = 0.0
+        listed, first_neg = [], n
+        pos, s, pend = 0, 1, False
+        while pos < n:
+            idx = [pos + s * k for k in range(BLOCK) if pos + s * k < n]
+            c["passes"] += 1
+            reach = [_reach(a[e], delta, ld, smax) if ld > 0.0 else 0 for e in idx]
+            if s > 1:
+                c["strided_passes"] += 1
+                last_good = None
+                for k, e in enumerate(idx):
+                    if not a[e] > delta:
+                        last_good = k - 1
+                        break
+                    if k < BLOCK - 1:
+                        gap = min(s - 1, n - 1 - e)
+                        if reach[k] + (reach[k + 1] if k + 1 < len(idx) else 0) < gap:
+                            last_good = k
+                            break
+                if last_good is not None:   # the rest of the block is discarded
+                    c["restarts"] += 1
+                    pos, s = pos + s * last_good + 1, 1
+                    continue
+            else:
+                ngood = [k for k, e in enumerate(idx) if not a[e] > delta]
+                if pend and not ngood:
+                    c["stride1_behind"] += 1
+                if not pend:
+                    c["stride1_fresh"] += 1
+                if ld > 0.0:
+                    for k in range(1, len(idx)):
+                        if ngood and k > ngood[0]:
+                            break
+                        c["obs_march"] += 1
+                        c["guard_march"] = max(c["guard_march"], max(abs(a[idx[k]] - a[idx[k] - 1]) - 0.5 * delta, 0.0) / ld)
+                neg = next((k for k, e in enumerate(idx) if a[e] < -delta), None)
+                unc = [e for e in idx[:neg] if not a[e] > delta and not a[e] < -delta]
+                for j, e in enumerate(unc):
+                    if ld > 0.0 and e > 0:
+                        c["obs_resolve"] += 1
+                        c["guard_resolve"] = max(c["guard_resolve"], max(abs(b[e] - a[e - 1]) - 0.5 * delta, 0.0) / ld)
+                    if ld > 0.0 and j > 0 and unc[j - 1] == e - 1:
+                        c["obs_pair"] += 1
+                        c["guard_pair"] = max(c["guard_pair"], abs(b[e] - b[e - 1]) / ld)
+                listed += unc
+                pend = pend or bool(unc)
+                if neg is not None:
+                    first_neg = idx[neg]
+                    break
+            last = pos + s * (BLOCK - 1)
+            s = 1 + reach[-1] if (ld > 0.0 and (pending_stride or not pend) and last < n and a[last] > delta) else 1
+            pos = last + s
+        c["pending_rays"] += pend
+        classified.append((tuple(listed), first_neg))
+    c["classified"] = classified
+    return c
+
+
+@torch.no_grad()
+def pending_report(sd, spec, res, smax=STRIDE_MAX, l_scale=1.0, samples=None):
+    """Pending rays striding (march_rays) against the march that kept them on stride 1 and against the all-stride-1 march: the pass
+    counts of the three, the rays whose stride-1 classification (listed samples, first certainly-negative sample) differs from the
+    all-stride-1 march's (must be none), and the guard's ratio and observation count per source, before and after."""
+    delta = SM.delta_of(sd, spec)
+    L = K_STRIDE * grad_max(sd, spec) * l_scale
+    if not (0.0 < L < math.inf):
+        L = 0.0
+    fe, f1, dz, width = samples if samples is not None else ray_samples(sd, spec, res)
+    one = march_rays(fe, f1, dz, width, delta, 0.0, smax)
+    old = march_rays(fe, f1, dz, width, delta, L, smax, pending_stride=False)
+    new = march_rays(fe, f1, dz, width, delta, L, smax, pending_stride=True)
+    out = {"sampled_rays": int(fe.shape[0]), "pending_rays": new["pending_rays"], "passes_stride1": one["passes"],
+           "class_mismatch_rays": sum(x != y for x, y in zip(new["classified"], one["classified"])),
+           "class_mismatch_rays_before": sum(x != y for x, y in zip(old["classified"], one["classified"])),
+           "listed_samples": sum(len(x[0]) for x in one["classified"])}
+    for tag, m in (("before", old), ("after", new)):
+        for k, v in m.items():
+            if k not in ("classified", "pending_rays"):
+                out["%s_%s" % (k, tag)] = v
+    return out
+
+
 @torch.no_grad()
 def stride_report(sd, spec, res, smax=STRIDE_MAX, l_scale=1.0, samples=None):
     """The figures of the module docstring for one network; `samples` = ray_samples(sd, spec, res) when the caller has them."""
@@ -183,10 +288,11 @@ def main():
     ap.add_argument("--stride-max", type=int, default=STRIDE_MAX)
     ap.add_argument("--l-scale", type=float, default=1.0, help="scale the slope bound (0.1: what trips the guard)")
     a = ap.parse_args()
-    for s in [x for x in a.scenes.split(",") if x]:
-        print(s, json.dumps(stride_report(*SM.scene_net(s), a.res, a.stride_max, a.l_scale)), flush=True)
-    for g in range(a.gen):
-        print("gen%d" % g, json.dumps(stride_report(*SM.generalised_net(g), a.res, a.stride_max, a.l_scale)), flush=True)
+    nets = [(s, SM.scene_net(s)) for s in a.scenes.split(",") if s] + [("gen%d" % g, SM.generalised_net(g)) for g in range(a.gen)]
+    for name, (sd, spec) in nets:
+        samples = ray_samples(sd, spec, a.res)
+        print(name, json.dumps(stride_report(sd, spec, a.res, a.stride_max, a.l_scale, samples)), flush=True)
+        print(name, "pending", json.dumps(pending_report(sd, spec, a.res, a.stride_max, a.l_scale, samples)), flush=True)
 
 
 if __name__ == "__main__":
