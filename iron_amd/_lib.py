@@ -363,3 +363,11 @@ def workspace(nbytes: int, device, tag: str):
         buf = torch.empty(nbytes + (nbytes >> 3), dtype=torch.uint8, device=device)
         _workspaces[key] = buf
     return buf
+
+
+def current_workspace(device, tag: str):
+    """The buffer workspace() last handed out for `tag` on the CURRENT stream of `device`, or None: for reading back what a call
+    left in it (iron_trace_screen_counts and its kin take the trace workspace of the call they report on)."""
+    import torch
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream, tag)
+    return _workspaces.get(key)

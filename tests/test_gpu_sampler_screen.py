@@ -16,6 +16,13 @@ pytestmark = pytest.mark.gpu
 KEYS = ("convergent_mask", "points", "sdf", "distance", "depth")
 
 
+def _field(scene):
+    if scene in ("S0", "S1", "S3"):
+        return scenes.build_networks(scene)["sdf_network"].cuda()
+    import _hard_fields   # bumpy03_s1 = bumpy(0.03, 1): overshoot and multi-root rays by the hundred
+    return _hard_fields.build(scene).cuda()
+
+
 def _counts_of(ws):
     out = (C.c_double * 5)()
     _lib.check(_lib.load().iron_trace_screen_counts(ws.data_ptr(), out, _lib.stream_ptr(torch.device("cuda", 0))))
@@ -23,9 +30,9 @@ def _counts_of(ws):
 
 
 def _counts():
-    ws = [b for k, b in _lib._workspaces.items() if k[2] == "trace"]
-    assert ws
-    return _counts_of(ws[0])
+    ws = _lib.current_workspace(torch.device("cuda", 0), "trace")   # this stream's: a process that rendered edges has a side stream's too
+    assert ws is not None
+    return _counts_of(ws)
 
 
 def _screened_anywhere(extra=()):
@@ -64,9 +71,9 @@ def _equal(sdf, res, max_rays=None):
 
 
 @torch.no_grad()
-@pytest.mark.parametrize("scene,res", [("S0", 800), ("S1", 800), ("S3", 400)])
+@pytest.mark.parametrize("scene,res", [("S0", 800), ("S1", 800), ("S3", 400), ("bumpy03_s1", 256)])
 def test_screened_sampler_is_bit_equal(scene, res):
-    sdf = scenes.build_networks(scene)["sdf_network"].cuda()
+    sdf = _field(scene)
     cnt = _equal(sdf, res)
     assert cnt["ratio"] <= 0.25, cnt
     assert cnt["overflow"] == 0, cnt

@@ -34,8 +34,8 @@ def _dev():
 
 def _counts():
     lib = _lib.load()
-    ws = [b for k, b in _lib._workspaces.items() if k[2] == "trace"]
-    assert ws
+    ws = [_lib.current_workspace(torch.device("cuda", 0), "trace")]   # this stream's, not a side stream's of an earlier render
+    assert ws[0] is not None
     a, b, d = (C.c_double * 5)(), (C.c_double * 4)(), (C.c_double * 9)()
     _lib.check(lib.iron_trace_screen_counts(ws[0].data_ptr(), a, _dev()))
     _lib.check(lib.iron_trace_stride_counts(ws[0].data_ptr(), b, _dev()))

@@ -63,8 +63,8 @@ def _agrees(net, x, label):
 
 
 def _counts():
-    ws = [b for k, b in _lib._workspaces.items() if k[2] == "trace"]
-    assert ws
+    ws = [_lib.current_workspace(torch.device("cuda", 0), "trace")]   # this stream's, not a side stream's of an earlier render
+    assert ws[0] is not None
     out = (C.c_double * 5)()
     _lib.check(_lib.load().iron_trace_screen_counts(ws[0].data_ptr(), out, _lib.stream_ptr(torch.device("cuda", 0))))
     return {"screened": out[0], "resolved": out[1], "overflow": out[2], "ratio": out[3]}
