@@ -1,14 +1,16 @@
 // Sphere tracer: RayTracer.forward = sphere_tracing + ray_sampler + rootfind
-// (models/raytracer.py:45-220) as four persistent kernels on one stream, no host sync.
+// (models/raytracer.py:45-220) as persistent kernels on one stream, no host sync: the four below, and on the h2 core the screened
+// form of the sampler (k_sampler_screen + k_screen_resolve + k_screen_fin_*, then k_sampler on the rays that overflowed).
 //
 //   k_sphere   one wave owns 32 ray slots.  Every pass evaluates the SDF MLP for all 32 slots, then
 //              each slot steps or retires; retired slots are refilled from a global ray queue
 //              (ballot -> rank among free slots -> one atomicAdd per wave), so MFMA tiles stay full
 //              although rays finish after 1..17 evaluations.  Rays still unfinished after the
 //              iteration cap are appended to the sampler list.
-//   k_sampler  one wave per listed ray: the 128 dense samples are evaluated 32 at a time in march
-//              order and the search stops at the first block that holds a negative sample (the
-//              reference evaluates all 128 and then takes the first sign change: same result).
+//   k_sampler  32 / kSamplerBlock ray slots per wave: a listed ray's dense samples are evaluated kSamplerBlock
+//              at a time in march order, as work items of kSamplerSeg blocks, and the search stops at the
+//              first block that holds a negative sample (the reference evaluates all n_steps and then
+//              takes the first sign change: same result).
 //   k_bisect_a 32 bracketed rays per wave, each bisected until ITS interval is <= 2*threshold;
 //              records the per-ray count and atomicMax-es it into the ray's chunk.
 //   k_bisect_b the reference loops while ANY ray of the call is unfinished and updates ALL rays, so
@@ -89,9 +91,10 @@ struct ResolveEntry {   // one uncertain sample: written by k_sampler_screen, f_
     float f1;           // screened value
     float f_prev1;      // screened value of sample s - 1 (the previous item's last sample for s % block == 0; 0 for s == 0)
     float f_ex;         // exact (h2) value
-    int pad0;           // f32 bits of the ray's ld (stride_ld; 0: the ray marched without the slope bound), for the resolve's slope guard
-    int pad1;
+    float ld;           // the ray's ld (stride_ld; 0: the ray marched without the slope bound), for the resolve's slope guard
+    int pad;
 };
+static_assert(sizeof(ResolveEntry) == 32, "resolve entry: two per 64-byte line");
 struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
     int first;          // first certainly-negative sample (n_steps: none); atomicMin-ed by the resolve with the negative listed samples
     float fhi, flo;     // bracket values at `first` (screened, or exact where the sample was listed)
@@ -100,8 +103,8 @@ struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
     int pad[3];
 };
 struct ScreenWs {
-    const unsigned* calib;   // per network: max |f_screen - f_h2| over the calibration set (f32 bits), device
-    int* flag;               // per network: the guard flag (pinned host word), may be null
+    const unsigned* calib;   // per network, device (f32 bits): [0] max |f_screen - f_h2| over the calibration set, [kScreenCalibG] G = max |grad f|
+    int* flag;               // per network, pinned host words, may be null: [0] the screen's guard flag, [1] the slope guard's
     float delta_override;    // test hook (> 0: this delta)
     int stride;              // kStrideOn: the adaptive march may run (switch on, guard not raised, n_steps <= kStrideMaxSteps,
                              // continuation items) | test hooks kStridePendingOff, kStrideMuteMarch
@@ -150,8 +153,8 @@ __device__ __forceinline__ float screen_delta(const ScreenWs& s) {
 
 struct TraceWs {
     TraceCounters* cnt;
-    int* sampler_list;  // [n]
-    int* root_list;     // [n]
+    int* sampler_list;  // [n] the rays k_sphere lists for the dense sampler (ovf_pass: the screen's overflow list)
+    int* root_list;     // [n] rays with a bracket, appended by the sampler (k_sampler, k_sampler_screen, k_screen_fin_rays)
     float* root_lo;     // [n] by list position
     float* root_hi;
     float* root_flo;
@@ -160,8 +163,8 @@ struct TraceWs {
     int* chunk_iters;   // [n_chunks]
     int* chunk_roots;   // [n_chunks] bisected rays per chunk (for the reference-equivalent eval count)
     int n_chunks;
-    unsigned long long* cont;  // k_sampler's continuation items, [cont_cap] (zeroed at the start of a call)
-    int cont_cap;
+    unsigned long long* cont;  // the sampler's continuation items (k_sampler's or k_sampler_screen's), [cont_cap] (zeroed at the start of a call)
+    int cont_cap;       // 0: no items, a slot keeps its ray to the end
     int ovf_pass;       // k_sampler: 0 = the list k_sphere fills (cnt->smp), 1 = the screen's overflow list (cnt->ovf, sampler_list = it)
     ScreenWs scr;
 };
@@ -188,6 +191,26 @@ struct TraceArgs {
 
 __device__ __forceinline__ int lane_rank(unsigned mask, int j) { return __popc(mask & ((1u << j) - 1u)); }
 __device__ __forceinline__ int lane_rank64(unsigned long long mask, int j) { return __popcll(mask & ((1ull << j) - 1ull)); }
+
+// butterfly reductions over the lanes whose numbers differ in the bits HI .. LO: every such lane ends with the result
+// (32, 1: the wave; 16, 1: each half of 32 lanes; 32, kSamplerBlock: the lanes with the same place in their slots)
+template <int HI = 32, int LO = 1, class T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int off = HI; off >= LO; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+template <int HI = 32, int LO = 1>
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+    for (int off = HI; off >= LO; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
+    return x;
+}
+
+__device__ __forceinline__ void ray_origin_dir(const TraceArgs& a, int ray, float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
+    ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
+    dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
+}
 
 // ---- evaluation back ends ---------------------------------------------------------------------------------
 // The tracer kernels are written once as per-wave state machines around three calls:
@@ -276,6 +299,24 @@ typedef BackendH2T<IRON_TRACE_DEFER != 0> BackendH2;
 #endif
 typedef BackendH2T<IRON_SAMPLER_DEFER != 0> BackendH2Sampler;
 
+// parked state that several kernels keep: a 64-bit counter in fields i, i + 1; two 3-vectors (a ray's origin or point, and its
+// direction) in fields i .. i + 5
+template <class BE>
+__device__ __forceinline__ void park_i64(BE& be, int i, long long v) { be.park(i, (int)(unsigned)v); be.park(i + 1, (int)(v >> 32)); }
+template <class BE>
+__device__ __forceinline__ long long unpark_i64(BE& be, int i, long long v) {
+    return (long long)(((unsigned long long)(unsigned)be.unpark(i + 1, (int)(v >> 32)) << 32) | (unsigned)be.unpark(i, (int)(unsigned)v));
+}
+template <class BE>
+__device__ __forceinline__ void park_vec6(BE& be, int i, float ox, float oy, float oz, float dx, float dy, float dz) {
+    be.park(i, ox); be.park(i + 1, oy); be.park(i + 2, oz); be.park(i + 3, dx); be.park(i + 4, dy); be.park(i + 5, dz);
+}
+template <class BE>
+__device__ __forceinline__ void unpark_vec6(BE& be, int i, float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
+    ox = be.unpark(i, ox); oy = be.unpark(i + 1, oy); oz = be.unpark(i + 2, oz);
+    dx = be.unpark(i + 3, dx); dy = be.unpark(i + 4, dy); dz = be.unpark(i + 5, dz);
+}
+
 #define IRON_TRACE_KERNEL_ARGS SdfNetDev net, H2StreamDev hs, H2Meta hm, TraceArgs a, TraceWs w
 
 template <class BE>
@@ -319,7 +360,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sphere(IRON_TRACE_KERNEL_AR
         if (!be.any(act2 != 0u)) break;
         evals += __popc(act2);
 
-        {   // the ray state waits in LDS while the evaluation has the registers
+        {   // the ray state waits in LDS while the evaluation has the registers (spelled out: with park_vec6 / park_i64 this kernel,
+            // the frame's longest, comes out with another register assignment and 18 more spilled SGPRs)
             const int flags = (active ? 1 : 0) | (unf ? 2 : 0) | (work ? 4 : 0) | (exhausted ? 8 : 0);
             be.park(0, flags); be.park(1, ray); be.park(2, steps);
             be.park(3, px); be.park(4, py); be.park(5, pz); be.park(6, dx); be.park(7, dy); be.park(8, dz); be.park(9, t); be.park(10, far);
@@ -422,6 +464,105 @@ static inline int64_t sampler_cont_cap(int64_t n, int n_steps) {
 
 __device__ __forceinline__ float sample_depth(float smin, float lin, float width) { return smin + lin * width; }   // raytracer.py:147-149
 
+// ---- the queue protocol and the outcome writes, shared by k_sampler and k_sampler_screen (the outcomes by k_screen_fin_rays too) ------
+// Per slot (uniform over its kSamplerBlock lanes): has_ray, or a ticket >= 0 for the next item, or retired (nothing more to draw);
+// publish: the slot's last pass ended a work item whose ray goes back to the queue.
+
+// the first-lane bits of a per-slot predicate's ballot, one bit per slot (Ballot: 32 bits where the slots are the lower wave half's)
+template <int SLOTS, class Ballot>
+__device__ __forceinline__ unsigned slot_heads(Ballot b) {
+    unsigned m = 0;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) m |= (unsigned)((b >> (s * kSamplerBlock)) & (Ballot)1) << s;
+    return m;
+}
+
+// Publishing the continuations of the last pass and drawing tickets for the free slots costs one atomicAdd each per wave: the
+// bases of the wave's tickets and of its items, from the slot masks of the two ballots.  (The kernels keep the few lines that
+// join these helpers: written as one function they compile to 20-30 more spilled VGPRs in both sampler kernels.)
+struct QueueBases { int tbase, pbase; };
+__device__ __forceinline__ QueueBases sampler_queue_bases(SamplerQ* q, int lane, unsigned need_slots, unsigned pub_slots) {
+    int v = 0;
+    if (lane == 0 && need_slots) v = atomicAdd(&q->head, __popc(need_slots));
+    if (lane == 1 && pub_slots) v = atomicAdd(&q->n_cont, __popc(pub_slots));
+    return QueueBases{__shfl(v, 0, 64), __shfl(v, 1, 64)};
+}
+// a publishing slot's item word [ray + 1][item_pos / item_unit][prev_f], stored by the slot's first lane with ORDER if it fits;
+// mark_pending: the ray's pending bit travels in ray_state, written before the item (so ORDER is release, and the taker acquires)
+template <int ORDER>
+__device__ __forceinline__ void sampler_publish_item(const TraceWs& w, int pbase, unsigned pub_slots, int slot, bool first_lane, int ray, int item_pos,
+                                                     int item_unit, float prev_f, bool mark_pending) {
+    const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
+    if (first_lane && c < w.cont_cap) {
+        if (mark_pending) w.scr.ray_state[ray] = kRayPending;
+        const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)(item_pos / item_unit) << kContRayBits) |
+                                        ((unsigned long long)__float_as_uint(prev_f) << 32);
+        __hip_atomic_store(&w.cont[c], item, ORDER, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// a free slot's ticket; -1: nothing beyond (every ray publishes at most segs - 1 items), the slot retires
+__device__ __forceinline__ int sampler_draw(int tbase, unsigned need_slots, int slot, long long n_tickets) {
+    const long long t = (long long)tbase + __popc(need_slots & ((1u << slot) - 1u));
+    return (t >= n_tickets || tbase < 0) ? -1 : (int)t;
+}
+
+// A held ticket: the list's ray (item position 0), or the continuation item once it is there (false: not yet).  item_pos is the
+// word's position field as published.
+__device__ __forceinline__ bool sampler_take(const TraceWs& w, int n_list, int ticket, int& ray, int& item_pos, float& prev_f) {
+    if (ticket < n_list) {
+        ray = w.sampler_list[ticket];
+        item_pos = 0;
+        prev_f = 0.f;
+        return true;
+    }
+    const unsigned long long item = __hip_atomic_load(&w.cont[ticket - n_list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (item == 0ull) return false;
+    ray = (int)(item & ((1u << kContRayBits) - 1u)) - 1;
+    item_pos = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u));
+    prev_f = __uint_as_float((unsigned)(item >> 32));
+    return true;
+}
+
+// raytracer.py:59-65: sample [t, far] if sdf > 0 else [near, t]
+__device__ __forceinline__ void ray_interval(const TraceArgs& a, int ray, float& smin, float& width) {
+    const float t = a.dist[ray], s0 = a.sdf[ray];
+    const bool pos_side = s0 > 0.0f;
+    smin = pos_side ? t : a.near[ray];
+    const float smax = pos_side ? a.far[ray] : t;
+    width = smax - smin;
+}
+
+// No ray in the workgroup: true when it is done -- no slot holds a ticket that can still be served (or a ray to publish), or every
+// listed ray has ended.  Otherwise one poll of the queue; the bound is a few seconds and never reached unless the protocol is
+// broken -- reported in the stats.
+template <class BE>
+__device__ __forceinline__ bool sampler_idle_done(BE& be, SamplerQ* q, int n_list, TraceCounters* cnt, bool holds, unsigned& idle_polls) {
+    const bool all_ended = __hip_atomic_load(&q->n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
+    const bool waiting = __ballot(holds) != 0ull && !all_ended;
+    if (!be.any(waiting)) return true;
+    if (++idle_polls > (1u << 22)) {
+        if (threadIdx.x == 0) atomicAdd((unsigned long long*)&cnt->sampler_abort, 1ull);
+        return true;
+    }
+    __builtin_amdgcn_s_sleep(16);
+    return false;
+}
+
+// a ray's outcome: a bracket for the bisection ...
+__device__ __forceinline__ void sampler_write_root(const TraceWs& w, int ray, float z_lo, float z_hi, float f_lo, float f_hi) {
+    const int pos_l = atomicAdd(&w.cnt->n_root, 1);
+    w.root_list[pos_l] = ray;
+    w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_hi;
+    w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_hi;
+}
+// ... or none (raytracer.py:158-160, 75-78: sampled rays without a root get zeros; `zero`: 0.f, as the caller wants it held)
+__device__ __forceinline__ void sampler_write_no_root(const TraceArgs& a, int ray, float zero) {
+    a.conv[ray] = 0;
+    a.points[3 * (size_t)ray] = zero; a.points[3 * (size_t)ray + 1] = zero; a.points[3 * (size_t)ray + 2] = zero;
+    a.sdf[ray] = zero;
+    a.dist[ray] = zero;
+}
+
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_ARGS) {
     BE be;
@@ -443,76 +584,28 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, smin = 0.f, width = 0.f, prev_z = 0.f, prev_f = 0.f;
     unsigned idle_polls = 0;
     for (;;) {
-        // ---- publish the continuations of the last pass and draw tickets for the free slots: one atomicAdd each per wave
-        unsigned pub_slots = 0, need_slots = 0;
-        {
-            const unsigned pub = (unsigned)__ballot(publish), need = (unsigned)__ballot(!has_ray && ticket < 0 && !retired);
-#pragma unroll
-            for (int q = 0; q < kSamplerSlots; ++q) {
-                pub_slots |= ((pub >> (q * kSamplerBlock)) & 1u) << q;
-                need_slots |= ((need >> (q * kSamplerBlock)) & 1u) << q;
-            }
-        }
+        const unsigned pub_slots = slot_heads<kSamplerSlots>((unsigned)__ballot(publish));
+        const unsigned need_slots = slot_heads<kSamplerSlots>((unsigned)__ballot(!has_ray && ticket < 0 && !retired));
         if (pub_slots | need_slots) {
-            int v = 0;
-            if (lane == 0 && need_slots) v = atomicAdd(&q->head, __popc(need_slots));
-            if (lane == 1 && pub_slots) v = atomicAdd(&q->n_cont, __popc(pub_slots));
-            const int tbase = __shfl(v, 0, 64), pbase = __shfl(v, 1, 64);
+            const QueueBases qb = sampler_queue_bases(q, lane, need_slots, pub_slots);
             if (publish) {
-                const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
-                if (lane == slot_lane0 && c < w.cont_cap) {
-                    const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)blk << kContRayBits) |
-                                                    ((unsigned long long)__float_as_uint(prev_f) << 32);
-                    __hip_atomic_store(&w.cont[c], item, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                sampler_publish_item<__ATOMIC_RELAXED>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, blk, 1, prev_f, false);
                 publish = false;
             }
             if (!has_ray && ticket < 0 && !retired) {
-                const long long t = (long long)tbase + __popc(need_slots & ((1u << slot) - 1u));
-                if (t >= n_tickets || tbase < 0) retired = true;   // nothing beyond: every ray publishes at most segs - 1 items
-                else ticket = (int)t;
+                ticket = sampler_draw(qb.tbase, need_slots, slot, n_tickets);
+                if (ticket < 0) retired = true;
             }
         }
-        // ---- a held ticket: the list's ray, or the continuation item once it is there
-        if (!has_ray && ticket >= 0) {
-            bool got = false;
-            if (ticket < n_list) {
-                ray = w.sampler_list[ticket];
-                blk = 0;
-                prev_f = 0.f;
-                got = true;
-            } else {
-                const unsigned long long item = __hip_atomic_load(&w.cont[ticket - n_list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (item != 0ull) {
-                    ray = (int)(item & ((1u << kContRayBits) - 1u)) - 1;
-                    blk = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u));
-                    prev_f = __uint_as_float((unsigned)(item >> 32));
-                    got = true;
-                }
-            }
-            if (got) {
-                ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
-                dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
-                const float t = a.dist[ray], s0 = a.sdf[ray];
-                const bool pos = s0 > 0.0f;  // raytracer.py:59-65: sample [t, far] if sdf > 0 else [near, t]
-                smin = pos ? t : a.near[ray];
-                const float smax = pos ? a.far[ray] : t;
-                width = smax - smin;
-                prev_z = blk > 0 ? sample_depth(smin, a.lin[blk * kSamplerBlock - 1], width) : 0.f;   // the sample before the item's first
-                has_ray = true;
-                ticket = -1;
-            }
+        if (!has_ray && ticket >= 0 && sampler_take(w, n_list, ticket, ray, blk, prev_f)) {
+            ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
+            ray_interval(a, ray, smin, width);
+            prev_z = blk > 0 ? sample_depth(smin, a.lin[blk * kSamplerBlock - 1], width) : 0.f;   // the sample before the item's first
+            has_ray = true;
+            ticket = -1;
         }
         if (!be.any(__ballot(has_ray) != 0ull)) {
-            // no ray in the workgroup: done when no slot holds a ticket that can still be served
-            const bool all_ended = __hip_atomic_load(&q->n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
-            const bool waiting = __ballot(ticket >= 0 || publish) != 0ull && !all_ended;
-            if (!be.any(waiting)) break;
-            if (++idle_polls > (1u << 22)) {   // the bound: a few seconds; never reached unless the protocol is broken -- reported in the stats
-                if (threadIdx.x == 0) atomicAdd((unsigned long long*)&w.cnt->sampler_abort, 1ull);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(16);
+            if (sampler_idle_done(be, q, n_list, w.cnt, ticket >= 0 || publish, idle_polls)) break;
             continue;
         }
         const int idx = blk * kSamplerBlock + s_in;
@@ -522,19 +615,19 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         {   // the slot's state waits in LDS while the evaluation has the registers
             const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0);
             be.park(0, flags); be.park(1, ray); be.park(2, blk); be.park(3, ticket);
-            be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
+            park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
-            be.park(15, (int)(unsigned)evals); be.park(16, (int)(evals >> 32));
+            park_i64(be, 15, evals);
         }
         const float f = be.eval(qx, qy, qz);
         const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0));
         has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4;
         const bool in_range_b = flags_back & 8;
         ray = be.unpark(1, ray); blk = be.unpark(2, blk); ticket = be.unpark(3, ticket);
-        ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
+        unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
         smin = be.unpark(10, smin); width = be.unpark(11, width); prev_z = be.unpark(12, prev_z); prev_f = be.unpark(13, prev_f);
         const float zb = be.unpark(14, z);
-        evals = (long long)(((unsigned long long)(unsigned)be.unpark(16, (int)(evals >> 32)) << 32) | (unsigned)be.unpark(15, (int)(unsigned)evals));
+        evals = unpark_i64(be, 15, evals);
         idle_polls = 0;
         evals += __popc((unsigned)__ballot(in_range_b));   // lanes 32..63 mirror 0..31: the low word counts every point once
         const unsigned neg_all = (unsigned)__ballot(in_range_b && f < 0.0f);  // sign(f) == -1 (raytracer.py:162-166)
@@ -552,17 +645,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         const bool done = has_ray && (found_neg || (blk + 1) * kSamplerBlock >= a.n_steps);
         const float z_lo = first > slot_lane0 ? z_before : prev_z, f_lo = first > slot_lane0 ? f_before : prev_f;
         if (done && lane == slot_lane0) {   // the slot's first lane (lower half of the wave) writes the outcome
-            if (root) {
-                const int pos_l = atomicAdd(&w.cnt->n_root, 1);
-                w.root_list[pos_l] = ray;
-                w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_first;
-                w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_first;
-            } else {  // raytracer.py:158-160, 75-78: sampled rays without a root get zeros
-                a.conv[ray] = 0;
-                a.points[3 * (size_t)ray] = 0.f; a.points[3 * (size_t)ray + 1] = 0.f; a.points[3 * (size_t)ray + 2] = 0.f;
-                a.sdf[ray] = 0.f;
-                a.dist[ray] = 0.f;
-            }
+            if (root) sampler_write_root(w, ray, z_lo, z_first, f_lo, f_first);
+            else sampler_write_no_root(a, ray, 0.f);
             atomicAdd(&q->n_done, 1);
         }
         prev_z = z_last;
@@ -606,8 +690,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // positive samples; 43 k are left).  A work item ends after kSamplerSeg passes once its position has entered a later segment
 // (kSamplerSeg blocks of samples) than the one it started in: at stride 1 exactly the items of k_sampler, and never more than
 // sampler_cont_cap() per ray.  The continuation word carries the next sample index where k_sampler's carries the block, and the
-// taker recomputes the stride from the carried f (a pending ray's too: ray_state carries its pending bit): that needs the index in 8 bits, so a call with n_steps >
-// kStrideMaxSteps (default 128) or without continuation items runs stride 1, as does a network whose G is zero or non-finite, a ray
+// taker recomputes the stride from the carried f (a pending ray's too: ray_state carries its pending bit): that needs the index in
+// 8 bits, so a call with n_steps > kStrideMaxSteps (256) or without continuation items runs stride 1, as does a network whose G is zero or non-finite, a ray
 // whose range is empty, reversed or non-finite, and everything after the slope guard was raised (IRON_SAMPLER_STRIDE=0 /
 // iron_set_sampler_stride: off).
 __device__ __forceinline__ int stride_reach(float f, float delta, float ld) {   // skipped samples next to a sample of value f that it certifies
@@ -627,9 +711,7 @@ static_assert(kSamplerSeg < (1 << kPassBits) && kStrideMax < (1 << kStrdBits), "
 
 // the per-lane counts of k_sampler_screen, by the lane's place in its slot (see there); ev_scr is the wave's
 __device__ __forceinline__ void screen_flush_counts(TraceCounters* cnt, unsigned ev_ref, unsigned ev_scr, int me) {
-    unsigned long long r = ev_ref;   // summed over the slots: lane k < kSamplerBlock ends with the total of place k
-#pragma unroll
-    for (int off = 32; off >= kSamplerBlock; off >>= 1) r += __shfl_xor(r, off, 64);
+    const unsigned long long r = wave_sum<32, kSamplerBlock>((unsigned long long)ev_ref);   // summed over the slots: lane k < kSamplerBlock ends with the total of place k
     static_assert(kSamplerBlock >= 7, "places of the per-lane counts");
     long long* const dst = me == 0 ? &cnt->n_evals : me == 1 ? &cnt->n_pass : me == 2 ? &cnt->n_pass_strided : me == 3 ? &cnt->n_pass_behind
                          : me == 4 ? &cnt->n_pass_fresh : me == 5 ? &cnt->n_restart : &cnt->n_obs_march;
@@ -687,87 +769,43 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, smin = 0.f, width = 0.f, prev_z = 0.f, prev_f = 0.f;
     unsigned idle_polls = 0;
     for (;;) {
-        unsigned pub_slots = 0, need_slots = 0;
-        {
-            const unsigned long long pub = __ballot(publish), need = __ballot(!has_ray && ticket < 0 && !retired);
-#pragma unroll
-            for (int qq = 0; qq < kScreenSlots; ++qq) {
-                pub_slots |= (unsigned)((pub >> (qq * kSamplerBlock)) & 1ull) << qq;
-                need_slots |= (unsigned)((need >> (qq * kSamplerBlock)) & 1ull) << qq;
-            }
-        }
+        const unsigned pub_slots = slot_heads<kScreenSlots>(__ballot(publish));
+        const unsigned need_slots = slot_heads<kScreenSlots>(__ballot(!has_ray && ticket < 0 && !retired));
         if (pub_slots | need_slots) {
-            int v = 0;
-            if (lane == 0 && need_slots) v = atomicAdd(&q->head, __popc(need_slots));
-            if (lane == 1 && pub_slots) v = atomicAdd(&q->n_cont, __popc(pub_slots));
-            const int tbase = __shfl(v, 0, 64), pbase = __shfl(v, 1, 64);
+            const QueueBases qb = sampler_queue_bases(q, lane, need_slots, pub_slots);
             if (publish) {
-                const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
-                if (lane == slot_lane0 && c < w.cont_cap) {
-                    // a pending ray's state travels in ray_state, published with the item (release here, acquire where it is taken)
-                    if (pend) w.scr.ray_state[ray] = kRayPending;
-                    const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)(pos / unit) << kContRayBits) |
-                                                    ((unsigned long long)__float_as_uint(prev_f) << 32);
-                    __hip_atomic_store(&w.cont[c], item, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                sampler_publish_item<__ATOMIC_RELEASE>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, pos, unit, prev_f, pend);
                 publish = false;
             }
             if (!has_ray && ticket < 0 && !retired) {
-                const long long t = (long long)tbase + __popc(need_slots & ((1u << slot) - 1u));
-                if (t >= n_tickets || tbase < 0) retired = true;
-                else ticket = (int)t;
+                ticket = sampler_draw(qb.tbase, need_slots, slot, n_tickets);
+                if (ticket < 0) retired = true;
             }
         }
-        if (!has_ray && ticket >= 0) {
-            bool got = false;
-            if (ticket < n_list) {
-                ray = w.sampler_list[ticket];
-                pos = 0;
-                prev_f = 0.f;
-                pend = false;
-                got = true;
-            } else {
-                const unsigned long long item = __hip_atomic_load(&w.cont[ticket - n_list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (item != 0ull) {
-                    // acquire only once the item is there (an acquiring poll invalidates the cache on every pass: +0.5 ms per frame)
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    ray = (int)(item & ((1u << kContRayBits) - 1u)) - 1;
-                    pos = (int)((item >> kContRayBits) & ((1u << kContBlkBits) - 1u)) * unit;
-                    pend = (w.scr.ray_state[ray] & kRayPending) != 0;
-                    prev_f = __uint_as_float((unsigned)(item >> 32));
-                    got = true;
-                }
+        if (!has_ray && ticket >= 0 && sampler_take(w, n_list, ticket, ray, pos, prev_f)) {
+            pend = false;
+            if (ticket >= n_list) {
+                // acquire only once the item is there (an acquiring poll invalidates the cache on every pass: +0.5 ms per frame)
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                pos *= unit;
+                pend = (w.scr.ray_state[ray] & kRayPending) != 0;
             }
-            if (got) {
-                ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
-                dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
-                const float t = a.dist[ray], s0 = a.sdf[ray];
-                const bool pos_side = s0 > 0.0f;
-                smin = pos_side ? t : a.near[ray];
-                const float smax = pos_side ? a.far[ray] : t;
-                width = smax - smin;
-                // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it
-                strd = 1;
-                if (stride_on && pos > 0 && (pend_strides || !pend)) {
-                    const float ld = stride_ld(Lg, lin_step, width, dx, dy, dz);
-                    if (ld > 0.0f && prev_f > delta) strd = 1 + stride_reach(prev_f, delta, ld);
-                }
-                prev_z = pos > 0 ? sample_depth(smin, a.lin[pos > strd ? pos - strd : 0], width) : 0.f;   // the sample before the item's first
-                npass = 0;
-                seg0 = pos / kSegSamples;
-                has_ray = true;
-                ticket = -1;
+            ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
+            ray_interval(a, ray, smin, width);
+            // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it
+            strd = 1;
+            if (stride_on && pos > 0 && (pend_strides || !pend)) {
+                const float ld = stride_ld(Lg, lin_step, width, dx, dy, dz);
+                if (ld > 0.0f && prev_f > delta) strd = 1 + stride_reach(prev_f, delta, ld);
             }
+            prev_z = pos > 0 ? sample_depth(smin, a.lin[pos > strd ? pos - strd : 0], width) : 0.f;   // the sample before the item's first
+            npass = 0;
+            seg0 = pos / kSegSamples;
+            has_ray = true;
+            ticket = -1;
         }
         if (!be.any(__ballot(has_ray) != 0ull)) {
-            const bool all_ended = __hip_atomic_load(&q->n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_list;
-            const bool waiting = __ballot(ticket >= 0 || publish) != 0ull && !all_ended;
-            if (!be.any(waiting)) break;
-            if (++idle_polls > (1u << 22)) {
-                if (threadIdx.x == 0) atomicAdd((unsigned long long*)&w.cnt->sampler_abort, 1ull);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(16);
+            if (sampler_idle_done(be, q, n_list, w.cnt, ticket >= 0 || publish, idle_polls)) break;
             continue;
         }
         const int idx = pos + strd * s_in;
@@ -778,7 +816,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0);
             const int ps = pos | (strd << kPosBits) | (npass << (kPosBits + kStrdBits)) | (seg0 << (kPosBits + kStrdBits + kPassBits));
             be.park(0, flags); be.park(1, ray); be.park(2, ps); be.park(3, ticket);
-            be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
+            park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
             be.park(15, (int)ev_ref); be.park(16, lane == 0 ? (int)ev_scr : __float_as_int(slope));
         }
@@ -798,7 +836,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             pos = ps & ((1 << kPosBits) - 1); strd = (ps >> kPosBits) & ((1 << kStrdBits) - 1);
             npass = (ps >> (kPosBits + kStrdBits)) & ((1 << kPassBits) - 1); seg0 = (int)((unsigned)ps >> (kPosBits + kStrdBits + kPassBits));
         }
-        ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
+        unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
         smin = be.unpark(10, smin); width = be.unpark(11, width); prev_z = be.unpark(12, prev_z); prev_f = be.unpark(13, prev_f);
         const float zb = be.unpark(14, z);
         ev_ref = (unsigned)be.unpark(15, (int)ev_ref);
@@ -867,7 +905,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             const int pos_e = rbase + lane_rank64(unc_wave, me);
             if (((unc >> me) & 1ull) && pos_e < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
                 ResolveEntry e;
-                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.pad0 = __float_as_int(ld); e.pad1 = 0;
+                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.ld = ld; e.pad = 0;
                 w.scr.ent[pos_e] = e;
             }
         }
@@ -903,17 +941,11 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
                 const int nb = found_neg ? (gidx / kSamplerBlock + 1) * kSamplerBlock : a.n_steps;   // k_sampler stops behind the block of gidx
                 ev_ref += (unsigned)(nb < a.n_steps ? nb : a.n_steps);
                 if (found_neg && gidx >= 1) {
-                    const int pos_l = atomicAdd(&w.cnt->n_root, 1);
-                    w.root_list[pos_l] = ray;
-                    w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_first;
-                    w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_first;
+                    sampler_write_root(w, ray, z_lo, z_first, f_lo, f_first);
                 } else {
                     float zero = 0.f;
                     asm volatile("" : "+v"(zero));   // (else the zeros of these stores are held in registers across the loop)
-                    a.conv[ray] = 0;
-                    a.points[3 * (size_t)ray] = zero; a.points[3 * (size_t)ray + 1] = zero; a.points[3 * (size_t)ray + 2] = zero;
-                    a.sdf[ray] = zero;
-                    a.dist[ray] = zero;
+                    sampler_write_no_root(a, ray, zero);
                 }
             }
             atomicAdd(&q->n_done, 1);
@@ -941,9 +973,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     }
     be.finish();
     screen_flush_counts(w.cnt, ev_ref, ev_scr, lane);
-    float r = lane == 0 ? 0.0f : slope;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
+    const float r = wave_max(lane == 0 ? 0.0f : slope);
     if (lane == 0) slope_guard_raise(w, &w.cnt->slope_march_bits, r);
 }
 
@@ -976,13 +1006,13 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
             qy = a.ray_o[3 * (size_t)ray + 1] + a.ray_d[3 * (size_t)ray + 1] * e.z;
             qz = a.ray_o[3 * (size_t)ray + 2] + a.ray_d[3 * (size_t)ray + 2] * e.z;
         }
-        be.park(0, valid ? 1 : 0); be.park(1, li); be.park(2, ratio); be.park(3, (int)(unsigned)resolved); be.park(4, (int)(resolved >> 32));
+        be.park(0, valid ? 1 : 0); be.park(1, li); be.park(2, ratio); park_i64(be, 3, resolved);
         be.park(5, slope); be.park(6, n_obs);
         const float f = be.eval(qx, qy, qz);
         const bool v = be.unpark(0, 0) != 0;
         const int lib = be.unpark(1, 0);
         ratio = be.unpark(2, 0.0f);
-        resolved = (long long)(((unsigned long long)(unsigned)be.unpark(4, 0) << 32) | (unsigned)be.unpark(3, 0));
+        resolved = unpark_i64(be, 3, resolved);
         slope = be.unpark(5, 0.0f); n_obs = be.unpark(6, 0);
         resolved += __popc((unsigned)__ballot(v));
         if (v && lane < 32) {
@@ -990,7 +1020,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
             e->f_ex = f;
             if (f < 0.0f) atomicMin(&w.scr.rec[e->ray].first, e->s);
             const float f1 = e->f1;
-            const float ld = __int_as_float(e->pad0);
+            const float ld = e->ld;
             if (ld > 0.0f && e->s > 0) {   // sample s - 1 was screened at stride 1, next to s
                 slope = fmaxf(slope, fmaxf(fabsf(f - e->f_prev1) - 0.5f * delta, 0.0f) / ld);
                 ++n_obs;
@@ -1001,13 +1031,9 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
         }
     }
     be.finish();
-    float r = ratio;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off, 64));
-    float sl = lane < 32 ? slope : 0.0f;
-    int obs = lane < 32 ? n_obs : 0;
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) { sl = fmaxf(sl, __shfl_xor(sl, off, 64)); obs += __shfl_xor(obs, off, 64); }
+    const float r = wave_max(ratio);
+    const float sl = wave_max<16>(lane < 32 ? slope : 0.0f);   // (the lower half's lanes hold the samples)
+    const int obs = wave_sum<16>(lane < 32 ? n_obs : 0);
     if (lane == 0) {
         if (obs) atomicAdd((unsigned long long*)&w.cnt->n_obs_res, (unsigned long long)obs);
         slope_guard_raise(w, &w.cnt->slope_res_bits, sl);
@@ -1028,7 +1054,7 @@ __global__ void k_screen_fin_entries(TraceWs w) {
     int n_obs = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_ent; i += gridDim.x * blockDim.x) {
         const ResolveEntry e = w.scr.ent[i];
-        const float ld = __int_as_float(e.pad0);
+        const float ld = e.ld;
         if (i > 0 && ld > 0.0f) {
             const ResolveEntry p = w.scr.ent[i - 1];
             if (p.ray == e.ray && p.s + 1 == e.s) {
@@ -1042,8 +1068,8 @@ __global__ void k_screen_fin_entries(TraceWs w) {
         if (e.s == g) { r->fhi = e.f_ex; r->flo = e.f_prev1; }   // (overwritten below when sample g - 1 was listed too)
         if (e.s == g - 1) { r->flo_ex = e.f_ex; r->has_flo_ex = 1; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { slope = fmaxf(slope, __shfl_xor(slope, off, 64)); n_obs += __shfl_xor(n_obs, off, 64); }
+    slope = wave_max(slope);
+    n_obs = wave_sum(n_obs);
     __shared__ float s_slope[16];   // one set of atomics per workgroup (blockDim.x <= 1024)
     __shared__ int s_obs[16];
     const int wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63) >> 6;
@@ -1067,26 +1093,15 @@ __global__ void k_screen_fin_rays(TraceArgs a, TraceWs w) {
         const int nb = (g / kSamplerBlock + 1) * kSamplerBlock;
         ev += (unsigned long long)(g < a.n_steps ? (nb < a.n_steps ? nb : a.n_steps) : a.n_steps);
         if (g >= 1 && g < a.n_steps) {
-            const float t = a.dist[ray], s0 = a.sdf[ray];
-            const bool pos = s0 > 0.0f;
-            const float smin = pos ? t : a.near[ray];
-            const float smax = pos ? a.far[ray] : t;
-            const float width = smax - smin;
-            const int pos_l = atomicAdd(&w.cnt->n_root, 1);
-            w.root_list[pos_l] = ray;
-            w.root_lo[pos_l] = sample_depth(smin, a.lin[g - 1], width);
-            w.root_hi[pos_l] = sample_depth(smin, a.lin[g], width);
-            w.root_flo[pos_l] = r.has_flo_ex ? r.flo_ex : r.flo;
-            w.root_fhi[pos_l] = r.fhi;
+            float smin, width;
+            ray_interval(a, ray, smin, width);
+            sampler_write_root(w, ray, sample_depth(smin, a.lin[g - 1], width), sample_depth(smin, a.lin[g], width),
+                               r.has_flo_ex ? r.flo_ex : r.flo, r.fhi);
         } else {
-            a.conv[ray] = 0;
-            a.points[3 * (size_t)ray] = 0.f; a.points[3 * (size_t)ray + 1] = 0.f; a.points[3 * (size_t)ray + 2] = 0.f;
-            a.sdf[ray] = 0.f;
-            a.dist[ray] = 0.f;
+            sampler_write_no_root(a, ray, 0.f);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ev += __shfl_xor(ev, off, 64);
+    ev = wave_sum(ev);
     if ((threadIdx.x & 63) == 0 && ev) atomicAdd((unsigned long long*)&w.cnt->n_evals, ev);
 }
 
@@ -1153,8 +1168,8 @@ __global__ __launch_bounds__(256, 1) void k_screen_calib(SdfNetDev net, H2Stream
         gm = gn <= 3.0e38f ? fmaxf(gm, gn) : __uint_as_float(0x7f800000u);
     }
     be.finish();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { m = fmaxf(m, __shfl_xor(m, off, 64)); gm = fmaxf(gm, __shfl_xor(gm, off, 64)); }
+    m = wave_max(m);
+    gm = wave_max(gm);
     if (lane == 0) { atomicMax(calib, __float_as_uint(m)); atomicMax(calib + kScreenCalibG, __float_as_uint(gm)); }
 }
 
@@ -1197,8 +1212,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_a(IRON_TRACE_KERNEL_
             ox = oy = oz = dx = dy = dz = lo = hi = 0.f;
             work = false;
             if (valid) {
-                ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
-                dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
+                ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
                 lo = w.root_lo[li]; hi = w.root_hi[li];
                 work = (w.root_flo[li] > 0.0f) && (w.root_fhi[li] < 0.0f);
             }
@@ -1212,17 +1226,17 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_a(IRON_TRACE_KERNEL_
         {   // the batch's state waits in LDS while the evaluation has the registers
             const int flags = (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0) | (work ? 8 : 0);
             be.park(0, flags); be.park(1, li); be.park(2, ray); be.park(3, k);
-            be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
-            be.park(10, lo); be.park(11, hi); be.park(12, mid); be.park(13, (int)(unsigned)evals); be.park(14, (int)(evals >> 32));
+            park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
+            be.park(10, lo); be.park(11, hi); be.park(12, mid); park_i64(be, 13, evals);
         }
         const float f = be.eval(ox + dx * mid, oy + dy * mid, oz + dz * mid);
         {
             const int flags = be.unpark(0, (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0) | (work ? 8 : 0));
             has_batch = flags & 1; exhausted = flags & 2; valid = flags & 4; work = flags & 8;
             li = be.unpark(1, li); ray = be.unpark(2, ray); k = be.unpark(3, k);
-            ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
+            unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             lo = be.unpark(10, lo); hi = be.unpark(11, hi); mid = be.unpark(12, mid);
-            evals = (long long)(((unsigned long long)(unsigned)be.unpark(14, (int)(evals >> 32)) << 32) | (unsigned)be.unpark(13, (int)(unsigned)evals));
+            evals = unpark_i64(be, 13, evals);
         }
         if (has_batch) {
             if (work) {
@@ -1268,8 +1282,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_b(IRON_TRACE_KERNEL_
                 ox = oy = oz = dx = dy = dz = lo = hi = 0.f;
                 remaining = 0;
                 if (valid) {
-                    ox = a.ray_o[3 * (size_t)ray]; oy = a.ray_o[3 * (size_t)ray + 1]; oz = a.ray_o[3 * (size_t)ray + 2];
-                    dx = a.ray_d[3 * (size_t)ray]; dy = a.ray_d[3 * (size_t)ray + 1]; dz = a.ray_d[3 * (size_t)ray + 2];
+                    ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
                     lo = w.root_lo[li]; hi = w.root_hi[li];
                     remaining = w.chunk_iters[ray_chunk(a, ray)] - w.root_k[li];
                 }
@@ -1283,8 +1296,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_b(IRON_TRACE_KERNEL_
         {   // the batch's state waits in LDS while the evaluation has the registers
             const int flags = (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0);
             be.park(0, flags); be.park(1, li); be.park(2, ray); be.park(3, remaining);
-            be.park(4, ox); be.park(5, oy); be.park(6, oz); be.park(7, dx); be.park(8, dy); be.park(9, dz);
-            be.park(10, lo); be.park(11, hi); be.park(12, mid); be.park(13, (int)(unsigned)evals); be.park(14, (int)(evals >> 32));
+            park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
+            be.park(10, lo); be.park(11, hi); be.park(12, mid); park_i64(be, 13, evals);
             be.park(15, (int)rem);
         }
         const float f = be.eval(qx, qy, qz);
@@ -1292,9 +1305,9 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_b(IRON_TRACE_KERNEL_
             const int flags = be.unpark(0, (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0));
             has_batch = flags & 1; exhausted = flags & 2; valid = flags & 4;
             li = be.unpark(1, li); ray = be.unpark(2, ray); remaining = be.unpark(3, remaining);
-            ox = be.unpark(4, ox); oy = be.unpark(5, oy); oz = be.unpark(6, oz); dx = be.unpark(7, dx); dy = be.unpark(8, dy); dz = be.unpark(9, dz);
+            unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             lo = be.unpark(10, lo); hi = be.unpark(11, hi); mid = be.unpark(12, mid);
-            evals = (long long)(((unsigned long long)(unsigned)be.unpark(14, (int)(evals >> 32)) << 32) | (unsigned)be.unpark(13, (int)(unsigned)evals));
+            evals = unpark_i64(be, 13, evals);
             qx = ox + dx * mid; qy = oy + dy * mid; qz = oz + dz * mid;   // (the same expressions: the evaluated point)
         }
         const unsigned rem_b = (unsigned)be.unpark(15, (int)rem);
@@ -1411,17 +1424,15 @@ static WsLayout ws_layout(int64_t n, const iron_trace_params* p) {
     return L;
 }
 
-// which: 0 sphere, 1 sampler, 2 bisect_a, 3 bisect_b; h2 only: 4 screened sampler, 5 resolve, 6 calibration; `units` = wave-sized work
-// items available
-static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t units,
-                                hipStream_t st);
-
 static int resident_waves() {
     // single-wave workgroups, one wave per SIMD (the kernels need > 256 registers per lane); iron_set_cu_limit narrows it
     return cu_budget() * 4;
 }
 
-static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t units,
+// the last three on the h2 core only; `units` = wave-sized work items available
+enum TraceKernel { kSphere = 0, kSampler = 1, kBisectA = 2, kBisectB = 3, kSamplerScreen = 4, kScreenResolve = 5, kScreenCalib = 6 };
+
+static void launch_trace_kernel(TraceKernel which, bool h2, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t units,
                                 hipStream_t st) {
     H2Meta m;
     m.n_hidden_layers = sdf->sdf.n_hidden_layers; m.skip_layer = sdf->sdf.skip_layer; m.scale = sdf->sdf.scale; m.b_last = sdf->sdf.b_last;
@@ -1429,35 +1440,32 @@ static void launch_trace_kernel(int which, bool h2, const iron_net* sdf, const T
     if (h2) {
         static bool attr = false;
         if (!attr) {
-            (void)hipFuncSetAttribute((const void*)k_sphere<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_sampler<BackendH2Sampler>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_bisect_a<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_bisect_b<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_sampler_screen<BackendH2Sampler>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_screen_resolve<BackendH2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
-            (void)hipFuncSetAttribute((const void*)k_screen_calib, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
+            const void* const kernels[] = {(const void*)k_sphere<BackendH2>, (const void*)k_sampler<BackendH2Sampler>, (const void*)k_bisect_a<BackendH2>,
+                                           (const void*)k_bisect_b<BackendH2>, (const void*)k_sampler_screen<BackendH2Sampler>,
+                                           (const void*)k_screen_resolve<BackendH2>, (const void*)k_screen_calib};
+            for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTraceTotal);
             attr = true;
         }
         const int64_t wgs = (units + 3) / 4;
         const int cus = resident_waves() / 4;
         const dim3 grid((unsigned)(wgs < cus ? wgs : cus)), block(256);
         switch (which) {
-            case 0: hipLaunchKernelGGL(k_sphere<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 1: hipLaunchKernelGGL(k_sampler<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 2: hipLaunchKernelGGL(k_bisect_a<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 4: hipLaunchKernelGGL(k_sampler_screen<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h1_trace, m, a, w); break;
-            case 5: hipLaunchKernelGGL(k_screen_resolve<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 6: hipLaunchKernelGGL(k_screen_calib, dim3(cus < kScreenCalibPoints / 128 ? cus : kScreenCalibPoints / 128), block,
-                                       kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, sdf->h1_trace, m, sdf->screen_calib); break;
+            case kSphere: hipLaunchKernelGGL(k_sphere<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kSampler: hipLaunchKernelGGL(k_sampler<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kBisectA: hipLaunchKernelGGL(k_bisect_a<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kSamplerScreen: hipLaunchKernelGGL(k_sampler_screen<BackendH2Sampler>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h1_trace, m, a, w); break;
+            case kScreenResolve: hipLaunchKernelGGL(k_screen_resolve<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kScreenCalib: hipLaunchKernelGGL(k_screen_calib, dim3(cus < kScreenCalibPoints / 128 ? cus : kScreenCalibPoints / 128), block,
+                                                  kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, sdf->h1_trace, m, sdf->screen_calib); break;
             default: hipLaunchKernelGGL(k_bisect_b<BackendH2>, grid, block, kLdsTraceTotal, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
         }
     } else {
         const int waves = resident_waves();
         const dim3 grid((unsigned)(units < waves ? units : waves)), block(64);
         switch (which) {
-            case 0: hipLaunchKernelGGL(k_sphere<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 1: hipLaunchKernelGGL(k_sampler<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
-            case 2: hipLaunchKernelGGL(k_bisect_a<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kSphere: hipLaunchKernelGGL(k_sphere<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kSampler: hipLaunchKernelGGL(k_sampler<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
+            case kBisectA: hipLaunchKernelGGL(k_bisect_a<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
             default: hipLaunchKernelGGL(k_bisect_b<BackendF32>, grid, block, 0, st, sdf->sdf, sdf->h2_trace, m, a, w); break;
         }
     }
@@ -1472,25 +1480,17 @@ std::atomic<float> g_stride_l_override{0.0f};   // test hook (iron_sampler_scree
 std::atomic<int> g_stride_hooks{0};             // test hooks (iron_sampler_screen_debug 4, 5): kStridePendingOff | kStrideMuteMarch
 void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
-static bool screen_switch() {
-    static int from_env = -1;
-    if (from_env < 0) {
-        const char* e = getenv("IRON_SAMPLER_SCREEN");
-        from_env = (e && e[0] == '0') ? 0 : 1;
+// a switch set by its setter (>= 0), else by the environment (NAME=0: off, read once), else on
+static bool env_switch(const char* name, const std::atomic<int>& set, int* from_env) {
+    if (*from_env < 0) {
+        const char* e = getenv(name);
+        *from_env = (e && e[0] == '0') ? 0 : 1;
     }
-    const int v = g_screen_switch.load(std::memory_order_relaxed);
-    return v < 0 ? from_env != 0 : v != 0;
+    const int v = set.load(std::memory_order_relaxed);
+    return v < 0 ? *from_env != 0 : v != 0;
 }
-
-static bool stride_switch() {
-    static int from_env = -1;
-    if (from_env < 0) {
-        const char* e = getenv("IRON_SAMPLER_STRIDE");
-        from_env = (e && e[0] == '0') ? 0 : 1;
-    }
-    const int v = g_stride_switch.load(std::memory_order_relaxed);
-    return v < 0 ? from_env != 0 : v != 0;
-}
+static bool screen_switch() { static int from_env = -1; return env_switch("IRON_SAMPLER_SCREEN", g_screen_switch, &from_env); }
+static bool stride_switch() { static int from_env = -1; return env_switch("IRON_SAMPLER_STRIDE", g_stride_switch, &from_env); }
 
 // at the start of a call: act on a guard flag an earlier call raised, then decide whether this call screens (h2 core only)
 static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use) {
@@ -1504,7 +1504,7 @@ static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use
         IRON_HIP_TRY(hipMemsetAsync(net->screen_calib, 0, 256, st));
         TraceArgs a{};
         TraceWs w{};
-        launch_trace_kernel(6, true, net, a, w, kScreenCalibPoints / 32, st);
+        launch_trace_kernel(kScreenCalib, true, net, a, w, kScreenCalibPoints / 32, st);
         net->screen_calibrated = 1;
     }
     *use = true;
@@ -1532,9 +1532,9 @@ static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayou
 // the dense sampler of one part: k_sampler, or (screen) k_sampler_screen + resolve + finalize + k_sampler on the overflow list
 static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t nk, hipStream_t st) {
     const int64_t units = (nk + kSamplerSlots - 1) / kSamplerSlots;
-    if (!screen) { launch_trace_kernel(1, h2, sdf, a, w, units, st); return; }
-    launch_trace_kernel(4, true, sdf, a, w, (nk + kScreenSlots - 1) / kScreenSlots, st);
-    launch_trace_kernel(5, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
+    if (!screen) { launch_trace_kernel(kSampler, h2, sdf, a, w, units, st); return; }
+    launch_trace_kernel(kSamplerScreen, true, sdf, a, w, (nk + kScreenSlots - 1) / kScreenSlots, st);
+    launch_trace_kernel(kScreenResolve, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
     const int64_t ge = ((int64_t)w.scr.cap + 255) / 256, gr = (nk + 255) / 256;
     hipLaunchKernelGGL(k_screen_fin_entries, dim3((unsigned)(ge < 1024 ? (ge > 0 ? ge : 1) : 1024)), dim3(256), 0, st, w);
     hipLaunchKernelGGL(k_screen_fin_rays, dim3((unsigned)(gr < 1024 ? (gr > 0 ? gr : 1) : 1024)), dim3(256), 0, st, a, w);
@@ -1542,24 +1542,53 @@ static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceAr
     w2.ovf_pass = 1;
     w2.sampler_list = w.scr.ovf_list;
     w2.cont_cap = 0;
-    launch_trace_kernel(1, true, sdf, a, w2, units, st);
+    launch_trace_kernel(kSampler, true, sdf, a, w2, units, st);
+}
+
+// what iron_trace_phase and iron_trace_stage check alike; `args_ok`: the entry's own pointers, which count only for a call
+// that has rays.  IRON_OK with n == 0: nothing to do (L is not set).
+static int check_trace_call(const iron_net_t* sdf, const iron_trace_params* p, int64_t n, bool args_ok, int64_t chunk, const void* workspace,
+                            size_t workspace_bytes, WsLayout* L) {
+    if (!sdf || sdf->desc.kind != IRON_NET_SDF || !p || n < 0) return IRON_ERR_BAD_ARG;
+    if (n > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
+    if (p->n_steps < 2 || p->n_steps > 4096 || p->sphere_tracing_iters < 0 || !(p->sdf_threshold > 0.0f)) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!args_ok || !workspace) return IRON_ERR_BAD_ARG;
+    iron_trace_params q = *p;
+    q.chunk = chunk;
+    *L = ws_layout(n, &q);
+    if (workspace_bytes < L->total) return IRON_ERR_WORKSPACE;
+    if (((uintptr_t)workspace & 15) != 0) return IRON_ERR_BAD_ARG;
+    return IRON_OK;
+}
+
+// the workspace's arrays as one part that holds all rays sees them (chunk table: the workspace's own)
+static TraceWs bind_workspace(char* base, const WsLayout& L) {
+    TraceWs w{};
+    w.cnt = (TraceCounters*)(base + L.cnt);
+    w.sampler_list = (int*)(base + L.sampler_list);
+    w.root_list = (int*)(base + L.root_list);
+    w.root_lo = (float*)(base + L.lo); w.root_hi = (float*)(base + L.hi);
+    w.root_flo = (float*)(base + L.flo); w.root_fhi = (float*)(base + L.fhi);
+    w.root_k = (int*)(base + L.k);
+    w.chunk_iters = (int*)(base + L.chunk_iters);
+    w.chunk_roots = (int*)(base + L.chunk_roots);
+    w.n_chunks = (int)L.n_chunks;
+    w.cont = (unsigned long long*)(base + L.cont);
+    w.cont_cap = (int)L.cont_cap;
+    return w;
 }
 
 }  // namespace iron
 
 using namespace iron;
 
-extern "C" int32_t iron_set_sampler_screen(int32_t on) {
-    const int prev = screen_switch() ? 1 : 0;
-    g_screen_switch.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
-    return prev;
+static int32_t set_switch(std::atomic<int>& set, bool prev, int32_t on) {
+    set.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return prev ? 1 : 0;
 }
-
-extern "C" int32_t iron_set_sampler_stride(int32_t on) {
-    const int prev = stride_switch() ? 1 : 0;
-    g_stride_switch.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t iron_set_sampler_screen(int32_t on) { return set_switch(g_screen_switch, screen_switch(), on); }
+extern "C" int32_t iron_set_sampler_stride(int32_t on) { return set_switch(g_stride_switch, stride_switch(), on); }
 
 extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 0) { g_screen_delta_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
@@ -1575,18 +1604,27 @@ extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     return IRON_ERR_BAD_ARG;
 }
 
+// the parts' counter blocks of a finished call, for the three entries below (synchronises the stream)
+static int read_counters(const void* workspace, hipStream_t stream, TraceCounters out[kMaxTraceSplits]) {
+    for (int k = 0; k < kMaxTraceSplits; ++k)
+        IRON_HIP_TRY(hipMemcpyAsync(&out[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost, stream));
+    IRON_HIP_TRY(hipStreamSynchronize(stream));
+    return IRON_OK;
+}
+static void max_f32_bits(double* m, unsigned bits) {
+    const float r = __builtin_bit_cast(float, bits);
+    if (r > *m) *m = r;
+}
+
 extern "C" int iron_trace_screen_counts(const void* workspace, double* out, void* stream) {
     if (!workspace || !out) return IRON_ERR_BAD_ARG;
     TraceCounters c[kMaxTraceSplits];
-    for (int k = 0; k < kMaxTraceSplits; ++k)
-        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
-                                    (hipStream_t)stream));
-    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const int rc = read_counters(workspace, (hipStream_t)stream, c);
+    if (rc != IRON_OK) return rc;
     double scr = 0, res = 0, ovf = 0, ratio = 0, pend = 0;
     for (int k = 0; k < kMaxTraceSplits; ++k) {
         scr += (double)c[k].n_screen; res += (double)c[k].n_resolved; ovf += (double)c[k].n_ovf; pend += (double)c[k].n_pend;
-        const float r = __builtin_bit_cast(float, c[k].ratio_bits);
-        if (r > ratio) ratio = r;
+        max_f32_bits(&ratio, c[k].ratio_bits);
     }
     out[0] = scr; out[1] = res; out[2] = ovf; out[3] = ratio; out[4] = pend;
     return IRON_OK;
@@ -1595,15 +1633,12 @@ extern "C" int iron_trace_screen_counts(const void* workspace, double* out, void
 extern "C" int iron_trace_stride_counts(const void* workspace, double* out, void* stream) {
     if (!workspace || !out) return IRON_ERR_BAD_ARG;
     TraceCounters c[kMaxTraceSplits];
-    for (int k = 0; k < kMaxTraceSplits; ++k)
-        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
-                                    (hipStream_t)stream));
-    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const int rc = read_counters(workspace, (hipStream_t)stream, c);
+    if (rc != IRON_OK) return rc;
     double passes = 0, strided = 0, ratio = 0, mode = 0;
     for (int k = 0; k < kMaxTraceSplits; ++k) {
         passes += (double)c[k].n_pass; strided += (double)c[k].n_pass_strided;
-        const float r = __builtin_bit_cast(float, c[k].slope_bits);
-        if (r > ratio) ratio = r;
+        max_f32_bits(&ratio, c[k].slope_bits);
         if (c[k].stride_mode) mode = 1;
     }
     out[0] = passes; out[1] = strided; out[2] = ratio; out[3] = mode;
@@ -1613,19 +1648,13 @@ extern "C" int iron_trace_stride_counts(const void* workspace, double* out, void
 extern "C" int iron_trace_stride_detail(const void* workspace, double* out, void* stream) {
     if (!workspace || !out) return IRON_ERR_BAD_ARG;
     TraceCounters c[kMaxTraceSplits];
-    for (int k = 0; k < kMaxTraceSplits; ++k)
-        IRON_HIP_TRY(hipMemcpyAsync(&c[k], (const char*)workspace + (size_t)k * kCntStride, sizeof(TraceCounters), hipMemcpyDeviceToHost,
-                                    (hipStream_t)stream));
-    IRON_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const int rc = read_counters(workspace, (hipStream_t)stream, c);
+    if (rc != IRON_OK) return rc;
     for (int i = 0; i < 9; ++i) out[i] = 0.0;
     for (int k = 0; k < kMaxTraceSplits; ++k) {
         out[0] += (double)c[k].n_pass_behind; out[1] += (double)c[k].n_pass_fresh; out[2] += (double)c[k].n_restart;
         out[3] += (double)c[k].n_obs_march; out[4] += (double)c[k].n_obs_res; out[5] += (double)c[k].n_obs_pair;
-        const unsigned bits[3] = {c[k].slope_march_bits, c[k].slope_res_bits, c[k].slope_pair_bits};
-        for (int s = 0; s < 3; ++s) {
-            const float r = __builtin_bit_cast(float, bits[s]);
-            if (r > out[6 + s]) out[6 + s] = r;
-        }
+        max_f32_bits(&out[6], c[k].slope_march_bits); max_f32_bits(&out[7], c[k].slope_res_bits); max_f32_bits(&out[8], c[k].slope_pair_bits);
     }
     return IRON_OK;
 }
@@ -1695,32 +1724,16 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
                                 const uint8_t* work, const int64_t* ray_index, int64_t n, int32_t* chunk_iters,
                                 int64_t n_chunks, uint8_t* conv, float* points, float* sdf_out, float* dist,
                                 iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!sdf || sdf->desc.kind != IRON_NET_SDF || !p || n < 0 || (phase != 0 && phase != 1)) return IRON_ERR_BAD_ARG;
-    if (n > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
-    if (p->n_steps < 2 || p->n_steps > 4096 || p->sphere_tracing_iters < 0 || !(p->sdf_threshold > 0.0f)) return IRON_ERR_BAD_ARG;
-    if (n == 0) return IRON_OK;
-    if (!lin_steps || !ray_o || !ray_d || !near || !far || !work || !conv || !points || !sdf_out || !dist || !workspace)
-        return IRON_ERR_BAD_ARG;
-    const WsLayout L = ws_layout(n, p);
-    if (workspace_bytes < L.total) return IRON_ERR_WORKSPACE;
-    if (((uintptr_t)workspace & 15) != 0) return IRON_ERR_BAD_ARG;
+    if (phase != 0 && phase != 1) return IRON_ERR_BAD_ARG;
+    const bool args_ok = lin_steps && ray_o && ray_d && near && far && work && conv && points && sdf_out && dist;
+    WsLayout L;
+    const int rcc = check_trace_call(sdf, p, n, args_ok, p ? p->chunk : 0, workspace, workspace_bytes, &L);
+    if (rcc != IRON_OK || n == 0) return rcc;
     if (chunk_iters && (n_chunks < 1 || n_chunks > 65536)) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)workspace;
-    TraceWs w0{};
-    w0.cnt = (TraceCounters*)(base + L.cnt);
-    w0.sampler_list = (int*)(base + L.sampler_list);
-    w0.root_list = (int*)(base + L.root_list);
-    w0.root_lo = (float*)(base + L.lo);
-    w0.root_hi = (float*)(base + L.hi);
-    w0.root_flo = (float*)(base + L.flo);
-    w0.root_fhi = (float*)(base + L.fhi);
-    w0.root_k = (int*)(base + L.k);
-    w0.chunk_iters = chunk_iters ? chunk_iters : (int*)(base + L.chunk_iters);
-    w0.chunk_roots = (int*)(base + L.chunk_roots);
-    w0.n_chunks = (int)(chunk_iters ? n_chunks : L.n_chunks);
-    w0.cont = (unsigned long long*)(base + L.cont);
-    w0.cont_cap = (int)L.cont_cap;
+    TraceWs w0 = bind_workspace(base, L);
+    if (chunk_iters) { w0.chunk_iters = chunk_iters; w0.n_chunks = (int)n_chunks; }
     if (chunk_iters && n_chunks > L.n_chunks) {
         // multi-rank: the chunk table covers the whole image, not just this rank's rays
         if (workspace_bytes < L.total + align256(sizeof(int) * (size_t)n_chunks)) return IRON_ERR_WORKSPACE;
@@ -1779,7 +1792,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
         if (phase == 0) {
             {
                 ProfScope ps(IRON_PROF_SPHERE, sk);
-                launch_trace_kernel(0, h2, sdf, a, w, tiles, sk);
+                launch_trace_kernel(kSphere, h2, sdf, a, w, tiles, sk);
             }
             {
                 ProfScope ps(IRON_PROF_SAMPLER, sk);
@@ -1787,11 +1800,11 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
             }
             {
                 ProfScope ps(IRON_PROF_BISECT_A, sk);
-                launch_trace_kernel(2, h2, sdf, a, w, tiles, sk);
+                launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, sk);
             }
         } else {
             ProfScope ps(IRON_PROF_BISECT_B, sk);
-            launch_trace_kernel(3, h2, sdf, a, w, tiles, sk);
+            launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, sk);
         }
         if (k > 0) IRON_HIP_TRY(hipEventRecord(S->join[k - 1], sk));
     }
@@ -1807,33 +1820,16 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
                                 const float* ray_o, const float* ray_d, const float* in0, const float* in1, const float* in2,
                                 const float* in3, const uint8_t* work, int64_t n, uint8_t* mask_out, uint8_t* unfinished_out,
                                 float* points, float* sdf_out, float* dist, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!sdf || sdf->desc.kind != IRON_NET_SDF || !p || n < 0 || stage < 0 || stage > 2) return IRON_ERR_BAD_ARG;
-    if (n > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
-    if (p->n_steps < 2 || p->n_steps > 4096 || p->sphere_tracing_iters < 0 || !(p->sdf_threshold > 0.0f)) return IRON_ERR_BAD_ARG;
-    if (n == 0) return IRON_OK;
-    if (!lin_steps || !ray_o || !ray_d || !in0 || !in1 || !mask_out || !points || !sdf_out || !dist || !workspace) return IRON_ERR_BAD_ARG;
-    if (stage == 0 && (!work || !unfinished_out)) return IRON_ERR_BAD_ARG;
-    if (stage == 2 && (!in2 || !in3)) return IRON_ERR_BAD_ARG;
-    iron_trace_params q = *p;
-    q.chunk = 0;   // one reference call = one chunk
-    const WsLayout L = ws_layout(n, &q);
-    if (workspace_bytes < L.total) return IRON_ERR_WORKSPACE;
-    if (((uintptr_t)workspace & 15) != 0) return IRON_ERR_BAD_ARG;
+    if (stage < 0 || stage > 2) return IRON_ERR_BAD_ARG;
+    const bool args_ok = lin_steps && ray_o && ray_d && in0 && in1 && mask_out && points && sdf_out && dist &&
+                         !(stage == 0 && (!work || !unfinished_out)) && !(stage == 2 && (!in2 || !in3));
+    WsLayout L;
+    const int rcc = check_trace_call(sdf, p, n, args_ok, 0, workspace, workspace_bytes, &L);   // chunk 0: one reference call = one chunk
+    if (rcc != IRON_OK || n == 0) return rcc;
     { const int rce = envelope_begin(sdf); if (rce != IRON_OK) return rce; }
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)workspace;
-    TraceWs w{};
-    w.cnt = (TraceCounters*)(base + L.cnt);
-    w.sampler_list = (int*)(base + L.sampler_list);
-    w.root_list = (int*)(base + L.root_list);
-    w.root_lo = (float*)(base + L.lo); w.root_hi = (float*)(base + L.hi);
-    w.root_flo = (float*)(base + L.flo); w.root_fhi = (float*)(base + L.fhi);
-    w.root_k = (int*)(base + L.k);
-    w.chunk_iters = (int*)(base + L.chunk_iters);
-    w.chunk_roots = (int*)(base + L.chunk_roots);
-    w.n_chunks = 1;
-    w.cont = (unsigned long long*)(base + L.cont);
-    w.cont_cap = (int)L.cont_cap;
+    TraceWs w = bind_workspace(base, L);
     TraceArgs a;
     a.ray_o = ray_o; a.ray_d = ray_d; a.work = work; a.ray_index = nullptr; a.lin = lin_steps;
     a.conv = mask_out; a.points = points; a.sdf = sdf_out; a.dist = dist;
@@ -1854,17 +1850,17 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     const unsigned gb = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     if (stage == 0) {            // sphere_tracing (raytracer.py:105-140): in0 = min_dis, in1 = max_dis
         IRON_HIP_TRY(hipMemsetAsync(unfinished_out, 0, (size_t)n, st));
-        launch_trace_kernel(0, h2, sdf, a, w, tiles, st);
+        launch_trace_kernel(kSphere, h2, sdf, a, w, tiles, st);
         hipLaunchKernelGGL(k_stage_mark_list, dim3(gb), dim3(256), 0, st, w.sampler_list, &w.cnt->smp.n_list, unfinished_out);
     } else if (stage == 1) {     // ray_sampler (:142-197): in0 = min_dis, in1 = max_dis, every ray sampled on its own interval
         hipLaunchKernelGGL(k_stage_sampler_init, dim3(gb), dim3(256), 0, st, a, w, in0);
         run_sampler(h2, screen, sdf, a, w, n, st);
-        launch_trace_kernel(2, h2, sdf, a, w, tiles, st);
-        launch_trace_kernel(3, h2, sdf, a, w, tiles, st);
+        launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, st);
+        launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, st);
     } else {                     // rootfind (:199-220): in0 = f_low, in1 = f_high, in2 = d_low, in3 = d_high
         hipLaunchKernelGGL(k_stage_root_init, dim3(gb), dim3(256), 0, st, w, (int)n, in0, in1, in2, in3);
-        launch_trace_kernel(2, h2, sdf, a, w, tiles, st);
-        launch_trace_kernel(3, h2, sdf, a, w, tiles, st);
+        launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, st);
+        launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, st);
     }
     if (h2) envelope_scan(sdf, sdf_out, n, nullptr, 1, st);
     IRON_HIP_TRY(hipGetLastError());
