@@ -248,6 +248,59 @@ int iron_bvh_boxes(const float* verts, int64_t n_verts, const int32_t* faces, in
                    void* stream);
 int iron_point_mesh_distance(const void* workspace, int64_t n_faces, const float* points, int64_t n_points, float* sqr_dist,
                              int32_t* face_idx, float* closest, void* stream);
+/* Flash render of an exported asset (mesh + baked material textures), csrc/meshrender.hip; DESIGN.md §15.  Every entry enqueues on
+ * `stream`; only iron_mesh_vertex_normals waits.
+ *   iron_mesh_raycast  per ray (ray_o, ray_d [n_rays,3]; directions need not be unit length) the closest hit with t in
+ *                       (t_min, t_max] over the BVH of iron_bvh_* (same workspace and n_faces): t [n_rays] along ray_d, face_idx
+ *                       [n_rays] int32, bary [n_rays,2] = the weights of the face's second and third vertex.  Faces are two-sided.
+ *                       A miss gives t = +inf, face -1, bary 0; so does a ray with a non-finite component or a zero direction.
+ *                       Watertight: a ray through an edge or a vertex shared by faces of a closed mesh hits one of them (ray-space
+ *                       edge functions, exact zeros re-decided in fp64 and counted as inside).  Among equal t the smallest face
+ *                       index wins, so for a fixed ray t does not depend on the order of the faces or on the tree.  The box test
+ *                       only errs towards visiting; zero direction components are allowed.
+ *   iron_mesh_vertex_normals  normals [n_verts,3]: per vertex the sum of its faces' un-normalised cross products (B-A) x (C-A)
+ *                       (area weighting; this project's choice), normalised; the zero vector where the sum is zero or no face
+ *                       references the vertex.  Faces with an index outside [0, n_verts) or a non-finite product are skipped.  The
+ *                       sums are int64 in units of 2^-40 of the mesh's largest product component: bitwise reproducible whatever the
+ *                       order of faces and atomics.  Allocates that accumulator (24 B per vertex), synchronises `stream` once and
+ *                       frees it.
+ *   iron_texture_fetch  values [n,C] (C <= 8) of tex [H,W,C] at uv [n,2] in the bake's convention: texel (row, col) covers
+ *                       [col, col+1) x [row, row+1) of (uv_x W, H - uv_y H).  IRON_TEX_BILINEAR: four taps around
+ *                       (uv_x W - 1/2, H - uv_y H - 1/2), clamped to the edge; IRON_TEX_NEAREST: the covering texel (clamped).
+ *                       The coordinates are formed in fp64 (exact for fp32 uv).  With `weight` [H,W] (the bake's weight image, may
+ *                       be NULL) taps whose weight is not > 0 are dropped and the others renormalised; with none left the value is
+ *                       0 and hole [n] (uint8, may be NULL) is 1.  A non-finite uv is a hole.  H * W <= 2^24.
+ *   iron_asset_shade_ggx  one lane per ray from iron_mesh_raycast's t / face_idx / bary (ray_d unit): point = o + t d, distance =
+ *                       |point - o|, uv interpolated through the face's own face_uvs, normal = the normalised interpolation of
+ *                       mesh->normals (NULL, or a zero result: the face's geometric normal (B-A) x (C-A); never flipped towards
+ *                       the viewer), material = the bilinear fetch of mesh->material [tex_h,tex_w,7] (kd 3, ks 3, roughness) with
+ *                       mesh->weight, colours = ggx_colocated_point (the function behind iron_ggx_colocated) with view = -ray_d.
+ *                       Every output pointer may be NULL; a miss (or a face with an index out of range) writes zeros. */
+enum { IRON_TEX_BILINEAR = 0, IRON_TEX_NEAREST = 1 };
+typedef struct iron_asset_mesh {
+    const float* verts; int64_t n_verts;       /* [n_verts,3] */
+    const int32_t* faces; int64_t n_faces;     /* [n_faces,3] */
+    const float* uvs; int64_t n_uvs;           /* [n_uvs,2] */
+    const int32_t* face_uvs;                   /* [n_faces,3] into uvs */
+    const float* normals;                      /* [n_verts,3] or NULL */
+    const float* material;                     /* [tex_h,tex_w,7] */
+    const float* weight;                       /* [tex_h,tex_w] or NULL */
+    int32_t tex_h, tex_w;
+} iron_asset_mesh;
+typedef struct iron_asset_out {
+    float *color, *diffuse_color, *specular_color, *normal, *points, *diffuse_albedo, *specular_albedo;  /* [n_rays,3] */
+    float *distance, *specular_roughness;      /* [n_rays] */
+    float* uv;                                 /* [n_rays,2] */
+    uint8_t* hole;                             /* [n_rays] */
+} iron_asset_out;
+int iron_mesh_raycast(const void* workspace, int64_t n_faces, const float* ray_o, const float* ray_d, int64_t n_rays, float t_min,
+                      float t_max, float* t, int32_t* face_idx, float* bary, void* stream);
+int iron_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, float* normals, void* stream);
+int iron_texture_fetch(const float* tex, const float* weight, int32_t H, int32_t W, int32_t C, const float* uv, int64_t n, int32_t mode,
+                       float* values, uint8_t* hole, void* stream);
+int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, const float* tab_trans, const float* tab_diff_trans, const float* ray_o,
+                         const float* ray_d, const float* t, const int32_t* face_idx, const float* bary, int64_t n_rays,
+                         const iron_asset_out* out, void* stream);
 /* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
  * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
  *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte

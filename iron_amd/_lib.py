@@ -78,6 +78,20 @@ class iron_shade_out(C.Structure):
                 ("specular_roughness", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class iron_asset_mesh(C.Structure):
+    _fields_ = [("verts", C.c_void_p), ("n_verts", C.c_int64), ("faces", C.c_void_p), ("n_faces", C.c_int64), ("uvs", C.c_void_p),
+                ("n_uvs", C.c_int64), ("face_uvs", C.c_void_p), ("normals", C.c_void_p), ("material", C.c_void_p), ("weight", C.c_void_p),
+                ("tex_h", C.c_int32), ("tex_w", C.c_int32)]
+
+
+ASSET_OUT_FIELDS = ("color", "diffuse_color", "specular_color", "normal", "points", "diffuse_albedo", "specular_albedo", "distance",
+                    "specular_roughness", "uv", "hole")
+
+
+class iron_asset_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ASSET_OUT_FIELDS]
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -118,6 +132,10 @@ SYMBOLS = {
     "iron_bvh_hierarchy": (C.c_int, [_P, _I64, _P, _P]),
     "iron_bvh_boxes": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_point_mesh_distance": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "iron_mesh_raycast": (C.c_int, [_P, _I64, _P, _P, _I64, _F, _F, _P, _P, _P, _P]),
+    "iron_mesh_vertex_normals": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
+    "iron_texture_fetch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),
+    "iron_asset_shade_ggx": (C.c_int, [C.POINTER(iron_asset_mesh), _F, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(iron_asset_out), _P]),
     "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
     "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),

@@ -1,0 +1,452 @@
+// Flash render of an exported asset (mesh + baked material textures): closest-hit ray cast over the linear
+// BVH of meshdist.hip, area-weighted vertex normals, the texture fetch in the bake's pixel convention, and the co-located GGX of
+// ggx_core.h on the hits.  Conventions: include/iron_hip.h, iron_mesh_raycast block.
+//
+// Ray cast (k_raycast): one lane per ray, depth-first, the child with the nearer box entry first, the other on a per-lane stack in
+// LDS (kBvStack entries, see bvh_common.h).
+//   Triangle test: Woop, Benthin, Wald, "Watertight Ray/Triangle Intersection" (JCGT 2013).  The vertices are translated to the
+//   ray origin and sheared into the ray's space (largest direction component = z); the edge functions U, V, W are differences of two
+//   products of the sheared x / y of two vertices.  An edge shared by two faces feeds the same two vertices into the same two
+//   products, so the two faces compute values that are exact negatives of each other (the library is built with
+//   -ffp-contract=off): a ray cannot pass between them.  An exact zero is re-decided in fp64 from the same fp32 operands (the
+//   products are then exact), and a zero that remains counts as inside.  Faces are two-sided.
+//   Box test: slabs with the reciprocal direction.  Every bound is moved outwards by 2^-21 (|lo| + |hi| + |o|) |1 / d| on its axis,
+//   8 ulps of the operands against the ~3 the slab arithmetic and the few the triangle's own t can be off by: the test errs towards
+//   visiting.  An axis whose reciprocal is not finite (zero component) passes when lo <= o <= hi, so a ray lying in a box plane
+//   visits the box.  A box whose entry equals the best t is visited.
+//   A face replaces the best when its t is smaller, or equal with a smaller face index: for a fixed ray, t is a function of the
+//   set of faces, not of their order or of the tree.
+#include "iron_common.h"
+#include "bvh_common.h"
+#include "ggx_core.h"
+
+namespace iron {
+
+constexpr float kInfF = __builtin_huge_valf();
+
+struct RayPre {
+    float3 o, inv, pad;   // origin, 1 / d, 2^-21 |1 / d| (0 on an axis whose reciprocal is not finite)
+    bool zx, zy, zz;      // that axis: the reciprocal is not finite
+    int kx, ky, kz;       // Woop's axis permutation
+    float sx, sy, sz;     // shear and scale
+};
+
+__device__ __forceinline__ float pick(float3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+__device__ __forceinline__ void ray_setup(float3 o, float3 d, RayPre& r) {
+    r.o = o;
+    r.inv = make_float3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    r.zx = !(fabsf(r.inv.x) < kInfF); r.zy = !(fabsf(r.inv.y) < kInfF); r.zz = !(fabsf(r.inv.z) < kInfF);
+    const float e = 4.76837158203125e-07f;  // 2^-21
+    r.pad = make_float3(r.zx ? 0.0f : fabsf(r.inv.x) * e, r.zy ? 0.0f : fabsf(r.inv.y) * e, r.zz ? 0.0f : fabsf(r.inv.z) * e);
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    r.kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    r.kx = r.kz == 2 ? 0 : r.kz + 1;
+    r.ky = r.kx == 2 ? 0 : r.kx + 1;
+    const float dz = pick(d, r.kz);
+    if (dz < 0.0f) { const int s = r.kx; r.kx = r.ky; r.ky = s; }  // keeps the winding
+    r.sx = pick(d, r.kx) / dz;
+    r.sy = pick(d, r.ky) / dz;
+    r.sz = 1.0f / dz;
+}
+
+// one slab: entry and exit of [lo, hi] on one axis, moved outwards (see the head of the file)
+__device__ __forceinline__ void slab(float lo, float hi, float o, float inv, float pad, bool zero, float& tn, float& tf) {
+    const float t0 = (lo - o) * inv, t1 = (hi - o) * inv;
+    const float p = ((fabsf(lo) + fabsf(hi)) + fabsf(o)) * pad;
+    const float n = fminf(t0, t1) - p, f = fmaxf(t0, t1) + p;
+    tn = fmaxf(tn, zero ? ((o >= lo && o <= hi) ? -kInfF : kInfF) : n);
+    tf = fminf(tf, zero ? kInfF : f);
+}
+
+// does the ray meet the box within [t_min, best]?  `tn`: the (conservative) entry distance
+__device__ __forceinline__ bool ray_box(const RayPre& r, float4 lo, float4 hi, float t_min, float best, float& tn) {
+    float tf = kInfF;
+    tn = -kInfF;
+    slab(lo.x, hi.x, r.o.x, r.inv.x, r.pad.x, r.zx, tn, tf);
+    slab(lo.y, hi.y, r.o.y, r.inv.y, r.pad.y, r.zy, tn, tf);
+    slab(lo.z, hi.z, r.o.z, r.inv.z, r.pad.z, r.zz, tn, tf);
+    return tn <= tf && tn <= best && tf >= t_min;
+}
+
+struct RayHit {
+    float t, b1, b2;  // distance along d, barycentric weights of the face's second and third vertex
+    int32_t face;     // INT32_MAX: none yet
+    int32_t leaf;     // its position in the leaf order
+};
+
+__device__ __forceinline__ void ray_leaf(const float4* __restrict__ tris, int32_t k, const RayPre& r, float t_min, RayHit& h) {
+    const float4 ta = tris[3 * (int64_t)k], tb = tris[3 * (int64_t)k + 1], tc = tris[3 * (int64_t)k + 2];
+    const int32_t f = __float_as_int(ta.w);
+    const float3 A = sub3(make_float3(ta.x, ta.y, ta.z), r.o), B = sub3(make_float3(tb.x, tb.y, tb.z), r.o),
+                 C = sub3(make_float3(tc.x, tc.y, tc.z), r.o);
+    const float Akz = pick(A, r.kz), Bkz = pick(B, r.kz), Ckz = pick(C, r.kz);
+    const float Ax = pick(A, r.kx) - r.sx * Akz, Ay = pick(A, r.ky) - r.sy * Akz;
+    const float Bx = pick(B, r.kx) - r.sx * Bkz, By = pick(B, r.ky) - r.sy * Bkz;
+    const float Cx = pick(C, r.kx) - r.sx * Ckz, Cy = pick(C, r.ky) - r.sy * Ckz;
+    float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    bool neg = U < 0.0f || V < 0.0f || W < 0.0f, pos = U > 0.0f || V > 0.0f || W > 0.0f;
+    if (U == 0.0f || V == 0.0f || W == 0.0f) {  // on an edge or a vertex (or an underflow): the signs from exact products
+        const double Ud = (double)Cx * (double)By - (double)Cy * (double)Bx;
+        const double Vd = (double)Ax * (double)Cy - (double)Ay * (double)Cx;
+        const double Wd = (double)Bx * (double)Ay - (double)By * (double)Ax;
+        neg = Ud < 0.0 || Vd < 0.0 || Wd < 0.0;
+        pos = Ud > 0.0 || Vd > 0.0 || Wd > 0.0;
+        U = (float)Ud; V = (float)Vd; W = (float)Wd;
+    }
+    if (neg && pos) return;
+    const float det = (U + V) + W;
+    if (det == 0.0f) return;  // edge-on or degenerate
+    const float T = (U * (r.sz * Akz) + V * (r.sz * Bkz)) + W * (r.sz * Ckz);
+    const float t = T / det;
+    if (!(t > t_min) || !(t < kInfF)) return;  // NaN fails too
+    if (t < h.t || (t == h.t && f < h.face)) {
+        h.t = t; h.face = f; h.leaf = k; h.b1 = V / det; h.b2 = W / det;
+    }
+}
+
+// The winner's barycentric weights once more, in fp64 from the fp32 inputs (Moeller-Trumbore; the differences are exact there).  The
+// ray-space edge functions decide the hit and t; as weights they carry the rounding of the vertices' translation to the ray origin,
+// ~2^-24 |A - o| / h (h the face's altitude), which grows with the distance to the camera.  These do not.
+__device__ __forceinline__ void refine_bary(const float4* __restrict__ tris, float3 o, float3 d, RayHit& h) {
+    const float4 ta = tris[3 * (int64_t)h.leaf], tb = tris[3 * (int64_t)h.leaf + 1], tc = tris[3 * (int64_t)h.leaf + 2];
+    const double e1[3] = {(double)tb.x - ta.x, (double)tb.y - ta.y, (double)tb.z - ta.z};
+    const double e2[3] = {(double)tc.x - ta.x, (double)tc.y - ta.y, (double)tc.z - ta.z};
+    const double s[3] = {(double)o.x - ta.x, (double)o.y - ta.y, (double)o.z - ta.z};
+    const double dd[3] = {d.x, d.y, d.z};
+    const double p[3] = {dd[1] * e2[2] - dd[2] * e2[1], dd[2] * e2[0] - dd[0] * e2[2], dd[0] * e2[1] - dd[1] * e2[0]};
+    const double q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
+    const double det = (e1[0] * p[0] + e1[1] * p[1]) + e1[2] * p[2];
+    if (det == 0.0) return;  // keeps the fp32 weights
+    const double u = ((s[0] * p[0] + s[1] * p[1]) + s[2] * p[2]) / det, v = ((dd[0] * q[0] + dd[1] * q[1]) + dd[2] * q[2]) / det;
+    if (!(fabs(u) <= 2.0) || !(fabs(v) <= 2.0)) return;  // a sliver seen edge-on: nothing gained
+    h.b1 = (float)fmin(fmax(u, 0.0), 1.0);  // a hit the fp32 test took on an edge may lie a rounding outside
+    h.b2 = (float)fmin(fmax(v, 0.0), 1.0);
+}
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_raycast(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf,
+                                                            const float* __restrict__ ray_o, const float* __restrict__ ray_d, int64_t n,
+                                                            float t_min, float t_max, float* __restrict__ t_out,
+                                                            int32_t* __restrict__ face_idx, float* __restrict__ bary) {
+    __shared__ int32_t stack[kBvStack][kBvQueryBlock];  // [depth][lane]: lane l always on bank l % 32
+    const int lane = threadIdx.x;
+    const int64_t q = (int64_t)blockIdx.x * kBvQueryBlock + lane;
+    if (q >= n) return;
+    const float3 o = ld3(ray_o, q), d = ld3(ray_d, q);
+    RayHit h;
+    h.t = t_max; h.face = 0x7fffffff; h.leaf = 0; h.b1 = h.b2 = 0.0f;  // the window's far end is inclusive: any face at t_max beats the sentinel
+    const bool valid = finite3(o) && finite3(d) && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f) && t_min <= t_max;  // NaN bounds fail
+    if (valid) {
+        RayPre r;
+        ray_setup(o, d, r);
+        if (nf == 1) {
+            ray_leaf(tris, 0, r, t_min, h);
+        } else {
+            int32_t node = 0, sp = 0;
+            for (;;) {
+                const float4* nd = nodes + 4 * (int64_t)node;
+                const float4 l0 = nd[0], h0 = nd[1], l1 = nd[2], h1 = nd[3];
+                const int32_t c0 = __float_as_int(l0.w), c1 = __float_as_int(h0.w);
+                float n0, n1;
+                const bool v0 = ray_box(r, l0, h0, t_min, h.t, n0);
+                if (c0 < 0 && v0) ray_leaf(tris, ~c0, r, t_min, h);
+                const bool v1 = ray_box(r, l1, h1, t_min, h.t, n1);
+                if (c1 < 0 && v1) ray_leaf(tris, ~c1, r, t_min, h);
+                const bool g0 = c0 >= 0 && v0 && n0 <= h.t, g1 = c1 >= 0 && v1 && n1 <= h.t;
+                if (g0 && g1) {
+                    const bool first1 = n1 < n0;
+                    if (sp < kBvStack) stack[sp++][lane] = first1 ? c0 : c1;  // never full (kBvStack)
+                    node = first1 ? c1 : c0;
+                } else if (g0) {
+                    node = c0;
+                } else if (g1) {
+                    node = c1;
+                } else {
+                    if (sp == 0) break;
+                    node = stack[--sp][lane];
+                }
+            }
+        }
+    }
+    const bool hit = h.face != 0x7fffffff;
+    if (hit) refine_bary(tris, o, d, h);
+    t_out[q] = hit ? h.t : kInfF;
+    face_idx[q] = hit ? h.face : -1;
+    bary[2 * q] = hit ? h.b1 : 0.0f;
+    bary[2 * q + 1] = hit ? h.b2 : 0.0f;
+}
+
+// ---- vertex normals ----
+// Every face adds its un-normalised cross product (twice its area times its normal) to its three vertices.  The product is formed
+// in fp64 (the differences of fp32 coordinates are exact there, so a sliver's product does not cancel).  The sums are int64 in
+// units of 2^-40 of the largest cross-product component of the mesh (found first: a max, so order-free), which makes them exact
+// integer sums: bitwise the same whatever the order of the atomics and of the faces.
+constexpr double kVnScale = 1099511627776.0;  // 2^40: up to 2^22 faces around one vertex fit int64
+
+__device__ __forceinline__ bool vn_face(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t f, int32_t idx[3],
+                                        double c[3]) {
+    idx[0] = faces[3 * f]; idx[1] = faces[3 * f + 1]; idx[2] = faces[3 * f + 2];
+    for (int k = 0; k < 3; ++k)
+        if (idx[k] < 0 || idx[k] >= nv) return false;
+    const float3 a = ld3(v, idx[0]), b = ld3(v, idx[1]), q = ld3(v, idx[2]);
+    const double ex = (double)b.x - (double)a.x, ey = (double)b.y - (double)a.y, ez = (double)b.z - (double)a.z;
+    const double gx = (double)q.x - (double)a.x, gy = (double)q.y - (double)a.y, gz = (double)q.z - (double)a.z;
+    c[0] = ey * gz - ez * gy; c[1] = ez * gx - ex * gz; c[2] = ex * gy - ey * gx;
+    return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
+}
+
+__global__ __launch_bounds__(256) void k_vn_max(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t nf,
+                                                 unsigned long long* __restrict__ vmax) {
+    __shared__ unsigned long long s[256];
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long m = 0;
+    int32_t idx[3];
+    double c[3];
+    if (f < nf && vn_face(v, nv, faces, f, idx, c))
+        m = (unsigned long long)__double_as_longlong(fmax(fmax(fabs(c[0]), fabs(c[1])), fabs(c[2])));  // >= 0: integer order
+    s[threadIdx.x] = m;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) s[threadIdx.x] = max(s[threadIdx.x], s[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && s[0]) atomicMax(vmax, s[0]);
+}
+
+__global__ __launch_bounds__(256) void k_vn_add(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t nf,
+                                                 const unsigned long long* __restrict__ vmax, unsigned long long* __restrict__ acc) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= nf) return;
+    int32_t idx[3];
+    double c[3];
+    const double m = __longlong_as_double((long long)*vmax);
+    if (!(m > 0.0) || !vn_face(v, nv, faces, f, idx, c)) return;
+    const double s = kVnScale / m;
+    const long long q[3] = {__double2ll_rn(c[0] * s), __double2ll_rn(c[1] * s), __double2ll_rn(c[2] * s)};
+    for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a)
+            if (q[a]) atomicAdd(acc + 3 * (int64_t)idx[k] + a, (unsigned long long)q[a]);
+}
+
+__global__ void k_vn_finish(const long long* __restrict__ acc, int64_t nv, float* __restrict__ normals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const double x = (double)acc[3 * i], y = (double)acc[3 * i + 1], z = (double)acc[3 * i + 2];
+    const double l = sqrt(x * x + y * y + z * z);
+    const double s = l > 0.0 ? 1.0 / l : 0.0;
+    normals[3 * i] = (float)(x * s);
+    normals[3 * i + 1] = (float)(y * s);
+    normals[3 * i + 2] = (float)(z * s);
+}
+
+// ---- texture fetch ----
+// The bake's pixel convention (texbake.hip: u = uv_x W, v = H - uv_y H, texel (row, col) covers [col, col + 1) x [row, row + 1)):
+// x = uv_x W - 1/2, y = (H - uv_y H) - 1/2 are the coordinates in texel centres.  They are formed in fp64, where they are exact for
+// fp32 uv and sizes below 2^24.  Returns true for a hole: no tap with a non-zero bake weight (or a non-finite uv); out is then 0.
+template <int MAXC>
+__device__ __forceinline__ bool texture_fetch(const float* __restrict__ tex, const float* __restrict__ weight, int H, int W, int C, float u,
+                                              float v, int mode, float out[MAXC]) {
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) out[c] = 0.0f;
+    if (!isfinite(u) || !isfinite(v)) return true;
+    const double xu = (double)u * (double)W, yv = (double)H - (double)v * (double)H;
+    if (mode == IRON_TEX_NEAREST) {
+        const int col = (int)fmin(fmax(floor(xu), 0.0), (double)(W - 1)), row = (int)fmin(fmax(floor(yv), 0.0), (double)(H - 1));
+        const int64_t t = (int64_t)row * W + col;
+        if (weight && !(weight[t] > 0.0f)) return true;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) out[c] = tex[t * C + c];
+        return false;
+    }
+    const double x = fmin(fmax(xu - 0.5, -1.0), (double)W), y = fmin(fmax(yv - 0.5, -1.0), (double)H);  // beyond the edge: the edge texel
+    const double x0 = floor(x), y0 = floor(y);
+    const float fx = (float)(x - x0), fy = (float)(y - y0);
+    const int c0 = min(max((int)x0, 0), W - 1), c1 = min(max((int)x0 + 1, 0), W - 1);
+    const int r0 = min(max((int)y0, 0), H - 1), r1 = min(max((int)y0 + 1, 0), H - 1);
+    const int64_t tap[4] = {(int64_t)r0 * W + c0, (int64_t)r0 * W + c1, (int64_t)r1 * W + c0, (int64_t)r1 * W + c1};
+    float w[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
+    if (weight) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!(weight[tap[k]] > 0.0f)) w[k] = 0.0f;
+            sum += w[k];
+        }
+        if (!(sum > 0.0f)) return true;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = w[k] / sum;
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) {
+            float a = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (w[k] != 0.0f) a += w[k] * tex[tap[k] * C + c];  // a dropped tap is not read: an unbaked texel may hold anything
+            out[c] = a;
+        }
+    return false;
+}
+
+constexpr int kTexMaxC = 8;
+
+__global__ void k_texture_fetch(const float* __restrict__ tex, const float* __restrict__ weight, int H, int W, int C,
+                                const float* __restrict__ uv, int64_t n, int mode, float* __restrict__ values, uint8_t* __restrict__ hole) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[kTexMaxC];
+    const bool hl = texture_fetch<kTexMaxC>(tex, weight, H, W, C, uv[2 * i], uv[2 * i + 1], mode, o);
+#pragma unroll
+    for (int c = 0; c < kTexMaxC; ++c)
+        if (c < C) values[i * C + c] = o[c];
+    if (hole) hole[i] = hl ? 1 : 0;
+}
+
+// ---- shading of the hits ----
+struct AssetShadeArgs {
+    iron_asset_mesh m;
+    iron_asset_out o;
+    const float *tab_trans, *tab_diff, *ray_o, *ray_d, *t, *bary;
+    const int32_t* face_idx;
+    float light;
+    int64_t n;
+};
+
+__device__ __forceinline__ float3 unit_or_zero(float3 v) {
+    const float l = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+    return l > 0.0f && l < kInfF ? make_float3(v.x / l, v.y / l, v.z / l) : make_float3(0.f, 0.f, 0.f);
+}
+
+__device__ __forceinline__ void st3(float* __restrict__ p, int64_t i, float x, float y, float z) {
+    if (p) { p[3 * i] = x; p[3 * i + 1] = y; p[3 * i + 2] = z; }
+}
+
+__global__ __launch_bounds__(256) void k_asset_shade(AssetShadeArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const iron_asset_mesh& m = a.m;
+    const int64_t f = a.face_idx[i];
+    const float t = a.t[i];
+    bool hit = f >= 0 && f < m.n_faces && t < kInfF && t == t;
+    int32_t iv[3] = {0, 0, 0}, it[3] = {0, 0, 0};
+    if (hit)
+        for (int k = 0; k < 3; ++k) {
+            iv[k] = m.faces[3 * f + k];
+            it[k] = m.face_uvs[3 * f + k];
+            if (iv[k] < 0 || iv[k] >= m.n_verts || it[k] < 0 || it[k] >= m.n_uvs) hit = false;
+        }
+    float3 pt = make_float3(0.f, 0.f, 0.f), nrm = pt;
+    float dist = 0.0f, uvx = 0.0f, uvy = 0.0f, mat[kTexMaxC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    GgxOut g;
+    for (int c = 0; c < 3; ++c) g.diffuse[c] = g.specular[c] = g.rgb[c] = 0.0f;
+    bool hl = false;
+    if (hit) {
+        const float3 o = ld3(a.ray_o, i), d = ld3(a.ray_d, i);
+        const float b1 = a.bary[2 * i], b2 = a.bary[2 * i + 1], b0 = (1.0f - b1) - b2;
+        pt = make_float3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);
+        const float3 rel = sub3(pt, o);
+        dist = sqrtf((rel.x * rel.x + rel.y * rel.y) + rel.z * rel.z);
+        uvx = (b0 * m.uvs[2 * (int64_t)it[0]] + b1 * m.uvs[2 * (int64_t)it[1]]) + b2 * m.uvs[2 * (int64_t)it[2]];
+        uvy = (b0 * m.uvs[2 * (int64_t)it[0] + 1] + b1 * m.uvs[2 * (int64_t)it[1] + 1]) + b2 * m.uvs[2 * (int64_t)it[2] + 1];
+        if (m.normals) {
+            const float3 n0 = ld3(m.normals, iv[0]), n1 = ld3(m.normals, iv[1]), n2 = ld3(m.normals, iv[2]);
+            nrm = unit_or_zero(make_float3((b0 * n0.x + b1 * n1.x) + b2 * n2.x, (b0 * n0.y + b1 * n1.y) + b2 * n2.y,
+                                           (b0 * n0.z + b1 * n1.z) + b2 * n2.z));
+        }
+        if (nrm.x == 0.0f && nrm.y == 0.0f && nrm.z == 0.0f) {  // no vertex normals, or they cancel: the face's own
+            const float3 va = ld3(m.verts, iv[0]);
+            nrm = unit_or_zero(cross3(sub3(ld3(m.verts, iv[1]), va), sub3(ld3(m.verts, iv[2]), va)));
+        }
+        hl = texture_fetch<kTexMaxC>(m.material, m.weight, m.tex_h, m.tex_w, 7, uvx, uvy, IRON_TEX_BILINEAR, mat);
+        const float nn[3] = {nrm.x, nrm.y, nrm.z}, vv[3] = {-d.x, -d.y, -d.z};
+        ggx_colocated_point(a.light, dist, nn, vv, mat, mat + 3, mat[6], a.tab_trans, a.tab_diff, g);
+    }
+    st3(a.o.color, i, g.rgb[0], g.rgb[1], g.rgb[2]);
+    st3(a.o.diffuse_color, i, g.diffuse[0], g.diffuse[1], g.diffuse[2]);
+    st3(a.o.specular_color, i, g.specular[0], g.specular[1], g.specular[2]);
+    st3(a.o.normal, i, nrm.x, nrm.y, nrm.z);
+    st3(a.o.points, i, pt.x, pt.y, pt.z);
+    st3(a.o.diffuse_albedo, i, mat[0], mat[1], mat[2]);
+    st3(a.o.specular_albedo, i, mat[3], mat[4], mat[5]);
+    if (a.o.distance) a.o.distance[i] = dist;
+    if (a.o.specular_roughness) a.o.specular_roughness[i] = mat[6];
+    if (a.o.uv) { a.o.uv[2 * i] = uvx; a.o.uv[2 * i + 1] = uvy; }
+    if (a.o.hole) a.o.hole[i] = hl ? 1 : 0;
+}
+
+}  // namespace iron
+
+using namespace iron;
+
+extern "C" int iron_mesh_raycast(const void* workspace, int64_t n_faces, const float* ray_o, const float* ray_d, int64_t n_rays, float t_min,
+                                 float t_max, float* t, int32_t* face_idx, float* bary, void* stream) {
+    if (n_faces <= 0 || n_faces >= 0x7fffffffLL || n_rays < 0 || !workspace) return IRON_ERR_BAD_ARG;
+    if (n_rays == 0) return IRON_OK;
+    if (!ray_o || !ray_d || !t || !face_idx || !bary) return IRON_ERR_BAD_ARG;
+    const BvLayout L = bv_layout(n_faces);
+    const char* ws = (const char*)workspace;
+    hipLaunchKernelGGL(k_raycast, dim3(bv_grid(n_rays, kBvQueryBlock)), dim3(kBvQueryBlock), 0, (hipStream_t)stream,
+                       (const float4*)(ws + L.nodes_off), (const float4*)(ws + L.tris_off), n_faces, ray_o, ray_d, n_rays, t_min, t_max, t,
+                       face_idx, bary);
+    IRON_HIP_TRY(hipGetLastError());
+    return IRON_OK;
+}
+
+extern "C" int iron_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, float* normals,
+                                        void* stream) {
+    if (n_verts < 0 || n_faces < 0 || n_verts > 0x7fffffffLL || n_faces >= 0x7fffffffLL) return IRON_ERR_BAD_ARG;
+    if (n_verts == 0) return IRON_OK;
+    if (!verts || !normals || (n_faces > 0 && !faces)) return IRON_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t acc_bytes = 24 * (size_t)n_verts;
+    char* buf = nullptr;
+    IRON_HIP_TRY(hipMalloc((void**)&buf, acc_bytes + 256));
+    unsigned long long* vmax = (unsigned long long*)(buf + acc_bytes);
+    hipError_t e = hipMemsetAsync(buf, 0, acc_bytes + 256, st);
+    if (e == hipSuccess && n_faces > 0) {
+        hipLaunchKernelGGL(k_vn_max, dim3(bv_grid(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, vmax);
+        hipLaunchKernelGGL(k_vn_add, dim3(bv_grid(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, (const unsigned long long*)vmax,
+                           (unsigned long long*)buf);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_vn_finish, dim3(bv_grid(n_verts, 256)), dim3(256), 0, st, (const long long*)buf, n_verts, normals);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);  // the accumulator is released below
+    (void)hipFree(buf);
+    if (e != hipSuccess) return hip_fail(e);
+    if (e2 != hipSuccess) return hip_fail(e2);
+    return IRON_OK;
+}
+
+extern "C" int iron_texture_fetch(const float* tex, const float* weight, int32_t H, int32_t W, int32_t C, const float* uv, int64_t n,
+                                  int32_t mode, float* values, uint8_t* hole, void* stream) {
+    if (H <= 0 || W <= 0 || C <= 0 || C > kTexMaxC || (int64_t)H * W > (1 << 24) || n < 0) return IRON_ERR_BAD_ARG;
+    if (mode != IRON_TEX_BILINEAR && mode != IRON_TEX_NEAREST) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!tex || !uv || !values) return IRON_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k_texture_fetch, dim3(bv_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, tex, weight, H, W, C, uv, n, mode, values,
+                       hole);
+    IRON_HIP_TRY(hipGetLastError());
+    return IRON_OK;
+}
+
+extern "C" int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, const float* tab_trans, const float* tab_diff_trans,
+                                    const float* ray_o, const float* ray_d, const float* t, const int32_t* face_idx, const float* bary,
+                                    int64_t n_rays, const iron_asset_out* out, void* stream) {
+    if (!mesh || !out || n_rays < 0) return IRON_ERR_BAD_ARG;
+    if (mesh->n_faces <= 0 || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
+        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
+        return IRON_ERR_BAD_ARG;
+    if (!mesh->verts || !mesh->faces || !mesh->uvs || !mesh->face_uvs || !mesh->material || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
+    if (n_rays == 0) return IRON_OK;
+    if (!ray_o || !ray_d || !t || !face_idx || !bary) return IRON_ERR_BAD_ARG;
+    AssetShadeArgs a;
+    a.m = *mesh; a.o = *out;
+    a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.ray_o = ray_o; a.ray_d = ray_d; a.t = t; a.bary = bary; a.face_idx = face_idx;
+    a.light = light; a.n = n_rays;
+    hipLaunchKernelGGL(k_asset_shade, dim3(bv_grid(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    IRON_HIP_TRY(hipGetLastError());
+    return IRON_OK;
+}

@@ -56,7 +56,8 @@ def _faces(faces, dev) -> torch.Tensor:
 class MeshBVH:
     """Linear BVH of a triangle mesh on the GPU: vertices [V, 3] (fp32; fp64 is rounded once), faces [F, 3] integer, numpy or
     CUDA tensors.  Built once at construction (one host wait, which reports a face index outside [0, V) or a non-finite
-    referenced vertex as IronError); vertices no face references are ignored.  `query(points)` answers on the current stream."""
+    referenced vertex as IronError); vertices no face references are ignored.  `query(points)` and `raycast(ray_o, ray_d)` answer
+    on the current stream."""
 
     def __init__(self, vertices, faces, device=None):
         dev = torch.device(device) if device is not None else _device(vertices, faces)
@@ -116,6 +117,26 @@ class MeshBVH:
                 _lib.check(_lib.load().iron_point_mesh_distance(self.workspace.data_ptr(), self.n_faces, p.data_ptr(), n, sqr.data_ptr(),
                                                                 idx.data_ptr(), cp.data_ptr(), _lib.stream_ptr(self.device)))
         return sqr, idx, cp
+
+    def raycast(self, ray_o, ray_d, t_min=0.0, t_max=float("inf")):
+        """ray_o, ray_d [N, 3] (numpy or CUDA tensors; directions need not be unit length) -> (t fp32 [N], face_idx int32 [N],
+        bary fp32 [N, 2]) device tensors: the closest hit with t in (t_min, t_max] along ray_d, two-sided faces, ties in t to the
+        smallest face index; bary holds the weights of the face's second and third vertex.  A miss, a non-finite ray or a zero
+        direction gives (+inf, -1, 0).  Watertight across shared edges and vertices (csrc/meshrender.hip)."""
+        with torch.cuda.device(self.device):
+            o = _dev(ray_o, torch.float32, self.device, "ray_o")
+            d = _dev(ray_d, torch.float32, self.device, "ray_d")
+            n = int(o.shape[0])
+            if d.shape[0] != n:
+                raise _lib.IronError("ray_o has %d rows, ray_d %d" % (n, d.shape[0]))
+            t = torch.empty((n,), dtype=torch.float32, device=self.device)
+            idx = torch.empty((n,), dtype=torch.int32, device=self.device)
+            bary = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+            if n:
+                _lib.check(_lib.load().iron_mesh_raycast(self.workspace.data_ptr(), self.n_faces, o.data_ptr(), d.data_ptr(), n,
+                                                         float(t_min), float(t_max), t.data_ptr(), idx.data_ptr(), bary.data_ptr(),
+                                                         _lib.stream_ptr(self.device)))
+        return t, idx, bary
 
 
 def point_mesh_squared_distance(P, V, F):
