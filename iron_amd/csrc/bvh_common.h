@@ -4,7 +4,8 @@
 // Node (64 B): float4 {lo0.xyz, child0}, {hi0.xyz, child1}, {lo1.xyz, 0}, {hi1.xyz, 0}; a child >= 0 is an internal node, a child
 // < 0 is leaf ~k, whose triangle record (48 B: {A.xyz, face}, {B.xyz, 0}, {C.xyz, 0}) sits at position k of the leaf order.
 #pragma once
-#include "iron_common.h"
+#include "host_util.h"
+#include "mesh_common.h"
 
 namespace iron {
 
@@ -15,16 +16,10 @@ constexpr int kBvQueryBlock = 64;  // one wave per block: the stack below is 16 
 constexpr int kBvStack = 64;
 
 struct BvHeader {
-    uint32_t lo[3], hi[3];  // centroid box, order-preserving uint encoding of fp32 (min / max by integer atomics)
+    uint32_t lo[3], hi[3];  // centroid box, f2ord of mesh_common.h (min / max by integer atomics)
     int32_t bad;            // a face indexes outside the vertices or has a non-finite coordinate
     int32_t pad;
 };
-
-__device__ __forceinline__ uint32_t f2ord(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
 __device__ __forceinline__ bool finite3(float3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
@@ -41,26 +36,18 @@ struct BvLayout {
     size_t hdr_off, nodes_off, tris_off, pint_off, pleaf_off, cnt_off, bytes;
 };
 
-inline size_t bv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline BvLayout bv_layout(int64_t nf) {
     BvLayout L{};
     const size_t ni = nf > 1 ? (size_t)(nf - 1) : 1;
-    size_t off = 0;
-    L.hdr_off = off;   off = bv_align(off + sizeof(BvHeader));
-    L.nodes_off = off; off = bv_align(off + 64 * ni);
-    L.tris_off = off;  off = bv_align(off + 48 * (size_t)nf);
-    L.pint_off = off;  off = bv_align(off + 4 * ni);
-    L.pleaf_off = off; off = bv_align(off + 4 * (size_t)nf);
-    L.cnt_off = off;   off = bv_align(off + 4 * ni);
-    L.bytes = off;
+    Carver c;
+    L.hdr_off = c.take(sizeof(BvHeader));
+    L.nodes_off = c.take(64 * ni);
+    L.tris_off = c.take(48 * (size_t)nf);
+    L.pint_off = c.take(4 * ni);
+    L.pleaf_off = c.take(4 * (size_t)nf);
+    L.cnt_off = c.take(4 * ni);
+    L.bytes = c.off;
     return L;
-}
-
-inline unsigned bv_grid(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
-inline bool bv_faces_ok(int64_t n_verts, int64_t n_faces) {
-    return n_verts >= 0 && n_faces > 0 && n_faces < 0x7fffffffLL && n_verts <= 0x7fffffffLL;
 }
 
 }  // namespace iron

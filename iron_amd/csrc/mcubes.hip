@@ -7,40 +7,25 @@
 // One thread per lattice point p, 256-point blocks over the linear index (z fastest: a wave reads 64 consecutive floats):
 //   k_mc_count     cube index of the cell at p (0 when p is on a max face) -> cube[p]; crossed owned edges -> emask[p];
 //                  per-block (vertices, triangles) -> sums[block]
-//   k_mc_scan      exclusive scan of the block sums, 1024 per block, totals one level up; repeated until one entry is left
-//                  (kernel boundaries make every level visible to the next on all XCDs), then k_mc_add_down spreads the
-//                  higher-level offsets back
+//   pair_scan      exclusive scan of the block sums over all blocks, the totals on the top level (pair_scan.h)
 //   k_mc_verts     in-block scan of popc(emask) -> vbase[p] and the vertex positions
 //   k_mc_tris      in-block scan of the triangle counts; each active cell looks its edges' vertices up in vbase / emask
 // emit reads only the crossing pattern the count left in the workspace, so every index it writes is below the counted totals.
-#include "iron_common.h"
 #include "mc_table.h"
+#include "pair_scan.h"
 
 namespace iron {
 
 constexpr int kMcBlock = 256;
-constexpr int kMcScanBlock = 1024;
 static_assert(sizeof(kMcTriEdges[0]) == 3 * kMcMaxTris, "table rows are sized to the generator's maximum");
 
-struct McSum {
-    int64_t v, t;
-};
+// block sums and their prefixes are Pair64 (pair_scan.h): a = vertices, b = triangles
 
 __device__ __forceinline__ int wave_incl_scan(int x) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int64_t wave_incl_scan64(int64_t x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t y = __shfl_up(x, d, 64);
         if (lane >= d) x += y;
     }
     return x;
@@ -68,7 +53,7 @@ __device__ __forceinline__ void block_excl_scan2(int& a, int& b, int* ta, int* t
 __device__ __forceinline__ bool above(float x, float thr) { return x > thr; }  // NaN: false
 
 __global__ __launch_bounds__(kMcBlock) void k_mc_count(const float* __restrict__ u, int nx, int ny, int nz, float thr,
-                                                       uint8_t* __restrict__ cube, uint8_t* __restrict__ emask, McSum* __restrict__ sums,
+                                                       uint8_t* __restrict__ cube, uint8_t* __restrict__ emask, Pair64* __restrict__ sums,
                                                        int64_t n) {
     const int64_t p = (int64_t)blockIdx.x * kMcBlock + threadIdx.x;
     const int64_t sy = nz, sx = (int64_t)ny * nz;
@@ -94,34 +79,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_count(const float* __restrict__
     }
     int tv, tt;
     block_excl_scan2(nv, nt, &tv, &tt);
-    if (threadIdx.x == 0) sums[blockIdx.x] = McSum{tv, tt};
-}
-
-// exclusive scan of s[0..n) in place, 1024 entries per block; block totals -> up[blockIdx.x]
-__global__ __launch_bounds__(kMcScanBlock) void k_mc_scan(McSum* __restrict__ s, int64_t n, McSum* __restrict__ up) {
-    __shared__ int64_t wv[kMcScanBlock / 64], wt[kMcScanBlock / 64];
-    const int64_t g = (int64_t)blockIdx.x * kMcScanBlock + threadIdx.x;
-    const McSum x = g < n ? s[g] : McSum{0, 0};
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t iv = wave_incl_scan64(x.v), it = wave_incl_scan64(x.t);
-    if (lane == 63) { wv[w] = iv; wt[w] = it; }
-    __syncthreads();
-    int64_t ov = 0, ot = 0, tv = 0, tt = 0;
-    for (int i = 0; i < kMcScanBlock / 64; ++i) {
-        if (i < w) { ov += wv[i]; ot += wt[i]; }
-        tv += wv[i]; tt += wt[i];
-    }
-    if (g < n) s[g] = McSum{ov + iv - x.v, ot + it - x.t};
-    if (threadIdx.x == 0) up[blockIdx.x] = McSum{tv, tt};
-}
-
-__global__ void k_mc_add_down(McSum* __restrict__ s, int64_t n, const McSum* __restrict__ up) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) {
-        const McSum o = up[g / kMcScanBlock];
-        s[g].v += o.v;
-        s[g].t += o.t;
-    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = Pair64{tv, tt};
 }
 
 __device__ __forceinline__ float edge_t(float u0, float u1, float thr) {
@@ -131,14 +89,14 @@ __device__ __forceinline__ float edge_t(float u0, float u1, float thr) {
 }
 
 __global__ __launch_bounds__(kMcBlock) void k_mc_verts(const float* __restrict__ u, int ny, int nz, float thr,
-                                                       const uint8_t* __restrict__ emask, const McSum* __restrict__ offs,
+                                                       const uint8_t* __restrict__ emask, const Pair64* __restrict__ offs,
                                                        int32_t* __restrict__ vbase, float* __restrict__ verts, int64_t n) {
     const int64_t p = (int64_t)blockIdx.x * kMcBlock + threadIdx.x;
     const int m = p < n ? emask[p] : 0;
     int nv = __popc(m), dummy = 0, tv, tt;
     block_excl_scan2(nv, dummy, &tv, &tt);
     if (p >= n) return;
-    const int64_t base = offs[blockIdx.x].v + nv;
+    const int64_t base = offs[blockIdx.x].a + nv;
     vbase[p] = (int32_t)base;
     if (!m) return;
     const int64_t sy = nz, sx = (int64_t)ny * nz;
@@ -161,7 +119,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_verts(const float* __restrict__
 }
 
 __global__ __launch_bounds__(kMcBlock) void k_mc_tris(int ny, int nz, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ emask,
-                                                      const int32_t* __restrict__ vbase, const McSum* __restrict__ offs,
+                                                      const int32_t* __restrict__ vbase, const Pair64* __restrict__ offs,
                                                       int32_t* __restrict__ tris, int64_t n) {
     const int64_t p = (int64_t)blockIdx.x * kMcBlock + threadIdx.x;
     const int c = p < n ? cube[p] : 0;
@@ -170,7 +128,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_tris(int ny, int nz, const uint
     block_excl_scan2(nt, dummy, &tv, &tt);
     if (p >= n || cnt == 0) return;
     const int64_t sy = nz, sx = (int64_t)ny * nz;
-    int32_t* o = tris + 3 * (offs[blockIdx.x].t + nt);
+    int32_t* o = tris + 3 * (offs[blockIdx.x].b + nt);
     for (int s = 0; s < 3 * cnt; ++s) {
         const int e = kMcTriEdges[c][s], axis = e >> 2;
         const int64_t q = p + kMcEdgeOrigin[e][0] * sx + kMcEdgeOrigin[e][1] * sy + kMcEdgeOrigin[e][2];
@@ -181,34 +139,20 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_tris(int ny, int nz, const uint
 // ---- workspace layout ----
 struct McLayout {
     int64_t n, blocks;
-    int levels;                 // scan levels; level `levels` holds the one total entry
-    int64_t level_len[24];
-    size_t level_off[25];       // byte offsets of the McSum arrays
     size_t cube_off, emask_off, vbase_off, bytes;
+    ScanLevels scan;  // over the block sums
 };
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static McLayout mc_layout(int32_t nx, int32_t ny, int32_t nz) {
     McLayout L{};
     L.n = (int64_t)nx * ny * nz;
     L.blocks = (L.n + kMcBlock - 1) / kMcBlock;
-    size_t off = 0;
-    L.cube_off = off;  off = align256(off + (size_t)L.n);
-    L.emask_off = off; off = align256(off + (size_t)L.n);
-    L.vbase_off = off; off = align256(off + 4 * (size_t)L.n);
-    int64_t len = L.blocks;
-    int lv = 0;
-    for (;;) {
-        L.level_len[lv] = len;
-        L.level_off[lv] = off;
-        off = align256(off + sizeof(McSum) * (size_t)len);
-        if (lv > 0 && len == 1) break;
-        len = (len + kMcScanBlock - 1) / kMcScanBlock;
-        ++lv;
-    }
-    L.levels = lv;
-    L.bytes = off;
+    Carver c;
+    L.cube_off = c.take((size_t)L.n);
+    L.emask_off = c.take((size_t)L.n);
+    L.vbase_off = c.take(4 * (size_t)L.n);
+    L.scan = scan_levels(L.blocks, c);
+    L.bytes = c.off;
     return L;
 }
 
@@ -234,28 +178,17 @@ extern "C" int iron_mc_count(const float* u, int32_t nx, int32_t ny, int32_t nz,
     const McLayout L = mc_layout(nx, ny, nz);
     if (L.blocks > 0x7fffffffLL) return IRON_ERR_RANGE;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    auto level = [&](int l) { return (McSum*)(ws + L.level_off[l]); };
-    hipLaunchKernelGGL(k_mc_count, dim3((unsigned)L.blocks), dim3(kMcBlock), 0, st, u, nx, ny, nz, threshold, (uint8_t*)(ws + L.cube_off),
-                       (uint8_t*)(ws + L.emask_off), level(0), L.n);
-    IRON_HIP_TRY(hipGetLastError());
-    for (int l = 0; l < L.levels; ++l) {
-        hipLaunchKernelGGL(k_mc_scan, dim3((unsigned)L.level_len[l + 1]), dim3(kMcScanBlock), 0, st, level(l), L.level_len[l], level(l + 1));
-        IRON_HIP_TRY(hipGetLastError());
-    }
-    // level `levels - 1` is one block: already global; spread its offsets down
-    for (int l = L.levels - 2; l >= 0; --l) {
-        hipLaunchKernelGGL(k_mc_add_down, dim3((unsigned)((L.level_len[l] + 255) / 256)), dim3(256), 0, st, level(l), L.level_len[l],
-                           level(l + 1));
-        IRON_HIP_TRY(hipGetLastError());
-    }
-    McSum total{0, 0};
-    IRON_HIP_TRY(hipMemcpyAsync(&total, level(L.levels), sizeof(total), hipMemcpyDeviceToHost, st));
+    IRON_LAUNCH(k_mc_count, (unsigned)L.blocks, kMcBlock, st, u, nx, ny, nz, threshold, ws_ptr<uint8_t>(workspace, L.cube_off),
+                ws_ptr<uint8_t>(workspace, L.emask_off), L.scan.level(workspace, 0), L.n);
+    const int rc = pair_scan(L.scan, workspace, st);
+    if (rc != IRON_OK) return rc;
+    Pair64 total{0, 0};
+    IRON_HIP_TRY(hipMemcpyAsync(&total, L.scan.level(workspace, L.scan.levels), sizeof(total), hipMemcpyDeviceToHost, st));
     IRON_HIP_TRY(hipStreamSynchronize(st));
     // vbase and the triangle indices are int32; kernel-side offsets fit int64 either way
-    if (total.v >= 0x7fffffffLL || total.t >= 0x7fffffffLL) return IRON_ERR_RANGE;
-    *n_verts = total.v;
-    *n_tris = total.t;
+    if (total.a >= 0x7fffffffLL || total.b >= 0x7fffffffLL) return IRON_ERR_RANGE;
+    *n_verts = total.a;
+    *n_tris = total.b;
     return IRON_OK;
 }
 
@@ -267,14 +200,11 @@ extern "C" int iron_mc_emit(const float* u, int32_t nx, int32_t ny, int32_t nz, 
     const McLayout L = mc_layout(nx, ny, nz);
     if (L.blocks > 0x7fffffffLL) return IRON_ERR_RANGE;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const McSum* offs = (const McSum*)(ws + L.level_off[0]);
-    const uint8_t* cube = (const uint8_t*)(ws + L.cube_off);
-    const uint8_t* emask = (const uint8_t*)(ws + L.emask_off);
-    int32_t* vbase = (int32_t*)(ws + L.vbase_off);
-    hipLaunchKernelGGL(k_mc_verts, dim3((unsigned)L.blocks), dim3(kMcBlock), 0, st, u, ny, nz, threshold, emask, offs, vbase, verts, L.n);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_mc_tris, dim3((unsigned)L.blocks), dim3(kMcBlock), 0, st, ny, nz, cube, emask, (const int32_t*)vbase, offs, tris, L.n);
-    IRON_HIP_TRY(hipGetLastError());
+    const Pair64* offs = L.scan.level(workspace, 0);
+    const uint8_t* cube = ws_ptr<uint8_t>(workspace, L.cube_off);
+    const uint8_t* emask = ws_ptr<uint8_t>(workspace, L.emask_off);
+    int32_t* vbase = ws_ptr<int32_t>(workspace, L.vbase_off);
+    IRON_LAUNCH(k_mc_verts, (unsigned)L.blocks, kMcBlock, st, u, ny, nz, threshold, emask, offs, vbase, verts, L.n);
+    IRON_LAUNCH(k_mc_tris, (unsigned)L.blocks, kMcBlock, st, ny, nz, cube, emask, (const int32_t*)vbase, offs, tris, L.n);
     return IRON_OK;
 }

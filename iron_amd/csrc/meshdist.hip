@@ -16,7 +16,6 @@
 // Query (iron_point_mesh_distance): one lane per point, depth-first; a child box whose squared-distance lower bound is <= the best
 // so far is visited (so ties are visited), the nearer internal child first, the other pushed on a per-lane stack in LDS.  A face
 // replaces the best when its fp32 distance is smaller, or equal with a smaller face index: the answer does not depend on the tree.
-#include "iron_common.h"
 #include "bvh_common.h"
 
 namespace iron {
@@ -26,7 +25,7 @@ __device__ __forceinline__ bool load_face(const float* __restrict__ v, int64_t n
                                           float3& b, float3& c) {
     const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
     a = b = c = make_float3(0.f, 0.f, 0.f);
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return false;
+    if (!face_in_range(i0, i1, i2, nv)) return false;
     a = ld3(v, i0); b = ld3(v, i1); c = ld3(v, i2);
     if (finite3(a) && finite3(b) && finite3(c)) return true;
     a = b = c = make_float3(0.f, 0.f, 0.f);
@@ -286,17 +285,14 @@ extern "C" int iron_bvh_workspace_bytes(int64_t n_faces, size_t* bytes) {
 
 extern "C" int iron_bvh_keys(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* workspace, uint64_t* keys,
                              void* stream) {
-    if (!bv_faces_ok(n_verts, n_faces) || !verts || !faces || !workspace || !keys) return IRON_ERR_BAD_ARG;
+    if (!mesh_sizes_ok(n_verts, n_faces) || !verts || !faces || !workspace || !keys) return IRON_ERR_BAD_ARG;
     const BvLayout L = bv_layout(n_faces);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    BvHeader* hdr = (BvHeader*)(ws + L.hdr_off);
-    IRON_HIP_TRY(hipMemsetAsync(ws, 0, L.bytes, st));            // padding included: the workspace is a function of the mesh
+    BvHeader* hdr = ws_ptr<BvHeader>(workspace, L.hdr_off);
+    IRON_HIP_TRY(hipMemsetAsync(workspace, 0, L.bytes, st));     // padding included: the workspace is a function of the mesh
     IRON_HIP_TRY(hipMemsetAsync(hdr->lo, 0xff, sizeof(hdr->lo), st));  // min identity of the ordered encoding
-    hipLaunchKernelGGL(k_bvh_bounds, dim3(bv_grid(n_faces, kBvBlock)), dim3(kBvBlock), 0, st, verts, n_verts, faces, n_faces, hdr);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bvh_keys, dim3(bv_grid(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, (const BvHeader*)hdr, keys);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bvh_bounds, blocks_for(n_faces, kBvBlock), kBvBlock, st, verts, n_verts, faces, n_faces, hdr);
+    IRON_LAUNCH(k_bvh_keys, blocks_for(n_faces, 256), 256, st, verts, n_verts, faces, n_faces, (const BvHeader*)hdr, keys);
     return IRON_OK;
 }
 
@@ -304,27 +300,24 @@ extern "C" int iron_bvh_hierarchy(const uint64_t* sorted_keys, int64_t n_faces, 
     if (n_faces <= 0 || n_faces >= 0x7fffffffLL || !sorted_keys || !workspace) return IRON_ERR_BAD_ARG;
     if (n_faces == 1) return IRON_OK;  // the root is the one leaf
     const BvLayout L = bv_layout(n_faces);
-    char* ws = (char*)workspace;
-    hipLaunchKernelGGL(k_bvh_karras, dim3(bv_grid(n_faces - 1, 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, n_faces,
-                       (float4*)(ws + L.nodes_off), (int32_t*)(ws + L.pint_off), (int32_t*)(ws + L.pleaf_off));
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bvh_karras, blocks_for(n_faces - 1, 256), 256, (hipStream_t)stream, sorted_keys, n_faces,
+                ws_ptr<float4>(workspace, L.nodes_off), ws_ptr<int32_t>(workspace, L.pint_off), ws_ptr<int32_t>(workspace, L.pleaf_off));
     return IRON_OK;
 }
 
 extern "C" int iron_bvh_boxes(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const uint64_t* sorted_keys,
                               void* workspace, void* stream) {
-    if (!bv_faces_ok(n_verts, n_faces) || !verts || !faces || !workspace || !sorted_keys) return IRON_ERR_BAD_ARG;
+    if (!mesh_sizes_ok(n_verts, n_faces) || !verts || !faces || !workspace || !sorted_keys) return IRON_ERR_BAD_ARG;
     const BvLayout L = bv_layout(n_faces);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* cnt = (int32_t*)(ws + L.cnt_off);
+    void* ws = workspace;
+    int32_t* cnt = ws_ptr<int32_t>(ws, L.cnt_off);
     IRON_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * (size_t)(n_faces > 1 ? n_faces - 1 : 1), st));  // the arrival counters
-    hipLaunchKernelGGL(k_bvh_refit, dim3(bv_grid(n_faces, kBvBlock)), dim3(kBvBlock), 0, st, verts, n_verts, faces, sorted_keys, n_faces,
-                       (float4*)(ws + L.nodes_off), (const int32_t*)(ws + L.pint_off), (const int32_t*)(ws + L.pleaf_off), cnt,
-                       (float4*)(ws + L.tris_off));
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bvh_refit, blocks_for(n_faces, kBvBlock), kBvBlock, st, verts, n_verts, faces, sorted_keys, n_faces,
+                ws_ptr<float4>(ws, L.nodes_off), ws_ptr<int32_t>(ws, L.pint_off), ws_ptr<int32_t>(ws, L.pleaf_off), cnt,
+                ws_ptr<float4>(ws, L.tris_off));
     int32_t bad = 0;
-    IRON_HIP_TRY(hipMemcpyAsync(&bad, &((BvHeader*)(ws + L.hdr_off))->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+    IRON_HIP_TRY(hipMemcpyAsync(&bad, &ws_ptr<BvHeader>(ws, L.hdr_off)->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
     IRON_HIP_TRY(hipStreamSynchronize(st));
     return bad ? IRON_ERR_BAD_ARG : IRON_OK;
 }
@@ -335,10 +328,8 @@ extern "C" int iron_point_mesh_distance(const void* workspace, int64_t n_faces, 
     if (n_points == 0) return IRON_OK;
     if (!points || !sqr_dist || !face_idx || !closest) return IRON_ERR_BAD_ARG;
     const BvLayout L = bv_layout(n_faces);
-    const char* ws = (const char*)workspace;
-    hipLaunchKernelGGL(k_bvh_query, dim3(bv_grid(n_points, kBvQueryBlock)), dim3(kBvQueryBlock), 0, (hipStream_t)stream,
-                       (const float4*)(ws + L.nodes_off), (const float4*)(ws + L.tris_off), n_faces, points, n_points, sqr_dist, face_idx,
-                       closest);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bvh_query, blocks_for(n_points, kBvQueryBlock), kBvQueryBlock, (hipStream_t)stream,
+                ws_ptr<float4>(workspace, L.nodes_off), ws_ptr<float4>(workspace, L.tris_off), n_faces, points, n_points, sqr_dist,
+                face_idx, closest);
     return IRON_OK;
 }

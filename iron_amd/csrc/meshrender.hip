@@ -16,7 +16,6 @@
 //   visits the box.  A box whose entry equals the best t is visited.
 //   A face replaces the best when its t is smaller, or equal with a smaller face index: for a fixed ray, t is a function of the
 //   set of faces, not of their order or of the tree.
-#include "iron_common.h"
 #include "bvh_common.h"
 #include "ggx_core.h"
 
@@ -186,8 +185,7 @@ constexpr double kVnScale = 1099511627776.0;  // 2^40: up to 2^22 faces around o
 __device__ __forceinline__ bool vn_face(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t f, int32_t idx[3],
                                         double c[3]) {
     idx[0] = faces[3 * f]; idx[1] = faces[3 * f + 1]; idx[2] = faces[3 * f + 2];
-    for (int k = 0; k < 3; ++k)
-        if (idx[k] < 0 || idx[k] >= nv) return false;
+    if (!face_in_range(idx, nv)) return false;
     const float3 a = ld3(v, idx[0]), b = ld3(v, idx[1]), q = ld3(v, idx[2]);
     const double ex = (double)b.x - (double)a.x, ey = (double)b.y - (double)a.y, ez = (double)b.z - (double)a.z;
     const double gx = (double)q.x - (double)a.x, gy = (double)q.y - (double)a.y, gz = (double)q.z - (double)a.z;
@@ -385,11 +383,8 @@ extern "C" int iron_mesh_raycast(const void* workspace, int64_t n_faces, const f
     if (n_rays == 0) return IRON_OK;
     if (!ray_o || !ray_d || !t || !face_idx || !bary) return IRON_ERR_BAD_ARG;
     const BvLayout L = bv_layout(n_faces);
-    const char* ws = (const char*)workspace;
-    hipLaunchKernelGGL(k_raycast, dim3(bv_grid(n_rays, kBvQueryBlock)), dim3(kBvQueryBlock), 0, (hipStream_t)stream,
-                       (const float4*)(ws + L.nodes_off), (const float4*)(ws + L.tris_off), n_faces, ray_o, ray_d, n_rays, t_min, t_max, t,
-                       face_idx, bary);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_raycast, blocks_for(n_rays, kBvQueryBlock), kBvQueryBlock, (hipStream_t)stream, ws_ptr<float4>(workspace, L.nodes_off),
+                ws_ptr<float4>(workspace, L.tris_off), n_faces, ray_o, ray_d, n_rays, t_min, t_max, t, face_idx, bary);
     return IRON_OK;
 }
 
@@ -405,12 +400,12 @@ extern "C" int iron_mesh_vertex_normals(const float* verts, int64_t n_verts, con
     unsigned long long* vmax = (unsigned long long*)(buf + acc_bytes);
     hipError_t e = hipMemsetAsync(buf, 0, acc_bytes + 256, st);
     if (e == hipSuccess && n_faces > 0) {
-        hipLaunchKernelGGL(k_vn_max, dim3(bv_grid(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, vmax);
-        hipLaunchKernelGGL(k_vn_add, dim3(bv_grid(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, (const unsigned long long*)vmax,
+        hipLaunchKernelGGL(k_vn_max, dim3(blocks_for(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, vmax);
+        hipLaunchKernelGGL(k_vn_add, dim3(blocks_for(n_faces, 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, (const unsigned long long*)vmax,
                            (unsigned long long*)buf);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_vn_finish, dim3(bv_grid(n_verts, 256)), dim3(256), 0, st, (const long long*)buf, n_verts, normals);
+        hipLaunchKernelGGL(k_vn_finish, dim3(blocks_for(n_verts, 256)), dim3(256), 0, st, (const long long*)buf, n_verts, normals);
         e = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(st);  // the accumulator is released below
@@ -426,9 +421,7 @@ extern "C" int iron_texture_fetch(const float* tex, const float* weight, int32_t
     if (mode != IRON_TEX_BILINEAR && mode != IRON_TEX_NEAREST) return IRON_ERR_BAD_ARG;
     if (n == 0) return IRON_OK;
     if (!tex || !uv || !values) return IRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_texture_fetch, dim3(bv_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, tex, weight, H, W, C, uv, n, mode, values,
-                       hole);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_texture_fetch, blocks_for(n, 256), 256, (hipStream_t)stream, tex, weight, H, W, C, uv, n, mode, values, hole);
     return IRON_OK;
 }
 
@@ -446,7 +439,6 @@ extern "C" int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, co
     a.m = *mesh; a.o = *out;
     a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.ray_o = ray_o; a.ray_d = ray_d; a.t = t; a.bary = bary; a.face_idx = face_idx;
     a.light = light; a.n = n_rays;
-    hipLaunchKernelGGL(k_asset_shade, dim3(bv_grid(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_asset_shade, blocks_for(n_rays, 256), 256, (hipStream_t)stream, a);
     return IRON_OK;
 }

@@ -5,8 +5,8 @@
 //   k_bake_area     fp32 area |cross(v0 - v2, v1 - v2)| -> area[f]; fp64 partial sums per block -> part[b]
 //   k_bake_sum      one block sums the partials in a fixed order -> the normaliser (rounded to fp32 like the reference's sum)
 //   k_bake_count    cnt[f] = ceil(n * (area / sum)) in fp32; pair[f] = (cnt, cnt > 0)
-//   scan            exclusive scan of the pairs (1024 per block, block totals one level up, then spread down); the top level
-//                   holds the totals: sum(cnt) and the number of faces with a sample
+//   pair_scan       exclusive scan of the pairs (pair_scan.h); the top level holds the totals: sum(cnt) and the number of faces
+//                   with a sample
 //   k_bake_compact  list of the faces with cnt > 0 (the reference's np.where(cnt > 0))
 //   k_bake_draw     floor_num = sum(cnt) - n draws with replacement among them (Philox, stream 0), each setting an idempotent flag
 //                   on its face: a face drawn twice loses one sample, like numpy's `cnt[idx] -= 1`
@@ -17,18 +17,14 @@
 // (C + 1) int64.  The taps follow the reference's fp32 arithmetic; every term is w * value in fp64, rounded to an integer number
 // of 2^-24 units; integer adds are associative, so the accumulator is the same whatever order the atomics land in.
 // Resolve (iron_bake_resolve): fp32 texel values and acc / (w + 1e-10) in fp32, like the reference's float32 images.
-#include "iron_common.h"
+#include "mesh_common.h"
+#include "pair_scan.h"
 
 namespace iron {
 
 constexpr int kBkBlock = 256;
-constexpr int kBkScanBlock = 1024;
 constexpr double kBkScale = 16777216.0;  // 2^24 fixed-point units per 1.0
 constexpr int kBkLanes = 16;             // lanes per sample in the splat
-
-struct BkPair {
-    int64_t a, b;
-};
 
 // ---- Philox4x32-10 (Salmon et al., SC'11), counter (index lo, index hi, round, stream), key = seed ----
 __device__ __forceinline__ uint4 philox(uint64_t seed, uint64_t index, uint32_t round, uint32_t stream) {
@@ -50,20 +46,6 @@ __device__ __forceinline__ double unit53(uint32_t lo, uint32_t hi) {  // [0, 1) 
     return (double)(x >> 11) * 0x1.0p-53;
 }
 
-__device__ __forceinline__ int64_t wave_incl_scan64(int64_t x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
-__device__ __forceinline__ bool face_ok(const int32_t* f, int64_t n) {
-    return f[0] >= 0 && f[1] >= 0 && f[2] >= 0 && f[0] < n && f[1] < n && f[2] < n;
-}
-
 __global__ __launch_bounds__(kBkBlock) void k_bake_area(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces,
                                                         const int32_t* __restrict__ fuv, int64_t nuv, int64_t nf,
                                                         float* __restrict__ area, double* __restrict__ part, int32_t* __restrict__ bad) {
@@ -72,7 +54,7 @@ __global__ __launch_bounds__(kBkBlock) void k_bake_area(const float* __restrict_
     float a = 0.0f;
     if (f < nf) {
         const int32_t* t = faces + 3 * f;
-        if (face_ok(t, nv) && face_ok(fuv + 3 * f, nuv)) {
+        if (face_in_range(t, nv) && face_in_range(fuv + 3 * f, nuv)) {
             const float* p0 = v + 3 * (int64_t)t[0];
             const float* p1 = v + 3 * (int64_t)t[1];
             const float* p2 = v + 3 * (int64_t)t[2];
@@ -109,7 +91,7 @@ __global__ __launch_bounds__(1024) void k_bake_sum(const double* __restrict__ pa
 }
 
 __global__ void k_bake_count(const float* __restrict__ area, const float* __restrict__ sum, int64_t nf, float n_samples,
-                             int32_t* __restrict__ cnt, BkPair* __restrict__ pair) {
+                             int32_t* __restrict__ cnt, Pair64* __restrict__ pair) {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nf) return;
     const float s = *sum;
@@ -119,37 +101,10 @@ __global__ void k_bake_count(const float* __restrict__ area, const float* __rest
         c = x > 0.0f ? (int32_t)x : 0;
     }
     cnt[f] = c;
-    pair[f] = BkPair{c, c > 0 ? 1 : 0};
+    pair[f] = Pair64{c, c > 0 ? 1 : 0};
 }
 
-// exclusive scan of s[0..n) in place, kBkScanBlock entries per block; block totals -> up[blockIdx.x]
-__global__ __launch_bounds__(kBkScanBlock) void k_bake_scan(BkPair* __restrict__ s, int64_t n, BkPair* __restrict__ up) {
-    __shared__ int64_t wa[kBkScanBlock / 64], wb[kBkScanBlock / 64];
-    const int64_t g = (int64_t)blockIdx.x * kBkScanBlock + threadIdx.x;
-    const BkPair x = g < n ? s[g] : BkPair{0, 0};
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t ia = wave_incl_scan64(x.a), ib = wave_incl_scan64(x.b);
-    if (lane == 63) { wa[w] = ia; wb[w] = ib; }
-    __syncthreads();
-    int64_t oa = 0, ob = 0, ta = 0, tb = 0;
-    for (int i = 0; i < kBkScanBlock / 64; ++i) {
-        if (i < w) { oa += wa[i]; ob += wb[i]; }
-        ta += wa[i]; tb += wb[i];
-    }
-    if (g < n) s[g] = BkPair{oa + ia - x.a, ob + ib - x.b};
-    if (threadIdx.x == 0) up[blockIdx.x] = BkPair{ta, tb};
-}
-
-__global__ void k_bake_add_down(BkPair* __restrict__ s, int64_t n, const BkPair* __restrict__ up) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) {
-        const BkPair o = up[g / kBkScanBlock];
-        s[g].a += o.a;
-        s[g].b += o.b;
-    }
-}
-
-__global__ void k_bake_compact(const int32_t* __restrict__ cnt, const BkPair* __restrict__ pair, int64_t nf, int32_t* __restrict__ pos,
+__global__ void k_bake_compact(const int32_t* __restrict__ cnt, const Pair64* __restrict__ pair, int64_t nf, int32_t* __restrict__ pos,
                                uint8_t* __restrict__ flag) {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nf) return;
@@ -157,7 +112,7 @@ __global__ void k_bake_compact(const int32_t* __restrict__ cnt, const BkPair* __
     if (cnt[f] > 0) pos[pair[f].b] = (int32_t)f;
 }
 
-__global__ void k_bake_draw(const int32_t* __restrict__ pos, const BkPair* __restrict__ tot, int64_t n_samples, uint64_t seed,
+__global__ void k_bake_draw(const int32_t* __restrict__ pos, const Pair64* __restrict__ tot, int64_t n_samples, uint64_t seed,
                             uint32_t round, uint8_t* __restrict__ flag) {
     const int64_t floor_num = tot->a - n_samples, n_pos = tot->b;
     if (n_pos <= 0) return;
@@ -169,12 +124,12 @@ __global__ void k_bake_draw(const int32_t* __restrict__ pos, const BkPair* __res
     }
 }
 
-__global__ void k_bake_sub(int32_t* __restrict__ cnt, const uint8_t* __restrict__ flag, int64_t nf, BkPair* __restrict__ pair) {
+__global__ void k_bake_sub(int32_t* __restrict__ cnt, const uint8_t* __restrict__ flag, int64_t nf, Pair64* __restrict__ pair) {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nf) return;
     const int32_t c = cnt[f] - (int32_t)flag[f];
     cnt[f] = c;
-    pair[f] = BkPair{c, 0};
+    pair[f] = Pair64{c, 0};
 }
 
 // P = (1 - sqrt(r1)) A + sqrt(r1) (1 - r2) B + sqrt(r1) r2 C in the reference's fp64 order, rounded to fp32
@@ -195,7 +150,7 @@ __device__ __forceinline__ void emit_sample(const float* __restrict__ v, const i
 }
 
 __global__ void k_bake_sample(const float* __restrict__ v, const int32_t* __restrict__ faces, const float* __restrict__ uvs,
-                              const int32_t* __restrict__ fuv, const BkPair* __restrict__ offs, int64_t nf, int64_t total, uint64_t seed,
+                              const int32_t* __restrict__ fuv, const Pair64* __restrict__ offs, int64_t nf, int64_t total, uint64_t seed,
                               uint32_t round, float* __restrict__ pts, float* __restrict__ uv, int32_t* __restrict__ face_out) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= total) return;
@@ -217,7 +172,7 @@ __global__ void k_bake_sample_explicit(const float* __restrict__ v, int64_t nv, 
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const int64_t f = face_idx[s];
-    if (f < 0 || f >= nf || !face_ok(faces + 3 * f, nv) || !face_ok(fuv + 3 * f, nuv)) {
+    if (f < 0 || f >= nf || !face_in_range(faces + 3 * f, nv) || !face_in_range(fuv + 3 * f, nuv)) {
         const float q = __builtin_nanf("");
         pts[3 * s] = pts[3 * s + 1] = pts[3 * s + 2] = q;
         uv[2 * s] = uv[2 * s + 1] = q;
@@ -281,56 +236,26 @@ __global__ void k_bake_resolve(const long long* __restrict__ acc, int32_t c, int
 // ---- workspace layout ----
 struct BkLayout {
     int64_t nf, blocks;
-    int levels;
-    int64_t level_len[24];
-    size_t level_off[25];
     size_t area_off, cnt_off, pos_off, flag_off, part_off, sum_off, bad_off, bytes;
+    ScanLevels scan;  // over the per-face pairs
 };
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static BkLayout bk_layout(int64_t nf) {
     BkLayout L{};
     L.nf = nf;
     L.blocks = (nf + kBkBlock - 1) / kBkBlock;
-    size_t off = 0;
-    L.area_off = off; off = align256(off + 4 * (size_t)nf);
-    L.cnt_off = off;  off = align256(off + 4 * (size_t)nf);
-    L.pos_off = off;  off = align256(off + 4 * (size_t)nf);
-    L.flag_off = off; off = align256(off + (size_t)nf);
-    L.part_off = off; off = align256(off + 8 * (size_t)L.blocks);
-    L.sum_off = off;  off = align256(off + 8);
-    L.bad_off = off;  off = align256(off + 8);
-    int64_t len = nf;
-    int lv = 0;
-    for (;;) {
-        L.level_len[lv] = len;
-        L.level_off[lv] = off;
-        off = align256(off + sizeof(BkPair) * (size_t)len);
-        if (lv > 0 && len == 1) break;
-        len = (len + kBkScanBlock - 1) / kBkScanBlock;
-        ++lv;
-    }
-    L.levels = lv;
-    L.bytes = off;
+    Carver c;
+    L.area_off = c.take(4 * (size_t)nf);
+    L.cnt_off = c.take(4 * (size_t)nf);
+    L.pos_off = c.take(4 * (size_t)nf);
+    L.flag_off = c.take((size_t)nf);
+    L.part_off = c.take(8 * (size_t)L.blocks);
+    L.sum_off = c.take(8);
+    L.bad_off = c.take(8);
+    L.scan = scan_levels(nf, c);
+    L.bytes = c.off;
     return L;
 }
-
-static int bk_scan(const BkLayout& L, char* ws, hipStream_t st) {
-    auto level = [&](int l) { return (BkPair*)(ws + L.level_off[l]); };
-    for (int l = 0; l < L.levels; ++l) {
-        hipLaunchKernelGGL(k_bake_scan, dim3((unsigned)L.level_len[l + 1]), dim3(kBkScanBlock), 0, st, level(l), L.level_len[l], level(l + 1));
-        IRON_HIP_TRY(hipGetLastError());
-    }
-    for (int l = L.levels - 2; l >= 0; --l) {
-        hipLaunchKernelGGL(k_bake_add_down, dim3((unsigned)((L.level_len[l] + 255) / 256)), dim3(256), 0, st, level(l), L.level_len[l],
-                           level(l + 1));
-        IRON_HIP_TRY(hipGetLastError());
-    }
-    return IRON_OK;
-}
-
-static inline unsigned grid(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace iron
 
@@ -353,38 +278,32 @@ extern "C" int iron_bake_count(const float* verts, int64_t n_verts, const int32_
     if (n_samples > (1LL << 24) || n_faces >= 0x7fffffffLL) return IRON_ERR_RANGE;
     const BkLayout L = bk_layout(n_faces);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* area = (float*)(ws + L.area_off);
-    int32_t* cnt = (int32_t*)(ws + L.cnt_off);
-    int32_t* pos = (int32_t*)(ws + L.pos_off);
-    uint8_t* flag = (uint8_t*)(ws + L.flag_off);
-    double* part = (double*)(ws + L.part_off);
-    float* sum = (float*)(ws + L.sum_off);
-    int32_t* bad = (int32_t*)(ws + L.bad_off);
-    BkPair* pair = (BkPair*)(ws + L.level_off[0]);
-    const BkPair* tot = (const BkPair*)(ws + L.level_off[L.levels]);
+    void* ws = workspace;
+    float* area = ws_ptr<float>(ws, L.area_off);
+    int32_t* cnt = ws_ptr<int32_t>(ws, L.cnt_off);
+    int32_t* pos = ws_ptr<int32_t>(ws, L.pos_off);
+    uint8_t* flag = ws_ptr<uint8_t>(ws, L.flag_off);
+    double* part = ws_ptr<double>(ws, L.part_off);
+    float* sum = ws_ptr<float>(ws, L.sum_off);
+    int32_t* bad = ws_ptr<int32_t>(ws, L.bad_off);
+    Pair64* pair = L.scan.level(ws, 0);
+    const Pair64* tot = L.scan.level(ws, L.scan.levels);
+    const unsigned grid = blocks_for(n_faces, 256);
     IRON_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_bake_area, dim3((unsigned)L.blocks), dim3(kBkBlock), 0, st, verts, n_verts, faces, face_uvs, n_uvs, n_faces, area, part, bad);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bake_sum, dim3(1), dim3(1024), 0, st, (const double*)part, L.blocks, sum);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bake_count, dim3(grid(n_faces, 256)), dim3(256), 0, st, (const float*)area, (const float*)sum, n_faces,
-                       (float)n_samples, cnt, pair);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bake_area, (unsigned)L.blocks, kBkBlock, st, verts, n_verts, faces, face_uvs, n_uvs, n_faces, area, part, bad);
+    IRON_LAUNCH(k_bake_sum, 1, 1024, st, (const double*)part, L.blocks, sum);
+    IRON_LAUNCH(k_bake_count, grid, 256, st, (const float*)area, (const float*)sum, n_faces, (float)n_samples, cnt, pair);
     if (ceil_counts) IRON_HIP_TRY(hipMemcpyAsync(ceil_counts, cnt, 4 * (size_t)n_faces, hipMemcpyDeviceToDevice, st));
-    int rc = bk_scan(L, ws, st);
+    int rc = pair_scan(L.scan, ws, st);
     if (rc != IRON_OK) return rc;
-    hipLaunchKernelGGL(k_bake_compact, dim3(grid(n_faces, 256)), dim3(256), 0, st, (const int32_t*)cnt, (const BkPair*)pair, n_faces, pos, flag);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bake_draw, dim3(grid(n_faces, 256)), dim3(256), 0, st, (const int32_t*)pos, tot, n_samples, seed, round, flag);
-    IRON_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bake_sub, dim3(grid(n_faces, 256)), dim3(256), 0, st, cnt, (const uint8_t*)flag, n_faces, pair);
-    IRON_HIP_TRY(hipGetLastError());
-    rc = bk_scan(L, ws, st);
+    IRON_LAUNCH(k_bake_compact, grid, 256, st, (const int32_t*)cnt, (const Pair64*)pair, n_faces, pos, flag);
+    IRON_LAUNCH(k_bake_draw, grid, 256, st, (const int32_t*)pos, tot, n_samples, seed, round, flag);
+    IRON_LAUNCH(k_bake_sub, grid, 256, st, cnt, (const uint8_t*)flag, n_faces, pair);
+    rc = pair_scan(L.scan, ws, st);
     if (rc != IRON_OK) return rc;
     if (counts) IRON_HIP_TRY(hipMemcpyAsync(counts, cnt, 4 * (size_t)n_faces, hipMemcpyDeviceToDevice, st));
-    struct { BkPair t; int32_t bad; } host{};
-    IRON_HIP_TRY(hipMemcpyAsync(&host.t, tot, sizeof(BkPair), hipMemcpyDeviceToHost, st));
+    struct { Pair64 t; int32_t bad; } host{};
+    IRON_HIP_TRY(hipMemcpyAsync(&host.t, tot, sizeof(Pair64), hipMemcpyDeviceToHost, st));
     IRON_HIP_TRY(hipMemcpyAsync(&host.bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     IRON_HIP_TRY(hipStreamSynchronize(st));
     if (host.bad) return IRON_ERR_BAD_ARG;
@@ -400,10 +319,8 @@ extern "C" int iron_bake_sample(const float* verts, const int32_t* faces, const 
     if (!verts || !faces || !uvs || !face_uvs || !workspace || !points || !uv || n_faces == 0) return IRON_ERR_BAD_ARG;
     const BkLayout L = bk_layout(n_faces);
     hipStream_t st = (hipStream_t)stream;
-    const BkPair* offs = (const BkPair*)((const char*)workspace + L.level_off[0]);
-    hipLaunchKernelGGL(k_bake_sample, dim3(grid(n_total, 256)), dim3(256), 0, st, verts, faces, uvs, face_uvs, offs, n_faces, n_total, seed,
-                       round, points, uv, face_idx);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bake_sample, blocks_for(n_total, 256), 256, st, verts, faces, uvs, face_uvs, L.scan.level(workspace, 0), n_faces, n_total,
+                seed, round, points, uv, face_idx);
     return IRON_OK;
 }
 
@@ -414,9 +331,8 @@ extern "C" int iron_bake_sample_explicit(const float* verts, int64_t n_verts, co
     if (n == 0) return IRON_OK;
     if (!verts || !faces || !uvs || !face_uvs || !face_idx || !r1 || !r2 || !points || !uv) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_bake_sample_explicit, dim3(grid(n, 256)), dim3(256), 0, st, verts, n_verts, faces, uvs, n_uvs, face_uvs, n_faces,
-                       face_idx, r1, r2, n, points, uv);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bake_sample_explicit, blocks_for(n, 256), 256, st, verts, n_verts, faces, uvs, n_uvs, face_uvs, n_faces, face_idx, r1, r2,
+                n, points, uv);
     return IRON_OK;
 }
 
@@ -428,9 +344,8 @@ extern "C" int iron_bake_splat(const float* uv, const float* values_a, int32_t c
     if (!uv || !acc || !flag || (c_a && !values_a) || (c_b && !values_b)) return IRON_ERR_BAD_ARG;
     if (n > (int64_t)0x7fffffff * 256 / kBkLanes) return IRON_ERR_RANGE;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_bake_splat, dim3(grid(n * kBkLanes, 256)), dim3(256), 0, st, uv, values_a, c_a, values_b, c_b, n, H, W,
-                       (double)term_bound, (unsigned long long*)acc, flag);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bake_splat, blocks_for(n * kBkLanes, 256), 256, st, uv, values_a, c_a, values_b, c_b, n, H, W, (double)term_bound,
+                (unsigned long long*)acc, flag);
     return IRON_OK;
 }
 
@@ -439,8 +354,7 @@ extern "C" int iron_bake_resolve(const int64_t* acc, int32_t c, int32_t H, int32
     if (H <= 0 || W <= 0 || c < 0 || c > 16 || !acc || !flag || !weight || (c && !out)) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nt = (int64_t)H * W;
-    hipLaunchKernelGGL(k_bake_resolve, dim3(grid(nt, 256)), dim3(256), 0, st, (const long long*)acc, c, nt, out, weight);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_bake_resolve, blocks_for(nt, 256), 256, st, (const long long*)acc, c, nt, out, weight);
     int32_t f = 0;
     IRON_HIP_TRY(hipMemcpyAsync(&f, flag, sizeof(f), hipMemcpyDeviceToHost, st));
     IRON_HIP_TRY(hipStreamSynchronize(st));

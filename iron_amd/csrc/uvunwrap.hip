@@ -32,7 +32,8 @@
 //   iron_uv_apply  k_uv_apply  one thread per vt: rotate, subtract the box minimum, offset, scale, clamp to [0, 1].
 #include <cstring>
 
-#include "iron_common.h"
+#include "host_util.h"
+#include "mesh_common.h"
 
 namespace iron {
 
@@ -46,12 +47,6 @@ struct UvState {
     int32_t changed;  // a hook round found two roots
 };
 
-__device__ __forceinline__ uint32_t uv_f2ord(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float uv_ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
 __device__ __forceinline__ float uv_dot(float ax, float ay, float az, const float* __restrict__ p) {
     return ax * p[0] + ay * p[1] + az * p[2];
 }
@@ -60,9 +55,8 @@ __device__ __forceinline__ float uv_dot(float ax, float ay, float az, const floa
 __device__ __forceinline__ bool uv_face(const float* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t f, int32_t* idx,
                                         float* p) {
     idx[0] = faces[3 * f]; idx[1] = faces[3 * f + 1]; idx[2] = faces[3 * f + 2];
+    if (!face_in_range(idx, nv)) return false;
     bool ok = true;
-    for (int c = 0; c < 3; ++c) ok = ok && idx[c] >= 0 && idx[c] < nv;
-    if (!ok) return false;
     for (int c = 0; c < 3; ++c)
         for (int d = 0; d < 3; ++d) {
             p[3 * c + d] = v[3 * (int64_t)idx[c] + d];
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(kUvBlock) void k_uv_geometry(const float* __restric
         }
         normals[3 * f] = nx; normals[3 * f + 1] = ny; normals[3 * f + 2] = nz;
         area[f] = a;
-        key = ((uint64_t)uv_f2ord(-a) << 32) | (uint64_t)f;
+        key = ((uint64_t)f2ord(-a) << 32) | (uint64_t)f;
     }
     block_min_u64(key, &st->best);
 }
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(kUvBlock) void k_uv_farthest(const float* __restric
         const float d = uv_dot(normals[3 * f], normals[3 * f + 1], normals[3 * f + 2], P + 3 * k);
         const float m = k == 0 ? d : fmaxf(runmax[f], d);
         runmax[f] = m;
-        key = ((uint64_t)uv_f2ord(m) << 32) | (uint64_t)f;
+        key = ((uint64_t)f2ord(m) << 32) | (uint64_t)f;
     }
     block_min_u64(key, &st->best);
 }
@@ -281,7 +275,7 @@ __global__ __launch_bounds__(kUvBlock) void k_uv_rot_boxes(const float* __restri
     for (int32_t a = 0; a < n_angles; ++a) {
         const float c = tab[2 * a], s = tab[2 * a + 1];
         const float xr = x * c - y * s, yr = x * s + y * c;
-        uint32_t w[4] = {uv_f2ord(-xr), uv_f2ord(-yr), uv_f2ord(xr), uv_f2ord(yr)};
+        uint32_t w[4] = {f2ord(-xr), f2ord(-yr), f2ord(xr), f2ord(yr)};
         uint32_t* dst = boxes + 4 * ((int64_t)me * n_angles + a);
         if (uniform) {
             if (!valid) { w[0] = w[1] = w[2] = w[3] = 0u; }
@@ -319,23 +313,16 @@ struct UvLayout {
     size_t normals_off, area_off, tag_off, runmax_off, partial_off, bytes;
 };
 
-static inline size_t uv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline unsigned uv_grid(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
 static UvLayout uv_layout(int64_t nf) {
     UvLayout L{};
-    size_t off = 0;
-    L.normals_off = off; off = uv_align(off + 12 * (size_t)nf);
-    L.area_off = off;    off = uv_align(off + 4 * (size_t)nf);
-    L.tag_off = off;     off = uv_align(off + 4 * (size_t)nf);
-    L.runmax_off = off;  off = uv_align(off + 4 * (size_t)nf);
-    L.partial_off = off; off = uv_align(off + 12 * (size_t)uv_grid(nf, kUvBlock));
-    L.bytes = off;
+    Carver c;
+    L.normals_off = c.take(12 * (size_t)nf);
+    L.area_off = c.take(4 * (size_t)nf);
+    L.tag_off = c.take(4 * (size_t)nf);
+    L.runmax_off = c.take(4 * (size_t)nf);
+    L.partial_off = c.take(12 * (size_t)blocks_for(nf, kUvBlock));
+    L.bytes = c.off;
     return L;
-}
-
-static inline bool uv_sizes_ok(int64_t n_verts, int64_t n_faces) {
-    return n_verts >= 0 && n_faces > 0 && n_faces < 0x7fffffffLL && n_verts <= 0x7fffffffLL;
 }
 
 static int uv_read_state(UvState* st, UvState* host, hipStream_t s) {
@@ -350,10 +337,9 @@ using namespace iron;
 
 extern "C" int iron_mesh_edge_keys(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, uint64_t* keys, void* state,
                                    void* stream) {
-    if (!uv_sizes_ok(n_verts, n_faces) || !verts || !faces || !keys || !state) return IRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_cc_keys, dim3(uv_grid(n_faces, kUvBlock)), dim3(kUvBlock), 0, (hipStream_t)stream, verts, n_verts, faces, n_faces,
-                       keys, (UvState*)state);
-    IRON_HIP_TRY(hipGetLastError());
+    if (!mesh_sizes_ok(n_verts, n_faces) || !verts || !faces || !keys || !state) return IRON_ERR_BAD_ARG;
+    IRON_LAUNCH(k_cc_keys, blocks_for(n_faces, kUvBlock), kUvBlock, (hipStream_t)stream, verts, n_verts, faces, n_faces, keys,
+                (UvState*)state);
     return IRON_OK;
 }
 
@@ -364,16 +350,12 @@ extern "C" int iron_mesh_components(const uint64_t* sorted_keys, const int64_t* 
         return IRON_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     UvState* st = (UvState*)state;
-    hipLaunchKernelGGL(k_cc_init, dim3(uv_grid(n_faces, 256)), dim3(256), 0, s, parent, n_faces);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_cc_init, blocks_for(n_faces, 256), 256, s, parent, n_faces);
     *rounds = 0;
     for (int32_t r = 0; r < max_rounds; ++r) {
         IRON_HIP_TRY(hipMemsetAsync(&st->changed, 0, sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_cc_hook, dim3(uv_grid(n_records, kUvBlock)), dim3(kUvBlock), 0, s, sorted_keys, perm, n_records, group, parent,
-                           st);
-        IRON_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_cc_jump, dim3(uv_grid(n_faces, 256)), dim3(256), 0, s, parent, n_faces);
-        IRON_HIP_TRY(hipGetLastError());
+        IRON_LAUNCH(k_cc_hook, blocks_for(n_records, kUvBlock), kUvBlock, s, sorted_keys, perm, n_records, group, parent, st);
+        IRON_LAUNCH(k_cc_jump, blocks_for(n_faces, 256), 256, s, parent, n_faces);
         UvState h;
         const int e = uv_read_state(st, &h, s);
         if (e != IRON_OK) return e;
@@ -393,37 +375,33 @@ extern "C" int iron_uv_workspace_bytes(int64_t n_faces, size_t* bytes) {
 extern "C" int iron_uv_projections(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, float cos_half,
                                    float cos_limit, int32_t max_normals, void* workspace, void* state, float* normals_out, float* P,
                                    int32_t* group, int32_t* n_normals, int32_t* n_waits, void* stream) {
-    if (!uv_sizes_ok(n_verts, n_faces) || !verts || !faces || !workspace || !state || !P || !group || !n_normals || !n_waits ||
+    if (!mesh_sizes_ok(n_verts, n_faces) || !verts || !faces || !workspace || !state || !P || !group || !n_normals || !n_waits ||
         max_normals < 1)
         return IRON_ERR_BAD_ARG;
     const UvLayout L = uv_layout(n_faces);
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+    void* ws = workspace;
     UvState* st = (UvState*)state;
-    float* nrm = (float*)(ws + L.normals_off);
-    float* area = (float*)(ws + L.area_off);
-    int32_t* tag = (int32_t*)(ws + L.tag_off);
-    float* runmax = (float*)(ws + L.runmax_off);
-    float* partial = (float*)(ws + L.partial_off);
-    const int64_t nblk = uv_grid(n_faces, kUvBlock);
+    float* nrm = ws_ptr<float>(ws, L.normals_off);
+    float* area = ws_ptr<float>(ws, L.area_off);
+    int32_t* tag = ws_ptr<int32_t>(ws, L.tag_off);
+    float* runmax = ws_ptr<float>(ws, L.runmax_off);
+    float* partial = ws_ptr<float>(ws, L.partial_off);
+    const int64_t nblk = blocks_for(n_faces, kUvBlock);
     *n_normals = 0;
     *n_waits = 0;
     IRON_HIP_TRY(hipMemsetAsync(tag, 0xff, 4 * (size_t)n_faces, s));  // -1: untagged
     IRON_HIP_TRY(hipMemsetAsync(&st->best, 0xff, sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_uv_geometry, dim3(nblk), dim3(kUvBlock), 0, s, verts, n_verts, faces, n_faces, nrm, area, st);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_uv_geometry, nblk, kUvBlock, s, verts, n_verts, faces, n_faces, nrm, area, st);
     for (int32_t k = 0;; ++k) {
         if (k == max_normals) return IRON_ERR_RANGE;
         // st->best holds the seed: the largest face for k = 0, the farthest untagged face afterwards
-        hipLaunchKernelGGL(k_uv_cone, dim3(nblk), dim3(kUvBlock), 0, s, (const float*)nrm, (const float*)area, n_faces, (const UvState*)st,
-                           cos_half, k, tag, partial);
-        IRON_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_uv_cone_sum, dim3(1), dim3(kUvBlock), 0, s, (const float*)partial, nblk, k, P);
-        IRON_HIP_TRY(hipGetLastError());
+        IRON_LAUNCH(k_uv_cone, nblk, kUvBlock, s, (const float*)nrm, (const float*)area, n_faces, (const UvState*)st, cos_half, k, tag,
+                    partial);
+        IRON_LAUNCH(k_uv_cone_sum, 1, kUvBlock, s, (const float*)partial, nblk, k, P);
         IRON_HIP_TRY(hipMemsetAsync(&st->best, 0xff, sizeof(uint64_t), s));
-        hipLaunchKernelGGL(k_uv_farthest, dim3(nblk), dim3(kUvBlock), 0, s, (const float*)nrm, (const float*)area, n_faces, (const float*)P,
-                           k, (const int32_t*)tag, runmax, st);
-        IRON_HIP_TRY(hipGetLastError());
+        IRON_LAUNCH(k_uv_farthest, nblk, kUvBlock, s, (const float*)nrm, (const float*)area, n_faces, (const float*)P, k,
+                    (const int32_t*)tag, runmax, st);
         UvState h;
         const int e = uv_read_state(st, &h, s);
         if (e != IRON_OK) return e;
@@ -437,9 +415,8 @@ extern "C" int iron_uv_projections(const float* verts, int64_t n_verts, const in
         memcpy(&m, &u, sizeof(m));
         if (m >= cos_limit) break;
     }
-    hipLaunchKernelGGL(k_uv_assign, dim3(uv_grid(n_faces, 256)), dim3(256), 0, s, (const float*)nrm, (const float*)area, n_faces,
-                       (const float*)P, *n_normals, group);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_uv_assign, blocks_for(n_faces, 256), 256, s, (const float*)nrm, (const float*)area, n_faces, (const float*)P, *n_normals,
+                group);
     if (normals_out) IRON_HIP_TRY(hipMemcpyAsync(normals_out, nrm, 12 * (size_t)n_faces, hipMemcpyDeviceToDevice, s));
     return IRON_OK;
 }
@@ -449,9 +426,7 @@ extern "C" int iron_uv_project(const float* verts, const int32_t* vt_vertex, con
     if (n_vt < 0) return IRON_ERR_BAD_ARG;
     if (n_vt == 0) return IRON_OK;
     if (!verts || !vt_vertex || !vt_island || !island_group || !P || !xy) return IRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_uv_project, dim3(uv_grid(n_vt, 256)), dim3(256), 0, (hipStream_t)stream, verts, vt_vertex, vt_island, n_vt,
-                       island_group, P, xy);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_uv_project, blocks_for(n_vt, 256), 256, (hipStream_t)stream, verts, vt_vertex, vt_island, n_vt, island_group, P, xy);
     return IRON_OK;
 }
 
@@ -460,9 +435,7 @@ extern "C" int iron_uv_rotation_search(const float* xy, const int32_t* vt_island
     if (n_vt <= 0 || n_islands <= 0 || n_angles < 1 || !xy || !vt_island || !cs || !boxes) return IRON_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     IRON_HIP_TRY(hipMemsetAsync(boxes, 0, 16 * (size_t)n_islands * (size_t)n_angles, s));
-    hipLaunchKernelGGL(k_uv_rot_boxes, dim3(uv_grid(n_vt, kUvBlock)), dim3(kUvBlock), 0, s, xy, vt_island, n_vt, cs, n_angles, per_island,
-                       boxes);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_uv_rot_boxes, blocks_for(n_vt, kUvBlock), kUvBlock, s, xy, vt_island, n_vt, cs, n_angles, per_island, boxes);
     return IRON_OK;
 }
 
@@ -471,7 +444,6 @@ extern "C" int iron_uv_apply(const float* xy, const int32_t* vt_island, int64_t 
     if (n_vt < 0) return IRON_ERR_BAD_ARG;
     if (n_vt == 0) return IRON_OK;
     if (!xy || !vt_island || !params || !swap || !uv) return IRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_uv_apply, dim3(uv_grid(n_vt, 256)), dim3(256), 0, (hipStream_t)stream, xy, vt_island, n_vt, params, swap, scale, uv);
-    IRON_HIP_TRY(hipGetLastError());
+    IRON_LAUNCH(k_uv_apply, blocks_for(n_vt, 256), 256, (hipStream_t)stream, xy, vt_island, n_vt, params, swap, scale, uv);
     return IRON_OK;
 }

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 # AlexNet's feature stack as LPIPS (net='alex', v0.1) taps it: (Cin, Cout, kernel, stride, padding), the index of the convolution in
 # torchvision's `features` Sequential, and whether a 3x3/2 max-pool follows the tap
@@ -49,10 +49,8 @@ def squared_error_device(pred, trgt) -> torch.Tensor:
     a, b, is_f32 = _pair(pred, trgt, "psnr")
     lib = _lib.load()
     n = a.numel()
-    nb = C.c_size_t(0)
-    _lib.check(lib.iron_img_sqerr_workspace_bytes(n, C.byref(nb)))
     with torch.cuda.device(a.device):
-        ws = _lib.workspace(nb.value, a.device, "img_sqerr")
+        ws = _args.sized_workspace(lib.iron_img_sqerr_workspace_bytes, n, device=a.device, tag="img_sqerr")
         out = torch.empty(2, dtype=torch.float64, device=a.device)
         _lib.check(lib.iron_img_sqerr(a.data_ptr(), b.data_ptr(), n, is_f32, ws.data_ptr(), out.data_ptr(), _lib.stream_ptr(a.device)))
     return out
@@ -81,10 +79,8 @@ def _ssim_sums(pred, trgt, want_map: bool):
     if H < 11 or W < 11:
         raise _lib.IronError("skimage_ssim: win_size 11 exceeds the image extent %d x %d" % (H, W))
     lib = _lib.load()
-    nb = C.c_size_t(0)
-    _lib.check(lib.iron_img_ssim_workspace_bytes(H, W, C.byref(nb)))
     with torch.cuda.device(a.device):
-        ws = _lib.workspace(nb.value, a.device, "img_ssim")
+        ws = _args.sized_workspace(lib.iron_img_ssim_workspace_bytes, H, W, device=a.device, tag="img_ssim")
         sums = torch.empty(3, dtype=torch.float64, device=a.device)
         smap = torch.empty((3, H - 10, W - 10), dtype=torch.float64, device=a.device) if want_map else None
         # skimage_ssim(pred, trgt) calls structural_similarity(trgt, pred); S is symmetric in its arguments term by term
@@ -196,10 +192,8 @@ class LPIPS:
         """fp64 device tensor [2]: the LPIPS distance and a flag (1.0 if an operand left fp16 range; the distance is then NaN)."""
         a, b, is_f32, H, W = self._images(pred, trgt)
         lib = _lib.load()
-        nb = C.c_size_t(0)
-        _lib.check(lib.iron_lpips_workspace_bytes(H, W, C.byref(nb)))
         with torch.cuda.device(self.device):
-            ws = _lib.workspace(nb.value, self.device, "lpips")
+            ws = _args.sized_workspace(lib.iron_lpips_workspace_bytes, H, W, device=self.device, tag="lpips")
             out = torch.empty(2, dtype=torch.float64, device=self.device)
             _lib.check(lib.iron_lpips_forward(a.data_ptr(), b.data_ptr(), H, W, is_f32, C.byref(self._weights), ws.data_ptr(), out.data_ptr(),
                                               _lib.stream_ptr(self.device)))

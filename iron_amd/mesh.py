@@ -12,7 +12,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 
 def marching_cubes(u: torch.Tensor, threshold: float = 0.0):
@@ -34,10 +34,8 @@ def marching_cubes(u: torch.Tensor, threshold: float = 0.0):
     lib = _lib.load()
     thr = float(threshold)
     with torch.cuda.device(dev):
-        nbytes = C.c_size_t(0)
-        _lib.check(lib.iron_mc_workspace_bytes(nx, ny, nz, C.byref(nbytes)))
         # call-scoped and released afterwards: at 512^3 it is ~0.8 GB, too much to keep cached between rare calls
-        ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+        ws = _args.sized_workspace(lib.iron_mc_workspace_bytes, nx, ny, nz, device=dev)
         nv, nt = C.c_int64(0), C.c_int64(0)
         st = lib.iron_mc_count(u.data_ptr(), nx, ny, nz, thr, ws.data_ptr(), C.byref(nv), C.byref(nt), _lib.stream_ptr(dev))
         if st == _lib.IRON_ERR_RANGE:

@@ -8,49 +8,11 @@ are rounded to fp32 once on the way in.  There is no CPU path: CPU tensors are r
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
-
-def _refuse_cpu(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and not x.is_cuda:
-            raise _lib.IronError("mesh distance: CPU tensors are not accepted (iron_amd has no CPU path); pass CUDA tensors or numpy")
-
-
-def _device(*xs) -> torch.device:
-    _refuse_cpu(*xs)
-    for x in xs:
-        if isinstance(x, torch.Tensor):
-            return x.device
-    if not torch.cuda.is_available():
-        raise _lib.IronError("mesh distance needs a GPU (iron_amd has no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _dev(x, dtype, dev, name) -> torch.Tensor:
-    _refuse_cpu(x)
-    t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise _lib.IronError("%s must be [n, 3], got %s" % (name, tuple(t.shape)))
-    return t.to(device=dev, dtype=dtype).contiguous()
-
-
-def _faces(faces, dev) -> torch.Tensor:
-    _refuse_cpu(faces)
-    f = faces.detach() if isinstance(faces, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(faces))
-    if f.dim() != 2 or f.shape[1] != 3:
-        raise _lib.IronError("faces must be [n, 3], got %s" % (tuple(f.shape),))
-    if f.is_floating_point() or f.dtype == torch.bool:
-        raise _lib.IronError("faces must hold integer vertex indices, got %s" % f.dtype)
-    f = f.to(device=dev)
-    if f.dtype == torch.int64:  # an index beyond int32 must stay out of range (the build flags it), not wrap
-        f = f.clamp(-1, (1 << 31) - 1)
-    return f.to(torch.int32).contiguous()
+WHAT = "mesh distance"  # what this module's messages begin with
 
 
 class MeshBVH:
@@ -60,12 +22,12 @@ class MeshBVH:
     on the current stream."""
 
     def __init__(self, vertices, faces, device=None):
-        dev = torch.device(device) if device is not None else _device(vertices, faces)
+        dev = torch.device(device) if device is not None else _args.pick_device(WHAT, vertices, faces)
         if dev.type != "cuda":
             raise _lib.IronError("MeshBVH: the device must be a GPU, got %s" % dev)
         with torch.cuda.device(dev):
-            self.vertices = _dev(vertices, torch.float32, dev, "vertices")
-            self.faces = _faces(faces, dev)
+            self.vertices = _args.device_array(vertices, torch.float32, dev, "vertices", (3,), what=WHAT)
+            self.faces = _args.face_array(faces, dev, what=WHAT)
         self.device = dev
         self.n_faces = int(self.faces.shape[0])
         if self.n_faces == 0:
@@ -81,9 +43,7 @@ class MeshBVH:
     # the four build steps, separately for tools/bench_meshdist.py
     def _keys(self):
         lib = _lib.load()
-        nb = C.c_size_t(0)
-        _lib.check(lib.iron_bvh_workspace_bytes(self.n_faces, C.byref(nb)))
-        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=self.device)
+        ws = _args.sized_workspace(lib.iron_bvh_workspace_bytes, self.n_faces, device=self.device)
         keys = torch.empty((self.n_faces,), dtype=torch.int64, device=self.device)
         _lib.check(lib.iron_bvh_keys(self.vertices.data_ptr(), self.vertices.shape[0], self.faces.data_ptr(), self.n_faces, ws.data_ptr(),
                                      keys.data_ptr(), _lib.stream_ptr(self.device)))
@@ -108,7 +68,7 @@ class MeshBVH:
         """points [N, 3] (numpy or CUDA tensor) -> (sqrD fp32 [N], I int32 [N], C fp32 [N, 3]) device tensors, in the order of
         the points: squared distance to the nearest face, its index (ties: the smallest) and the closest point on it."""
         with torch.cuda.device(self.device):
-            p = _dev(points, torch.float32, self.device, "points")
+            p = _args.device_array(points, torch.float32, self.device, "points", (3,), what=WHAT)
             n = int(p.shape[0])
             sqr = torch.empty((n,), dtype=torch.float32, device=self.device)
             idx = torch.empty((n,), dtype=torch.int32, device=self.device)
@@ -124,8 +84,8 @@ class MeshBVH:
         smallest face index; bary holds the weights of the face's second and third vertex.  A miss, a non-finite ray or a zero
         direction gives (+inf, -1, 0).  Watertight across shared edges and vertices (csrc/meshrender.hip)."""
         with torch.cuda.device(self.device):
-            o = _dev(ray_o, torch.float32, self.device, "ray_o")
-            d = _dev(ray_d, torch.float32, self.device, "ray_d")
+            o = _args.device_array(ray_o, torch.float32, self.device, "ray_o", (3,), what=WHAT)
+            d = _args.device_array(ray_d, torch.float32, self.device, "ray_d", (3,), what=WHAT)
             n = int(o.shape[0])
             if d.shape[0] != n:
                 raise _lib.IronError("ray_o has %d rows, ray_d %d" % (n, d.shape[0]))
@@ -142,7 +102,7 @@ class MeshBVH:
 def point_mesh_squared_distance(P, V, F):
     """igl.point_mesh_squared_distance(P, V, F) -> (sqrD [N], I [N], C [N, 3]).  numpy in, numpy out (float64, int64 indices);
     CUDA tensors in, tensors out on their device (sqrD and C in P's floating dtype, I int64), computed on the current stream."""
-    dev = _device(P, V, F)
+    dev = _args.pick_device(WHAT, P, V, F)
     bvh = MeshBVH(V, F, device=dev)
     sqr, idx, cp = bvh.query(P)
     if isinstance(P, torch.Tensor):
@@ -155,7 +115,7 @@ def chamfer_distance(va, fa, vb, fb) -> float:
     """cal_mesh_err of evaluation/eval_mesh.py: 0.5 * (mean sqrt(sqrD(va -> mesh b)) + mean sqrt(sqrD(vb -> mesh a))), every
     vertex of each mesh queried against the other's surface.  The square roots and means run on the device in fp64; returns a
     Python float."""
-    dev = _device(va, fa, vb, fb)
+    dev = _args.pick_device(WHAT, va, fa, vb, fb)
     with torch.cuda.device(dev):
         a = MeshBVH(va, fa, device=dev)
         b = MeshBVH(vb, fb, device=dev)

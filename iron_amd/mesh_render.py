@@ -17,43 +17,22 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from .mesh_distance import MeshBVH, _dev, _faces
+from . import _args, _lib
+from .mesh_distance import MeshBVH
 
 TEX_MODES = {"bilinear": 0, "nearest": 1}
 
 
-def _refuse_cpu(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and not x.is_cuda:
-            raise _lib.IronError("mesh render: CPU tensors are not accepted (iron_amd has no CPU path); pass CUDA tensors or numpy")
-
-
-def _device(*xs) -> torch.device:
-    _refuse_cpu(*xs)
-    for x in xs:
-        if isinstance(x, torch.Tensor):
-            return x.device
-    if not torch.cuda.is_available():
-        raise _lib.IronError("mesh render needs a GPU (iron_amd has no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _arr(x, dtype, dev, name, shape_tail) -> torch.Tensor:
-    _refuse_cpu(x)
-    t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
-    if t.dim() != 1 + len(shape_tail) or tuple(t.shape[1:]) != tuple(shape_tail):
-        raise _lib.IronError("%s must be [n, %s], got %s" % (name, ", ".join(str(k) for k in shape_tail), tuple(t.shape)))
-    return t.to(device=dev, dtype=dtype).contiguous()
+WHAT = "mesh render"  # what this module's messages begin with
 
 
 def vertex_normals(V, F) -> torch.Tensor:
     """Area-weighted vertex normals [V, 3] fp32 on the device: per vertex the sum of its faces' un-normalised cross products,
     normalised; the zero vector where the sum is zero.  Accumulated in int64 fixed point: bitwise reproducible.  Waits once."""
-    dev = _device(V, F)
+    dev = _args.pick_device(WHAT, V, F)
     with torch.cuda.device(dev):
-        v = _dev(V, torch.float32, dev, "vertices")
-        f = _faces(F, dev)
+        v = _args.device_array(V, torch.float32, dev, "vertices", (3,), what=WHAT)
+        f = _args.face_array(F, dev, what=WHAT)
         out = torch.empty_like(v)
         _lib.check(_lib.load().iron_mesh_vertex_normals(v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], out.data_ptr(),
                                                         _lib.stream_ptr(dev)))
@@ -61,8 +40,7 @@ def vertex_normals(V, F) -> torch.Tensor:
 
 
 def _texture(tex, dev, name="tex") -> torch.Tensor:
-    _refuse_cpu(tex)
-    t = tex.detach() if isinstance(tex, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(tex))
+    t = _args.as_tensor(tex, WHAT)
     if t.dim() == 2:
         t = t.unsqueeze(-1)
     if t.dim() != 3 or not 1 <= t.shape[2] <= 8 or t.shape[0] * t.shape[1] == 0 or t.shape[0] * t.shape[1] > 1 << 24:
@@ -73,8 +51,7 @@ def _texture(tex, dev, name="tex") -> torch.Tensor:
 def _weight(weight, tex, dev):
     if weight is None:
         return None
-    _refuse_cpu(weight)
-    w = weight.detach() if isinstance(weight, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(weight))
+    w = _args.as_tensor(weight, WHAT)
     if tuple(w.shape) != tuple(tex.shape[:2]):
         raise _lib.IronError("weight must be [H, W] = %s, got %s" % (tuple(tex.shape[:2]), tuple(w.shape)))
     return w.to(device=dev, dtype=torch.float32).contiguous()
@@ -85,11 +62,11 @@ def sample_texture(tex, uv, weight=None, mode="bilinear"):
     [H, W]: the bake's weight image; taps it marks unwritten (0) are dropped and the rest renormalised, `hole` where none is left."""
     if mode not in TEX_MODES:
         raise _lib.IronError("mode must be one of %s, got %r" % (sorted(TEX_MODES), mode))
-    dev = _device(tex, uv, weight)
+    dev = _args.pick_device(WHAT, tex, uv, weight)
     with torch.cuda.device(dev):
         t = _texture(tex, dev)
         w = _weight(weight, t, dev)
-        q = _arr(uv, torch.float32, dev, "uv", (2,))
+        q = _args.device_array(uv, torch.float32, dev, "uv", (2,), what=WHAT)
         n, (H, W, Cn) = int(q.shape[0]), t.shape
         val = torch.empty((n, Cn), dtype=torch.float32, device=dev)
         hole = torch.empty((n,), dtype=torch.uint8, device=dev)
@@ -152,14 +129,14 @@ class MeshAsset:
     def __init__(self, vertices, faces, uvs, face_uvs, material, weight=None, normals="vertex", device=None):
         if normals not in ("vertex", "face"):
             raise _lib.IronError("normals must be 'vertex' or 'face', got %r" % (normals,))
-        dev = torch.device(device) if device is not None else _device(vertices, faces, uvs, face_uvs, material, weight)
-        _refuse_cpu(vertices, faces, uvs, face_uvs, material, weight)
+        dev = torch.device(device) if device is not None else _args.pick_device(WHAT, vertices, faces, uvs, face_uvs, material, weight)
+        _args.refuse_cpu(WHAT, vertices, faces, uvs, face_uvs, material, weight)
         self.device = dev
         with torch.cuda.device(dev):
             self.bvh = MeshBVH(vertices, faces, device=dev)
             self.vertices, self.faces = self.bvh.vertices, self.bvh.faces
-            self.uvs = _arr(uvs, torch.float32, dev, "uvs", (2,))
-            self.face_uvs = _faces(face_uvs, dev)
+            self.uvs = _args.device_array(uvs, torch.float32, dev, "uvs", (2,), what=WHAT)
+            self.face_uvs = _args.face_array(face_uvs, dev, what=WHAT)
             if self.face_uvs.shape[0] != self.faces.shape[0]:
                 raise _lib.IronError("face_uvs has %d rows, faces %d" % (self.face_uvs.shape[0], self.faces.shape[0]))
             if self.uvs.shape[0] == 0 or int(self.face_uvs.min()) < 0 or int(self.face_uvs.max()) >= self.uvs.shape[0]:
@@ -175,7 +152,7 @@ class MeshAsset:
     def load(cls, obj_path, texture_dir, normals="vertex", device=None):
         """The asset on disk (read_asset) on the GPU."""
         a = read_asset(obj_path, texture_dir)
-        dev = torch.device(device) if device is not None else _device()
+        dev = torch.device(device) if device is not None else _args.pick_device(WHAT)
         return cls(a["vertices"], a["faces"], a["uvs"], a["face_uvs"], a["material"], weight=a["weight"], normals=normals, device=dev)
 
     def shade(self, ray_o, ray_d, t, face_idx, bary, light, tables):
@@ -214,7 +191,7 @@ def _mts_tables(dev):
 def render_asset_uv(camera, asset, light, uv):
     """One ray per entry of uv [H, W, 2] (pixel coordinates of `camera`): the dictionary of render_asset_camera for one sample
     per pixel.  Pixels go to the ray cast's lanes row-major: one 8x8 pixel tile per 64-lane wave measured slower."""
-    _refuse_cpu(uv, camera.K)
+    _args.refuse_cpu(WHAT, uv, camera.K)
     dev = asset.device
     H, W = int(uv.shape[0]), int(uv.shape[1])
     with torch.cuda.device(dev):
@@ -258,7 +235,7 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1):
     s = int(samples_per_axis)
     if s < 1:
         raise _lib.IronError("samples_per_axis must be >= 1")
-    _refuse_cpu(camera.K)
+    _args.refuse_cpu(WHAT, camera.K)
     if s == 1:
         res = render_asset_uv(camera, asset, light, camera.get_uv())
         res["coverage"] = res["convergent_mask"].float()

@@ -9,35 +9,19 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 SCALE = float(1 << 24)   # fixed-point units per 1.0 in the splat accumulator
 MAX_CHANNELS = 16        # splatted channels per sample (xyz + values), the weight comes on top
 
 
-def _device(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _dev(x, dtype, dev, name, cols):
-    t = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
-    t = t.detach().to(device=dev, dtype=dtype).contiguous()
-    if t.dim() != 2 or t.shape[1] != cols:
-        raise _lib.IronError("%s must be [n, %d], got %s" % (name, cols, tuple(t.shape)))
-    return t
-
-
 def _mesh(vertices, faces, uvs, face_uvs, dev):
-    v = _dev(vertices, torch.float32, dev, "vertices", 3)
-    f = _dev(faces, torch.int32, dev, "faces", 3)
-    t = _dev(uvs, torch.float32, dev, "uvs", 2)
-    ft = _dev(face_uvs, torch.int32, dev, "face_uvs", 3)
+    v = _args.device_array(vertices, torch.float32, dev, "vertices", (3,), strict=False)
+    f = _args.device_array(faces, torch.int32, dev, "faces", (3,), strict=False)
+    t = _args.device_array(uvs, torch.float32, dev, "uvs", (2,), strict=False)
+    ft = _args.device_array(face_uvs, torch.int32, dev, "face_uvs", (3,), strict=False)
     if ft.shape[0] != f.shape[0]:
         raise _lib.IronError("face_uvs has %d rows, faces %d" % (ft.shape[0], f.shape[0]))
     return v, f, t, ft
@@ -46,9 +30,7 @@ def _mesh(vertices, faces, uvs, face_uvs, dev):
 def _count(v, f, ft, n_uvs, n_samples, seed, round, ceil_counts=None, counts=None):
     """iron_bake_count: per-face counts and their offsets in a call-scoped workspace -> (workspace, total).  Waits once."""
     lib = _lib.load()
-    nb = C.c_size_t(0)
-    _lib.check(lib.iron_bake_workspace_bytes(f.shape[0], C.byref(nb)))
-    ws = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=v.device)
+    ws = _args.sized_workspace(lib.iron_bake_workspace_bytes, f.shape[0], device=v.device)
     total = C.c_int64(0)
     st = lib.iron_bake_count(v.data_ptr(), v.shape[0], f.data_ptr(), n_uvs, ft.data_ptr(), f.shape[0], int(n_samples),
                              int(seed) & ((1 << 64) - 1), int(round) & 0xFFFFFFFF, ws.data_ptr(), _lib.ptr(ceil_counts),
@@ -76,7 +58,7 @@ def sample_surface_gpu(vertices, faces, uvs, face_uvs, n_samples, seed, round=0,
     """models/export_materials.py:13-55 on the device: -> (points fp32 [N,3], uv fp32 [N,2]) with N = sum of the per-face counts
     (N >= n_samples, like the reference), ordered by face.  `return_face_idx` appends int32 [N]; `return_counts` appends the
     int32 [F] counts before and after the excess removal.  Mesh arrays may be numpy or tensors; fp32 / int32 on the GPU."""
-    dev = _device(vertices, faces, uvs, face_uvs)
+    dev = _args.pick_device("texture bake", vertices, faces, uvs, face_uvs, strict=False)
     n_samples = int(n_samples)
     if n_samples < 0:
         raise _lib.IronError("n_samples must be >= 0")
@@ -105,7 +87,7 @@ def sample_surface_gpu(vertices, faces, uvs, face_uvs, n_samples, seed, round=0,
 def sample_surface_explicit(vertices, faces, uvs, face_uvs, face_idx, r1, r2):
     """The point rule of sample_surface for caller-given draws: face_idx [N], r1 / r2 fp64 [N] (the reference's np.random.rand
     columns) -> (points fp32 [N,3], uv fp32 [N,2]); a sample with an out-of-range face comes out NaN."""
-    dev = _device(vertices, faces, uvs, face_uvs, face_idx, r1, r2)
+    dev = _args.pick_device("texture bake", vertices, faces, uvs, face_uvs, face_idx, r1, r2, strict=False)
     with torch.cuda.device(dev):
         v, f, t, ft = _mesh(vertices, faces, uvs, face_uvs, dev)
         fi = torch.as_tensor(face_idx).detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
@@ -146,9 +128,9 @@ class SplatAccumulator:
 
     def add(self, points, uvs, values):
         dev = self.device
-        p = _dev(points, torch.float32, dev, "points", 3)
-        uv = _dev(uvs, torch.float32, dev, "uvs", 2)
-        val = _dev(values, torch.float32, dev, "values", self.n_values)
+        p = _args.device_array(points, torch.float32, dev, "points", (3,), strict=False)
+        uv = _args.device_array(uvs, torch.float32, dev, "uvs", (2,), strict=False)
+        val = _args.device_array(values, torch.float32, dev, "values", (self.n_values,), strict=False)
         n = p.shape[0]
         if uv.shape[0] != n or val.shape[0] != n:
             raise _lib.IronError("points, uvs and values must have the same number of rows")
@@ -184,7 +166,7 @@ def bake_materials(vertices, faces, uvs, face_uvs, material_predictor, texture_H
     material query in splits of max_num_pts (rendering_func.query_materials; predictors returning CPU tensors are accepted),
     the splat, then the normalisation.  -> (xyz [H,W,3], material [H,W,7], weight [H,W]) device fp32 tensors."""
     from .rendering_func import query_materials
-    dev = _device(vertices, faces, uvs, face_uvs)
+    dev = _args.pick_device("texture bake", vertices, faces, uvs, face_uvs, strict=False)
     with torch.cuda.device(dev):
         v, f, t, ft = _mesh(vertices, faces, uvs, face_uvs, dev)
         acc = SplatAccumulator(texture_H, texture_W, 7, max_samples=max(1, int(n_rounds) * (int(n_samples) + f.shape[0])), device=dev)

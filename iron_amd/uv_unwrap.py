@@ -30,8 +30,9 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
-from .mesh_distance import _dev, _device, _faces
+from . import _args, _lib
+
+WHAT = "mesh distance"  # what the argument messages of this module begin with: it shares mesh_distance's input rules
 
 COARSE_STEP_DEG, COARSE_N = 1.0, 90
 FINE_STEP_DEG, FINE_HALF = 0.05, 20
@@ -76,10 +77,10 @@ def face_components(vertices, faces, group=None):
     """Connected components of the faces over shared edges (faces sharing only a vertex are not joined, nor through an edge whose two
     indices are equal); with `group` [F] only faces of equal group are joined.  -> (labels int32 [F] on the device, numbered 0..K-1
     in order of each component's first face, K).  A face index outside [0, V) or a non-finite referenced vertex raises IronError."""
-    dev = _device(vertices, faces)
+    dev = _args.pick_device(WHAT, vertices, faces)
     with torch.cuda.device(dev):
-        v = _dev(vertices, torch.float32, dev, "vertices")
-        f = _faces(faces, dev)
+        v = _args.device_array(vertices, torch.float32, dev, "vertices", (3,), what=WHAT)
+        f = _args.face_array(faces, dev, what=WHAT)
         n = int(f.shape[0])
         if n == 0:
             return torch.zeros((0,), dtype=torch.int32, device=dev), 0
@@ -196,12 +197,12 @@ def smart_uv_project(vertices, faces, angle_limit=66.0, island_margin=0.0, stats
     """vertices [V, 3], faces [F, 3] (CUDA tensors or numpy) -> (uvs fp32 [T, 2], face_uvs int32 [F, 3]) on the vertices' device,
     computed on the current stream (the module docstring states the algorithm).  Vertices and faces are not modified.  `stats`
     (a dict, optional) receives per-stage times and counts for tools/bench_uv.py (the stage timers synchronise the device)."""
-    dev = _device(vertices, faces)
+    dev = _args.pick_device(WHAT, vertices, faces)
     if not (0.0 < float(angle_limit) < 90.0):
         raise _lib.IronError("angle_limit must lie in (0, 90) degrees, got %r" % angle_limit)
     with torch.cuda.device(dev):
-        v = _dev(vertices, torch.float32, dev, "vertices")
-        f = _faces(faces, dev)
+        v = _args.device_array(vertices, torch.float32, dev, "vertices", (3,), what=WHAT)
+        f = _args.face_array(faces, dev, what=WHAT)
         F, V = int(f.shape[0]), int(v.shape[0])
         if F == 0:
             return torch.zeros((0, 2), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
@@ -213,9 +214,7 @@ def smart_uv_project(vertices, faces, angle_limit=66.0, island_margin=0.0, stats
         # projection normals and the assignment g(f)
         alpha = math.radians(float(angle_limit))
         max_p = min(F, int(math.ceil(2.0 / (1.0 - math.cos(alpha / 4.0)))) + 1)  # seeds lie > limit/2 apart: a cap-packing bound
-        nb = C.c_size_t(0)
-        _lib.check(lib.iron_uv_workspace_bytes(F, C.byref(nb)))
-        ws = torch.empty((int(nb.value),), dtype=torch.uint8, device=dev)
+        ws = _args.sized_workspace(lib.iron_uv_workspace_bytes, F, device=dev)
         state = _state(dev)
         P = torch.empty((max_p, 3), dtype=torch.float32, device=dev)
         group = torch.empty((F,), dtype=torch.int32, device=dev)

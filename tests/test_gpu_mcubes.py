@@ -38,9 +38,9 @@ def test_sphere_64_matches_oracle():
 
 
 @pytest.mark.parametrize("shape,threshold,seed", [((33, 40, 47), 0.0, 0), ((17, 9, 64), 0.0, 1), ((33, 40, 47), 0.37, 2),
-                                                  ((5, 70, 3), -0.2, 3)])
+                                                  ((5, 70, 3), -0.2, 3), ((65, 64, 66), 0.0, 4)])
 def test_noise_fields_match_oracle(shape, threshold, seed):
-    """White noise: about a third of the faces are ambiguous."""
+    """White noise: about a third of the faces are ambiguous.  (65, 64, 66) has 1073 blocks of lattice points: two scan levels."""
     u = np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
     _same(u, threshold)
 

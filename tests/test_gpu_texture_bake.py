@@ -51,6 +51,44 @@ def test_counts_follow_the_reference_rule(g21, k):
     assert np.isfinite(pts.cpu().numpy()).all() and np.isfinite(uv.cpu().numpy()).all()
 
 
+def _grid_mesh(F):
+    """The first F faces of a planar vertex grid (jittered, fixed seed; two triangles per cell), about one face in ten made
+    degenerate by repeating a vertex index, and one shared UV triangle -> (v, f, uvs, face_uvs, degenerate mask)."""
+    side = 726 if F > 1058 else 24  # 2 * 725^2 = 1 051 250 faces; 2 * 23^2 = 1058
+    rng = np.random.default_rng(1234)
+    ii, jj = np.meshgrid(np.arange(side), np.arange(side), indexing="ij")
+    v = np.stack([ii, jj, np.zeros_like(ii)], -1).reshape(-1, 3).astype(np.float32)
+    v[:, :2] += rng.uniform(-0.3, 0.3, (side * side, 2)).astype(np.float32)
+    a = (ii[:-1, :-1] * side + jj[:-1, :-1]).reshape(-1)
+    f = np.stack([np.stack([a, a + side, a + 1], -1), np.stack([a + 1, a + side, a + side + 1], -1)], 1).reshape(-1, 3)[:F].copy()
+    assert len(f) == F
+    degenerate = rng.random(F) < 0.1
+    degenerate[0] = False  # the one-face mesh keeps its area
+    f[degenerate, 2] = f[degenerate, 1]
+    t = np.array([[0, 0], [1, 0], [0, 1]], dtype=np.float32)
+    return v, f, t, np.tile(np.array([[0, 1, 2]]), (F, 1)), degenerate
+
+
+@pytest.mark.parametrize("F", [1, 1023, 1024, 1025, 1051250])
+def test_counts_and_offsets_across_the_scan_boundaries(F):
+    """The pair scan (csrc/pair_scan.hip) at its block boundaries, through the bake: level lengths [1, 1], [1023, 1], [1024, 1],
+    [1025, 2, 1] and [1051250, 1027, 2, 1] (three scan levels).  The sample offsets are the exclusive scan of the counts, so the
+    face of every sample must be repeat_interleave(arange(F), counts); the count rule is test_counts_follow_the_reference_rule's."""
+    from iron_amd.texture_bake import sample_surface_gpu
+    v, f, t, ft, degenerate = _grid_mesh(F)
+    n = min(3 * F, 1 << 24)
+    run = lambda: sample_surface_gpu(v, f, t, ft, n, seed=13, return_face_idx=True, return_counts=True)  # noqa: E731
+    pts, uv, fi, ceil_c, cnt = first = run()
+    assert torch.equal(fi.long(), torch.repeat_interleave(torch.arange(F, device=fi.device), cnt.long()))  # ordered by face
+    assert len(pts) == len(uv) == int(cnt.sum()) >= n
+    removed = (ceil_c - cnt).cpu().numpy()
+    ceil_np = ceil_c.cpu().numpy()
+    assert set(np.unique(removed)) <= {0, 1} and (removed[ceil_np == 0] == 0).all()
+    assert 0 <= int(removed.sum()) <= int(ceil_np.sum()) - n
+    assert (cnt.cpu().numpy()[degenerate] == 0).all() and (ceil_np[~degenerate] > 0).all()
+    assert all(torch.equal(x, y) for x, y in zip(first, run()))
+
+
 def test_seeded_sampling_is_reproducible_and_seed_dependent():
     from iron_amd.texture_bake import sample_surface_gpu
     v, f, t, ft = O.g21_mesh()
