@@ -301,6 +301,65 @@ int iron_texture_fetch(const float* tex, const float* weight, int32_t H, int32_t
 int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, const float* tab_trans, const float* tab_diff_trans, const float* ray_o,
                          const float* ray_d, const float* t, const int32_t* face_idx, const float* bary, int64_t n_rays,
                          const iron_asset_out* out, void* stream);
+/* Environment-map relighting of an exported asset, csrc/envlight.hip; DESIGN.md §16.  Direct illumination only.  Every entry
+ * enqueues on `stream`; none waits.
+ *   iron_mesh_occluded  per ray occluded [n_rays] (uint8) = 1 when any face is met with t in (t_min, t_max], over the BVH of
+ *                       iron_bvh_* (same workspace and n_faces).  skip_face [n_rays] int32 (may be NULL): that face is ignored for
+ *                       that ray, -1 ignores none.  A non-finite ray or a zero direction gives 0.  The walk uses the triangle and
+ *                       box tests of iron_mesh_raycast (one header, csrc/ray_core.h) and leaves at the first accepted face, so
+ *                       occluded == (iron_mesh_raycast(...).face_idx >= 0) for the same window, exactly: there is no tolerance.
+ *   Environment map     image [h,w,3] fp32 linear radiance, finite and >= 0 (the caller checks), lat-long in Mitsuba 0.6's
+ *                       convention: with local = to_world^T world, u = atan2(local.x, -local.z) / 2 pi wrapped to [0,1), v =
+ *                       acos(local.y) / pi, texel (floor(v h), floor(u w)) clamped.  to_world: row-major rotation.  Radiance is
+ *                       constant per texel (Mitsuba interpolates).  h * w <= 2^24.
+ *   iron_envmap_build   the sampling distribution into `workspace` (iron_envmap_workspace_bytes): texel weight (0.2126 R + 0.7152 G
+ *                       + 0.0722 B) sin(pi (row + 1/2) / h), fp64 row CDFs and the marginal CDF by block scans in a fixed order
+ *                       (bitwise reproducible), and P(texel) in fp32.  iron_envmap.dist is this workspace.
+ *   iron_envmap_sample  u [n,2] in (0,1): u[:,0] picks the column through the row's CDF, u[:,1] the row through the marginal; the
+ *                       direction is uniform in (u, v) inside the texel.  texel [n,2] int32 (row, col), dir [n,3] world, pdf [n] =
+ *                       P(texel) w h / (2 pi^2 sin theta(dir)), the solid-angle density.  A texel of weight 0 is never returned; an
+ *                       all-black map returns texel (0,0) with pdf 0.
+ *   iron_envmap_pdf     that density at dir [n,3] (need not be unit length; 0 in a texel of weight 0 and for a zero direction).
+ *   iron_envmap_lookup  the radiance rgb [n,3] at dir.
+ *   iron_roughplastic   (diffuse, specular) [count,3] = roughplastic_point (csrc/ggx_core.h): the rough-plastic BRDF times cos_i for
+ *                       normal n, view v and light direction l [count,3] (unit), kd, ks [count,3], rough [count].
+ *   iron_asset_shade_env  per primary hit (the point, normal and material of iron_asset_shade_ggx, one shared function) the sum
+ *                       over n_light environment samples and n_brdf BRDF samples (u2 < 1/2: cosine-weighted about the normal, else
+ *                       a GGX half vector with density D cos_h, reflected) of
+ *                         L(w) roughplastic_point(n, v, w) V(w) / (n_light p_light(w) + n_brdf p_brdf(w)),
+ *                       the multi-sample balance heuristic; a count of 0 drops its term.  p_brdf = (n.w / pi + D(h) n.h / (4 v.h))
+ *                       / 2.  V(w) = 1 when n.w > 0, (n_g.w)(n_g.v) > 0 (n_g the face's unit geometric normal) and the shadow ray
+ *                       from x + sign(n_g.w) shadow_eps D n_g (D the diagonal of the BVH's root box) along w meets no face other
+ *                       than the primary one with t in (0, inf]; the walk is iron_mesh_occluded's, inside this kernel.  Random
+ *                       numbers are a pure function of (seed, pixel_idx[ray] (NULL: the ray's position), sample, dimension) on the
+ *                       odd points of the 24-bit grid; sums run in an order fixed by the sample index: a pixel's result depends on
+ *                       no other pixel, on no launch geometry and on no run.  bvh_workspace: the mesh's iron_bvh_* workspace.  out:
+ *                       as iron_asset_shade_ggx (color = diffuse_color + specular_color, linear radiance).  dump (may be NULL, and
+ *                       each pointer in it) for tests, N = n_light + n_brdf, environment samples first: dir [n_rays,N,3] (zero for
+ *                       a BRDF sample with v.h <= 0), denom [n_rays,N] the denominator above, vis [n_rays,N] uint8 V(w), contrib
+ *                       [n_rays,N,3] the sample's term; zeros on a miss. */
+typedef struct iron_envmap {
+    const float* image;                        /* [h,w,3] */
+    const void* dist;                          /* iron_envmap_build's workspace */
+    int32_t h, w;
+    float to_world[9];
+} iron_envmap;
+typedef struct iron_env_dump {
+    float* dir; float* denom; uint8_t* vis; float* contrib;
+} iron_env_dump;
+int iron_mesh_occluded(const void* workspace, int64_t n_faces, const float* ray_o, const float* ray_d, int64_t n_rays, float t_min,
+                       float t_max, const int32_t* skip_face, uint8_t* occluded, void* stream);
+int iron_envmap_workspace_bytes(int32_t h, int32_t w, size_t* bytes);
+int iron_envmap_build(const float* image, int32_t h, int32_t w, void* workspace, void* stream);
+int iron_envmap_sample(const iron_envmap* env, const float* u, int64_t n, int32_t* texel, float* dir, float* pdf, void* stream);
+int iron_envmap_pdf(const iron_envmap* env, const float* dir, int64_t n, float* pdf, void* stream);
+int iron_envmap_lookup(const iron_envmap* env, const float* dir, int64_t n, float* rgb, void* stream);
+int iron_roughplastic(const float* n, const float* v, const float* l, const float* kd, const float* ks, const float* rough,
+                      const float* tab_trans, const float* tab_diff_trans, int64_t count, float* diffuse, float* specular, void* stream);
+int iron_asset_shade_env(const iron_asset_mesh* mesh, const void* bvh_workspace, const iron_envmap* env, const float* tab_trans,
+                         const float* tab_diff_trans, const float* ray_o, const float* ray_d, const float* t, const int32_t* face_idx,
+                         const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_light, int32_t n_brdf, uint32_t seed,
+                         float shadow_eps, const iron_asset_out* out, const iron_env_dump* dump, void* stream);
 /* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
  * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
  *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte

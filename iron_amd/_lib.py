@@ -92,6 +92,14 @@ class iron_asset_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ASSET_OUT_FIELDS]
 
 
+class iron_envmap(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("dist", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("to_world", C.c_float * 9)]
+
+
+class iron_env_dump(C.Structure):
+    _fields_ = [("dir", C.c_void_p), ("denom", C.c_void_p), ("vis", C.c_void_p), ("contrib", C.c_void_p)]
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -136,6 +144,15 @@ SYMBOLS = {
     "iron_mesh_vertex_normals": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
     "iron_texture_fetch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P]),
     "iron_asset_shade_ggx": (C.c_int, [C.POINTER(iron_asset_mesh), _F, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(iron_asset_out), _P]),
+    "iron_mesh_occluded": (C.c_int, [_P, _I64, _P, _P, _I64, _F, _F, _P, _P, _P]),
+    "iron_envmap_workspace_bytes": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
+    "iron_envmap_build": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "iron_envmap_sample": (C.c_int, [C.POINTER(iron_envmap), _P, _I64, _P, _P, _P, _P]),
+    "iron_envmap_pdf": (C.c_int, [C.POINTER(iron_envmap), _P, _I64, _P, _P]),
+    "iron_envmap_lookup": (C.c_int, [C.POINTER(iron_envmap), _P, _I64, _P, _P]),
+    "iron_roughplastic": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "iron_asset_shade_env": (C.c_int, [C.POINTER(iron_asset_mesh), _P, C.POINTER(iron_envmap), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32,
+                                       C.c_uint32, _F, C.POINTER(iron_asset_out), C.POINTER(iron_env_dump), _P]),
     "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
     "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),

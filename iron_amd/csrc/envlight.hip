@@ -1,0 +1,568 @@
+// Environment-map relighting of an exported asset: an occlusion query over the linear BVH, a lat-long
+// environment map with its sampling distribution, and a direct-illumination integrator that combines environment samples and BRDF
+// samples with the multi-sample balance heuristic.  Conventions: include/iron_hip.h, iron_mesh_occluded block.
+//
+// Occlusion (bvh_any_hit): the walk of k_raycast (meshrender.hip) with the primitive tests of ray_core.h, a fixed far end t_max in
+// place of the shrinking best t, and an exit at the first accepted face.  A face is accepted under exactly k_raycast's condition
+// (ray_tri and t <= t_max), and the walk visits a superset of the boxes k_raycast visits; a ray for which k_raycast finds nothing
+// walks exactly the same boxes here.  Hence occluded == (raycast.face_idx >= 0), bitwise.
+//
+// Environment map: lat-long [He, We, 3], Mitsuba 0.6's convention: a local direction d has u = atan2(d.x, -d.z) / 2 pi wrapped to
+// [0, 1), v = acos(d.y) / pi, texel (floor(v He), floor(u We)) clamped; world = to_world local.  Radiance is constant per texel.
+// The distribution is over texels, weight = luminance sin(pi (row + 1/2) / He), as fp64 row CDFs and a marginal CDF (block scans in
+// a fixed order: reproducible); a direction is uniform in (u, v) inside its texel, so its solid-angle density is
+// P(texel) We He / (2 pi^2 sin theta).
+//
+// Integrator (k_shade_env): kEnvGroup lanes work one pixel; sample s of the pixel's n_light + n_brdf runs on lane s % kEnvGroup in
+// round s / kEnvGroup, every lane adds its rounds in order, and a fixed butterfly adds the lanes: a pixel's sums depend on nothing
+// but its own samples.  Random numbers: env_rand, a pure function of (seed, pixel index, sample, dimension).
+#include "asset_common.h"
+#include "ggx_core.h"
+#include "ray_core.h"
+
+namespace iron {
+
+// ---- occlusion ----
+__device__ __forceinline__ bool tri_blocks(const float4* __restrict__ tris, int32_t k, const RayPre& r, float t_min, float t_max,
+                                           int32_t skip) {
+    TriHit x;
+    return ray_tri(tris, k, r, t_min, x) && x.t <= t_max && x.face != skip;
+}
+
+// is any face other than `skip` met with t in (t_min, t_max]?  `stack`: the per-lane LDS stack of k_raycast
+__device__ __forceinline__ bool bvh_any_hit(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf, const RayPre& r,
+                                            float t_min, float t_max, int32_t skip, int32_t (*stack)[kBvQueryBlock], int lane) {
+    if (nf == 1) return tri_blocks(tris, 0, r, t_min, t_max, skip);
+    int32_t node = 0, sp = 0;
+    for (;;) {
+        const float4* nd = nodes + 4 * (int64_t)node;
+        const float4 l0 = nd[0], h0 = nd[1], l1 = nd[2], h1 = nd[3];
+        const int32_t c0 = __float_as_int(l0.w), c1 = __float_as_int(h0.w);
+        float n0, n1;
+        const bool v0 = ray_box(r, l0, h0, t_min, t_max, n0);
+        if (c0 < 0 && v0 && tri_blocks(tris, ~c0, r, t_min, t_max, skip)) return true;
+        const bool v1 = ray_box(r, l1, h1, t_min, t_max, n1);
+        if (c1 < 0 && v1 && tri_blocks(tris, ~c1, r, t_min, t_max, skip)) return true;
+        const bool g0 = c0 >= 0 && v0, g1 = c1 >= 0 && v1;
+        if (g0 && g1) {
+            const bool first1 = n1 < n0;
+            if (sp < kBvStack) stack[sp++][lane] = first1 ? c0 : c1;  // never full (kBvStack)
+            node = first1 ? c1 : c0;
+        } else if (g0) {
+            node = c0;
+        } else if (g1) {
+            node = c1;
+        } else {
+            if (sp == 0) return false;
+            node = stack[--sp][lane];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_occluded(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf,
+                                                             const float* __restrict__ ray_o, const float* __restrict__ ray_d, int64_t n,
+                                                             float t_min, float t_max, const int32_t* __restrict__ skip_face,
+                                                             uint8_t* __restrict__ occluded) {
+    __shared__ int32_t stack[kBvStack][kBvQueryBlock];
+    const int lane = threadIdx.x;
+    const int64_t q = (int64_t)blockIdx.x * kBvQueryBlock + lane;
+    if (q >= n) return;
+    const float3 o = ld3(ray_o, q), d = ld3(ray_d, q);
+    bool hit = false;
+    if (ray_valid(o, d) && t_min <= t_max) {  // NaN bounds fail
+        RayPre r;
+        ray_setup(o, d, r);
+        hit = bvh_any_hit(nodes, tris, nf, r, t_min, t_max, skip_face ? skip_face[q] : -1, stack, lane);
+    }
+    occluded[q] = hit ? 1 : 0;
+}
+
+// the diagonal of the root box (the box of every referenced vertex)
+__device__ __forceinline__ float bvh_diagonal(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf) {
+    float4 a, b, c, d;
+    if (nf == 1) {
+        a = tris[0]; b = tris[1]; c = d = tris[2];
+    } else {
+        a = nodes[0]; b = nodes[1]; c = nodes[2]; d = nodes[3];
+    }
+    const float lx = fminf(fminf(a.x, b.x), fminf(c.x, d.x)), ly = fminf(fminf(a.y, b.y), fminf(c.y, d.y)),
+                lz = fminf(fminf(a.z, b.z), fminf(c.z, d.z));
+    const float hx = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), hy = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
+                hz = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z));
+    const float ex = hx - lx, ey = hy - ly, ez = hz - lz;
+    return sqrtf((ex * ex + ey * ey) + ez * ez);
+}
+
+// ---- environment map ----
+constexpr double kPiD = 3.141592653589793;
+constexpr float kTwoPi = 6.28318530717958647692f;
+constexpr float kTwoPiSq = 19.7392088021787172376f;  // 2 pi^2
+constexpr int kEnvBlock = 256;
+
+struct EnvLayout {
+    size_t total_off, mcdf_off, rowsum_off, rowcdf_off, ptex_off, bytes;
+};
+
+inline EnvLayout env_layout(int64_t He, int64_t We) {
+    EnvLayout L{};
+    Carver c;
+    L.total_off = c.take(8);
+    L.mcdf_off = c.take(8 * (size_t)(He + 1));
+    L.rowsum_off = c.take(8 * (size_t)He);
+    L.rowcdf_off = c.take(8 * (size_t)(He * (We + 1)));
+    L.ptex_off = c.take(4 * (size_t)(He * We));
+    L.bytes = c.off;
+    return L;
+}
+
+struct EnvDev {
+    const float* image;    // [He, We, 3]
+    const double* total;   // the sum of the weights
+    const double* mcdf;    // [He + 1] marginal CDF over rows, 0 .. 1
+    const double* rowcdf;  // [He, We + 1] CDF of every row, 0 .. 1 (zeros for a row without weight)
+    const float* ptex;     // [He, We] P(texel)
+    int32_t He, We;
+    float R[9];            // world = R local
+};
+
+__device__ __forceinline__ double env_weight(const float* __restrict__ img, int64_t r, int64_t c, int64_t He, int64_t We) {
+    const float* p = img + 3 * (r * We + c);
+    const double lum = (0.2126 * (double)p[0] + 0.7152 * (double)p[1]) + 0.0722 * (double)p[2];
+    return lum * sin(kPiD * ((double)r + 0.5) / (double)He);
+}
+
+// inclusive scan of n values w(k) by one block, in a fixed order: out[k + 1] = w(0) + .. + w(k), out[0] = 0; returns (to every
+// thread) the last entry.  Thread t owns a contiguous segment; the segment sums are scanned in LDS.
+template <class W>
+__device__ __forceinline__ double block_cdf(int64_t n, W w, double* __restrict__ out, double* sh) {
+    const int t = threadIdx.x;
+    const int64_t seg = (n + kEnvBlock - 1) / kEnvBlock, k0 = min((int64_t)t * seg, n), k1 = min(k0 + seg, n);
+    double s = 0.0;
+    for (int64_t k = k0; k < k1; ++k) s += w(k);
+    sh[t] = s;
+    __syncthreads();
+    for (int h = 1; h < kEnvBlock; h <<= 1) {
+        const double add = t >= h ? sh[t - h] : 0.0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    double run = t > 0 ? sh[t - 1] : 0.0;
+    __syncthreads();
+    if (t == 0) out[0] = 0.0;
+    for (int64_t k = k0; k < k1; ++k) {
+        run += w(k);
+        out[k + 1] = run;
+    }
+    if (k1 == n && k0 < n) sh[kEnvBlock] = run;  // the owner of the last entry
+    __syncthreads();
+    return sh[kEnvBlock];
+}
+
+__global__ __launch_bounds__(kEnvBlock) void k_env_rows(const float* __restrict__ img, int He, int We, double* __restrict__ rowcdf,
+                                                         double* __restrict__ rowsum) {
+    __shared__ double sh[kEnvBlock + 1];
+    const int64_t r = blockIdx.x;
+    const double last = block_cdf(We, [&](int64_t c) { return env_weight(img, r, c, He, We); }, rowcdf + r * (We + 1), sh);
+    if (threadIdx.x == 0) rowsum[r] = last;
+}
+
+__global__ __launch_bounds__(kEnvBlock) void k_env_marginal(const double* __restrict__ rowsum, int He, double* __restrict__ mcdf,
+                                                             double* __restrict__ total) {
+    __shared__ double sh[kEnvBlock + 1];
+    const double tot = block_cdf(He, [&](int64_t r) { return rowsum[r]; }, mcdf, sh);
+    if (threadIdx.x == 0) *total = tot;
+    __syncthreads();
+    for (int k = threadIdx.x; k <= He; k += kEnvBlock) mcdf[k] = tot > 0.0 ? (k == He ? 1.0 : mcdf[k] / tot) : 0.0;
+}
+
+__global__ void k_env_normalise(const float* __restrict__ img, int He, int We, const double* __restrict__ rowsum,
+                                const double* __restrict__ total, double* __restrict__ rowcdf, float* __restrict__ ptex) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)He * (We + 1)) return;
+    const int64_t r = i / (We + 1), c = i % (We + 1);
+    const double rs = rowsum[r], tot = *total;
+    rowcdf[i] = rs > 0.0 ? (c == We ? 1.0 : rowcdf[i] / rs) : 0.0;
+    if (c < We) ptex[r * We + c] = tot > 0.0 ? (float)(env_weight(img, r, c, He, We) / tot) : 0.0f;
+}
+
+__device__ __forceinline__ float3 mat_mul(const float R[9], float3 d) {
+    return make_float3((R[0] * d.x + R[1] * d.y) + R[2] * d.z, (R[3] * d.x + R[4] * d.y) + R[5] * d.z, (R[6] * d.x + R[7] * d.y) + R[8] * d.z);
+}
+__device__ __forceinline__ float3 mat_tmul(const float R[9], float3 d) {
+    return make_float3((R[0] * d.x + R[3] * d.y) + R[6] * d.z, (R[1] * d.x + R[4] * d.y) + R[7] * d.z, (R[2] * d.x + R[5] * d.y) + R[8] * d.z);
+}
+
+// the texel a world direction looks up, and sin theta of its local direction; false for a zero or non-finite direction
+__device__ __forceinline__ bool env_texel(const EnvDev& E, float3 world, int& r, int& c, float& sin_theta) {
+    const float3 d = mat_tmul(E.R, world);
+    const float len = sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);
+    r = c = 0; sin_theta = 0.0f;
+    if (!(len > 0.0f) || !(len < kInfF)) return false;
+    float u = atan2f(d.x, -d.z) / kTwoPi;
+    if (u < 0.0f) u += 1.0f;
+    const float v = acosf(fminf(fmaxf(d.y / len, -1.0f), 1.0f)) / kPi;
+    r = min(max((int)floorf(v * (float)E.He), 0), E.He - 1);
+    c = min(max((int)floorf(u * (float)E.We), 0), E.We - 1);
+    sin_theta = sqrtf(d.x * d.x + d.z * d.z) / len;
+    return true;
+}
+
+__device__ __forceinline__ float env_density(const EnvDev& E, int r, int c, float sin_theta) {
+    const float p = E.ptex[(int64_t)r * E.We + c];
+    return p > 0.0f ? p * ((float)E.We * (float)E.He) / (kTwoPiSq * sin_theta) : 0.0f;
+}
+
+// radiance and solid-angle density of the map at a world direction
+__device__ __forceinline__ float env_eval(const EnvDev& E, float3 world, float L[3]) {
+    int r, c;
+    float st;
+    L[0] = L[1] = L[2] = 0.0f;
+    if (!env_texel(E, world, r, c, st)) return 0.0f;
+    const float* p = E.image + 3 * ((int64_t)r * E.We + c);
+    L[0] = p[0]; L[1] = p[1]; L[2] = p[2];
+    return env_density(E, r, c, st);
+}
+
+// the number of entries of cdf[1 .. n] that are <= u: the interval [cdf[k], cdf[k + 1]) that holds u, never an empty one
+__device__ __forceinline__ int cdf_find(const double* __restrict__ cdf, int n, double u) {
+    int lo = 0, hi = n;  // the answer lies in [lo, hi]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid + 1] <= u) lo = mid + 1; else hi = mid;
+    }
+    return min(lo, n - 1);
+}
+
+__device__ __forceinline__ float cdf_remap(const double* __restrict__ cdf, int k, double u) {
+    const double w = cdf[k + 1] - cdf[k];
+    const float f = w > 0.0 ? (float)((u - cdf[k]) / w) : 0.5f;
+    return fminf(fmaxf(f, 0.0f), 0.99999994f);
+}
+
+// u0 picks the column, u1 the row; the direction is uniform in (u, v) inside the texel.  An all-black map: texel (0, 0), pdf 0.
+__device__ __forceinline__ float env_sample(const EnvDev& E, float u0, float u1, int& r, int& c, float3& world) {
+    const bool black = !(*E.total > 0.0);
+    r = black ? 0 : cdf_find(E.mcdf, E.He, (double)u1);
+    const double* row = E.rowcdf + (int64_t)r * (E.We + 1);
+    c = black ? 0 : cdf_find(row, E.We, (double)u0);
+    const float dv = black ? 0.5f : cdf_remap(E.mcdf, r, (double)u1), du = black ? 0.5f : cdf_remap(row, c, (double)u0);
+    const float phi = kTwoPi * (((float)c + du) / (float)E.We), theta = kPi * (((float)r + dv) / (float)E.He);
+    // sin(theta) through the nearer pole: pi v loses (1 - v)'s leading digits as v -> 1, (He - 1 - r) + (1 - dv) does not
+    const float to_south = kPi * (((float)(E.He - 1 - r) + (1.0f - dv)) / (float)E.He);
+    const float st = sinf(fminf(theta, to_south));
+    world = mat_mul(E.R, make_float3(st * sinf(phi), cosf(theta), -(st * cosf(phi))));
+    return black ? 0.0f : env_density(E, r, c, st);
+}
+
+__global__ void k_env_sample(EnvDev E, const float* __restrict__ u, int64_t n, int32_t* __restrict__ texel, float* __restrict__ dir,
+                             float* __restrict__ pdf) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int r, c;
+    float3 w;
+    const float p = env_sample(E, u[2 * i], u[2 * i + 1], r, c, w);
+    texel[2 * i] = r; texel[2 * i + 1] = c;
+    dir[3 * i] = w.x; dir[3 * i + 1] = w.y; dir[3 * i + 2] = w.z;
+    pdf[i] = p;
+}
+
+__global__ void k_env_eval(EnvDev E, const float* __restrict__ dir, int64_t n, float* __restrict__ pdf, float* __restrict__ rgb) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float L[3];
+    const float p = env_eval(E, ld3(dir, i), L);
+    if (pdf) pdf[i] = p;
+    if (rgb) { rgb[3 * i] = L[0]; rgb[3 * i + 1] = L[1]; rgb[3 * i + 2] = L[2]; }
+}
+
+// ---- BRDF sampling ----
+// 23 random bits k -> (2 k + 1) 2^-24: the odd points of the 24-bit grid, exact in fp32, never 0 or 1
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ float env_rand(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
+    uint32_t h = lowbias32(seed);
+    h = lowbias32(h ^ pixel);
+    h = lowbias32(h + sample);
+    h = lowbias32(h + 0x9e3779b9u * (dim + 1u));
+    return (float)(((h >> 9) << 1) | 1u) * 5.9604644775390625e-08f;
+}
+
+// orthonormal tangent frame of a unit normal (Duff et al., "Building an Orthonormal Basis, Revisited", JCGT 2017)
+__device__ __forceinline__ void tangent_frame(float3 n, float3& t, float3& b) {
+    const float sg = copysignf(1.0f, n.z), a = -1.0f / (sg + n.z), q = n.x * n.y * a;
+    t = make_float3(1.0f + sg * n.x * n.x * a, sg * q, -sg * n.x);
+    b = make_float3(q, sg + n.y * n.y * a, -n.y);
+}
+
+// density of the BRDF technique at w: half cosine-weighted (n.w / pi), half GGX half-vector sampling (D(h) n.h / (4 v.h), D the
+// exact GGX density alpha^2 / (pi (alpha^2 cos^2 + sin^2)^2) with sin^2 = |n x h|^2, h = normalize(v + w))
+__device__ __forceinline__ float brdf_pdf(float3 n, float3 v, float3 w, float alpha) {
+    const float nw = dot3(n, w);
+    const float pc = nw > 0.0f ? nw / kPi : 0.0f;
+    float pg = 0.0f;
+    float3 h = make_float3(v.x + w.x, v.y + w.y, v.z + w.z);
+    const float hl = sqrtf(dot3(h, h));
+    if (hl > 0.0f) {
+        h = make_float3(h.x / hl, h.y / hl, h.z / hl);
+        const float c = dot3(n, h), vh = dot3(v, h);
+        if (c > 0.0f && vh > 0.0f) {
+            const float3 x = cross3(n, h);
+            const float a2 = alpha * alpha, den = a2 * c * c + dot3(x, x);
+            pg = (a2 / (kPi * den * den)) * c / (4.0f * vh);
+        }
+    }
+    return 0.5f * (pc + pg);
+}
+
+// u2 < 1/2: cosine-weighted about n; else a GGX half vector h (tan^2 = alpha^2 u0 / (1 - u0)) and w = 2 (v.h) h - v, which is
+// no sample (false) when v.h <= 0
+__device__ __forceinline__ bool brdf_sample(float3 n, float3 v, float alpha, float u0, float u1, float u2, float3& w) {
+    float3 t, b;
+    tangent_frame(n, t, b);
+    const float phi = kTwoPi * u1, cp = cosf(phi), sp = sinf(phi);
+    float x, y, z;
+    const bool cosine = u2 < 0.5f;
+    if (cosine) {
+        const float rr = sqrtf(u0);
+        x = rr * cp; y = rr * sp; z = sqrtf(1.0f - u0);
+    } else {
+        const float tan2 = alpha * alpha * u0 / (1.0f - u0);
+        z = 1.0f / sqrtf(1.0f + tan2);
+        const float s = sqrtf(tan2) * z;
+        x = s * cp; y = s * sp;
+    }
+    const float3 d = make_float3((x * t.x + y * b.x) + z * n.x, (x * t.y + y * b.y) + z * n.y, (x * t.z + y * b.z) + z * n.z);
+    if (cosine) { w = d; return true; }
+    const float vh = dot3(v, d);
+    w = make_float3(2.0f * vh * d.x - v.x, 2.0f * vh * d.y - v.y, 2.0f * vh * d.z - v.z);
+    return vh > 0.0f;
+}
+
+__global__ void k_roughplastic(const float* __restrict__ n, const float* __restrict__ v, const float* __restrict__ l,
+                               const float* __restrict__ kd, const float* __restrict__ ks, const float* __restrict__ rough,
+                               const float* __restrict__ tab_trans, const float* __restrict__ tab_diff, int64_t cnt,
+                               float* __restrict__ diffuse, float* __restrict__ specular) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    PlasticOut o;
+    roughplastic_point(n + 3 * i, v + 3 * i, l + 3 * i, kd + 3 * i, ks + 3 * i, rough[i], tab_trans, tab_diff, o);
+    st3(diffuse, i, o.diffuse[0], o.diffuse[1], o.diffuse[2]);
+    st3(specular, i, o.specular[0], o.specular[1], o.specular[2]);
+}
+
+// ---- the integrator ----
+constexpr int kEnvGroup = 16;  // lanes per pixel
+constexpr int kEnvPixels = kBvQueryBlock / kEnvGroup;
+
+struct EnvShadeArgs {
+    iron_asset_mesh m;
+    iron_asset_out o;
+    iron_env_dump dump;
+    EnvDev env;
+    const float4 *nodes, *tris;
+    const float *tab_trans, *tab_diff, *ray_o, *ray_d, *t, *bary;
+    const int32_t *face_idx, *pixel_idx;
+    int64_t n;
+    int32_t n_light, n_brdf;
+    uint32_t seed;
+    float shadow_eps;
+};
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
+    __shared__ int32_t stack[kBvStack][kBvQueryBlock];
+    const int lane = threadIdx.x, sl = lane % kEnvGroup;
+    const int64_t i = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;
+    if (i >= a.n) return;  // a whole group leaves together
+    SurfHit s;
+    asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s);
+    const int32_t N = a.n_light + a.n_brdf;
+    const uint32_t pixel = a.pixel_idx ? (uint32_t)a.pixel_idx[i] : (uint32_t)i;
+    float3 ng = make_float3(0.f, 0.f, 0.f), v = ng;
+    float off = 0.0f, ngv = 0.0f, alpha = 0.0f;
+    if (s.hit) {
+        const float3 va = ld3(a.m.verts, s.iv[0]);
+        ng = unit_or_zero(cross3(sub3(ld3(a.m.verts, s.iv[1]), va), sub3(ld3(a.m.verts, s.iv[2]), va)));
+        v = make_float3(-s.d.x, -s.d.y, -s.d.z);
+        ngv = dot3(ng, v);
+        off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
+        alpha = fmaxf(s.mat[6], 0.0001f);
+    }
+    const float nn[3] = {s.nrm.x, s.nrm.y, s.nrm.z}, vv[3] = {v.x, v.y, v.z};
+    float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
+    for (int32_t base = 0; base < N; base += kEnvGroup) {
+        const int32_t k = base + sl;
+        if (k >= N) break;  // the ragged tail of the last round
+        float3 w = make_float3(0.f, 0.f, 0.f);
+        float denom = 0.0f, cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
+        bool vis = false;
+        if (s.hit) {
+            float L[3], pl;
+            bool ok;
+            if (k < a.n_light) {
+                int r, c;
+                pl = env_sample(a.env, env_rand(a.seed, pixel, k, 0), env_rand(a.seed, pixel, k, 1), r, c, w);
+                const float* p = a.env.image + 3 * ((int64_t)r * a.env.We + c);
+                L[0] = p[0]; L[1] = p[1]; L[2] = p[2];
+                ok = true;
+            } else {
+                ok = brdf_sample(s.nrm, v, alpha, env_rand(a.seed, pixel, k, 0), env_rand(a.seed, pixel, k, 1), env_rand(a.seed, pixel, k, 2), w);
+                if (!ok) w = make_float3(0.f, 0.f, 0.f);
+                pl = env_eval(a.env, w, L);
+            }
+            const float pb = ok ? brdf_pdf(s.nrm, v, w, alpha) : 0.0f;
+            denom = (a.n_light > 0 ? (float)a.n_light * pl : 0.0f) + (a.n_brdf > 0 ? (float)a.n_brdf * pb : 0.0f);
+            const float ngw = dot3(ng, w);
+            if (ok && dot3(s.nrm, w) > 0.0f && ngw * ngv > 0.0f && finite3(w)) {
+                const float sg = ngw > 0.0f ? off : -off;
+                const float3 org = make_float3(s.pt.x + sg * ng.x, s.pt.y + sg * ng.y, s.pt.z + sg * ng.z);
+                if (ray_valid(org, w)) {
+                    RayPre r;
+                    ray_setup(org, w, r);
+                    vis = !bvh_any_hit(a.nodes, a.tris, a.m.n_faces, r, 0.0f, kInfF, (int32_t)s.face, stack, lane);
+                }
+            }
+            if (vis && denom > 0.0f) {
+                PlasticOut f;
+                const float ww[3] = {w.x, w.y, w.z};
+                roughplastic_point(nn, vv, ww, s.mat, s.mat + 3, s.mat[6], a.tab_trans, a.tab_diff, f);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    cd[c] = L[c] * f.diffuse[c] / denom;  // an infinite density (the map's poles) gives 0
+                    cs[c] = L[c] * f.specular[c] / denom;
+                    accd[c] += cd[c];
+                    accs[c] += cs[c];
+                }
+            }
+        }
+        const int64_t at = i * N + k;
+        st3(a.dump.dir, at, w.x, w.y, w.z);
+        if (a.dump.denom) a.dump.denom[at] = denom;
+        if (a.dump.vis) a.dump.vis[at] = vis ? 1 : 0;
+        st3(a.dump.contrib, at, cd[0] + cs[0], cd[1] + cs[1], cd[2] + cs[2]);
+    }
+#pragma unroll
+    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
+            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
+        }
+    if (sl != 0) return;
+    st3(a.o.color, i, accd[0] + accs[0], accd[1] + accs[1], accd[2] + accs[2]);
+    st3(a.o.diffuse_color, i, accd[0], accd[1], accd[2]);
+    st3(a.o.specular_color, i, accs[0], accs[1], accs[2]);
+    asset_store_maps(a.o, i, s);
+}
+
+static bool env_dev(const iron_envmap* env, EnvDev& E) {
+    if (!env || !env->image || !env->dist || env->h <= 0 || env->w <= 0 || (int64_t)env->h * env->w > (1 << 24)) return false;
+    const EnvLayout L = env_layout(env->h, env->w);
+    E.image = env->image;
+    E.total = ws_ptr<double>(env->dist, L.total_off);
+    E.mcdf = ws_ptr<double>(env->dist, L.mcdf_off);
+    E.rowcdf = ws_ptr<double>(env->dist, L.rowcdf_off);
+    E.ptex = ws_ptr<float>(env->dist, L.ptex_off);
+    E.He = env->h; E.We = env->w;
+    for (int k = 0; k < 9; ++k) E.R[k] = env->to_world[k];
+    return true;
+}
+
+}  // namespace iron
+
+using namespace iron;
+
+extern "C" int iron_mesh_occluded(const void* workspace, int64_t n_faces, const float* ray_o, const float* ray_d, int64_t n_rays, float t_min,
+                                  float t_max, const int32_t* skip_face, uint8_t* occluded, void* stream) {
+    if (n_faces <= 0 || n_faces >= 0x7fffffffLL || n_rays < 0 || !workspace) return IRON_ERR_BAD_ARG;
+    if (n_rays == 0) return IRON_OK;
+    if (!ray_o || !ray_d || !occluded) return IRON_ERR_BAD_ARG;
+    const BvLayout L = bv_layout(n_faces);
+    IRON_LAUNCH(k_occluded, blocks_for(n_rays, kBvQueryBlock), kBvQueryBlock, (hipStream_t)stream, ws_ptr<float4>(workspace, L.nodes_off),
+                ws_ptr<float4>(workspace, L.tris_off), n_faces, ray_o, ray_d, n_rays, t_min, t_max, skip_face, occluded);
+    return IRON_OK;
+}
+
+extern "C" int iron_envmap_workspace_bytes(int32_t h, int32_t w, size_t* bytes) {
+    if (!bytes || h <= 0 || w <= 0 || (int64_t)h * w > (1 << 24)) return IRON_ERR_BAD_ARG;
+    *bytes = env_layout(h, w).bytes;
+    return IRON_OK;
+}
+
+extern "C" int iron_envmap_build(const float* image, int32_t h, int32_t w, void* workspace, void* stream) {
+    if (!image || !workspace || h <= 0 || w <= 0 || (int64_t)h * w > (1 << 24)) return IRON_ERR_BAD_ARG;
+    const EnvLayout L = env_layout(h, w);
+    hipStream_t st = (hipStream_t)stream;
+    double* rowcdf = ws_ptr<double>(workspace, L.rowcdf_off);
+    double* rowsum = ws_ptr<double>(workspace, L.rowsum_off);
+    double* total = ws_ptr<double>(workspace, L.total_off);
+    IRON_LAUNCH(k_env_rows, h, kEnvBlock, st, image, h, w, rowcdf, rowsum);
+    IRON_LAUNCH(k_env_marginal, 1, kEnvBlock, st, (const double*)rowsum, h, ws_ptr<double>(workspace, L.mcdf_off), total);
+    IRON_LAUNCH(k_env_normalise, blocks_for((int64_t)h * (w + 1), 256), 256, st, image, h, w, (const double*)rowsum, (const double*)total, rowcdf,
+                ws_ptr<float>(workspace, L.ptex_off));
+    return IRON_OK;
+}
+
+extern "C" int iron_envmap_sample(const iron_envmap* env, const float* u, int64_t n, int32_t* texel, float* dir, float* pdf, void* stream) {
+    EnvDev E;
+    if (!env_dev(env, E) || n < 0) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!u || !texel || !dir || !pdf) return IRON_ERR_BAD_ARG;
+    IRON_LAUNCH(k_env_sample, blocks_for(n, 256), 256, (hipStream_t)stream, E, u, n, texel, dir, pdf);
+    return IRON_OK;
+}
+
+static int env_eval_entry(const iron_envmap* env, const float* dir, int64_t n, float* pdf, float* rgb, void* stream) {
+    EnvDev E;
+    if (!env_dev(env, E) || n < 0) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!dir || (!pdf && !rgb)) return IRON_ERR_BAD_ARG;
+    IRON_LAUNCH(k_env_eval, blocks_for(n, 256), 256, (hipStream_t)stream, E, dir, n, pdf, rgb);
+    return IRON_OK;
+}
+
+extern "C" int iron_envmap_pdf(const iron_envmap* env, const float* dir, int64_t n, float* pdf, void* stream) {
+    return env_eval_entry(env, dir, n, pdf, nullptr, stream);
+}
+
+extern "C" int iron_envmap_lookup(const iron_envmap* env, const float* dir, int64_t n, float* rgb, void* stream) {
+    return env_eval_entry(env, dir, n, nullptr, rgb, stream);
+}
+
+extern "C" int iron_roughplastic(const float* n, const float* v, const float* l, const float* kd, const float* ks, const float* rough,
+                                 const float* tab_trans, const float* tab_diff_trans, int64_t count, float* diffuse, float* specular,
+                                 void* stream) {
+    if (count < 0) return IRON_ERR_BAD_ARG;
+    if (count == 0) return IRON_OK;
+    if (!n || !v || !l || !kd || !ks || !rough || !tab_trans || !tab_diff_trans || !diffuse || !specular) return IRON_ERR_BAD_ARG;
+    IRON_LAUNCH(k_roughplastic, blocks_for(count, 256), 256, (hipStream_t)stream, n, v, l, kd, ks, rough, tab_trans, tab_diff_trans, count, diffuse,
+                specular);
+    return IRON_OK;
+}
+
+extern "C" int iron_asset_shade_env(const iron_asset_mesh* mesh, const void* bvh_workspace, const iron_envmap* env, const float* tab_trans,
+                                    const float* tab_diff_trans, const float* ray_o, const float* ray_d, const float* t,
+                                    const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_light,
+                                    int32_t n_brdf, uint32_t seed, float shadow_eps, const iron_asset_out* out, const iron_env_dump* dump,
+                                    void* stream) {
+    if (!mesh || !out || !bvh_workspace || n_rays < 0 || n_light < 0 || n_brdf < 0 || (int64_t)n_light + n_brdf > (1 << 20)) return IRON_ERR_BAD_ARG;
+    if (mesh->n_faces <= 0 || mesh->n_faces >= 0x7fffffffLL || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
+        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
+        return IRON_ERR_BAD_ARG;
+    if (!mesh->verts || !mesh->faces || !mesh->uvs || !mesh->face_uvs || !mesh->material || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
+    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    EnvShadeArgs a;
+    if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
+    if (n_rays == 0) return IRON_OK;
+    if (!ray_o || !ray_d || !t || !face_idx || !bary) return IRON_ERR_BAD_ARG;
+    const BvLayout L = bv_layout(mesh->n_faces);
+    a.m = *mesh; a.o = *out;
+    a.dump = dump ? *dump : iron_env_dump{nullptr, nullptr, nullptr, nullptr};
+    a.nodes = ws_ptr<float4>(bvh_workspace, L.nodes_off); a.tris = ws_ptr<float4>(bvh_workspace, L.tris_off);
+    a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.ray_o = ray_o; a.ray_d = ray_d; a.t = t; a.bary = bary; a.face_idx = face_idx;
+    a.pixel_idx = pixel_idx; a.n = n_rays; a.n_light = n_light; a.n_brdf = n_brdf; a.seed = seed; a.shadow_eps = shadow_eps;
+    IRON_LAUNCH(k_shade_env, blocks_for(n_rays, kEnvPixels), kBvQueryBlock, (hipStream_t)stream, a);
+    return IRON_OK;
+}

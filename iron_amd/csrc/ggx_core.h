@@ -175,6 +175,49 @@ __device__ __forceinline__ void ggx_colocated_point(float light, float distance,
     }
 }
 
+// The same rough plastic for a light direction l other than the view direction v (the environment render, envlight.hip): the
+// BRDF times cos_i, split like GgxOut, from the blocks above only.  h = normalize(v + l); cos_o = n.v, cos_i = n.l, cos_h = n.h
+// and cos_d = v.h are clamped to [1e-5, 0.99999] as in every co-located head; n.l <= 0 (or v + l = 0) gives zero.
+//   specular cos_i = ks F(cos_d) D(cos_h) G1(cos_i) G1(cos_o) / (4 cos_o + 1e-10)
+//   diffuse cos_i  = (kd / fd / pi) cos_i T12(cos_i) T12(cos_o) / eta^2
+// At l = v this is ggx_colocated_point with intensity 1, except that the Fresnel term is computed (0.0386729 at normal incidence)
+// where that head takes its 4-digit rounding kFr.
+struct PlasticOut {
+    float diffuse[3];
+    float specular[3];
+};
+
+__device__ __forceinline__ float clamp_cos(float c) { return fminf(fmaxf(c, 0.00001f), 0.99999f); }
+
+__device__ __forceinline__ void roughplastic_point(const float n[3], const float v[3], const float l[3], const float kd[3],
+                                                   const float ks[3], float rough, const float* __restrict__ tab_trans,
+                                                   const float* __restrict__ tab_diff, PlasticOut& o) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o.diffuse[c] = o.specular[c] = 0.0f;
+    const float nl = (l[0] * n[0] + l[1] * n[1]) + l[2] * n[2];
+    const float hx = v[0] + l[0], hy = v[1] + l[1], hz = v[2] + l[2];
+    const float hl = sqrtf((hx * hx + hy * hy) + hz * hz);
+    if (!(nl > 0.0f) || !(hl > 0.0f)) return;
+    const float h[3] = {hx / hl, hy / hl, hz / hl};
+    const float cos_o = clamp_cos((v[0] * n[0] + v[1] * n[1]) + v[2] * n[2]);
+    const float cos_i = clamp_cos(nl);
+    const float cos_h = clamp_cos((h[0] * n[0] + h[1] * n[1]) + h[2] * n[2]);
+    const float cos_d = clamp_cos((h[0] * v[0] + h[1] * v[1]) + h[2] * v[2]);
+    const float alpha = fmaxf(rough, 0.0001f);
+    const float F = fresnel_dielectric_pos(cos_d, (float)kEta);
+    const float D = ggx_ndf(cos_h, alpha);
+    const float G = smith_g1(cos_i, alpha) * smith_g1(cos_o, alpha);
+    const float denom = 4.0f * cos_o + 1e-10f;
+    float Ti, To, fd, fd_o;
+    rtrans_lookup(cos_i, alpha, tab_trans, tab_diff, Ti, fd);
+    rtrans_lookup(cos_o, alpha, tab_trans, tab_diff, To, fd_o);  // fd depends on alpha alone
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o.specular[c] = ks[c] * F * D * G / denom;
+        o.diffuse[c] = (kd[c] / fd / kPi) * cos_i * Ti * To * kInvEta2;
+    }
+}
+
 // ---- the fork's other co-located heads (models/renderer_ggx.py:149-517, 520-858) -----------------
 
 struct CompositeOut {

@@ -16,57 +16,11 @@
 //   visits the box.  A box whose entry equals the best t is visited.
 //   A face replaces the best when its t is smaller, or equal with a smaller face index: for a fixed ray, t is a function of the
 //   set of faces, not of their order or of the tree.
-#include "bvh_common.h"
+#include "asset_common.h"
 #include "ggx_core.h"
+#include "ray_core.h"
 
 namespace iron {
-
-constexpr float kInfF = __builtin_huge_valf();
-
-struct RayPre {
-    float3 o, inv, pad;   // origin, 1 / d, 2^-21 |1 / d| (0 on an axis whose reciprocal is not finite)
-    bool zx, zy, zz;      // that axis: the reciprocal is not finite
-    int kx, ky, kz;       // Woop's axis permutation
-    float sx, sy, sz;     // shear and scale
-};
-
-__device__ __forceinline__ float pick(float3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
-
-__device__ __forceinline__ void ray_setup(float3 o, float3 d, RayPre& r) {
-    r.o = o;
-    r.inv = make_float3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    r.zx = !(fabsf(r.inv.x) < kInfF); r.zy = !(fabsf(r.inv.y) < kInfF); r.zz = !(fabsf(r.inv.z) < kInfF);
-    const float e = 4.76837158203125e-07f;  // 2^-21
-    r.pad = make_float3(r.zx ? 0.0f : fabsf(r.inv.x) * e, r.zy ? 0.0f : fabsf(r.inv.y) * e, r.zz ? 0.0f : fabsf(r.inv.z) * e);
-    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
-    r.kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-    r.kx = r.kz == 2 ? 0 : r.kz + 1;
-    r.ky = r.kx == 2 ? 0 : r.kx + 1;
-    const float dz = pick(d, r.kz);
-    if (dz < 0.0f) { const int s = r.kx; r.kx = r.ky; r.ky = s; }  // keeps the winding
-    r.sx = pick(d, r.kx) / dz;
-    r.sy = pick(d, r.ky) / dz;
-    r.sz = 1.0f / dz;
-}
-
-// one slab: entry and exit of [lo, hi] on one axis, moved outwards (see the head of the file)
-__device__ __forceinline__ void slab(float lo, float hi, float o, float inv, float pad, bool zero, float& tn, float& tf) {
-    const float t0 = (lo - o) * inv, t1 = (hi - o) * inv;
-    const float p = ((fabsf(lo) + fabsf(hi)) + fabsf(o)) * pad;
-    const float n = fminf(t0, t1) - p, f = fmaxf(t0, t1) + p;
-    tn = fmaxf(tn, zero ? ((o >= lo && o <= hi) ? -kInfF : kInfF) : n);
-    tf = fminf(tf, zero ? kInfF : f);
-}
-
-// does the ray meet the box within [t_min, best]?  `tn`: the (conservative) entry distance
-__device__ __forceinline__ bool ray_box(const RayPre& r, float4 lo, float4 hi, float t_min, float best, float& tn) {
-    float tf = kInfF;
-    tn = -kInfF;
-    slab(lo.x, hi.x, r.o.x, r.inv.x, r.pad.x, r.zx, tn, tf);
-    slab(lo.y, hi.y, r.o.y, r.inv.y, r.pad.y, r.zy, tn, tf);
-    slab(lo.z, hi.z, r.o.z, r.inv.z, r.pad.z, r.zz, tn, tf);
-    return tn <= tf && tn <= best && tf >= t_min;
-}
 
 struct RayHit {
     float t, b1, b2;  // distance along d, barycentric weights of the face's second and third vertex
@@ -75,32 +29,10 @@ struct RayHit {
 };
 
 __device__ __forceinline__ void ray_leaf(const float4* __restrict__ tris, int32_t k, const RayPre& r, float t_min, RayHit& h) {
-    const float4 ta = tris[3 * (int64_t)k], tb = tris[3 * (int64_t)k + 1], tc = tris[3 * (int64_t)k + 2];
-    const int32_t f = __float_as_int(ta.w);
-    const float3 A = sub3(make_float3(ta.x, ta.y, ta.z), r.o), B = sub3(make_float3(tb.x, tb.y, tb.z), r.o),
-                 C = sub3(make_float3(tc.x, tc.y, tc.z), r.o);
-    const float Akz = pick(A, r.kz), Bkz = pick(B, r.kz), Ckz = pick(C, r.kz);
-    const float Ax = pick(A, r.kx) - r.sx * Akz, Ay = pick(A, r.ky) - r.sy * Akz;
-    const float Bx = pick(B, r.kx) - r.sx * Bkz, By = pick(B, r.ky) - r.sy * Bkz;
-    const float Cx = pick(C, r.kx) - r.sx * Ckz, Cy = pick(C, r.ky) - r.sy * Ckz;
-    float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-    bool neg = U < 0.0f || V < 0.0f || W < 0.0f, pos = U > 0.0f || V > 0.0f || W > 0.0f;
-    if (U == 0.0f || V == 0.0f || W == 0.0f) {  // on an edge or a vertex (or an underflow): the signs from exact products
-        const double Ud = (double)Cx * (double)By - (double)Cy * (double)Bx;
-        const double Vd = (double)Ax * (double)Cy - (double)Ay * (double)Cx;
-        const double Wd = (double)Bx * (double)Ay - (double)By * (double)Ax;
-        neg = Ud < 0.0 || Vd < 0.0 || Wd < 0.0;
-        pos = Ud > 0.0 || Vd > 0.0 || Wd > 0.0;
-        U = (float)Ud; V = (float)Vd; W = (float)Wd;
-    }
-    if (neg && pos) return;
-    const float det = (U + V) + W;
-    if (det == 0.0f) return;  // edge-on or degenerate
-    const float T = (U * (r.sz * Akz) + V * (r.sz * Bkz)) + W * (r.sz * Ckz);
-    const float t = T / det;
-    if (!(t > t_min) || !(t < kInfF)) return;  // NaN fails too
-    if (t < h.t || (t == h.t && f < h.face)) {
-        h.t = t; h.face = f; h.leaf = k; h.b1 = V / det; h.b2 = W / det;
+    TriHit x;
+    if (!ray_tri(tris, k, r, t_min, x)) return;
+    if (x.t < h.t || (x.t == h.t && x.face < h.face)) {
+        h.t = x.t; h.face = x.face; h.leaf = k; h.b1 = x.V / x.det; h.b2 = x.W / x.det;
     }
 }
 
@@ -237,58 +169,6 @@ __global__ void k_vn_finish(const long long* __restrict__ acc, int64_t nv, float
     normals[3 * i + 2] = (float)(z * s);
 }
 
-// ---- texture fetch ----
-// The bake's pixel convention (texbake.hip: u = uv_x W, v = H - uv_y H, texel (row, col) covers [col, col + 1) x [row, row + 1)):
-// x = uv_x W - 1/2, y = (H - uv_y H) - 1/2 are the coordinates in texel centres.  They are formed in fp64, where they are exact for
-// fp32 uv and sizes below 2^24.  Returns true for a hole: no tap with a non-zero bake weight (or a non-finite uv); out is then 0.
-template <int MAXC>
-__device__ __forceinline__ bool texture_fetch(const float* __restrict__ tex, const float* __restrict__ weight, int H, int W, int C, float u,
-                                              float v, int mode, float out[MAXC]) {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) out[c] = 0.0f;
-    if (!isfinite(u) || !isfinite(v)) return true;
-    const double xu = (double)u * (double)W, yv = (double)H - (double)v * (double)H;
-    if (mode == IRON_TEX_NEAREST) {
-        const int col = (int)fmin(fmax(floor(xu), 0.0), (double)(W - 1)), row = (int)fmin(fmax(floor(yv), 0.0), (double)(H - 1));
-        const int64_t t = (int64_t)row * W + col;
-        if (weight && !(weight[t] > 0.0f)) return true;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c)
-            if (c < C) out[c] = tex[t * C + c];
-        return false;
-    }
-    const double x = fmin(fmax(xu - 0.5, -1.0), (double)W), y = fmin(fmax(yv - 0.5, -1.0), (double)H);  // beyond the edge: the edge texel
-    const double x0 = floor(x), y0 = floor(y);
-    const float fx = (float)(x - x0), fy = (float)(y - y0);
-    const int c0 = min(max((int)x0, 0), W - 1), c1 = min(max((int)x0 + 1, 0), W - 1);
-    const int r0 = min(max((int)y0, 0), H - 1), r1 = min(max((int)y0 + 1, 0), H - 1);
-    const int64_t tap[4] = {(int64_t)r0 * W + c0, (int64_t)r0 * W + c1, (int64_t)r1 * W + c0, (int64_t)r1 * W + c1};
-    float w[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
-    if (weight) {
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!(weight[tap[k]] > 0.0f)) w[k] = 0.0f;
-            sum += w[k];
-        }
-        if (!(sum > 0.0f)) return true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = w[k] / sum;
-    }
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-        if (c < C) {
-            float a = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (w[k] != 0.0f) a += w[k] * tex[tap[k] * C + c];  // a dropped tap is not read: an unbaked texel may hold anything
-            out[c] = a;
-        }
-    return false;
-}
-
-constexpr int kTexMaxC = 8;
-
 __global__ void k_texture_fetch(const float* __restrict__ tex, const float* __restrict__ weight, int H, int W, int C,
                                 const float* __restrict__ uv, int64_t n, int mode, float* __restrict__ values, uint8_t* __restrict__ hole) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -311,66 +191,22 @@ struct AssetShadeArgs {
     int64_t n;
 };
 
-__device__ __forceinline__ float3 unit_or_zero(float3 v) {
-    const float l = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
-    return l > 0.0f && l < kInfF ? make_float3(v.x / l, v.y / l, v.z / l) : make_float3(0.f, 0.f, 0.f);
-}
-
-__device__ __forceinline__ void st3(float* __restrict__ p, int64_t i, float x, float y, float z) {
-    if (p) { p[3 * i] = x; p[3 * i + 1] = y; p[3 * i + 2] = z; }
-}
 
 __global__ __launch_bounds__(256) void k_asset_shade(AssetShadeArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
-    const iron_asset_mesh& m = a.m;
-    const int64_t f = a.face_idx[i];
-    const float t = a.t[i];
-    bool hit = f >= 0 && f < m.n_faces && t < kInfF && t == t;
-    int32_t iv[3] = {0, 0, 0}, it[3] = {0, 0, 0};
-    if (hit)
-        for (int k = 0; k < 3; ++k) {
-            iv[k] = m.faces[3 * f + k];
-            it[k] = m.face_uvs[3 * f + k];
-            if (iv[k] < 0 || iv[k] >= m.n_verts || it[k] < 0 || it[k] >= m.n_uvs) hit = false;
-        }
-    float3 pt = make_float3(0.f, 0.f, 0.f), nrm = pt;
-    float dist = 0.0f, uvx = 0.0f, uvy = 0.0f, mat[kTexMaxC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    SurfHit s;
+    asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s);
     GgxOut g;
     for (int c = 0; c < 3; ++c) g.diffuse[c] = g.specular[c] = g.rgb[c] = 0.0f;
-    bool hl = false;
-    if (hit) {
-        const float3 o = ld3(a.ray_o, i), d = ld3(a.ray_d, i);
-        const float b1 = a.bary[2 * i], b2 = a.bary[2 * i + 1], b0 = (1.0f - b1) - b2;
-        pt = make_float3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);
-        const float3 rel = sub3(pt, o);
-        dist = sqrtf((rel.x * rel.x + rel.y * rel.y) + rel.z * rel.z);
-        uvx = (b0 * m.uvs[2 * (int64_t)it[0]] + b1 * m.uvs[2 * (int64_t)it[1]]) + b2 * m.uvs[2 * (int64_t)it[2]];
-        uvy = (b0 * m.uvs[2 * (int64_t)it[0] + 1] + b1 * m.uvs[2 * (int64_t)it[1] + 1]) + b2 * m.uvs[2 * (int64_t)it[2] + 1];
-        if (m.normals) {
-            const float3 n0 = ld3(m.normals, iv[0]), n1 = ld3(m.normals, iv[1]), n2 = ld3(m.normals, iv[2]);
-            nrm = unit_or_zero(make_float3((b0 * n0.x + b1 * n1.x) + b2 * n2.x, (b0 * n0.y + b1 * n1.y) + b2 * n2.y,
-                                           (b0 * n0.z + b1 * n1.z) + b2 * n2.z));
-        }
-        if (nrm.x == 0.0f && nrm.y == 0.0f && nrm.z == 0.0f) {  // no vertex normals, or they cancel: the face's own
-            const float3 va = ld3(m.verts, iv[0]);
-            nrm = unit_or_zero(cross3(sub3(ld3(m.verts, iv[1]), va), sub3(ld3(m.verts, iv[2]), va)));
-        }
-        hl = texture_fetch<kTexMaxC>(m.material, m.weight, m.tex_h, m.tex_w, 7, uvx, uvy, IRON_TEX_BILINEAR, mat);
-        const float nn[3] = {nrm.x, nrm.y, nrm.z}, vv[3] = {-d.x, -d.y, -d.z};
-        ggx_colocated_point(a.light, dist, nn, vv, mat, mat + 3, mat[6], a.tab_trans, a.tab_diff, g);
+    if (s.hit) {
+        const float nn[3] = {s.nrm.x, s.nrm.y, s.nrm.z}, vv[3] = {-s.d.x, -s.d.y, -s.d.z};
+        ggx_colocated_point(a.light, s.dist, nn, vv, s.mat, s.mat + 3, s.mat[6], a.tab_trans, a.tab_diff, g);
     }
     st3(a.o.color, i, g.rgb[0], g.rgb[1], g.rgb[2]);
     st3(a.o.diffuse_color, i, g.diffuse[0], g.diffuse[1], g.diffuse[2]);
     st3(a.o.specular_color, i, g.specular[0], g.specular[1], g.specular[2]);
-    st3(a.o.normal, i, nrm.x, nrm.y, nrm.z);
-    st3(a.o.points, i, pt.x, pt.y, pt.z);
-    st3(a.o.diffuse_albedo, i, mat[0], mat[1], mat[2]);
-    st3(a.o.specular_albedo, i, mat[3], mat[4], mat[5]);
-    if (a.o.distance) a.o.distance[i] = dist;
-    if (a.o.specular_roughness) a.o.specular_roughness[i] = mat[6];
-    if (a.o.uv) { a.o.uv[2 * i] = uvx; a.o.uv[2 * i + 1] = uvy; }
-    if (a.o.hole) a.o.hole[i] = hl ? 1 : 0;
+    asset_store_maps(a.o, i, s);
 }
 
 }  // namespace iron

@@ -18,7 +18,7 @@ WHAT = "mesh distance"  # what this module's messages begin with
 class MeshBVH:
     """Linear BVH of a triangle mesh on the GPU: vertices [V, 3] (fp32; fp64 is rounded once), faces [F, 3] integer, numpy or
     CUDA tensors.  Built once at construction (one host wait, which reports a face index outside [0, V) or a non-finite
-    referenced vertex as IronError); vertices no face references are ignored.  `query(points)` and `raycast(ray_o, ray_d)` answer
+    referenced vertex as IronError); vertices no face references are ignored.  `query(points)`, `raycast(ray_o, ray_d)` and `occluded(ray_o, ray_d)` answer
     on the current stream."""
 
     def __init__(self, vertices, faces, device=None):
@@ -97,6 +97,29 @@ class MeshBVH:
                                                          float(t_min), float(t_max), t.data_ptr(), idx.data_ptr(), bary.data_ptr(),
                                                          _lib.stream_ptr(self.device)))
         return t, idx, bary
+
+    def occluded(self, ray_o, ray_d, t_min=0.0, t_max=float("inf"), skip_face=None):
+        """ray_o, ray_d [N, 3] -> uint8 [N] device tensor: 1 when any face is met with t in (t_min, t_max].  skip_face [N] integer
+        (optional): that face is ignored for that ray, -1 ignores none.  A non-finite ray or a zero direction gives 0.  The walk
+        shares raycast's triangle and box tests and leaves at the first accepted face: the answer is exactly
+        raycast(ray_o, ray_d, t_min, t_max)[1] >= 0 (csrc/envlight.hip)."""
+        with torch.cuda.device(self.device):
+            o = _args.device_array(ray_o, torch.float32, self.device, "ray_o", (3,), what=WHAT)
+            d = _args.device_array(ray_d, torch.float32, self.device, "ray_d", (3,), what=WHAT)
+            n = int(o.shape[0])
+            if d.shape[0] != n:
+                raise _lib.IronError("ray_o has %d rows, ray_d %d" % (n, d.shape[0]))
+            skip = None
+            if skip_face is not None:
+                skip = _args.device_array(skip_face, torch.int32, self.device, "skip_face", (), what=WHAT)
+                if skip.shape[0] != n:
+                    raise _lib.IronError("ray_o has %d rows, skip_face %d" % (n, skip.shape[0]))
+            occ = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            if n:
+                _lib.check(_lib.load().iron_mesh_occluded(self.workspace.data_ptr(), self.n_faces, o.data_ptr(), d.data_ptr(), n,
+                                                          float(t_min), float(t_max), _lib.ptr(skip), occ.data_ptr(),
+                                                          _lib.stream_ptr(self.device)))
+        return occ
 
 
 def point_mesh_squared_distance(P, V, F):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _args, _lib
+from .envmap import EnvMap  # noqa: F401  (render_asset_env's light)
 from .mesh_distance import MeshBVH
 
 TEX_MODES = {"bilinear": 0, "nearest": 1}
@@ -155,10 +156,9 @@ class MeshAsset:
         dev = torch.device(device) if device is not None else _args.pick_device(WHAT)
         return cls(a["vertices"], a["faces"], a["uvs"], a["face_uvs"], a["material"], weight=a["weight"], normals=normals, device=dev)
 
-    def shade(self, ray_o, ray_d, t, face_idx, bary, light, tables):
-        """iron_asset_shade_ggx on n rays (ray_d unit) -> dict of per-ray device tensors, _lib.ASSET_OUT_FIELDS."""
+    def _shade_buffers(self, n):
+        """The per-ray outputs of the shading entries and the two C structures that describe them and the mesh."""
         dev = self.device
-        n = int(ray_o.shape[0])
         out = {k: torch.empty((n, 3), dtype=torch.float32, device=dev)
                for k in ("color", "diffuse_color", "specular_color", "normal", "points", "diffuse_albedo", "specular_albedo")}
         out["distance"] = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -169,11 +169,48 @@ class MeshAsset:
         mesh = _lib.iron_asset_mesh(self.vertices.data_ptr(), self.vertices.shape[0], self.faces.data_ptr(), self.faces.shape[0],
                                     self.uvs.data_ptr(), self.uvs.shape[0], self.face_uvs.data_ptr(), _lib.ptr(self.normals),
                                     self.material.data_ptr(), _lib.ptr(self.weight), H, W)
-        o = _lib.iron_asset_out(*[out[k].data_ptr() for k in _lib.ASSET_OUT_FIELDS])
+        return out, mesh, _lib.iron_asset_out(*[out[k].data_ptr() for k in _lib.ASSET_OUT_FIELDS])
+
+    def shade(self, ray_o, ray_d, t, face_idx, bary, light, tables):
+        """iron_asset_shade_ggx on n rays (ray_d unit) -> dict of per-ray device tensors, _lib.ASSET_OUT_FIELDS."""
+        dev = self.device
+        n = int(ray_o.shape[0])
+        out, mesh, o = self._shade_buffers(n)
         with torch.cuda.device(dev):
             _lib.check(_lib.load().iron_asset_shade_ggx(C.byref(mesh), float(light), tables[0].data_ptr(), tables[1].data_ptr(),
                                                         ray_o.data_ptr(), ray_d.data_ptr(), t.data_ptr(), face_idx.data_ptr(),
                                                         bary.data_ptr(), n, C.byref(o), _lib.stream_ptr(dev)))
+        return out
+
+    def shade_env(self, ray_o, ray_d, t, face_idx, bary, envmap, tables, n_light=64, n_brdf=64, seed=0, shadow_eps=1e-4, pixel_idx=None,
+                  dump=False):
+        """iron_asset_shade_env on n rays (ray_d unit): direct illumination by `envmap` (EnvMap) with n_light environment samples
+        and n_brdf BRDF samples per ray, combined by the balance heuristic -> the dictionary of `shade`.  pixel_idx [n] int32
+        (default: the ray's position) keys the random numbers, so a subset of the rays with their own indices reproduces the whole
+        call bitwise.  dump=True adds the per-sample "dump_dir" [n, N, 3], "dump_denom" [n, N], "dump_vis" [n, N] uint8 and
+        "dump_contrib" [n, N, 3] (N = n_light + n_brdf, environment samples first) for tests."""
+        dev = self.device
+        n, N = int(ray_o.shape[0]), int(n_light) + int(n_brdf)
+        if n_light < 0 or n_brdf < 0 or N > 1 << 20:
+            raise _lib.IronError("shade_env: n_light and n_brdf must be >= 0 with at most 2^20 samples together")
+        out, mesh, o = self._shade_buffers(n)
+        d = _lib.iron_env_dump(None, None, None, None)
+        if dump:
+            out["dump_dir"] = torch.empty((n, N, 3), dtype=torch.float32, device=dev)
+            out["dump_denom"] = torch.empty((n, N), dtype=torch.float32, device=dev)
+            out["dump_vis"] = torch.empty((n, N), dtype=torch.uint8, device=dev)
+            out["dump_contrib"] = torch.empty((n, N, 3), dtype=torch.float32, device=dev)
+            d = _lib.iron_env_dump(*[out[k].data_ptr() for k in ("dump_dir", "dump_denom", "dump_vis", "dump_contrib")])
+        with torch.cuda.device(dev):
+            pix = None if pixel_idx is None else _args.device_array(pixel_idx, torch.int32, dev, "pixel_idx", (), what=WHAT)
+            if pix is not None and pix.shape[0] != n:
+                raise _lib.IronError("ray_o has %d rows, pixel_idx %d" % (n, pix.shape[0]))
+            env = envmap.c_struct()
+            _lib.check(_lib.load().iron_asset_shade_env(C.byref(mesh), self.bvh.workspace.data_ptr(), C.byref(env), tables[0].data_ptr(),
+                                                        tables[1].data_ptr(), ray_o.data_ptr(), ray_d.data_ptr(), t.data_ptr(),
+                                                        face_idx.data_ptr(), bary.data_ptr(), _lib.ptr(pix), n, int(n_light), int(n_brdf),
+                                                        int(seed) & 0xFFFFFFFF, float(shadow_eps), C.byref(o), C.byref(d),
+                                                        _lib.stream_ptr(dev)))
         return out
 
 
@@ -188,9 +225,10 @@ def _mts_tables(dev):
     return _tables[key]
 
 
-def render_asset_uv(camera, asset, light, uv):
+def render_asset_uv(camera, asset, light, uv, env=None):
     """One ray per entry of uv [H, W, 2] (pixel coordinates of `camera`): the dictionary of render_asset_camera for one sample
-    per pixel.  Pixels go to the ray cast's lanes row-major: one 8x8 pixel tile per 64-lane wave measured slower."""
+    per pixel.  Pixels go to the ray cast's lanes row-major: one 8x8 pixel tile per 64-lane wave measured slower.
+    env: None for the flash of intensity `light`, else the keywords of MeshAsset.shade_env plus `background` (render_asset_env)."""
     _args.refuse_cpu(WHAT, uv, camera.K)
     dev = asset.device
     H, W = int(uv.shape[0]), int(uv.shape[1])
@@ -198,7 +236,14 @@ def render_asset_uv(camera, asset, light, uv):
         ray_o, ray_d, ray_d_norm = camera.get_rays(uv)
         o, d = ray_o.reshape(-1, 3), ray_d.reshape(-1, 3)
         t, face, bary = asset.bvh.raycast(o, d)
-        s = asset.shade(o, d, t, face, bary, light, _mts_tables(dev))
+        if env is None:
+            s = asset.shade(o, d, t, face, bary, light, _mts_tables(dev))
+        else:
+            env = dict(env)
+            background = env.pop("background", False)
+            s = asset.shade_env(o, d, t, face, bary, tables=_mts_tables(dev), **env)
+            if background:  # the map itself behind the asset
+                s["color"] = torch.where((face < 0)[:, None], env["envmap"].lookup(d), s["color"])
     img = lambda x: x.reshape([H, W] + list(x.shape[1:]))  # noqa: E731
     res = {k: img(s[k]) for k in ("color", "diffuse_color", "specular_color", "normal", "diffuse_albedo", "specular_albedo",
                                   "specular_roughness", "distance", "points")}
@@ -223,7 +268,7 @@ def subpixel_uvs(camera, samples_per_axis):
 
 
 @torch.no_grad()
-def render_asset_camera(camera, asset, light, samples_per_axis=1):
+def render_asset_camera(camera, asset, light, samples_per_axis=1, _env=None):
     """Render `asset` (MeshAsset) from `camera` (raytracer.Camera, on the asset's device) under a point light of intensity `light`
     at the camera origin.  Returns render_camera's keys, all [H, W, ...] device tensors: color, diffuse_color, specular_color,
     normal, diffuse_albedo, specular_albedo, specular_roughness, convergent_mask, distance, depth, points, uv, ray_o, ray_d, plus
@@ -237,12 +282,12 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1):
         raise _lib.IronError("samples_per_axis must be >= 1")
     _args.refuse_cpu(WHAT, camera.K)
     if s == 1:
-        res = render_asset_uv(camera, asset, light, camera.get_uv())
+        res = render_asset_uv(camera, asset, light, camera.get_uv(), env=_env and _env(0))
         res["coverage"] = res["convergent_mask"].float()
         return res
     res = None
-    for uv in subpixel_uvs(camera, s):
-        f = render_asset_uv(camera, asset, light, uv)
+    for k, uv in enumerate(subpixel_uvs(camera, s)):
+        f = render_asset_uv(camera, asset, light, uv, env=_env and _env(k))
         if res is None:
             res = f
             res["coverage"] = f["convergent_mask"].float()
@@ -256,3 +301,15 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1):
     res["convergent_mask"] = res["coverage"] >= 0.5
     res["uv"] = camera.get_uv()
     return res
+
+
+@torch.no_grad()
+def render_asset_env(camera, asset, envmap, n_light=64, n_brdf=64, seed=0, samples_per_axis=1, background=False, shadow_eps=1e-4):
+    """Render `asset` from `camera` under the environment map `envmap` (EnvMap on the asset's device): direct illumination with
+    visibility, n_light environment samples and n_brdf BRDF samples per ray combined by the balance heuristic (csrc/envlight.hip,
+    DESIGN.md §16).  Returns render_asset_camera's dictionary with the same keys; distance and depth keep their meaning.  Sub-pixel
+    frames are averaged exactly as there, sample k of the sub-pixel grid with seed + k.  background=True fills `color` of every
+    ray that misses with envmap.lookup(ray_d) (before the averaging); the default leaves zeros there, like the flash render."""
+    return render_asset_camera(camera, asset, 0.0, samples_per_axis=samples_per_axis,
+                               _env=lambda k: {"envmap": envmap, "n_light": n_light, "n_brdf": n_brdf, "seed": int(seed) + k,
+                                               "shadow_eps": shadow_eps, "background": background})
