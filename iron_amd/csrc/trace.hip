@@ -11,11 +11,13 @@
 //              at a time in march order, as work items of kSamplerSeg blocks, and the search stops at the
 //              first block that holds a negative sample (the reference evaluates all n_steps and then
 //              takes the first sign change: same result).
-//   k_bisect_a 32 bracketed rays per wave, each bisected until ITS interval is <= 2*threshold;
-//              records the per-ray count and atomicMax-es it into the ray's chunk.
-//   k_bisect_b the reference loops while ANY ray of the call is unfinished and updates ALL rays, so
-//              every ray runs the chunk-wide maximum count: finish the remaining iterations, then
-//              the final mid-point evaluation.
+//   k_bisect_a 32 bracketed rays per wave, slots refilled like k_sphere's: each ray is bisected until ITS interval is
+//              <= 2*threshold and then evaluates the mid-point it ends on -- its result if no ray of its chunk needs
+//              more iterations, and the value the next iteration consumes if one does (made here too once the chunk's
+//              table shows it is needed); the counts are atomicMax-ed into the ray's chunk, once per wave and chunk.
+//   k_bisect_b the reference loops while ANY ray of the call is unfinished and updates ALL rays, so every ray runs the
+//              chunk-wide maximum count: the rays whose own count is below it (k_bisect_list) finish the remaining
+//              iterations on the value phase a kept; the last evaluation is the result.  No such ray: no weight ring.
 //
 // Tails (an experiment kept behind IRON_TRACE_SPLIT = 2..4, default 1 = off): a persistent kernel ends on its slowest rays'
 // chains of dependent evaluations (up to 17 / 16 / 10 of ~90 us each) with part of the chip idle.  The split form cuts the
@@ -28,6 +30,7 @@
 // 65/35/80 %: 9.1-9.3) -- stream priorities do not order workgroup dispatch between two resident persistent grids.
 #include <atomic>
 #include <mutex>
+#include <stddef.h>
 #include <stdlib.h>
 #include "mlp_h2.h"
 #include "ggx_core.h"
@@ -54,7 +57,8 @@ struct TraceCounters {  // zeroed at the start of every call
     SamplerQ smp;       // the dense sampler's list: n_list = rays appended by k_sphere
     int n_root;         // rays with a sign-change bracket
     int root_head_a;
-    int root_head_b;
+    int root_head_b;    // the queue of k_bisect_b's list; with n_root_b behind it, zeroed again at the start of phase b
+    int n_root_b;       // rays whose chunk's count is above their own (k_bisect_list)
     long long n_evals;
     long long n_sphere_conv;
     long long n_evals_sphere;
@@ -565,6 +569,9 @@ __device__ __forceinline__ void sampler_write_no_root(const TraceArgs& a, int ra
 
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_ARGS) {
+    SamplerQ* const q = w.ovf_pass ? &w.cnt->ovf : &w.cnt->smp;
+    const int n_list = q->n_list;
+    if (n_list == 0) return;   // (uniform over the grid) an empty list, as the screen's overflow list usually is: no weight ring is started
     BE be;
     be.init(net, hs, hm);
     const int lane = be.lane;
@@ -572,8 +579,6 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
     const int slot = j / kSamplerBlock, s_in = j % kSamplerBlock;   // this lane's ray slot and its sample within the slot's block
     const int slot_lane0 = slot * kSamplerBlock;
     const unsigned slot_bits = (kSamplerBlock == 32 ? 0xffffffffu : ((1u << kSamplerBlock) - 1u)) << slot_lane0;
-    SamplerQ* const q = w.ovf_pass ? &w.cnt->ovf : &w.cnt->smp;
-    const int n_list = q->n_list;
     const bool dyn = w.cont_cap > 0;
     const long long n_tickets = (long long)n_list + (dyn ? (long long)w.cont_cap : 0ll);
     long long evals = 0;
@@ -1178,158 +1183,238 @@ __device__ __forceinline__ long long ray_chunk(const TraceArgs& a, int ray) {
     return a.chunk > 0 ? gi / a.chunk : 0;
 }
 
-// rootfind, per-ray part (raytracer.py:199-217)
+// ---- rootfind (raytracer.py:199-220) ------------------------------------------------------------------------------------------------
+// The reference evaluates T + 1 mid-points per bracketed ray, T = the largest own count among the rays of its chunk: mid_1 .. mid_T
+// inside the loop (every ray is updated while ANY is unfinished) and mid_{T+1} after it.  "Iteration t" and "the final evaluation"
+// compute the same thing, f(o + d * mid_t), so a ray that has done its own k iterations evaluates mid_{k+1} in the slot it already
+// holds (k_bisect_a: k + 1 evaluations, or more where its chunk's count is already known to be higher) and leaves that value with
+// lo, hi and k.  If T == k it is the ray's result; if T > k it is the f that iteration k + 1 consumes, and the ray needs exactly
+// T - k more evaluations, the last of which is its result (k_bisect_b).
+// Both kernels hold 32 rays per wave and refill a retired slot at once (ballot -> rank -> one atomicAdd per wave, as k_sphere).
+// A ray's evaluations, their order and what is made of them are the reference's; only where they run changes.
+
+// the chunk counters after a pass, by one leader lane per distinct chunk among the wave's rays: chunk_roots += the rays loaded for
+// this pass, chunk_iters = max(.., bound), a lane's bound being a count its chunk is now known to reach (0: none).  A plain look
+// first: the table only grows and every wave posts the same few counts, so nearly all of the atomicMax-es are never issued.
+// Returns the largest bound among the wave's rays of the lane's chunk.  (ballots are read by their low word: lanes 32..63 mirror 0..31)
+__device__ __forceinline__ int bisect_count_chunks(const TraceWs& w, int lane, bool active, bool fresh, int ch, int bound) {
+    unsigned left = (unsigned)__ballot(active);
+    int wave_bound = 0;
+    while (left) {
+        const int lead = __ffs(left) - 1;
+        const int ch0 = __shfl(ch, lead, 64);
+        const bool mine = active && ch == ch0;
+        const unsigned came = (unsigned)__ballot(mine && fresh);
+        int b = mine ? bound : 0;
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) b = max(b, __shfl_xor(b, off, 64));
+        if (lane == lead) {
+            if (came) atomicAdd(&w.chunk_roots[ch0], __popc(came));
+            if (b > __hip_atomic_load(&w.chunk_iters[ch0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&w.chunk_iters[ch0], b);
+        }
+        if (mine) wave_bound = b;
+        left &= ~(unsigned)__ballot(mine);
+    }
+    return wave_bound;
+}
+
+// the free slots' places in a list of n entries behind *head: the wave's base, and how many of its nfree requests are served
+struct SlotDraw { int base, avail; };
+__device__ __forceinline__ SlotDraw bisect_draw(int* head, int lane, int nfree, int n) {
+    int base = 0;
+    if (lane == 0) base = atomicAdd(head, nfree);
+    base = __shfl(base, 0, 64);
+    const int left = n - base;
+    return SlotDraw{base, left < 0 ? 0 : (left > nfree ? nfree : left)};
+}
+
+// a retired ray's result (raytracer.py:75-78: the sampler's mask overwrites convergent)
+__device__ __forceinline__ void bisect_write(const TraceArgs& a, int ray, float qx, float qy, float qz, float f, float mid) {
+    a.conv[ray] = 1;
+    a.points[3 * (size_t)ray] = qx; a.points[3 * (size_t)ray + 1] = qy; a.points[3 * (size_t)ray + 2] = qz;
+    a.sdf[ray] = f;
+    a.dist[ray] = mid;
+}
+
+// per-ray part (raytracer.py:199-217): the ray's own iterations until ITS interval is <= 2 * threshold (none for a bracket without
+// a sign change), then the evaluation of the mid-point it ends on.  Leaves lo, hi, the iterations done k and that value (in root_flo,
+// dead once the ray is loaded), writes the ray's outputs as if it were final, and counts the ray into its chunk.
+// The chunk table is kept as a running lower bound of the chunk's count T: a ray posts k + 1 while it still has an iteration of its own
+// to make, so the table ends as the largest own count, as the reference's loop counts it.  A ray whose own iterations are done looks
+// at it, and at what its own wave's rays of the same chunk post in this pass: a bound above its k proves that iteration k + 1 is
+// needed, and the ray makes it here, in its slot, on the value it has just evaluated ("follows") instead of waiting for phase b.
+// That matters because a ray far below its chunk's count (a bracket without a sign change in a chunk that runs 7) is a chain of
+// T + 1 dependent evaluations: left to phase b, the chain is that kernel's whole duration with the chip idle around it (measured:
+// phase b took the same 0.63 ms with two thirds of its evaluations removed); here it runs under the other rays' work.  How many of a
+// ray's T + 1 evaluations run in which phase depends on timing; which points are evaluated, and every result, do not.
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_a(IRON_TRACE_KERNEL_ARGS) {
+    const int n_root = w.cnt->n_root;
+    if (n_root == 0) return;   // (uniform over the grid) nothing to bisect: no weight ring is started
     BE be;
     be.init(net, hs, hm);
     const int lane = be.lane;
     const int j = lane & 31;
-    const int n_root = w.cnt->n_root;
     const float thr2 = 2.0f * a.thr;
     long long evals = 0;
-    bool has_batch = false, exhausted = false, valid = false, work = false;
-    int li = 0, ray = 0, k = 0;
+    bool active = false, exhausted = false, work = false, fresh = false;
+    int li = 0, ray = 0, k = 0, ch = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, lo = 0.f, hi = 0.f, mid = 0.f;
-    auto store = [&]() {
-        if (valid && lane < 32) {
-            w.root_lo[li] = lo; w.root_hi[li] = hi;
-            w.root_k[li] = k;
-            const long long ch = ray_chunk(a, ray);
-            atomicAdd(&w.chunk_roots[ch], 1);
-            if (k > 0) atomicMax(&w.chunk_iters[ch], k);
-        }
-    };
     for (;;) {
-        while (!has_batch && !exhausted) {  // wave-local: batches that need no evaluation are finished here
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&w.cnt->root_head_a, 32);
-            base = __shfl(base, 0, 64);
-            if (base >= n_root) { exhausted = true; break; }
-            li = base + j;
-            valid = li < n_root;
-            ray = valid ? w.root_list[li] : 0;
-            ox = oy = oz = dx = dy = dz = lo = hi = 0.f;
-            work = false;
-            if (valid) {
+        // ---- refill free slots from the root list
+        const unsigned act = (unsigned)__ballot(active);
+        const int nfree = 32 - __popc(act);
+        if (nfree > 0 && !exhausted) {
+            const SlotDraw dr = bisect_draw(&w.cnt->root_head_a, lane, nfree, n_root);
+            if (dr.base + nfree >= n_root) exhausted = true;
+            if (!active && lane_rank(~act, j) < dr.avail) {
+                li = dr.base + lane_rank(~act, j);
+                ray = w.root_list[li];
+                ch = (int)ray_chunk(a, ray);
                 ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
                 lo = w.root_lo[li]; hi = w.root_hi[li];
                 work = (w.root_flo[li] > 0.0f) && (w.root_fhi[li] < 0.0f);
+                mid = (lo + hi) / 2.0f;
+                k = 0;
+                active = true;
+                fresh = true;
             }
-            mid = (lo + hi) / 2.0f;
-            k = 0;
-            if (__ballot(work) != 0ull) has_batch = true;
-            else store();
         }
-        if (!be.any(has_batch)) break;
-        evals += has_batch ? __popc((unsigned)__ballot(work)) : 0;
-        {   // the batch's state waits in LDS while the evaluation has the registers
-            const int flags = (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0) | (work ? 8 : 0);
+        const unsigned act2 = (unsigned)__ballot(active);
+        if (!be.any(act2 != 0u)) break;
+        evals += __popc(act2);
+        {   // the rays' state waits in LDS while the evaluation has the registers
+            const int flags = (active ? 1 : 0) | (exhausted ? 2 : 0) | (work ? 4 : 0) | (fresh ? 8 : 0);
             be.park(0, flags); be.park(1, li); be.park(2, ray); be.park(3, k);
             park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             be.park(10, lo); be.park(11, hi); be.park(12, mid); park_i64(be, 13, evals);
+            be.park(15, ch);
         }
         const float f = be.eval(ox + dx * mid, oy + dy * mid, oz + dz * mid);
         {
-            const int flags = be.unpark(0, (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0) | (work ? 8 : 0));
-            has_batch = flags & 1; exhausted = flags & 2; valid = flags & 4; work = flags & 8;
+            const int flags = be.unpark(0, (active ? 1 : 0) | (exhausted ? 2 : 0) | (work ? 4 : 0) | (fresh ? 8 : 0));
+            active = flags & 1; exhausted = flags & 2; work = flags & 4; fresh = flags & 8;
             li = be.unpark(1, li); ray = be.unpark(2, ray); k = be.unpark(3, k);
             unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
             lo = be.unpark(10, lo); hi = be.unpark(11, hi); mid = be.unpark(12, mid);
             evals = unpark_i64(be, 13, evals);
+            ch = be.unpark(15, ch);
         }
-        if (has_batch) {
-            if (work) {
-                if (f > 0.0f) lo = mid; else hi = mid;
-                mid = (lo + hi) / 2.0f;
-                ++k;
-                work = ((hi - lo) > thr2) && (k < 64);  // k < 64: exit bound for non-finite intervals
-            }
-            if (__ballot(work) == 0ull) {
-                store();
-                has_batch = false;
-                ox = oy = oz = dx = dy = dz = mid = 0.f;
-            }
+        // outcome of the pass for the slot (straight-line): an iteration of the ray's own, one its chunk is known to need, or the
+        // ray's last evaluation here
+        const bool own = active && work;
+        const float qx = ox + dx * mid, qy = oy + dy * mid, qz = oz + dz * mid;   // (the same expressions: the evaluated point)
+        const float f_lo = (f > 0.0f) ? mid : lo, f_hi = (f > 0.0f) ? hi : mid;    // the interval after an iteration on f
+        int bound = 0;
+        if (own) {
+            work = ((f_hi - f_lo) > thr2) && (k + 1 < 64);  // k < 64: exit bound for non-finite intervals
+            bound = k + 1 + (work ? 1 : 0);
+        }
+        const int wave_bound = bisect_count_chunks(w, lane, active, fresh, ch, bound);
+        fresh = false;
+        const int table = (active && !own) ? __hip_atomic_load(&w.chunk_iters[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        const bool follow = active && !own && max(table, wave_bound) > k;
+        const bool retire = active && !own && !follow;
+        if (retire && lane < 32) {
+            w.root_lo[li] = lo; w.root_hi[li] = hi;
+            w.root_k[li] = k;
+            w.root_flo[li] = f;
+            bisect_write(a, ray, qx, qy, qz, f, mid);
+        }
+        if (own || follow) {
+            lo = f_lo; hi = f_hi;
+            mid = (lo + hi) / 2.0f;
+            ++k;
+        }
+        if (retire) {
+            active = false;
+            ox = oy = oz = dx = dy = dz = mid = 0.f;
         }
     }
     be.finish();
     if (lane == 0) atomicAdd((unsigned long long*)&w.cnt->n_evals, (unsigned long long)evals);
 }
 
-// rootfind, chunk-global remainder + final evaluation (raytracer.py:204-219)
+// the rays phase b has to touch: those whose chunk's count (MAX-reduced over the ranks by then, in the multi-rank form) is above
+// their own.  Their list positions are compacted into root_fhi's storage (dead like root_flo); cnt->n_root_b counts them.
+__global__ void k_bisect_list(TraceArgs a, TraceWs w) {
+    const int n_root = w.cnt->n_root;
+    int* const list = reinterpret_cast<int*>(w.root_fhi);
+    const int lane = threadIdx.x & 63;
+    for (int i0 = blockIdx.x * blockDim.x; i0 < n_root; i0 += gridDim.x * blockDim.x) {
+        const int li = i0 + threadIdx.x;
+        const bool more = li < n_root && w.chunk_iters[ray_chunk(a, w.root_list[li])] - w.root_k[li] > 0;
+        const unsigned long long m = __ballot(more);
+        int base = 0;
+        if (lane == 0 && m) base = atomicAdd(&w.cnt->n_root_b, __popcll(m));
+        base = __shfl(base, 0, 64);
+        if (more) list[base + lane_rank64(m, lane)] = li;
+    }
+}
+
+// chunk-global remainder (raytracer.py:204-219): a listed ray applies the update its stored value decides and evaluates
+// `remaining` more mid-points; the last one is its result.
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_b(IRON_TRACE_KERNEL_ARGS) {
+    const int n_list = w.cnt->n_root_b;
+    if (n_list == 0) return;   // (uniform over the grid) every ray ran to its chunk's count in phase a: no weight ring is started
     BE be;
     be.init(net, hs, hm);
     const int lane = be.lane;
     const int j = lane & 31;
-    const int n_root = w.cnt->n_root;
+    const int* const list = reinterpret_cast<const int*>(w.root_fhi);
     long long evals = 0;
-    bool has_batch = false, exhausted = false, valid = false;
-    int li = 0, ray = 0, remaining = 0;
+    bool active = false, exhausted = false;
+    int ray = 0, remaining = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, lo = 0.f, hi = 0.f, mid = 0.f;
     for (;;) {
-        if (!has_batch && !exhausted) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&w.cnt->root_head_b, 32);
-            base = __shfl(base, 0, 64);
-            if (base >= n_root) {
-                exhausted = true;
-            } else {
-                li = base + j;
-                valid = li < n_root;
-                ray = valid ? w.root_list[li] : 0;
-                ox = oy = oz = dx = dy = dz = lo = hi = 0.f;
-                remaining = 0;
-                if (valid) {
-                    ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
-                    lo = w.root_lo[li]; hi = w.root_hi[li];
-                    remaining = w.chunk_iters[ray_chunk(a, ray)] - w.root_k[li];
-                }
+        const unsigned act = (unsigned)__ballot(active);
+        const int nfree = 32 - __popc(act);
+        if (nfree > 0 && !exhausted) {
+            const SlotDraw dr = bisect_draw(&w.cnt->root_head_b, lane, nfree, n_list);
+            if (dr.base + nfree >= n_list) exhausted = true;
+            if (!active && lane_rank(~act, j) < dr.avail) {
+                const int li = list[dr.base + lane_rank(~act, j)];
+                ray = w.root_list[li];
+                ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
+                lo = w.root_lo[li]; hi = w.root_hi[li];
                 mid = (lo + hi) / 2.0f;
-                has_batch = true;
+                if (w.root_flo[li] > 0.0f) lo = mid; else hi = mid;   // iteration k + 1 on the value phase a left
+                mid = (lo + hi) / 2.0f;
+                remaining = w.chunk_iters[ray_chunk(a, ray)] - w.root_k[li];
+                active = true;
             }
         }
-        if (!be.any(has_batch)) break;
-        const unsigned rem = has_batch ? (unsigned)__ballot(remaining > 0) : 0u;
-        float qx = ox + dx * mid, qy = oy + dy * mid, qz = oz + dz * mid;
-        {   // the batch's state waits in LDS while the evaluation has the registers
-            const int flags = (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0);
-            be.park(0, flags); be.park(1, li); be.park(2, ray); be.park(3, remaining);
-            park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
-            be.park(10, lo); be.park(11, hi); be.park(12, mid); park_i64(be, 13, evals);
-            be.park(15, (int)rem);
+        const unsigned act2 = (unsigned)__ballot(active);
+        if (!be.any(act2 != 0u)) break;
+        evals += __popc(act2);
+        {   // the rays' state waits in LDS while the evaluation has the registers
+            const int flags = (active ? 1 : 0) | (exhausted ? 2 : 0);
+            be.park(0, flags); be.park(1, ray); be.park(2, remaining);
+            park_vec6(be, 3, ox, oy, oz, dx, dy, dz);
+            be.park(9, lo); be.park(10, hi); be.park(11, mid); park_i64(be, 12, evals);
         }
-        const float f = be.eval(qx, qy, qz);
+        const float f = be.eval(ox + dx * mid, oy + dy * mid, oz + dz * mid);
         {
-            const int flags = be.unpark(0, (has_batch ? 1 : 0) | (exhausted ? 2 : 0) | (valid ? 4 : 0));
-            has_batch = flags & 1; exhausted = flags & 2; valid = flags & 4;
-            li = be.unpark(1, li); ray = be.unpark(2, ray); remaining = be.unpark(3, remaining);
-            unpark_vec6(be, 4, ox, oy, oz, dx, dy, dz);
-            lo = be.unpark(10, lo); hi = be.unpark(11, hi); mid = be.unpark(12, mid);
-            evals = unpark_i64(be, 13, evals);
-            qx = ox + dx * mid; qy = oy + dy * mid; qz = oz + dz * mid;   // (the same expressions: the evaluated point)
+            const int flags = be.unpark(0, (active ? 1 : 0) | (exhausted ? 2 : 0));
+            active = flags & 1; exhausted = flags & 2;
+            ray = be.unpark(1, ray); remaining = be.unpark(2, remaining);
+            unpark_vec6(be, 3, ox, oy, oz, dx, dy, dz);
+            lo = be.unpark(9, lo); hi = be.unpark(10, hi); mid = be.unpark(11, mid);
+            evals = unpark_i64(be, 12, evals);
         }
-        const unsigned rem_b = (unsigned)be.unpark(15, (int)rem);
-        if (has_batch) {
-            if (rem_b) {
-                evals += __popc(rem_b);
-                if (remaining > 0) {
-                    if (f > 0.0f) lo = mid; else hi = mid;
-                    mid = (lo + hi) / 2.0f;
-                    --remaining;
-                }
-            } else {  // this was the final mid-point evaluation (raytracer.py:218-219)
-                evals += __popc((unsigned)__ballot(valid));
-                if (valid && lane < 32) {  // raytracer.py:75-78: the sampler's mask overwrites convergent
-                    a.conv[ray] = 1;
-                    a.points[3 * (size_t)ray] = qx; a.points[3 * (size_t)ray + 1] = qy; a.points[3 * (size_t)ray + 2] = qz;
-                    a.sdf[ray] = f;
-                    a.dist[ray] = mid;
-                }
-                has_batch = false;
-                ox = oy = oz = dx = dy = dz = mid = 0.f;
-            }
+        // outcome of the pass for the slot (straight-line): the ray's last evaluation, or one more iteration
+        const bool retire = active && remaining <= 1;
+        const float qx = ox + dx * mid, qy = oy + dy * mid, qz = oz + dz * mid;   // (the same expressions: the evaluated point)
+        if (retire && lane < 32) bisect_write(a, ray, qx, qy, qz, f, mid);
+        if (active && !retire) {
+            if (f > 0.0f) lo = mid; else hi = mid;
+            mid = (lo + hi) / 2.0f;
+            --remaining;
+        }
+        if (retire) {
+            active = false;
+            ox = oy = oz = dx = dy = dz = mid = 0.f;
         }
     }
     be.finish();
@@ -1543,6 +1628,18 @@ static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceAr
     w2.sampler_list = w.scr.ovf_list;
     w2.cont_cap = 0;
     launch_trace_kernel(kSampler, true, sdf, a, w2, units, st);
+}
+
+// phase b of the bisection: the list of the rays that have iterations left, then the kernel that runs them.  `again`: the
+// counters are not fresh from the call's memset (iron_trace_phase 1: the chunk table may have changed since phase 0, and a
+// repeated phase 1 starts over from what phase a left)
+static int run_bisect_b(bool h2, const iron_net* sdf, const TraceArgs& a, const TraceWs& w, int64_t nk, bool again, hipStream_t st) {
+    static_assert(offsetof(TraceCounters, n_root_b) == offsetof(TraceCounters, root_head_b) + sizeof(int), "zeroed together");
+    if (again) IRON_HIP_TRY(hipMemsetAsync(&w.cnt->root_head_b, 0, 2 * sizeof(int), st));
+    const int64_t gb = (nk + 255) / 256;
+    hipLaunchKernelGGL(k_bisect_list, dim3((unsigned)(gb < 1024 ? (gb > 0 ? gb : 1) : 1024)), dim3(256), 0, st, a, w);
+    launch_trace_kernel(kBisectB, h2, sdf, a, w, (nk + 31) / 32, st);
+    return IRON_OK;
 }
 
 // what iron_trace_phase and iron_trace_stage check alike; `args_ok`: the entry's own pointers, which count only for a call
@@ -1804,7 +1901,8 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
             }
         } else {
             ProfScope ps(IRON_PROF_BISECT_B, sk);
-            launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, sk);
+            const int rcb = run_bisect_b(h2, sdf, a, w, nk, true, sk);
+            if (rcb != IRON_OK) return rcb;
         }
         if (k > 0) IRON_HIP_TRY(hipEventRecord(S->join[k - 1], sk));
     }
@@ -1856,11 +1954,11 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
         hipLaunchKernelGGL(k_stage_sampler_init, dim3(gb), dim3(256), 0, st, a, w, in0);
         run_sampler(h2, screen, sdf, a, w, n, st);
         launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, st);
-        launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, st);
+        { const int rcb = run_bisect_b(h2, sdf, a, w, n, false, st); if (rcb != IRON_OK) return rcb; }
     } else {                     // rootfind (:199-220): in0 = f_low, in1 = f_high, in2 = d_low, in3 = d_high
         hipLaunchKernelGGL(k_stage_root_init, dim3(gb), dim3(256), 0, st, w, (int)n, in0, in1, in2, in3);
         launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, st);
-        launch_trace_kernel(kBisectB, h2, sdf, a, w, tiles, st);
+        { const int rcb = run_bisect_b(h2, sdf, a, w, n, false, st); if (rcb != IRON_OK) return rcb; }
     }
     if (h2) envelope_scan(sdf, sdf_out, n, nullptr, 1, st);
     IRON_HIP_TRY(hipGetLastError());
