@@ -745,7 +745,7 @@ int iron_sdf_screen_forward(const iron_net_t* net, const float* x, int64_t n, fl
  * outputs and iron_trace_stats are those of the unscreened sampler.  The margin is empirical: a guard (iron_net_numeric_status
  * bit 3) turns the screen off for a network whose exactly evaluated samples came within half the margin, for every call that
  * starts after the call that raised it has completed (the flag is a pinned host word; calls already queued behind it still screen).
- * The trace workspace (iron_trace_workspace_bytes) holds the screen's lists on every path: ~105 bytes per ray.
+ * The trace workspace (iron_trace_workspace_bytes) holds the screen's lists on every path: ~113 bytes per ray.
  *   iron_set_sampler_screen:   on = 1 screen, 0 don't, -1 the default (IRON_SAMPLER_SCREEN=0: off, else on).  Process-wide;
  *                              returns the previous state.
  *   iron_sampler_screen_debug: test hooks, process-wide.  what 0: value > 0 forces the margin delta (0 restores the calibrated
@@ -785,6 +785,21 @@ int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
 int32_t iron_set_sampler_stride(int32_t on);
 int iron_trace_stride_counts(const void* workspace, double* out, void* stream);
 int iron_trace_stride_detail(const void* workspace, double* out, void* stream);
+
+/* The resolve's two rounds (csrc/trace.hip k_resolve_list; results do not depend on them).  A ray's outcome uses the exact value of
+ * its first listed sample that is negative and of the sample before it.  The samples a ray lists behind its first listed one with a
+ * negative screened value are deferred: round 1 evaluates the others, round 2 the deferred ones that lie in front of what round 1
+ * left as the ray's first negative sample (usually none).  out[1] of iron_trace_screen_counts still counts every listed sample:
+ * evaluated, or settled without an evaluation.  A call that collects iron_trace_stats evaluates every listed sample (round 2 takes
+ * all deferred ones), so that the counts and guard maxima read after it are those of the whole list; the guards of a call that
+ * does not collect them see the evaluated samples only.
+ *   iron_set_resolve_defer:   on = 1 two rounds, 0 every listed sample in one, -1 the default (IRON_RESOLVE_DEFER=0: off, else on).
+ *                             Process-wide; returns the previous state.
+ *   iron_trace_resolve_counts: synchronises `stream`; out[4] from the workspace of the last traced call: out[0] / out[1] exact
+ *                             evaluations of listed samples made by round 1 / round 2 (deferral off: all in out[0]), out[2] / out[3]
+ *                             entries on round 1's / round 2's list. */
+int32_t iron_set_resolve_defer(int32_t on);
+int iron_trace_resolve_counts(const void* workspace, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the

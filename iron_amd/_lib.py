@@ -208,6 +208,8 @@ SYMBOLS = {
     "iron_set_sampler_stride": (_I32, [_I32]),
     "iron_trace_stride_counts": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "iron_trace_stride_detail": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "iron_set_resolve_defer": (_I32, [_I32]),
+    "iron_trace_resolve_counts": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),

@@ -1,6 +1,7 @@
 // Sphere tracer: RayTracer.forward = sphere_tracing + ray_sampler + rootfind
 // (models/raytracer.py:45-220) as persistent kernels on one stream, no host sync: the four below, and on the h2 core the screened
-// form of the sampler (k_sampler_screen + k_screen_resolve + k_screen_fin_*, then k_sampler on the rays that overflowed).
+// form of the sampler (k_sampler_screen + k_resolve_list / k_screen_resolve in two rounds + k_screen_fin_*, then k_sampler on the rays
+// that overflowed).
 //
 //   k_sphere   one wave owns 32 ray slots.  Every pass evaluates the SDF MLP for all 32 slots, then
 //              each slot steps or retires; retired slots are refilled from a global ray queue
@@ -85,6 +86,10 @@ struct TraceCounters {  // zeroed at the start of every call
     long long n_obs_res;       // ... k_screen_resolve's exact value of a listed sample against its screened predecessor,
     long long n_obs_pair;      // ... k_screen_fin_entries' exact values of two adjacent listed samples
     unsigned slope_march_bits, slope_res_bits, slope_pair_bits;   // the largest ratio of each source (f32 bits)
+    // the resolve's two rounds (read through iron_trace_resolve_counts)
+    int n_res1, n_res2;    // entries on round 1's / round 2's index list (k_resolve_list)
+    int res_head2;         // round 2's queue (round 1's: res_head)
+    long long n_eval_r1, n_eval_r2;   // exact evaluations of listed samples made by each round (deferral off: all in n_eval_r1)
 };
 
 // The screened sampler's state (see k_sampler_screen)
@@ -96,7 +101,7 @@ struct ResolveEntry {   // one uncertain sample: written by k_sampler_screen, f_
     float f_prev1;      // screened value of sample s - 1 (the previous item's last sample for s % block == 0; 0 for s == 0)
     float f_ex;         // exact (h2) value
     float ld;           // the ray's ld (stride_ld; 0: the ray marched without the slope bound), for the resolve's slope guard
-    int pad;
+    int mark;           // kEntDeferred: listed behind a listed sample of its ray with f1 < 0 | kEntRound2: taken by round 2 after all
 };
 static_assert(sizeof(ResolveEntry) == 32, "resolve entry: two per 64-byte line");
 struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
@@ -118,7 +123,10 @@ struct ScreenWs {
     PendRec* rec;            // [rays of the call] by ray id
     int* pend_list;          // [rays of the part]
     int* ovf_list;           // [rays of the part]
-    uint8_t* ray_state;      // [rays of the call] by ray id (zeroed at the start of a call): kRayPending | kRayOverflowed
+    uint8_t* ray_state;      // [rays of the call] by ray id (zeroed at the start of a call): kRayPending [| kRayNegListed] | kRayOverflowed
+    int* res_idx;            // [cap] the resolve's index list of the round that runs (k_resolve_list)
+    int defer;               // kDeferOn: samples behind a ray's first listed f1 < 0 wait for round 2 | kDeferAudit: round 2 takes them all
+    int res_round;           // k_screen_resolve: 0 every listed sample in list order, 1 / 2 the round's index list
 };
 
 // margin of the screen: delta = max(K * max|f_screen - f_h2| on the calibration set, floor).  EMPIRICAL, not a certified bound:
@@ -151,6 +159,9 @@ static_assert(kStrideMax >= 1 && kStrideMax <= 16, "stride field of the slot's p
 constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
 constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
 constexpr uint8_t kRayOverflowed = 1;  // ray_state: the ray's samples did not fit the list; k_sampler marches it again
+constexpr uint8_t kRayNegListed = 4;   // ray_state, with kRayPending: the ray has listed a sample with f1 < 0 (carried like kRayPending)
+constexpr int kEntDeferred = 1, kEntRound2 = 2;   // ResolveEntry::mark
+constexpr int kDeferOn = 1, kDeferAudit = 2;      // ScreenWs::defer
 __device__ __forceinline__ float screen_delta(const ScreenWs& s) {
     return s.delta_override > 0.0f ? s.delta_override : fmaxf(kScreenK * __uint_as_float(*s.calib), kScreenFloor);
 }
@@ -492,13 +503,13 @@ __device__ __forceinline__ QueueBases sampler_queue_bases(SamplerQ* q, int lane,
     return QueueBases{__shfl(v, 0, 64), __shfl(v, 1, 64)};
 }
 // a publishing slot's item word [ray + 1][item_pos / item_unit][prev_f], stored by the slot's first lane with ORDER if it fits;
-// mark_pending: the ray's pending bit travels in ray_state, written before the item (so ORDER is release, and the taker acquires)
+// state != 0: the ray's pending bits travel in ray_state, written before the item (so ORDER is release, and the taker acquires)
 template <int ORDER>
 __device__ __forceinline__ void sampler_publish_item(const TraceWs& w, int pbase, unsigned pub_slots, int slot, bool first_lane, int ray, int item_pos,
-                                                     int item_unit, float prev_f, bool mark_pending) {
+                                                     int item_unit, float prev_f, uint8_t state) {
     const int c = pbase + __popc(pub_slots & ((1u << slot) - 1u));
     if (first_lane && c < w.cont_cap) {
-        if (mark_pending) w.scr.ray_state[ray] = kRayPending;
+        if (state) w.scr.ray_state[ray] = state;
         const unsigned long long item = (unsigned long long)(unsigned)(ray + 1) | ((unsigned long long)(unsigned)(item_pos / item_unit) << kContRayBits) |
                                         ((unsigned long long)__float_as_uint(prev_f) << 32);
         __hip_atomic_store(&w.cont[c], item, ORDER, __HIP_MEMORY_SCOPE_AGENT);
@@ -594,7 +605,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         if (pub_slots | need_slots) {
             const QueueBases qb = sampler_queue_bases(q, lane, need_slots, pub_slots);
             if (publish) {
-                sampler_publish_item<__ATOMIC_RELAXED>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, blk, 1, prev_f, false);
+                sampler_publish_item<__ATOMIC_RELAXED>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, blk, 1, prev_f, 0);
                 publish = false;
             }
             if (!has_ray && ticket < 0 && !retired) {
@@ -673,7 +684,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // certainly negative if f1 < -delta, uncertain otherwise (NaN and zeros included).  A ray whose samples before its first certainly-
 // negative one are all certainly positive (or that ends with all of them certainly positive) is decided here, exactly as k_sampler
 // decides it.  Otherwise its uncertain samples before that point go to the resolve list and the ray ends "pending" at its first
-// certainly-negative sample (or its end); k_screen_resolve evaluates the listed samples on the h2 core, 32 per wave from any rays,
+// certainly-negative sample (or its end); k_screen_resolve evaluates the listed samples on the h2 core, 32 per wave from any rays
+// (those behind a ray's first listed f1 < 0 only where they can still matter: the rounds, see k_resolve_list),
 // and k_screen_fin_* give each pending ray the bracket, root-list entry or zeros k_sampler would have written.  A ray whose samples
 // do not fit the list is marched again from its start by k_sampler on a second list.  n_evals still counts what k_sampler evaluates.
 // A wave screens 64 samples per pass, 8 ray slots of 8 (k_sampler: 32, 4 slots, lanes j and j + 32 on one point): the screen's
@@ -769,6 +781,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     unsigned ev_scr = 0;   // per wave: screened evaluations (parked by lane 0; the other lanes park their `slope` in that field)
     float slope = 0.0f;    // lanes with a predecessor in their block: the slope guard's ratio
     bool has_ray = false, retired = false, publish = false, pend = false;
+    bool negl = false;     // the slot's ray has listed a sample with f1 < 0: what it lists from here on is deferred (k_resolve_list)
     int ticket = -1;
     int ray = 0, pos = 0, strd = 1, npass = 0, seg0 = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, smin = 0.f, width = 0.f, prev_z = 0.f, prev_f = 0.f;
@@ -779,7 +792,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         if (pub_slots | need_slots) {
             const QueueBases qb = sampler_queue_bases(q, lane, need_slots, pub_slots);
             if (publish) {
-                sampler_publish_item<__ATOMIC_RELEASE>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, pos, unit, prev_f, pend);
+                sampler_publish_item<__ATOMIC_RELEASE>(w, qb.pbase, pub_slots, slot, lane == slot_lane0, ray, pos, unit, prev_f,
+                                                       (uint8_t)(pend ? (negl ? kRayPending | kRayNegListed : kRayPending) : 0));
                 publish = false;
             }
             if (!has_ray && ticket < 0 && !retired) {
@@ -789,11 +803,14 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         }
         if (!has_ray && ticket >= 0 && sampler_take(w, n_list, ticket, ray, pos, prev_f)) {
             pend = false;
+            negl = false;
             if (ticket >= n_list) {
                 // acquire only once the item is there (an acquiring poll invalidates the cache on every pass: +0.5 ms per frame)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 pos *= unit;
-                pend = (w.scr.ray_state[ray] & kRayPending) != 0;
+                const uint8_t st = w.scr.ray_state[ray];
+                pend = (st & kRayPending) != 0;
+                negl = (st & kRayNegListed) != 0;
             }
             ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
             ray_interval(a, ray, smin, width);
@@ -818,7 +835,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const float z = sample_depth(smin, a.lin[in_range ? idx : a.n_steps - 1], width);
         const float qx = has_ray ? ox + dx * z : 0.f, qy = has_ray ? oy + dy * z : 0.f, qz = has_ray ? oz + dz * z : 0.f;
         {
-            const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0);
+            const int flags = (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0) | (negl ? 32 : 0);
             const int ps = pos | (strd << kPosBits) | (npass << (kPosBits + kStrdBits)) | (seg0 << (kPosBits + kStrdBits + kPassBits));
             be.park(0, flags); be.park(1, ray); be.park(2, ps); be.park(3, ticket);
             park_vec6(be, 4, ox, oy, oz, dx, dy, dz);
@@ -832,8 +849,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         asm volatile("" : "+v"(me));
         const int sl0 = (me / kSamplerBlock) * kSamplerBlock, s_in_b = me % kSamplerBlock;
         const unsigned long long sbits = ((1ull << kSamplerBlock) - 1ull) << sl0;   // the slot's lanes
-        const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0));
-        has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4; pend = flags_back & 16;
+        const int flags_back = be.unpark(0, (has_ray ? 1 : 0) | (retired ? 2 : 0) | (publish ? 4 : 0) | (in_range ? 8 : 0) | (pend ? 16 : 0) | (negl ? 32 : 0));
+        has_ray = flags_back & 1; retired = flags_back & 2; publish = flags_back & 4; pend = flags_back & 16; negl = flags_back & 32;
         const bool in_range_b = flags_back & 8;
         ray = be.unpark(1, ray); ticket = be.unpark(3, ticket);
         {
@@ -903,6 +920,11 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             if (me == 0) rbase = atomicAdd(&w.cnt->n_res, __popcll(unc_wave));
             rbase = __shfl(rbase, 0, 64);
         }
+        // deferred: an earlier listed sample of the ray (of this pass or, negl, of an earlier one) has f1 < 0 -- strictly, as the
+        // resolve's f < 0: NaN and zeros are not negative; the ray's first such sample itself is not deferred
+        const unsigned long long unc_neg = __ballot(((unc >> me) & 1ull) && f < 0.0f) & sbits;
+        const bool deferred = (w.scr.defer & kDeferOn) && (negl || (unc_neg & ((1ull << me) - 1ull)) != 0ull);
+        negl = negl || unc_neg != 0ull;
         bool overflow = false;
         if (unc) {
             const int pos_last = rbase + lane_rank64(unc_wave, 63 - __clzll((long long)unc));
@@ -910,7 +932,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             const int pos_e = rbase + lane_rank64(unc_wave, me);
             if (((unc >> me) & 1ull) && pos_e < w.scr.cap) {   // written even for a ray that overflows: every slot below cap is valid
                 ResolveEntry e;
-                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.ld = ld; e.pad = 0;
+                e.ray = ray; e.s = idx_b; e.z = zb; e.f1 = f; e.f_prev1 = s_in_b > 0 ? f_up : prev_f; e.f_ex = 0.f; e.ld = ld; e.mark = deferred ? kEntDeferred : 0;
                 w.scr.ent[pos_e] = e;
             }
         }
@@ -982,15 +1004,77 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     if (lane == 0) slope_guard_raise(w, &w.cnt->slope_march_bits, r);
 }
 
-// exact (h2) values of the listed samples, 32 per wave from any rays; the first negative one of each ray lowers its `first`
+// The resolve's rounds.  A pending ray's outcome uses the exact value of its first listed sample that is negative
+// (PendRec::first) and of the sample before it, nothing else; the screen's sign is right for all but a few samples, so the samples
+// listed behind a ray's first one with f1 < 0 (kEntDeferred, marked by k_sampler_screen) almost never matter.  Round 1 evaluates the
+// entries that are not deferred.  Round 2 takes a deferred entry only where it can still matter: e.s < first after round 1 (the
+// screen called an earlier sample negative and its exact value is not); kDeferAudit: every deferred entry.  `first` only falls, and
+// a deferred entry with e.s >= first after round 1 can neither lower it nor be the sample before it: the minimum over the rounds is
+// the minimum over all listed samples.  Each round's entries are compacted into an index list so that its waves stay full.
+// One atomicAdd per workgroup and batch of kListBatch entries per thread (per wave and 64 entries, the form of k_bisect_list, the
+// 14 k atomics of a C1 frame's list on one counter took 0.16 ms, ten times the reading of the marks).
+constexpr int kListBatch = 4;
+__global__ __launch_bounds__(256) void k_resolve_list(TraceWs w, int round) {
+    const int n_res = w.cnt->n_res;
+    const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
+    int* const count = round == 1 ? &w.cnt->n_res1 : &w.cnt->n_res2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_cnt[4];
+    __shared__ int s_base;
+    unsigned long long moot = 0;   // deferred entries round 2 leaves alone: settled without an evaluation
+    for (long long i0 = (long long)blockIdx.x * (256 * kListBatch); i0 < n_ent; i0 += (long long)gridDim.x * (256 * kListBatch)) {
+        bool take[kListBatch];
+        int rank[kListBatch];
+        int n_wave = 0;   // the wave's entries of this batch
+#pragma unroll
+        for (int k = 0; k < kListBatch; ++k) {
+            const long long li = i0 + k * 256 + threadIdx.x;
+            take[k] = false;
+            if (li < n_ent) {
+                ResolveEntry* const e = &w.scr.ent[li];
+                const int mark = e->mark;
+                if (round == 1) {
+                    take[k] = mark == 0;
+                } else if (mark == kEntDeferred) {
+                    const int ray = e->ray;
+                    take[k] = (w.scr.defer & kDeferAudit) || (w.scr.ray_state[ray] != kRayOverflowed && e->s < w.scr.rec[ray].first);
+                    if (take[k]) e->mark = kEntDeferred | kEntRound2; else ++moot;
+                }
+            }
+            const unsigned long long m = __ballot(take[k]);
+            rank[k] = n_wave + lane_rank64(m, lane);
+            n_wave += __popcll(m);
+        }
+        if (lane == 0) s_cnt[wave] = n_wave;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_base = total ? atomicAdd(count, total) : 0;
+        }
+        __syncthreads();
+        int base = s_base;
+        for (int v = 0; v < wave; ++v) base += s_cnt[v];
+#pragma unroll
+        for (int k = 0; k < kListBatch; ++k)
+            if (take[k]) w.scr.res_idx[base + rank[k]] = (int)(i0 + k * 256 + threadIdx.x);
+        __syncthreads();   // s_cnt and s_base are written again by the next batch
+    }
+    moot = wave_sum(moot);
+    if (lane == 0 && moot) atomicAdd((unsigned long long*)&w.cnt->n_resolved, moot);
+}
+
+// exact (h2) values of listed samples, 32 per wave from any rays; the first negative one of each ray lowers its `first`
 template <class BE>
 __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_KERNEL_ARGS) {
+    const int round = w.scr.res_round;
+    const int n_res = w.cnt->n_res;
+    const int n_ent = round == 0 ? (n_res < w.scr.cap ? n_res : w.scr.cap) : round == 1 ? w.cnt->n_res1 : w.cnt->n_res2;
+    if (n_ent == 0) return;   // (uniform over the grid) an empty round, as round 2 usually is: no weight ring is started
+    int* const head = round == 2 ? &w.cnt->res_head2 : &w.cnt->res_head;
     BE be;
     be.init(net, hs, hm);
     const int lane = be.lane;
     const int j = lane & 31;
-    const int n_res = w.cnt->n_res;
-    const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
     const float delta = screen_delta(w.scr);
     long long resolved = 0;
     float ratio = 0.0f;
@@ -998,10 +1082,10 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
     int n_obs = 0;
     for (;;) {
         int base = 0;
-        if (lane == 0) base = atomicAdd(&w.cnt->res_head, 32);
+        if (lane == 0) base = atomicAdd(head, 32);
         base = __shfl(base, 0, 64);
-        const int li = base + j;
-        const bool valid = li < n_ent;
+        const bool valid = base + j < n_ent;
+        const int li = !valid || round == 0 ? base + j : w.scr.res_idx[base + j];
         if (!be.any(base < n_ent)) break;
         float qx = 0.f, qy = 0.f, qz = 0.f;
         if (valid) {
@@ -1043,6 +1127,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
         if (obs) atomicAdd((unsigned long long*)&w.cnt->n_obs_res, (unsigned long long)obs);
         slope_guard_raise(w, &w.cnt->slope_res_bits, sl);
         atomicAdd((unsigned long long*)&w.cnt->n_resolved, (unsigned long long)resolved);
+        atomicAdd((unsigned long long*)(round == 2 ? &w.cnt->n_eval_r2 : &w.cnt->n_eval_r1), (unsigned long long)resolved);
         atomicMax(&w.cnt->ratio_bits, __float_as_uint(r));
         if (r > kScreenGuard && w.scr.flag) {   // the guard: the network's next call runs the unscreened sampler
             *reinterpret_cast<volatile int*>(w.scr.flag) = 1;
@@ -1051,7 +1136,11 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
     }
 }
 
-// the exact values at each pending ray's bracket: its first negative sample and the one before it, where those were listed
+// the exact values at each pending ray's bracket: its first negative sample and the one before it, where those were listed.
+// A deferred entry no round evaluated (mark == kEntDeferred) has no f_ex, and is neither: it failed e.s < first after round 1, the
+// final g is at or below that `first`, and e.s == g is impossible -- g is a sample some round found negative, or the march's
+// certainly-negative one, which is not listed.  Sample g - 1, where listed, was evaluated: by round 1, or (deferred, g - 1 < g <= the
+// `first` round 2 compared it with) by round 2.
 __global__ void k_screen_fin_entries(TraceWs w) {
     const int n_res = w.cnt->n_res;
     const int n_ent = n_res < w.scr.cap ? n_res : w.scr.cap;
@@ -1059,10 +1148,11 @@ __global__ void k_screen_fin_entries(TraceWs w) {
     int n_obs = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_ent; i += gridDim.x * blockDim.x) {
         const ResolveEntry e = w.scr.ent[i];
+        if (e.mark == kEntDeferred) continue;
         const float ld = e.ld;
         if (i > 0 && ld > 0.0f) {
             const ResolveEntry p = w.scr.ent[i - 1];
-            if (p.ray == e.ray && p.s + 1 == e.s) {
+            if (p.ray == e.ray && p.s + 1 == e.s && p.mark != kEntDeferred) {
                 slope = fmaxf(slope, fabsf(e.f_ex - p.f_ex) / ld);
                 ++n_obs;
             }
@@ -1477,7 +1567,7 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct WsLayout {
     size_t cnt, sampler_list, root_list, lo, hi, flo, fhi, k, chunk_iters, chunk_roots, cont, total;
-    size_t s_rec, s_pend, s_ovf, s_flag, s_ent;   // the screened sampler's arrays
+    size_t s_rec, s_pend, s_ovf, s_flag, s_ent, s_idx;   // the screened sampler's arrays
     int64_t n_chunks, cont_cap;
 };
 
@@ -1505,6 +1595,7 @@ static WsLayout ws_layout(int64_t n, const iron_trace_params* p) {
     L.s_ovf = o; o += align256(sizeof(int) * nn);
     L.s_flag = o; o += align256(nn);
     L.s_ent = o; o += align256(sizeof(ResolveEntry) * nn * kResolvePerRay);
+    L.s_idx = o; o += align256(sizeof(int) * nn * kResolvePerRay);   // the resolve's index list (whatever the deferral's switch says)
     L.total = o;
     return L;
 }
@@ -1563,6 +1654,7 @@ std::atomic<int> g_screen_cap_override{0};
 std::atomic<int> g_stride_switch{-1};           // iron_set_sampler_stride; -1 = the environment's (IRON_SAMPLER_STRIDE=0: off) / default on
 std::atomic<float> g_stride_l_override{0.0f};   // test hook (iron_sampler_screen_debug 3)
 std::atomic<int> g_stride_hooks{0};             // test hooks (iron_sampler_screen_debug 4, 5): kStridePendingOff | kStrideMuteMarch
+std::atomic<int> g_defer_switch{-1};            // iron_set_resolve_defer; -1 = the environment's (IRON_RESOLVE_DEFER=0: off) / default on
 void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
 // a switch set by its setter (>= 0), else by the environment (NAME=0: off, read once), else on
@@ -1576,6 +1668,7 @@ static bool env_switch(const char* name, const std::atomic<int>& set, int* from_
 }
 static bool screen_switch() { static int from_env = -1; return env_switch("IRON_SAMPLER_SCREEN", g_screen_switch, &from_env); }
 static bool stride_switch() { static int from_env = -1; return env_switch("IRON_SAMPLER_STRIDE", g_stride_switch, &from_env); }
+static bool defer_switch() { static int from_env = -1; return env_switch("IRON_RESOLVE_DEFER", g_defer_switch, &from_env); }
 
 // at the start of a call: act on a guard flag an earlier call raised, then decide whether this call screens (h2 core only)
 static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use) {
@@ -1596,7 +1689,9 @@ static int screen_begin(const iron_net* cnet, bool h2, hipStream_t st, bool* use
     return IRON_OK;
 }
 
-static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk, int n_steps) {
+// `audit`: the call collects statistics -- its resolve evaluates every listed sample, so that the counts and the guards' maxima it
+// reports are those of the whole list (the deferral then only orders the work: round 2 takes every deferred entry)
+static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayout& L, int64_t b0, int64_t nk, int n_steps, bool audit) {
     w.scr.calib = net->screen_calib;
     w.scr.stride = (stride_switch() && !net->stride_off && n_steps <= kStrideMaxSteps && w.cont_cap > 0)
                        ? (kStrideOn | g_stride_hooks.load(std::memory_order_relaxed)) : 0;
@@ -1608,6 +1703,9 @@ static void screen_ws(TraceWs& w, const iron_net* net, char* base, const WsLayou
     w.scr.pend_list = (int*)(base + L.s_pend) + b0;
     w.scr.ovf_list = (int*)(base + L.s_ovf) + b0;
     w.scr.ent = (ResolveEntry*)(base + L.s_ent) + b0 * kResolvePerRay;
+    w.scr.res_idx = (int*)(base + L.s_idx) + b0 * kResolvePerRay;
+    w.scr.defer = defer_switch() ? (kDeferOn | (audit ? kDeferAudit : 0)) : 0;
+    w.scr.res_round = 0;
     int64_t cap = nk * kResolvePerRay;
     const int ov = g_screen_cap_override.load(std::memory_order_relaxed);
     if (ov > 0 && ov < cap) cap = ov;
@@ -1619,8 +1717,18 @@ static void run_sampler(bool h2, bool screen, const iron_net* sdf, const TraceAr
     const int64_t units = (nk + kSamplerSlots - 1) / kSamplerSlots;
     if (!screen) { launch_trace_kernel(kSampler, h2, sdf, a, w, units, st); return; }
     launch_trace_kernel(kSamplerScreen, true, sdf, a, w, (nk + kScreenSlots - 1) / kScreenSlots, st);
-    launch_trace_kernel(kScreenResolve, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
     const int64_t ge = ((int64_t)w.scr.cap + 255) / 256, gr = (nk + 255) / 256;
+    if (w.scr.defer & kDeferOn) {   // the resolve in two rounds, each on its compacted index list; round 2's is almost always empty
+        TraceWs wr = w;
+        const int64_t gl = ((int64_t)w.scr.cap + 256 * kListBatch - 1) / (256 * kListBatch);
+        for (int round = 1; round <= 2; ++round) {
+            wr.scr.res_round = round;
+            hipLaunchKernelGGL(k_resolve_list, dim3((unsigned)(gl < 1024 ? (gl > 0 ? gl : 1) : 1024)), dim3(256), 0, st, wr, round);
+            launch_trace_kernel(kScreenResolve, true, sdf, a, wr, ((int64_t)w.scr.cap + 31) / 32, st);
+        }
+    } else {
+        launch_trace_kernel(kScreenResolve, true, sdf, a, w, ((int64_t)w.scr.cap + 31) / 32, st);
+    }
     hipLaunchKernelGGL(k_screen_fin_entries, dim3((unsigned)(ge < 1024 ? (ge > 0 ? ge : 1) : 1024)), dim3(256), 0, st, w);
     hipLaunchKernelGGL(k_screen_fin_rays, dim3((unsigned)(gr < 1024 ? (gr > 0 ? gr : 1) : 1024)), dim3(256), 0, st, a, w);
     TraceWs w2 = w;   // rays that overflowed the resolve list: k_sampler from their first sample (one slot per ray to the end)
@@ -1686,6 +1794,7 @@ static int32_t set_switch(std::atomic<int>& set, bool prev, int32_t on) {
 }
 extern "C" int32_t iron_set_sampler_screen(int32_t on) { return set_switch(g_screen_switch, screen_switch(), on); }
 extern "C" int32_t iron_set_sampler_stride(int32_t on) { return set_switch(g_stride_switch, stride_switch(), on); }
+extern "C" int32_t iron_set_resolve_defer(int32_t on) { return set_switch(g_defer_switch, defer_switch(), on); }
 
 extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 0) { g_screen_delta_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
@@ -1752,6 +1861,18 @@ extern "C" int iron_trace_stride_detail(const void* workspace, double* out, void
         out[0] += (double)c[k].n_pass_behind; out[1] += (double)c[k].n_pass_fresh; out[2] += (double)c[k].n_restart;
         out[3] += (double)c[k].n_obs_march; out[4] += (double)c[k].n_obs_res; out[5] += (double)c[k].n_obs_pair;
         max_f32_bits(&out[6], c[k].slope_march_bits); max_f32_bits(&out[7], c[k].slope_res_bits); max_f32_bits(&out[8], c[k].slope_pair_bits);
+    }
+    return IRON_OK;
+}
+
+extern "C" int iron_trace_resolve_counts(const void* workspace, double* out, void* stream) {
+    if (!workspace || !out) return IRON_ERR_BAD_ARG;
+    TraceCounters c[kMaxTraceSplits];
+    const int rc = read_counters(workspace, (hipStream_t)stream, c);
+    if (rc != IRON_OK) return rc;
+    for (int i = 0; i < 4; ++i) out[i] = 0.0;
+    for (int k = 0; k < kMaxTraceSplits; ++k) {
+        out[0] += (double)c[k].n_eval_r1; out[1] += (double)c[k].n_eval_r2; out[2] += (double)c[k].n_res1; out[3] += (double)c[k].n_res2;
     }
     return IRON_OK;
 }
@@ -1884,7 +2005,7 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
         w.sampler_list += b0; w.root_list += b0; w.root_lo += b0; w.root_hi += b0; w.root_flo += b0; w.root_fhi += b0; w.root_k += b0;
         a.ray0 = (int)b0; a.n = (int)nk;
         if (L.cont_cap > 0) { const int64_t per_ray = L.cont_cap / n; w.cont += b0 * per_ray; w.cont_cap = (int)(nk * per_ray); }
-        if (screen) screen_ws(w, sdf, base, L, b0, nk, p->n_steps);
+        if (screen) screen_ws(w, sdf, base, L, b0, nk, p->n_steps, stats != nullptr);
         const int64_t tiles = (nk + 31) / 32;
         if (phase == 0) {
             {
@@ -1938,7 +2059,7 @@ extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron
     if (stage == 1) {
         const int rcs = screen_begin(sdf, h2, st, &screen);
         if (rcs != IRON_OK) return rcs;
-        if (screen) { IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st)); screen_ws(w, sdf, base, L, 0, n, p->n_steps); }
+        if (screen) { IRON_HIP_TRY(hipMemsetAsync(base + L.s_flag, 0, (size_t)n, st)); screen_ws(w, sdf, base, L, 0, n, p->n_steps, false); }
     }
     IRON_HIP_TRY(hipMemsetAsync(base + L.cnt, 0, kCntStride * kMaxTraceSplits, st));
     IRON_HIP_TRY(hipMemsetAsync(base + L.chunk_iters, 0, align256(sizeof(int)), st));
