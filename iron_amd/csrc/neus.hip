@@ -17,6 +17,19 @@ static inline int ray_grid(int64_t n) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplusf_(float x) { return x > 20.0f ? x : log1pf(expf(x)); }  // F.softplus(beta=1, threshold=20)
 
+// Compensated (Kahan) running sum for the normaliser and the CDF of the inverse-CDF kernels.  A sample that falls into a section
+// of CDF width ~2e-5 is moved by (bin width / CDF width) ~ 500 times the error of the CDF knot below it; the rounding a plain
+// fp32 running sum of up to 191 terms collects (a few 1e-7) then shows as several 1e-5 of depth.
+struct KahanSum {
+    float s = 0.0f, c = 0.0f;
+    __device__ __forceinline__ float add(float x) {
+        const float y = x - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+        return s;
+    }
+};
+
 // z[r][j] = near[r] + (far[r] - near[r]) * lin[j]   (renderer.py:357-358)
 __global__ void k_neus_linspace(const float* __restrict__ near, const float* __restrict__ far, const float* __restrict__ lin, int n,
                                 int m, float* __restrict__ z) {
@@ -67,7 +80,8 @@ __global__ void k_neus_up_sample(const float* __restrict__ o, const float* __res
     float cdf[kMaxSamples];  // cdf[0] = 0, cdf[j+1] = cumulative pdf of section j (m-1 sections)
     float w[kMaxSamples];
     const float ox = o[3 * r], oy = o[3 * r + 1], oz = o[3 * r + 2], dx = d[3 * r], dy = d[3 * r + 1], dz = d[3 * r + 2];
-    float prev_cos = 0.0f, trans = 1.0f, wsum = 0.0f;
+    float prev_cos = 0.0f, trans = 1.0f;
+    KahanSum wsum;
     float rad_prev;
     {
         const float px = ox + dx * zr[0], py = oy + dy * zr[0], pz = oz + dz * zr[0];
@@ -90,14 +104,11 @@ __global__ void k_neus_up_sample(const float* __restrict__ o, const float* __res
         const float alpha = (prev_cdf - next_cdf + 1e-5f) / (prev_cdf + 1e-5f);
         w[j] = alpha * trans + 1e-5f;  // sample_pdf: weights + 1e-5
         trans = trans * (1.0f - alpha + 1e-7f);
-        wsum += w[j];
+        wsum.add(w[j]);
     }
     cdf[0] = 0.0f;
-    float acc = 0.0f;
-    for (int j = 0; j < m - 1; ++j) {
-        acc += w[j] / wsum;
-        cdf[j + 1] = acc;
-    }
+    KahanSum acc;
+    for (int j = 0; j < m - 1; ++j) cdf[j + 1] = acc.add(w[j] / wsum.s);
     // inverse CDF at u_k = (k + 0.5) / n_imp; bins = z (m entries), cdf has m entries
     int ind = 0;
     for (int k = 0; k < n_imp; ++k) {
@@ -291,14 +302,11 @@ __global__ void k_neus_sample_pdf(const float* __restrict__ bins, const float* _
     const float* b = bins + (size_t)r * mb;
     const float* w = weights + (size_t)r * (mb - 1);
     float cdf[kMaxSamples];
-    float wsum = 0.0f;
-    for (int j = 0; j < mb - 1; ++j) wsum += w[j] + 1e-5f;
+    KahanSum wsum;
+    for (int j = 0; j < mb - 1; ++j) wsum.add(w[j] + 1e-5f);
     cdf[0] = 0.0f;
-    float acc = 0.0f;
-    for (int j = 0; j < mb - 1; ++j) {
-        acc += (w[j] + 1e-5f) / wsum;
-        cdf[j + 1] = acc;
-    }
+    KahanSum acc;
+    for (int j = 0; j < mb - 1; ++j) cdf[j + 1] = acc.add((w[j] + 1e-5f) / wsum.s);
     const float start = 0.5f / k_samples, end = 1.0f - 0.5f / k_samples;
     const float step = k_samples > 1 ? (end - start) / (float)(k_samples - 1) : 0.0f;
     for (int k = 0; k < k_samples; ++k) {

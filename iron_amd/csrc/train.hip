@@ -1160,7 +1160,8 @@ __global__ void k_neus_composite_back(NeusBackArgs a) {
                     const float px = f.pts[3 * q], py = f.pts[3 * q + 1], pz = f.pts[3 * q + 2];
                     if (sqrtf((px * px + py * py) + pz * pz) < 1.2f) {
                         const float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
-                        const float k = dge * inv_cnt * 2.0f * (gn - 1.0f) / gn;
+                        // d|g|/dg at g = 0 is taken as 0, as torch's norm backward does (the quotient would be -inf, times 0 = NaN)
+                        const float k = gn > 0.0f ? dge * inv_cnt * 2.0f * (gn - 1.0f) / gn : 0.0f;
                         dg[0] += k * gx; dg[1] += k * gy; dg[2] += k * gz;
                     }
                 }
