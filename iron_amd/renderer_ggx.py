@@ -79,7 +79,7 @@ class GGXColocatedRenderer(nn.Module):
         dev = nrm.device
         dist = _lib.require_cuda_f32(distance.detach(), "distance").reshape(-1)
         vd = _lib.require_cuda_f32(viewdir.detach(), "viewdir").reshape(-1, 3)
-        kd = _lib.require_cuda_f32(params["diffuse_albedo"].detach(), "diffuse_albedo").reshape(-1, 3)
+        kd = _lib.require_cuda_f32(params["diffuse_albedo"].detach().expand(sh + [3]), "diffuse_albedo").reshape(-1, 3)
         ks = _lib.require_cuda_f32(params["specular_albedo"].detach().expand(sh + [3]), "specular_albedo").reshape(-1, 3)
         al = _lib.require_cuda_f32(params["specular_roughness"].detach(), "specular_roughness").reshape(-1)
         t1, t2 = self._tables_on(dev)
@@ -94,10 +94,9 @@ class GGXColocatedRenderer(nn.Module):
 
 
 def _flat(name, x, width, sh):
-    v = _lib.require_cuda_f32(x.detach(), name)
-    if width == 3:
-        return v.expand(sh + [3]).reshape(-1, 3) if v.shape[-1] != 3 else v.reshape(-1, 3)
-    return v.reshape(-1)
+    if width == 3:  # a [..., 1] albedo is broadcast over the channels; the kernels read n x 3 packed floats, so the copy comes after the expand
+        return _lib.require_cuda_f32(x.detach().expand(sh + [3]), name).reshape(-1, 3)
+    return _lib.require_cuda_f32(x.detach(), name).reshape(-1)
 
 
 class CompositeRenderer(nn.Module):
