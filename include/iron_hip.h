@@ -40,7 +40,8 @@ typedef enum iron_status {
     IRON_ERR_HIP = -3,          /* a HIP runtime call failed; see iron_last_hip_error()        */
     IRON_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
     IRON_ERR_WORKSPACE = -5,    /* workspace too small                                         */
-    IRON_ERR_RANGE = -6         /* IRON_H2_OVERFLOW=error: the previous call on this network left the fp16 range of the h2 core;
+    IRON_ERR_RANGE = -6         /* IRON_H2_OVERFLOW=error: the previous call on this network left the fp16 range of the h2 core
+                                   (returned by every entry on that handle until iron_net_force_exact(net, 1));
                                    iron_mc_count: a vertex or triangle count reaches 2^31;
                                    iron_bake_*: see that block */
 } iron_status;
@@ -108,14 +109,18 @@ int iron_net_destroy(iron_net_t* net);
 /* Numeric envelope of the default ("h2", split-fp16) core: weights are checked at create (a network with a folded |w| >= 65 504
  * runs on the exact-fp32 core); activations and features are guarded at run time: every entry that ran a network on the h2 core
  * scans the values it returns, a non-finite one raises the network's flag, and the NEXT entry on that handle moves the network to
- * the exact-fp32 MFMA core for good (IRON_H2_OVERFLOW=error: returns IRON_ERR_RANGE instead).  The reference is plain fp32
- * (models/fields.py:82-98, 203-239), which the exact core reproduces over the whole fp32 range.
+ * the exact-fp32 MFMA core for good (IRON_H2_OVERFLOW=error: returns IRON_ERR_RANGE instead, and keeps returning it until
+ * iron_net_force_exact(net, 1) has pinned the handle to the exact core).  The reference is plain fp32
+ * (models/fields.py:82-98, 203-239), which the exact core reproduces over the whole fp32 range.  The call that overflowed is loud
+ * row by row: a returned row that an out-of-range operand reached is non-finite (the tracer and the edge walk write NaN into
+ * sdf_out / dist / points of such a ray or candidate), never a plausible number.  Not covered: IRON_MLP_CORE=w16 (opt-in, per
+ * process) and iron_sdf_screen_forward (a debug entry with a guard word of its own).
  *   iron_net_numeric_status: synchronises `stream`; *status_out = bit 0: an overflow was seen, bit 1: the network runs on the exact
  *                            core, bit 2: a flag is pending (the call just finished overflowed),
  *                            bit 3: the dense sampler's screen guard has turned the screen off for this network (iron_set_sampler_screen),
  *                            bit 4: the slope guard has put the screen's adaptive march on stride 1 for this network (iron_set_sampler_stride).
- *   iron_net_force_exact:    on != 0 pins the network to the exact core; 0 returns it to the default core and clears the status
- *                            (bits 0-4). */
+ *   iron_net_force_exact:    on != 0 pins the network to the exact core and answers a pending flag (bit 2 falls, bit 0 records it);
+ *                            0 returns it to the default core and clears the status (bits 0-4). */
 int iron_net_numeric_status(const iron_net_t* net, int32_t* status_out, void* stream);
 int iron_net_force_exact(iron_net_t* net, int32_t on);
 

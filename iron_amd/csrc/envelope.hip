@@ -10,6 +10,14 @@
 // MFMA core for good (or returns IRON_ERR_RANGE with IRON_H2_OVERFLOW=error); iron_net_numeric_status() reports it.  The
 // call that overflowed has returned non-finite values -- loud, not plausible-looking -- and the callers that can afford a
 // synchronisation re-run it (iron_amd/fields.py: IRON_H2_OVERFLOW=rerun).
+//
+// Loud means row by row (tests/test_gpu_envelope_entries.py): a returned row that an out-of-range operand reached is non-finite, a row
+// it did not reach is finite and right in the same call.  Where an entry makes decisions from values instead of returning them, it
+// turns the decision into a value: the tracer ends a ray at an overflowed sample or mid-point with NaN in sdf_out / dist / points
+// (trace.hip: lost_value), the edge walk writes NaN points for a candidate whose s or gradient overflowed (shade.hip), and the scans
+// below see those.  Operands are activations, features, input coordinates and, in the forward-mode kernels (k_sdf_grad_h2, the walk),
+// the tangents d/dx_k of the activations.
+// Not covered: IRON_MLP_CORE=w16 (opt-in, chosen per process) and iron_sdf_screen_forward (a debug entry with its own guard word).
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
@@ -89,7 +97,8 @@ int envelope_begin(const iron_net* cnet) {
     if (!net || !net->flag_host) return IRON_OK;
     if (*(volatile int*)net->flag_host) {
         net->overflow_seen = 1;
-        if (overflow_mode() == 1) return IRON_ERR_RANGE;
+        // error mode: the handle refuses work until the caller has chosen the exact core (iron_net_force_exact(net, 1) also clears the flag)
+        if (overflow_mode() == 1 && !net->h2_disabled) return IRON_ERR_RANGE;
         net->h2_disabled = 1;
         *(volatile int*)net->flag_host = 0;
     }
@@ -126,7 +135,9 @@ extern "C" int iron_net_numeric_status(const iron_net_t* net, int32_t* status_ou
 extern "C" int iron_net_force_exact(iron_net_t* net, int32_t on) {
     if (!net) return IRON_ERR_BAD_ARG;
     net->h2_disabled = on ? 1 : 0;
-    if (!on) {
+    if (on) {   // the pending overflow is answered: the exact core has no fp16 range to leave (IRON_H2_OVERFLOW=error: the handle works again)
+        if (net->flag_host && *(volatile int*)net->flag_host) { net->overflow_seen = 1; *(volatile int*)net->flag_host = 0; }
+    } else {
         net->overflow_seen = 0;
         net->screen_off = 0;   // the sampler's guards (status bits 3 and 4) are part of the status, cleared with it
         net->stride_off = 0;

@@ -152,6 +152,11 @@ struct GgxOut {
     float rgb[3];
 };
 
+// torch.clamp keeps a NaN; fminf / fmaxf return the OTHER operand, so a clamped NaN input (a normal or a material value the h2 core
+// lost to an overflow, csrc/envelope.hip, or a NaN of the network's own) would come out as a finite, plausible colour.  The heads
+// below add nan_of() of every input they clamp to what depends on it: 0 for any number, the NaN itself otherwise.
+__device__ __forceinline__ float nan_of(float x) { return x != x ? x : 0.0f; }
+
 // GGXColocatedRenderer.forward (models/renderer_ggx.py:82-146) for one point.
 __device__ __forceinline__ void ggx_colocated_point(float light, float distance, const float n[3], const float v[3],
                                                     const float kd[3], const float ks[3], float rough,
@@ -159,6 +164,7 @@ __device__ __forceinline__ void ggx_colocated_point(float light, float distance,
                                                     const float* __restrict__ tab_diff, GgxOut& o) {
     const float intensity = intensity_at(light, distance);
     float dot = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
+    const float lost = nan_of(dot) + nan_of(rough);
     dot = fminf(fmaxf(dot, 0.00001f), 0.99999f);
     const float alpha = fmaxf(rough, 0.0001f);
     const float D = ggx_ndf(dot, alpha);
@@ -169,8 +175,8 @@ __device__ __forceinline__ void ggx_colocated_point(float light, float distance,
     rtrans_lookup(dot, alpha, tab_trans, tab_diff, T12, fd);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        o.specular[c] = intensity * ks[c] * kFr * D * G / denom;
-        o.diffuse[c] = intensity * (kd[c] / fd / kPi) * dot * T12 * T12 * kInvEta2;
+        o.specular[c] = intensity * ks[c] * kFr * D * G / denom + lost;
+        o.diffuse[c] = intensity * (kd[c] / fd / kPi) * dot * T12 * T12 * kInvEta2 + lost;
         o.rgb[c] = o.diffuse[c] + o.specular[c];
     }
 }
@@ -236,6 +242,8 @@ __device__ __forceinline__ void composite_point(float intensity, const float n[3
     const float m_eta = fminf(fmaxf(m_eta_in, 0.099999f), 4.999999f);
     const float m_k = fminf(fmaxf(m_k_in, 0.099999f), 9.999999f);
     float cos_i = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
+    const float lost_m = (nan_of(cos_i) + nan_of(m_eta_in)) + nan_of(m_k_in);        // what the metallic term clamps
+    const float lost_d = (nan_of(cos_i) + nan_of(d_eta_in)) + nan_of(rough_in);      // ... the dielectric term, and the diffuse one
     cos_i = fminf(fmaxf(cos_i, 0.00001f), 0.99999f);
     const float D = composite_ndf(cos_i);
     const float g1 = smith_g1(cos_i, rough);
@@ -249,10 +257,10 @@ __device__ __forceinline__ void composite_point(float intensity, const float n[3
     for (int c = 0; c < 3; ++c) {
         const float ks = fmaxf(ks_in[c], 0.00001f);
         const float kd = fmaxf(kd_in[c], 0.00001f);
-        o.metallic[c] = (ks * Fm) * intensity;
-        o.dielectric[c] = (ks * Fd * D * G / denom) * intensity;
+        o.metallic[c] = (ks * Fm) * intensity + (lost_m + nan_of(ks_in[c]));
+        o.dielectric[c] = (ks * Fd * D * G / denom) * intensity + (lost_d + nan_of(ks_in[c]));
         o.specular[c] = o.dielectric[c] + o.metallic[c];
-        const float diffuse = intensity * (kd / fd / kPi) * cos_i * T12 * T12 * kInvEta2;
+        const float diffuse = intensity * (kd / fd / kPi) * cos_i * T12 * T12 * kInvEta2 + (lost_d + nan_of(kd_in[c]));
         o.rgb[c] = diffuse + o.specular[c];
     }
 }

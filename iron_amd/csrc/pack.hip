@@ -147,7 +147,8 @@ extern "C" const char* iron_strerror(int status) {
         case IRON_ERR_NO_DEVICE: return "no gfx950 device visible";
         case IRON_ERR_WORKSPACE: return "workspace too small";
         case IRON_ERR_RANGE: return "an activation or feature left the fp16 range of the h2 core (|x| >= 65504 or non-finite): results of the "
-                                    "previous call on this network were non-finite; use iron_net_force_exact / IRON_MLP_CORE=f32";
+                                    "previous call on this network were non-finite; iron_net_force_exact(net, 1) puts the handle back to work on the exact core (or start with "
+                                    "IRON_MLP_CORE=f32)";
         default: return "unknown iron status";
     }
 }

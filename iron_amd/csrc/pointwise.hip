@@ -268,6 +268,7 @@ __global__ void k_edge_project_first(const float* __restrict__ points, const uin
         uv[2 * i] = u;
         uv[2 * i + 1] = v;
         if (!found[i]) continue;
+        if (!(fabsf(u) <= 3.0e38f) || !(fabsf(v) <= 3.0e38f)) continue;   // no pixel (the edge walk's NaN points, envelope.hip); a float -> integer conversion of such a value is undefined
         const long long pix = (long long)floorf(v) * (long long)W + (long long)floorf(u);
         if (pix < 0 || pix >= (long long)H * W) continue;
         atomicMin(&first[pix], (int)i);

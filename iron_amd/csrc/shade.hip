@@ -368,6 +368,9 @@ __global__ __launch_bounds__(256, 1) void k_edge_walk_h2(H2StreamDev hs, H2Meta 
         float px = 0.f, py = 0.f, pz = 0.f;
         if (ok) { px = a.start[3 * (size_t)li]; py = a.start[3 * (size_t)li + 1]; pz = a.start[3 * (size_t)li + 2]; }
         bool found = !ok;  // padding lanes never keep the tile alive
+        // envelope guard (envelope.hip): a non-finite s or gradient here is an overflow of the fp16 split, not a value of the network.
+        // Such a candidate still "counts as found" below, but it leaves with NaN points so that iron_edge_walk's scan raises the flag
+        bool lost = false;
         for (int it = 0;; ++it) {
             TileFrag in[kHidTiles], out[kHidTiles];
             const float res = sdf_value_or_tangent_h2(ring, lds, sbuf, m, px, py, pz, is_value, axis, wave, lane, in, out);
@@ -381,7 +384,8 @@ __global__ __launch_bounds__(256, 1) void k_edge_walk_h2(H2StreamDev hs, H2Meta 
             const float gn = sqrtf((gx * gx + gy * gy) + gz * gz) + 1e-10f;
             const float nx = gx / gn, ny = gy / gn, nz = gz / gn;
             const float dot = (nx * vx + ny * vy) + nz * vz;
-            const bool moving = !found && (fabsf(dot) > a.dot_threshold);  // a NaN dot counts as found, as in the reference
+            lost = lost || (!found && !((fabsf(s) <= 3.0e38f) && (fabsf(gx) <= 3.0e38f) && (fabsf(gy) <= 3.0e38f) && (fabsf(gz) <= 3.0e38f)));
+            const bool moving = !found && !lost && (fabsf(dot) > a.dot_threshold);  // a NaN dot counts as found, as in the reference
             found = !moving;
             const bool any_moving = __ballot(moving) != 0ull;  // identical in the four waves (same inputs, same arithmetic)
             __syncthreads();                                  // xch is rewritten by the next evaluation
@@ -394,6 +398,7 @@ __global__ __launch_bounds__(256, 1) void k_edge_walk_h2(H2StreamDev hs, H2Meta 
             }
         }
         if (ok && wave == 0 && lane < 32) {
+            if (lost) px = py = pz = __uint_as_float(0x7fc00000u);
             a.points[3 * (size_t)li] = px; a.points[3 * (size_t)li + 1] = py; a.points[3 * (size_t)li + 2] = pz;
             a.found[li] = found ? 1 : 0;
         }
@@ -986,10 +991,12 @@ extern "C" int iron_sdf_get_all(const iron_net_t* sdf, const float* x, int64_t n
     a.x = x; a.list = nullptr; a.count_ptr = nullptr; a.count = (int)n;
     a.feat_packed = nullptr; a.sdf_out = sdf_out; a.grad_out = grad; a.feat_rows = feature;
     const int rc = launch_sdf_grad(sdf, a, (n + kTile - 1) / kTile, (hipStream_t)stream, workspace, workspace_bytes);
-    // the envelope guard (envelope.hip): sdf and gradient carry every hidden activation's overflow; the feature rows are guarded where
-    // they are split (the material networks' outputs)
+    // the envelope guard (envelope.hip): every value the call returns.  The feature rows too: sdf and gradient do not carry every
+    // overflow -- the distance head reads the last hidden layer's fp32 accumulators, the feature head its fp16 split, so an
+    // activation >= 65 504 in that layer loses the features alone
     envelope_scan(sdf, sdf_out, n, nullptr, 1, (hipStream_t)stream);
     envelope_scan(sdf, grad, n, nullptr, 3, (hipStream_t)stream);
+    if (feature) envelope_scan(sdf, feature, n, nullptr, sdf->desc.d_out - 1, (hipStream_t)stream);
     return rc;
 }
 

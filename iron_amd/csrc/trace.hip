@@ -109,7 +109,8 @@ struct PendRec {        // a ray whose outcome waits for the resolve, by ray id
     float fhi, flo;     // bracket values at `first` (screened, or exact where the sample was listed)
     float flo_ex;       // exact value of sample first - 1 when it was listed
     int has_flo_ex;
-    int pad[3];
+    int first_lost;     // first listed sample whose exact value overflowed (0x7fffffff: none); atomicMin-ed by the resolve (lost_value)
+    int pad[2];
 };
 struct ScreenWs {
     const unsigned* calib;   // per network, device (f32 bits): [0] max |f_screen - f_h2| over the calibration set, [kScreenCalibG] G = max |grad f|
@@ -236,6 +237,7 @@ __device__ __forceinline__ void ray_origin_dir(const TraceArgs& a, int ray, floa
 // BackendH2 : four waves per workgroup in lock step on the split-fp16 core (mlp_h2.h) sharing the LDS ring.
 struct BackendF32 {
     static constexpr int kThreads = 64;
+    static constexpr bool kSplit = false;   // a non-finite value of this core is the network's own, as the reference's would be
     SdfNetDev net;
     WStream ws;
     int lane;
@@ -266,6 +268,7 @@ static_assert(kLdsTraceTotal <= 160 * 1024, "LDS of a tracer workgroup");
 template <bool DEFER_TILES>
 struct BackendH2T {
     static constexpr int kThreads = 256;
+    static constexpr bool kSplit = true;    // a non-finite value of this core is an overflow of the fp16 split (envelope.hip): see lost_value
     Ring ring;
     char* lds;
     H2Meta m;
@@ -331,6 +334,17 @@ __device__ __forceinline__ void unpark_vec6(BE& be, int i, float& ox, float& oy,
     ox = be.unpark(i, ox); oy = be.unpark(i + 1, oy); oz = be.unpark(i + 2, oz);
     dx = be.unpark(i + 3, dx); dy = be.unpark(i + 4, dy); dz = be.unpark(i + 5, dz);
 }
+
+// The envelope guard of the tracer (envelope.hip).  On the h2 core a non-finite evaluation means that an activation left fp16's range
+// where the reference's fp32 has an ordinary number, so nothing may be made of it: not "not negative" (the sampler would march on and
+// return a later root, or zeros like any miss), not "f <= 0" (the bisection would take the upper half).  The ray that met it ends
+// loud instead: NaN in sdf_out / dist / points, conv = 0 (the sampler) or the bracket's 1 (the bisection), and the scan of sdf_out
+// behind the call raises the network's flag.  k_sphere needs nothing: a NaN step retires the ray with that NaN as its sdf.  No loop's
+// exit depends on a finite value: the march counts samples, the bisection iterations (k < 64 / `remaining`).  On the exact core
+// (kSplit false) a non-finite value is treated as the reference treats it.
+template <class BE>
+__device__ __forceinline__ bool lost_value(float f) { return BE::kSplit && !(fabsf(f) <= 3.0e38f); }
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
 
 #define IRON_TRACE_KERNEL_ARGS SdfNetDev net, H2StreamDev hs, H2Meta hm, TraceArgs a, TraceWs w
 
@@ -570,12 +584,13 @@ __device__ __forceinline__ void sampler_write_root(const TraceWs& w, int ray, fl
     w.root_lo[pos_l] = z_lo; w.root_hi[pos_l] = z_hi;
     w.root_flo[pos_l] = f_lo; w.root_fhi[pos_l] = f_hi;
 }
-// ... or none (raytracer.py:158-160, 75-78: sampled rays without a root get zeros; `zero`: 0.f, as the caller wants it held)
-__device__ __forceinline__ void sampler_write_no_root(const TraceArgs& a, int ray, float zero) {
+// ... or none (raytracer.py:158-160, 75-78: sampled rays without a root get zeros).  `fill`: 0.f as the caller wants it held, or
+// NaN for a ray that ended at an overflowed value (lost_value)
+__device__ __forceinline__ void sampler_write_no_root(const TraceArgs& a, int ray, float fill) {
     a.conv[ray] = 0;
-    a.points[3 * (size_t)ray] = zero; a.points[3 * (size_t)ray + 1] = zero; a.points[3 * (size_t)ray + 2] = zero;
-    a.sdf[ray] = zero;
-    a.dist[ray] = zero;
+    a.points[3 * (size_t)ray] = fill; a.points[3 * (size_t)ray + 1] = fill; a.points[3 * (size_t)ray + 2] = fill;
+    a.sdf[ray] = fill;
+    a.dist[ray] = fill;
 }
 
 template <class BE>
@@ -649,6 +664,9 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         const unsigned neg_all = (unsigned)__ballot(in_range_b && f < 0.0f);  // sign(f) == -1 (raytracer.py:162-166)
         // the slot's neighbours' values, fetched by every lane (shuffles are wave-wide operations)
         const unsigned neg = neg_all & slot_bits;
+        // envelope guard: an overflowed sample at or in front of the slot's first negative one (or without one) ends the ray, loud
+        const unsigned bad = (unsigned)__ballot(in_range_b && lost_value<BE>(f)) & slot_bits;
+        const bool lost = has_ray && bad != 0u && (neg == 0u || __ffs(bad) <= __ffs(neg));   // (<=: -inf is overflowed and negative)
         const int first = neg ? (__ffs(neg) - 1) : slot_lane0;          // wave lane of the slot's first negative sample
         const float z_first = __shfl(zb, first, 64), f_first = __shfl(f, first, 64);
         const float z_before = __shfl(zb, first > slot_lane0 ? first - 1 : slot_lane0, 64);
@@ -656,13 +674,13 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
         const float z_last = __shfl(zb, slot_lane0 + kSamplerBlock - 1, 64), f_last = __shfl(f, slot_lane0 + kSamplerBlock - 1, 64);
         // outcome of this block for the slot (straight-line: every lane of the slot computes the same)
         const int gidx = blk * kSamplerBlock + (first - slot_lane0);          // index of the first negative sample, if any
-        const bool found_neg = has_ray && neg != 0u;
+        const bool found_neg = has_ray && neg != 0u && !lost;
         const bool root = found_neg && gidx >= 1;                              // raytracer.py:167
-        const bool done = has_ray && (found_neg || (blk + 1) * kSamplerBlock >= a.n_steps);
+        const bool done = has_ray && (found_neg || lost || (blk + 1) * kSamplerBlock >= a.n_steps);
         const float z_lo = first > slot_lane0 ? z_before : prev_z, f_lo = first > slot_lane0 ? f_before : prev_f;
         if (done && lane == slot_lane0) {   // the slot's first lane (lower half of the wave) writes the outcome
             if (root) sampler_write_root(w, ray, z_lo, z_first, f_lo, f_first);
-            else sampler_write_no_root(a, ray, 0.f);
+            else sampler_write_no_root(a, ray, lost ? quiet_nan() : 0.f);
             atomicAdd(&q->n_done, 1);
         }
         prev_z = z_last;
@@ -842,7 +860,10 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             be.park(10, smin); be.park(11, width); be.park(12, prev_z); be.park(13, prev_f); be.park(14, z);
             be.park(15, (int)ev_ref); be.park(16, lane == 0 ? (int)ev_scr : __float_as_int(slope));
         }
-        const float f = be.template eval_screen<kH1PointTiles>(qx, qy, qz);
+        // envelope guard: an infinite screened value is no sign to rely on (+inf would pass as certainly positive and certify the
+        // samples around it): as a NaN it is uncertain in every comparison below, is listed, and the resolve's exact value decides
+        float f = be.template eval_screen<kH1PointTiles>(qx, qy, qz);
+        if (!(fabsf(f) <= 3.0e38f)) f = quiet_nan();
         // the lane-derived masks after the evaluation come from an opaque copy of the lane: hoisted out of the loop, they are held
         // across the evaluation (in scratch, at 64 samples per wave)
         int me = lane;
@@ -960,7 +981,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             if (pend_now) {          // decided by k_screen_fin_* once the listed samples have their exact values
                 PendRec r;
                 r.first = found_neg ? gidx : a.n_steps;
-                r.fhi = f_first; r.flo = f_lo; r.flo_ex = 0.f; r.has_flo_ex = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+                r.fhi = f_first; r.flo = f_lo; r.flo_ex = 0.f; r.has_flo_ex = 0; r.first_lost = 0x7fffffff; r.pad[0] = r.pad[1] = 0;
                 w.scr.rec[ray] = r;
                 const int p = atomicAdd(&w.cnt->n_pend, 1);
                 w.scr.pend_list[p] = ray;
@@ -1108,6 +1129,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_screen_resolve(IRON_TRACE_K
             ResolveEntry* e = &w.scr.ent[lib];
             e->f_ex = f;
             if (f < 0.0f) atomicMin(&w.scr.rec[e->ray].first, e->s);
+            if (lost_value<BE>(f)) atomicMin(&w.scr.rec[e->ray].first_lost, e->s);   // (an overflowed ray's record is not read)
             const float f1 = e->f1;
             const float ld = e->ld;
             if (ld > 0.0f && e->s > 0) {   // sample s - 1 was screened at stride 1, next to s
@@ -1187,7 +1209,9 @@ __global__ void k_screen_fin_rays(TraceArgs a, TraceWs w) {
         const int g = r.first;
         const int nb = (g / kSamplerBlock + 1) * kSamplerBlock;
         ev += (unsigned long long)(g < a.n_steps ? (nb < a.n_steps ? nb : a.n_steps) : a.n_steps);
-        if (g >= 1 && g < a.n_steps) {
+        if (r.first_lost <= g) {   // envelope guard: an overflowed sample at or in front of the first negative one, as k_sampler ends such a ray
+            sampler_write_no_root(a, ray, quiet_nan());
+        } else if (g >= 1 && g < a.n_steps) {
             float smin, width;
             ray_interval(a, ray, smin, width);
             sampler_write_root(w, ray, sample_depth(smin, a.lin[g - 1], width), sample_depth(smin, a.lin[g], width),
@@ -1320,6 +1344,7 @@ __device__ __forceinline__ SlotDraw bisect_draw(int* head, int lane, int nfree, 
 
 // a retired ray's result (raytracer.py:75-78: the sampler's mask overwrites convergent)
 __device__ __forceinline__ void bisect_write(const TraceArgs& a, int ray, float qx, float qy, float qz, float f, float mid) {
+    if (!(mid == mid)) f = mid;   // a NaN interval (lost_value, or the caller's): sdf, the output the envelope scan reads, says so itself
     a.conv[ray] = 1;
     a.points[3 * (size_t)ray] = qx; a.points[3 * (size_t)ray + 1] = qy; a.points[3 * (size_t)ray + 2] = qz;
     a.sdf[ray] = f;
@@ -1390,6 +1415,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_a(IRON_TRACE_KERNEL_
             evals = unpark_i64(be, 13, evals);
             ch = be.unpark(15, ch);
         }
+        if (lost_value<BE>(f)) mid = quiet_nan();   // envelope guard: the interval, every later mid-point and the ray's outputs are NaN from here
         // outcome of the pass for the slot (straight-line): an iteration of the ray's own, one its chunk is known to need, or the
         // ray's last evaluation here
         const bool own = active && work;
@@ -1493,6 +1519,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_bisect_b(IRON_TRACE_KERNEL_
             lo = be.unpark(9, lo); hi = be.unpark(10, hi); mid = be.unpark(11, mid);
             evals = unpark_i64(be, 12, evals);
         }
+        if (lost_value<BE>(f)) mid = quiet_nan();   // envelope guard, as in k_bisect_a
         // outcome of the pass for the slot (straight-line): the ray's last evaluation, or one more iteration
         const bool retire = active && remaining <= 1;
         const float qx = ox + dx * mid, qy = oy + dy * mid, qz = oz + dz * mid;   // (the same expressions: the evaluated point)
