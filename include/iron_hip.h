@@ -306,8 +306,8 @@ int iron_texture_fetch(const float* tex, const float* weight, int32_t H, int32_t
 int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, const float* tab_trans, const float* tab_diff_trans, const float* ray_o,
                          const float* ray_d, const float* t, const int32_t* face_idx, const float* bary, int64_t n_rays,
                          const iron_asset_out* out, void* stream);
-/* Environment-map relighting of an exported asset, csrc/envlight.hip; DESIGN.md §16.  Direct illumination only.  Every entry
- * enqueues on `stream`; none waits.
+/* Environment-map relighting of an exported asset, csrc/envlight.hip; DESIGN.md §16, §17.  iron_asset_shade_env is direct
+ * illumination only; iron_asset_shade_env_indirect adds the interreflections.  Every entry enqueues on `stream`; none waits.
  *   iron_mesh_occluded  per ray occluded [n_rays] (uint8) = 1 when any face is met with t in (t_min, t_max], over the BVH of
  *                       iron_bvh_* (same workspace and n_faces).  skip_face [n_rays] int32 (may be NULL): that face is ignored for
  *                       that ray, -1 ignores none.  A non-finite ray or a zero direction gives 0.  The walk uses the triangle and
@@ -342,7 +342,33 @@ int iron_asset_shade_ggx(const iron_asset_mesh* mesh, float light, const float* 
  *                       as iron_asset_shade_ggx (color = diffuse_color + specular_color, linear radiance).  dump (may be NULL, and
  *                       each pointer in it) for tests, N = n_light + n_brdf, environment samples first: dir [n_rays,N,3] (zero for
  *                       a BRDF sample with v.h <= 0), denom [n_rays,N] the denominator above, vis [n_rays,N] uint8 V(w), contrib
- *                       [n_rays,N,3] the sample's term; zeros on a miss. */
+ *                       [n_rays,N,3] the sample's term; zeros on a miss.
+ *   iron_asset_shade_env_indirect  the light that leaves a primary hit after at least one interreflection, by n_paths (1 .. 2^16)
+ *                       paths per ray of at most max_depth (2 .. 8, else IRON_ERR_BAD_ARG) surface vertices, the primary hit (vertex
+ *                       0) included; no Russian roulette.  The arguments up to shadow_eps are iron_asset_shade_env's.  At vertex j
+ *                       (surface record, view v_j, alpha and n_g as there) with the random numbers of (seed, pixel, sample = path,
+ *                       dimension 8 (j + 1) + c):
+ *                         c = 3, 4, j >= 1: an environment sample w_l adds T L(w_l) f_j(w_l) V(w_l) / (p_light(w_l) + p_brdf(w_l)),
+ *                                 V and the densities as in iron_asset_shade_env with both counts 1, f = roughplastic_point's
+ *                                 diffuse + specular;
+ *                         c = 0, 1, 2: a BRDF sample w_b; unless it is a sample with n.w_b > 0 and (n_g.w_b)(n_g.v_j) > 0 the path
+ *                                 ends.  Its ray from x_j + sign(n_g.w_b) shadow_eps D n_g is iron_mesh_raycast's walk (one
+ *                                 function) over t in (0, inf], the vertex's own face ignored.  It escapes: for j >= 1 add
+ *                                 T L(w_b) f_j(w_b) / (p_light(w_b) + p_brdf(w_b)), and the path ends.  It meets a face from behind
+ *                                 (n_g'.w_b >= 0): the path ends.  Else the hit is vertex j + 1, v_(j+1) = -w_b, and for j >= 1
+ *                                 T <- T (f_d + f_s)(w_b) / p_brdf(w_b) per channel (T = 1 at vertex 1); at j = 0 the primary's two
+ *                                 lobe weights b_d = f_d / p_brdf and b_s = f_s / p_brdf are kept apart.
+ *                       The last vertex j = max_depth - 1 runs the same steps and hands the path to nobody, so the first D' vertices
+ *                       of a run with max_depth = D are those of a run with max_depth = D', bitwise.  With C the sum of a path's
+ *                       terms, indirect_diffuse [n_rays,3] = sum over paths of b_d C / n_paths and indirect_specular likewise with
+ *                       b_s (either may be NULL); zeros on a miss.  Sums run in an order fixed by the path index, as in
+ *                       iron_asset_shade_env: bitwise reproducible, for any subset of the rays with their own pixel_idx.  dump (may
+ *                       be NULL, and each pointer in it) for tests, per (ray, path, vertex) [n_rays,n_paths,max_depth,...]:
+ *                       bounce_dir [..,3] w_b (zero: no sample), bounce_org [..,3] its ray's origin, face int32 the face it reached
+ *                       (-1: escaped, -2: no ray cast), t, light_dir [..,3] w_l, light_vis uint8 V(w_l), denom_light and denom_brdf
+ *                       the two denominators, light_term and escape_term [..,3] the two terms above, throughput [..,3] T after the
+ *                       vertex (ones after vertex 0; zeros where the path ended); per (ray, path) lobe_diffuse, lobe_specular
+ *                       [n_rays,n_paths,3] = b_d, b_s.  A vertex a path never reached has face -2 and zeros. */
 typedef struct iron_envmap {
     const float* image;                        /* [h,w,3] */
     const void* dist;                          /* iron_envmap_build's workspace */
@@ -352,6 +378,11 @@ typedef struct iron_envmap {
 typedef struct iron_env_dump {
     float* dir; float* denom; uint8_t* vis; float* contrib;
 } iron_env_dump;
+typedef struct iron_env_path_dump {
+    float* bounce_dir; float* bounce_org; int32_t* face; float* t; float* light_dir; uint8_t* light_vis; float* denom_light;
+    float* denom_brdf; float* light_term; float* escape_term; float* throughput;  /* per (ray, path, vertex) */
+    float* lobe_diffuse; float* lobe_specular;                                     /* per (ray, path) */
+} iron_env_path_dump;
 int iron_mesh_occluded(const void* workspace, int64_t n_faces, const float* ray_o, const float* ray_d, int64_t n_rays, float t_min,
                        float t_max, const int32_t* skip_face, uint8_t* occluded, void* stream);
 int iron_envmap_workspace_bytes(int32_t h, int32_t w, size_t* bytes);
@@ -365,6 +396,11 @@ int iron_asset_shade_env(const iron_asset_mesh* mesh, const void* bvh_workspace,
                          const float* tab_diff_trans, const float* ray_o, const float* ray_d, const float* t, const int32_t* face_idx,
                          const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_light, int32_t n_brdf, uint32_t seed,
                          float shadow_eps, const iron_asset_out* out, const iron_env_dump* dump, void* stream);
+int iron_asset_shade_env_indirect(const iron_asset_mesh* mesh, const void* bvh_workspace, const iron_envmap* env, const float* tab_trans,
+                                  const float* tab_diff_trans, const float* ray_o, const float* ray_d, const float* t,
+                                  const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_paths,
+                                  int32_t max_depth, uint32_t seed, float shadow_eps, float* indirect_diffuse, float* indirect_specular,
+                                  const iron_env_path_dump* dump, void* stream);
 /* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
  * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
  *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte

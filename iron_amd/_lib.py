@@ -100,6 +100,14 @@ class iron_env_dump(C.Structure):
     _fields_ = [("dir", C.c_void_p), ("denom", C.c_void_p), ("vis", C.c_void_p), ("contrib", C.c_void_p)]
 
 
+ENV_PATH_DUMP_FIELDS = ("bounce_dir", "bounce_org", "face", "t", "light_dir", "light_vis", "denom_light", "denom_brdf", "light_term",
+                        "escape_term", "throughput", "lobe_diffuse", "lobe_specular")
+
+
+class iron_env_path_dump(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ENV_PATH_DUMP_FIELDS]
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -153,6 +161,8 @@ SYMBOLS = {
     "iron_roughplastic": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "iron_asset_shade_env": (C.c_int, [C.POINTER(iron_asset_mesh), _P, C.POINTER(iron_envmap), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32,
                                        C.c_uint32, _F, C.POINTER(iron_asset_out), C.POINTER(iron_env_dump), _P]),
+    "iron_asset_shade_env_indirect": (C.c_int, [C.POINTER(iron_asset_mesh), _P, C.POINTER(iron_envmap), _P, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                                _I32, _I32, C.c_uint32, _F, _P, _P, C.POINTER(iron_env_path_dump), _P]),
     "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
     "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),

@@ -1,5 +1,5 @@
-// What the flash render (meshrender.hip) and the environment render (envlight.hip) share on a primary hit of an exported asset: the
-// texture fetch in the bake's convention and the surface record (point, shading normal, material) of one ray.
+// What the flash render (meshrender.hip) and the environment render (envlight.hip) share on a hit of an exported asset: the texture
+// fetch in the bake's convention and the surface record (point, shading normal, material) of one ray, primary or bounced.
 #pragma once
 #include "ray_core.h"
 
@@ -78,11 +78,15 @@ struct SurfHit {
     float dist, uvx, uvy, mat[kTexMaxC];
 };
 
-__device__ __forceinline__ void asset_surface(const iron_asset_mesh& m, const int32_t* __restrict__ face_idx, const float* __restrict__ t_in,
-                                              const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-                                              const float* __restrict__ bary, int64_t i, SurfHit& s) {
-    const int64_t f = face_idx[i];
-    const float t = t_in[i];
+// the unit geometric normal (B - A) x (C - A) of the record's face (zero for a degenerate face)
+__device__ __forceinline__ float3 asset_face_normal(const iron_asset_mesh& m, const SurfHit& s) {
+    const float3 va = ld3(m.verts, s.iv[0]);
+    return unit_or_zero(cross3(sub3(ld3(m.verts, s.iv[1]), va), sub3(ld3(m.verts, s.iv[2]), va)));
+}
+
+// one face, t, ray and barycentric pair by value: a primary hit of the array form below, or a vertex of a path
+__device__ __forceinline__ void asset_surface_at(const iron_asset_mesh& m, int64_t f, float t, float3 o, float3 d, float b1, float b2,
+                                                 SurfHit& s) {
     bool hit = f >= 0 && f < m.n_faces && t < kInfF && t == t;
     int32_t it[3] = {0, 0, 0};
     s.iv[0] = s.iv[1] = s.iv[2] = 0;
@@ -98,8 +102,7 @@ __device__ __forceinline__ void asset_surface(const iron_asset_mesh& m, const in
 #pragma unroll
     for (int c = 0; c < kTexMaxC; ++c) s.mat[c] = 0.0f;
     if (!hit) return;
-    const float3 o = ld3(ray_o, i), d = ld3(ray_d, i);
-    const float b1 = bary[2 * i], b2 = bary[2 * i + 1], b0 = (1.0f - b1) - b2;
+    const float b0 = (1.0f - b1) - b2;
     s.o = o; s.d = d;
     s.pt = make_float3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);
     const float3 rel = sub3(s.pt, o);
@@ -111,11 +114,16 @@ __device__ __forceinline__ void asset_surface(const iron_asset_mesh& m, const in
         s.nrm = unit_or_zero(make_float3((b0 * n0.x + b1 * n1.x) + b2 * n2.x, (b0 * n0.y + b1 * n1.y) + b2 * n2.y,
                                          (b0 * n0.z + b1 * n1.z) + b2 * n2.z));
     }
-    if (s.nrm.x == 0.0f && s.nrm.y == 0.0f && s.nrm.z == 0.0f) {  // no vertex normals, or they cancel: the face's own
-        const float3 va = ld3(m.verts, s.iv[0]);
-        s.nrm = unit_or_zero(cross3(sub3(ld3(m.verts, s.iv[1]), va), sub3(ld3(m.verts, s.iv[2]), va)));
-    }
+    if (s.nrm.x == 0.0f && s.nrm.y == 0.0f && s.nrm.z == 0.0f)  // no vertex normals, or they cancel: the face's own
+        s.nrm = asset_face_normal(m, s);
     s.hole = texture_fetch<kTexMaxC>(m.material, m.weight, m.tex_h, m.tex_w, 7, s.uvx, s.uvy, IRON_TEX_BILINEAR, s.mat);
+}
+
+// ray i of iron_mesh_raycast's arrays
+__device__ __forceinline__ void asset_surface(const iron_asset_mesh& m, const int32_t* __restrict__ face_idx, const float* __restrict__ t_in,
+                                              const float* __restrict__ ray_o, const float* __restrict__ ray_d,
+                                              const float* __restrict__ bary, int64_t i, SurfHit& s) {
+    asset_surface_at(m, face_idx[i], t_in[i], ld3(ray_o, i), ld3(ray_d, i), bary[2 * i], bary[2 * i + 1], s);
 }
 
 // the geometry and material maps of iron_asset_out (the colours are the caller's)

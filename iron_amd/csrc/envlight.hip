@@ -1,6 +1,7 @@
-// Environment-map relighting of an exported asset (DESIGN.md row f-9, §16): an occlusion query over the linear BVH, a lat-long
-// environment map with its sampling distribution, and a direct-illumination integrator that combines environment samples and BRDF
-// samples with the multi-sample balance heuristic.  Conventions: include/iron_hip.h, iron_mesh_occluded block.
+// Environment-map relighting of an exported asset (DESIGN.md row f-9, §16, §17): an occlusion query over the linear BVH, a lat-long
+// environment map with its sampling distribution, a direct-illumination integrator that combines environment samples and BRDF
+// samples with the multi-sample balance heuristic, and a path integrator for the interreflections.  Conventions: include/iron_hip.h,
+// iron_mesh_occluded block.
 //
 // Occlusion (bvh_any_hit): the walk of k_raycast (meshrender.hip) with the primitive tests of ray_core.h, a fixed far end t_max in
 // place of the shrinking best t, and an exit at the first accepted face.  A face is accepted under exactly k_raycast's condition
@@ -16,9 +17,13 @@
 // Integrator (k_shade_env): kEnvGroup lanes work one pixel; sample s of the pixel's n_light + n_brdf runs on lane s % kEnvGroup in
 // round s / kEnvGroup, every lane adds its rounds in order, and a fixed butterfly adds the lanes: a pixel's sums depend on nothing
 // but its own samples.  Random numbers: env_rand, a pure function of (seed, pixel index, sample, dimension).
+//
+// Interreflections (k_shade_env_indirect): the light that reaches a primary hit after at least one more surface, by
+// paths of a fixed largest length.  The same lane scheme with a path in a sample's place; the bounce rays walk bvh_closest_hit of
+// ray_walk.h (k_raycast's walk), the shadow rays bvh_any_hit, both on the one LDS stack in turn.  The direct term stays k_shade_env's.
 #include "asset_common.h"
 #include "ggx_core.h"
-#include "ray_core.h"
+#include "ray_walk.h"
 
 namespace iron {
 
@@ -371,6 +376,30 @@ struct EnvShadeArgs {
     float shadow_eps;
 };
 
+// the origin of a ray that leaves x along w: x moved by `off` along n_g to w's side
+__device__ __forceinline__ float3 leave_origin(float3 x, float3 ng, float ngw, float off) {
+    const float sg = ngw > 0.0f ? off : -off;
+    return make_float3(x.x + sg * ng.x, x.y + sg * ng.y, x.z + sg * ng.z);
+}
+
+// may a sample direction w count at a vertex (shading normal n, geometric normal n_g, n_g.v)?  Above the shading horizon, on the
+// viewer's side of the face, finite
+__device__ __forceinline__ bool dir_counts(float3 n, float3 ng, float ngv, float3 w) {
+    return dot3(n, w) > 0.0f && dot3(ng, w) * ngv > 0.0f && finite3(w);
+}
+
+// V(w) of the integrators: w counts and the shadow ray from x meets no face other than x's own
+__device__ __forceinline__ bool env_visible(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf, float3 x, float3 n,
+                                            float3 ng, float ngv, float3 w, float off, int32_t face, int32_t (*stack)[kBvQueryBlock],
+                                            int lane) {
+    if (!dir_counts(n, ng, ngv, w)) return false;
+    const float3 org = leave_origin(x, ng, dot3(ng, w), off);
+    if (!ray_valid(org, w)) return false;
+    RayPre r;
+    ray_setup(org, w, r);
+    return !bvh_any_hit(nodes, tris, nf, r, 0.0f, kInfF, face, stack, lane);
+}
+
 __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
     __shared__ int32_t stack[kBvStack][kBvQueryBlock];
     const int lane = threadIdx.x, sl = lane % kEnvGroup;
@@ -383,8 +412,7 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
     float3 ng = make_float3(0.f, 0.f, 0.f), v = ng;
     float off = 0.0f, ngv = 0.0f, alpha = 0.0f;
     if (s.hit) {
-        const float3 va = ld3(a.m.verts, s.iv[0]);
-        ng = unit_or_zero(cross3(sub3(ld3(a.m.verts, s.iv[1]), va), sub3(ld3(a.m.verts, s.iv[2]), va)));
+        ng = asset_face_normal(a.m, s);
         v = make_float3(-s.d.x, -s.d.y, -s.d.z);
         ngv = dot3(ng, v);
         off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
@@ -414,16 +442,7 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
             }
             const float pb = ok ? brdf_pdf(s.nrm, v, w, alpha) : 0.0f;
             denom = (a.n_light > 0 ? (float)a.n_light * pl : 0.0f) + (a.n_brdf > 0 ? (float)a.n_brdf * pb : 0.0f);
-            const float ngw = dot3(ng, w);
-            if (ok && dot3(s.nrm, w) > 0.0f && ngw * ngv > 0.0f && finite3(w)) {
-                const float sg = ngw > 0.0f ? off : -off;
-                const float3 org = make_float3(s.pt.x + sg * ng.x, s.pt.y + sg * ng.y, s.pt.z + sg * ng.z);
-                if (ray_valid(org, w)) {
-                    RayPre r;
-                    ray_setup(org, w, r);
-                    vis = !bvh_any_hit(a.nodes, a.tris, a.m.n_faces, r, 0.0f, kInfF, (int32_t)s.face, stack, lane);
-                }
-            }
+            vis = ok && env_visible(a.nodes, a.tris, a.m.n_faces, s.pt, s.nrm, ng, ngv, w, off, (int32_t)s.face, stack, lane);
             if (vis && denom > 0.0f) {
                 PlasticOut f;
                 const float ww[3] = {w.x, w.y, w.z};
@@ -455,6 +474,179 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
     st3(a.o.diffuse_color, i, accd[0], accd[1], accd[2]);
     st3(a.o.specular_color, i, accs[0], accs[1], accs[2]);
     asset_store_maps(a.o, i, s);
+}
+
+// ---- the path integrator ----
+struct EnvPathArgs {
+    iron_asset_mesh m;
+    iron_env_path_dump dump;
+    EnvDev env;
+    const float4 *nodes, *tris;
+    const float *tab_trans, *tab_diff, *ray_o, *ray_d, *t, *bary;
+    const int32_t *face_idx, *pixel_idx;
+    float *indirect_diffuse, *indirect_specular;
+    int64_t n;
+    int32_t n_paths, max_depth;
+    uint32_t seed;
+    float shadow_eps;
+};
+
+// what a path keeps of its current vertex
+struct PathVertex {
+    float3 pt, nrm, ng, v;  // point, shading normal, geometric normal, direction back along the path
+    float mat[7];
+    int32_t face;
+};
+
+__device__ __forceinline__ void path_vertex(const iron_asset_mesh& m, const SurfHit& s, PathVertex& x) {
+    x.pt = s.pt; x.nrm = s.nrm;
+    x.ng = asset_face_normal(m, s);
+    x.v = make_float3(-s.d.x, -s.d.y, -s.d.z);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) x.mat[c] = s.mat[c];
+    x.face = (int32_t)s.face;
+}
+
+// Path p of a pixel runs on lane p % kEnvGroup in round p / kEnvGroup.  Vertex 0 is the primary hit; at vertex j the random numbers
+// are env_rand(seed, pixel, p, 8 (j + 1) + c): c = 0, 1, 2 the BRDF sample that continues the path, c = 3, 4 the environment sample
+// (vertices j >= 1: the primary's direct light is k_shade_env's).  T is the throughput past the primary, the product of
+// (f_d + f_s) / p_brdf over the vertices 1 .. j; the primary's own two lobe weights f_d / p_brdf and f_s / p_brdf stay apart and
+// multiply what the path gathered, C, when it ends.  Every vertex runs the same code, the last one included (its closest hit decides
+// between the escape term and nothing), so the first D' vertices of a path do not depend on max_depth.
+__global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArgs a) {
+    __shared__ int32_t stack[kBvStack][kBvQueryBlock];
+    const int lane = threadIdx.x, sl = lane % kEnvGroup;
+    const int64_t i = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;
+    if (i >= a.n) return;  // a whole group leaves together
+    const uint32_t pixel = a.pixel_idx ? (uint32_t)a.pixel_idx[i] : (uint32_t)i;
+    const float off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
+    const int32_t D = a.max_depth;
+    PathVertex x0;
+    bool hit0;
+    {
+        SurfHit s;
+        asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s);
+        hit0 = s.hit;
+        path_vertex(a.m, s, x0);
+    }
+    float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
+    for (int32_t base = 0; base < a.n_paths; base += kEnvGroup) {
+        const int32_t p = base + sl;
+        if (p >= a.n_paths) break;  // the ragged tail of the last round
+        PathVertex x = x0;
+        float T[3] = {1.f, 1.f, 1.f}, C[3] = {0.f, 0.f, 0.f}, bd[3] = {0.f, 0.f, 0.f}, bs[3] = {0.f, 0.f, 0.f};
+        bool alive = hit0;
+        for (int32_t j = 0; j < D; ++j) {
+            float3 wl = make_float3(0.f, 0.f, 0.f), wb = wl, org = wl;
+            float dl = 0.0f, db = 0.0f, th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
+            bool lvis = false;
+            int32_t reached = -2;
+            if (alive) {
+                alive = false;  // until the vertex hands the path on
+                const uint32_t dim = 8u * (uint32_t)(j + 1);
+                const float alpha = fmaxf(x.mat[6], 0.0001f), ngv = dot3(x.ng, x.v);
+                const float nn[3] = {x.nrm.x, x.nrm.y, x.nrm.z}, vv[3] = {x.v.x, x.v.y, x.v.z};
+                if (j >= 1) {  // the environment sample
+                    int r, c;
+                    const float pl = env_sample(a.env, env_rand(a.seed, pixel, p, dim + 3u), env_rand(a.seed, pixel, p, dim + 4u), r, c, wl);
+                    const float* L = a.env.image + 3 * ((int64_t)r * a.env.We + c);
+                    dl = pl + brdf_pdf(x.nrm, x.v, wl, alpha);
+                    lvis = env_visible(a.nodes, a.tris, a.m.n_faces, x.pt, x.nrm, x.ng, ngv, wl, off, x.face, stack, lane);
+                    if (lvis && dl > 0.0f) {
+                        PlasticOut f;
+                        const float ww[3] = {wl.x, wl.y, wl.z};
+                        roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+#pragma unroll
+                        for (int c3 = 0; c3 < 3; ++c3) {
+                            lt[c3] = (T[c3] * L[c3]) * (f.diffuse[c3] + f.specular[c3]) / dl;  // an infinite density gives 0
+                            C[c3] += lt[c3];
+                        }
+                    }
+                }
+                // the BRDF sample and its ray
+                const bool ok = brdf_sample(x.nrm, x.v, alpha, env_rand(a.seed, pixel, p, dim), env_rand(a.seed, pixel, p, dim + 1u),
+                                            env_rand(a.seed, pixel, p, dim + 2u), wb);
+                if (!ok) wb = make_float3(0.f, 0.f, 0.f);
+                if (ok && dir_counts(x.nrm, x.ng, ngv, wb)) {
+                    float L[3];
+                    const float pl = env_eval(a.env, wb, L), pb = brdf_pdf(x.nrm, x.v, wb, alpha);
+                    db = pl + pb;
+                    org = leave_origin(x.pt, x.ng, dot3(x.ng, wb), off);
+                    if (ray_valid(org, wb)) {
+                        RayPre r;
+                        ray_setup(org, wb, r);
+                        RayHit h = ray_hit_none(kInfF);
+                        bvh_closest_hit(a.nodes, a.tris, a.m.n_faces, r, 0.0f, x.face, stack, lane, h);
+                        const bool hit = h.face != kNoFace;
+                        if (hit) refine_bary(a.tris, org, wb, h);
+                        reached = hit ? h.face : -1;
+                        th = hit ? h.t : kInfF;
+                        PlasticOut f;
+                        const float ww[3] = {wb.x, wb.y, wb.z};
+                        roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+                        if (!hit) {
+                            if (j >= 1 && db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) {
+                                    et[c] = (T[c] * L[c]) * (f.diffuse[c] + f.specular[c]) / db;
+                                    C[c] += et[c];
+                                }
+                            }
+                        } else {
+                            SurfHit s;
+                            asset_surface_at(a.m, h.face, h.t, org, wb, h.b1, h.b2, s);
+                            const float3 ng2 = asset_face_normal(a.m, s);
+                            // a face met from behind is black, like a back-facing primary hit
+                            if (s.hit && -dot3(ng2, wb) > 0.0f && pb > 0.0f) {
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) {
+                                    if (j == 0) {
+                                        bd[c] = f.diffuse[c] / pb;
+                                        bs[c] = f.specular[c] / pb;
+                                    } else {
+                                        T[c] = T[c] * (f.diffuse[c] + f.specular[c]) / pb;
+                                    }
+                                    tp[c] = T[c];
+                                }
+                                path_vertex(a.m, s, x);
+                                alive = true;
+                            }
+                        }
+                    }
+                }
+            }
+            const int64_t at = ((int64_t)i * a.n_paths + p) * D + j;
+            st3(a.dump.bounce_dir, at, wb.x, wb.y, wb.z);
+            st3(a.dump.bounce_org, at, org.x, org.y, org.z);
+            if (a.dump.face) a.dump.face[at] = reached;
+            if (a.dump.t) a.dump.t[at] = th;
+            st3(a.dump.light_dir, at, wl.x, wl.y, wl.z);
+            if (a.dump.light_vis) a.dump.light_vis[at] = lvis ? 1 : 0;
+            if (a.dump.denom_light) a.dump.denom_light[at] = dl;
+            if (a.dump.denom_brdf) a.dump.denom_brdf[at] = db;
+            st3(a.dump.light_term, at, lt[0], lt[1], lt[2]);
+            st3(a.dump.escape_term, at, et[0], et[1], et[2]);
+            st3(a.dump.throughput, at, tp[0], tp[1], tp[2]);
+        }
+        st3(a.dump.lobe_diffuse, (int64_t)i * a.n_paths + p, bd[0], bd[1], bd[2]);
+        st3(a.dump.lobe_specular, (int64_t)i * a.n_paths + p, bs[0], bs[1], bs[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += bd[c] * C[c];
+            accs[c] += bs[c] * C[c];
+        }
+    }
+#pragma unroll
+    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
+            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
+        }
+    if (sl != 0) return;
+    const float np = (float)a.n_paths;
+    st3(a.indirect_diffuse, i, accd[0] / np, accd[1] / np, accd[2] / np);
+    st3(a.indirect_specular, i, accs[0] / np, accs[1] / np, accs[2] / np);
 }
 
 static bool env_dev(const iron_envmap* env, EnvDev& E) {
@@ -564,5 +756,31 @@ extern "C" int iron_asset_shade_env(const iron_asset_mesh* mesh, const void* bvh
     a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.ray_o = ray_o; a.ray_d = ray_d; a.t = t; a.bary = bary; a.face_idx = face_idx;
     a.pixel_idx = pixel_idx; a.n = n_rays; a.n_light = n_light; a.n_brdf = n_brdf; a.seed = seed; a.shadow_eps = shadow_eps;
     IRON_LAUNCH(k_shade_env, blocks_for(n_rays, kEnvPixels), kBvQueryBlock, (hipStream_t)stream, a);
+    return IRON_OK;
+}
+
+extern "C" int iron_asset_shade_env_indirect(const iron_asset_mesh* mesh, const void* bvh_workspace, const iron_envmap* env, const float* tab_trans,
+                                             const float* tab_diff_trans, const float* ray_o, const float* ray_d, const float* t,
+                                             const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays,
+                                             int32_t n_paths, int32_t max_depth, uint32_t seed, float shadow_eps, float* indirect_diffuse,
+                                             float* indirect_specular, const iron_env_path_dump* dump, void* stream) {
+    if (!mesh || !bvh_workspace || n_rays < 0 || n_paths < 1 || n_paths > (1 << 16) || max_depth < 2 || max_depth > 8) return IRON_ERR_BAD_ARG;
+    if (mesh->n_faces <= 0 || mesh->n_faces >= 0x7fffffffLL || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
+        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
+        return IRON_ERR_BAD_ARG;
+    if (!mesh->verts || !mesh->faces || !mesh->uvs || !mesh->face_uvs || !mesh->material || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
+    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    EnvPathArgs a;
+    if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
+    if (n_rays == 0) return IRON_OK;
+    if (!ray_o || !ray_d || !t || !face_idx || !bary) return IRON_ERR_BAD_ARG;
+    const BvLayout L = bv_layout(mesh->n_faces);
+    a.m = *mesh;
+    a.dump = dump ? *dump : iron_env_path_dump{};
+    a.nodes = ws_ptr<float4>(bvh_workspace, L.nodes_off); a.tris = ws_ptr<float4>(bvh_workspace, L.tris_off);
+    a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.ray_o = ray_o; a.ray_d = ray_d; a.t = t; a.bary = bary; a.face_idx = face_idx;
+    a.pixel_idx = pixel_idx; a.indirect_diffuse = indirect_diffuse; a.indirect_specular = indirect_specular; a.n = n_rays;
+    a.n_paths = n_paths; a.max_depth = max_depth; a.seed = seed; a.shadow_eps = shadow_eps;
+    IRON_LAUNCH(k_shade_env_indirect, blocks_for(n_rays, kEnvPixels), kBvQueryBlock, (hipStream_t)stream, a);
     return IRON_OK;
 }

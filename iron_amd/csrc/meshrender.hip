@@ -2,8 +2,9 @@
 // BVH of meshdist.hip, area-weighted vertex normals, the texture fetch in the bake's pixel convention, and the co-located GGX of
 // ggx_core.h on the hits.  Conventions: include/iron_hip.h, iron_mesh_raycast block.
 //
-// Ray cast (k_raycast): one lane per ray, depth-first, the child with the nearer box entry first, the other on a per-lane stack in
-// LDS (kBvStack entries, see bvh_common.h).
+// Ray cast (k_raycast; the walk itself is bvh_closest_hit of ray_walk.h, which the path integrator of envlight.hip shares): one lane
+// per ray, depth-first, the child with the nearer box entry first, the other on a per-lane stack in LDS (kBvStack entries, see
+// bvh_common.h).
 //   Triangle test: Woop, Benthin, Wald, "Watertight Ray/Triangle Intersection" (JCGT 2013).  The vertices are translated to the
 //   ray origin and sheared into the ray's space (largest direction component = z); the edge functions U, V, W are differences of two
 //   products of the sheared x / y of two vertices.  An edge shared by two faces feeds the same two vertices into the same two
@@ -18,42 +19,9 @@
 //   set of faces, not of their order or of the tree.
 #include "asset_common.h"
 #include "ggx_core.h"
-#include "ray_core.h"
+#include "ray_walk.h"
 
 namespace iron {
-
-struct RayHit {
-    float t, b1, b2;  // distance along d, barycentric weights of the face's second and third vertex
-    int32_t face;     // INT32_MAX: none yet
-    int32_t leaf;     // its position in the leaf order
-};
-
-__device__ __forceinline__ void ray_leaf(const float4* __restrict__ tris, int32_t k, const RayPre& r, float t_min, RayHit& h) {
-    TriHit x;
-    if (!ray_tri(tris, k, r, t_min, x)) return;
-    if (x.t < h.t || (x.t == h.t && x.face < h.face)) {
-        h.t = x.t; h.face = x.face; h.leaf = k; h.b1 = x.V / x.det; h.b2 = x.W / x.det;
-    }
-}
-
-// The winner's barycentric weights once more, in fp64 from the fp32 inputs (Moeller-Trumbore; the differences are exact there).  The
-// ray-space edge functions decide the hit and t; as weights they carry the rounding of the vertices' translation to the ray origin,
-// ~2^-24 |A - o| / h (h the face's altitude), which grows with the distance to the camera.  These do not.
-__device__ __forceinline__ void refine_bary(const float4* __restrict__ tris, float3 o, float3 d, RayHit& h) {
-    const float4 ta = tris[3 * (int64_t)h.leaf], tb = tris[3 * (int64_t)h.leaf + 1], tc = tris[3 * (int64_t)h.leaf + 2];
-    const double e1[3] = {(double)tb.x - ta.x, (double)tb.y - ta.y, (double)tb.z - ta.z};
-    const double e2[3] = {(double)tc.x - ta.x, (double)tc.y - ta.y, (double)tc.z - ta.z};
-    const double s[3] = {(double)o.x - ta.x, (double)o.y - ta.y, (double)o.z - ta.z};
-    const double dd[3] = {d.x, d.y, d.z};
-    const double p[3] = {dd[1] * e2[2] - dd[2] * e2[1], dd[2] * e2[0] - dd[0] * e2[2], dd[0] * e2[1] - dd[1] * e2[0]};
-    const double q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
-    const double det = (e1[0] * p[0] + e1[1] * p[1]) + e1[2] * p[2];
-    if (det == 0.0) return;  // keeps the fp32 weights
-    const double u = ((s[0] * p[0] + s[1] * p[1]) + s[2] * p[2]) / det, v = ((dd[0] * q[0] + dd[1] * q[1]) + dd[2] * q[2]) / det;
-    if (!(fabs(u) <= 2.0) || !(fabs(v) <= 2.0)) return;  // a sliver seen edge-on: nothing gained
-    h.b1 = (float)fmin(fmax(u, 0.0), 1.0);  // a hit the fp32 test took on an edge may lie a rounding outside
-    h.b2 = (float)fmin(fmax(v, 0.0), 1.0);
-}
 
 __global__ __launch_bounds__(kBvQueryBlock) void k_raycast(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf,
                                                             const float* __restrict__ ray_o, const float* __restrict__ ray_d, int64_t n,
@@ -64,42 +32,14 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_raycast(const float4* __restr
     const int64_t q = (int64_t)blockIdx.x * kBvQueryBlock + lane;
     if (q >= n) return;
     const float3 o = ld3(ray_o, q), d = ld3(ray_d, q);
-    RayHit h;
-    h.t = t_max; h.face = 0x7fffffff; h.leaf = 0; h.b1 = h.b2 = 0.0f;  // the window's far end is inclusive: any face at t_max beats the sentinel
+    RayHit h = ray_hit_none(t_max);
     const bool valid = finite3(o) && finite3(d) && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f) && t_min <= t_max;  // NaN bounds fail
     if (valid) {
         RayPre r;
         ray_setup(o, d, r);
-        if (nf == 1) {
-            ray_leaf(tris, 0, r, t_min, h);
-        } else {
-            int32_t node = 0, sp = 0;
-            for (;;) {
-                const float4* nd = nodes + 4 * (int64_t)node;
-                const float4 l0 = nd[0], h0 = nd[1], l1 = nd[2], h1 = nd[3];
-                const int32_t c0 = __float_as_int(l0.w), c1 = __float_as_int(h0.w);
-                float n0, n1;
-                const bool v0 = ray_box(r, l0, h0, t_min, h.t, n0);
-                if (c0 < 0 && v0) ray_leaf(tris, ~c0, r, t_min, h);
-                const bool v1 = ray_box(r, l1, h1, t_min, h.t, n1);
-                if (c1 < 0 && v1) ray_leaf(tris, ~c1, r, t_min, h);
-                const bool g0 = c0 >= 0 && v0 && n0 <= h.t, g1 = c1 >= 0 && v1 && n1 <= h.t;
-                if (g0 && g1) {
-                    const bool first1 = n1 < n0;
-                    if (sp < kBvStack) stack[sp++][lane] = first1 ? c0 : c1;  // never full (kBvStack)
-                    node = first1 ? c1 : c0;
-                } else if (g0) {
-                    node = c0;
-                } else if (g1) {
-                    node = c1;
-                } else {
-                    if (sp == 0) break;
-                    node = stack[--sp][lane];
-                }
-            }
-        }
+        bvh_closest_hit(nodes, tris, nf, r, t_min, -1, stack, lane, h);
     }
-    const bool hit = h.face != 0x7fffffff;
+    const bool hit = h.face != kNoFace;
     if (hit) refine_bary(tris, o, d, h);
     t_out[q] = hit ? h.t : kInfF;
     face_idx[q] = hit ? h.face : -1;

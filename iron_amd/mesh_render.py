@@ -213,6 +213,54 @@ class MeshAsset:
                                                         _lib.stream_ptr(dev)))
         return out
 
+    def shade_env_indirect(self, ray_o, ray_d, t, face_idx, bary, envmap, tables, n_paths=64, max_depth=2, seed=0, shadow_eps=1e-4,
+                           pixel_idx=None, dump=False):
+        """iron_asset_shade_env_indirect on n rays (ray_d unit): the light that leaves the primary hits after at least one
+        interreflection, by n_paths (1 .. 2^16) paths per ray of at most max_depth (2 .. 8) surface vertices, the primary hit
+        included -> {"indirect_diffuse", "indirect_specular" (through the primary hit's diffuse and specular lobe),
+        "indirect_color" (their sum)}, [n, 3] each.  seed, shadow_eps and pixel_idx as in shade_env; a path's random numbers are
+        disjoint from that call's.  dump=True adds "dump_" + every name of _lib.ENV_PATH_DUMP_FIELDS, per (ray, path, vertex)
+        ([n, n_paths, max_depth, ...]; the two lobe weights per (ray, path)), for tests."""
+        check_path_args(max_depth, n_paths, indirect=True)
+        dev = self.device
+        n, P, D = int(ray_o.shape[0]), int(n_paths), int(max_depth)
+        out = {k: torch.empty((n, 3), dtype=torch.float32, device=dev) for k in ("indirect_diffuse", "indirect_specular")}
+        d = _lib.iron_env_path_dump()
+        if dump:
+            for k in _lib.ENV_PATH_DUMP_FIELDS:
+                shape = (n, P) if k.startswith("lobe_") else (n, P, D)
+                kind = {"face": ((), torch.int32), "light_vis": ((), torch.uint8), "t": ((), torch.float32),
+                        "denom_light": ((), torch.float32), "denom_brdf": ((), torch.float32)}.get(k, ((3,), torch.float32))
+                out["dump_" + k] = torch.empty(shape + kind[0], dtype=kind[1], device=dev)
+            d = _lib.iron_env_path_dump(*[out["dump_" + k].data_ptr() for k in _lib.ENV_PATH_DUMP_FIELDS])
+        H, W = self.material.shape[:2]
+        mesh = _lib.iron_asset_mesh(self.vertices.data_ptr(), self.vertices.shape[0], self.faces.data_ptr(), self.faces.shape[0],
+                                    self.uvs.data_ptr(), self.uvs.shape[0], self.face_uvs.data_ptr(), _lib.ptr(self.normals),
+                                    self.material.data_ptr(), _lib.ptr(self.weight), H, W)
+        with torch.cuda.device(dev):
+            pix = None if pixel_idx is None else _args.device_array(pixel_idx, torch.int32, dev, "pixel_idx", (), what=WHAT)
+            if pix is not None and pix.shape[0] != n:
+                raise _lib.IronError("ray_o has %d rows, pixel_idx %d" % (n, pix.shape[0]))
+            env = envmap.c_struct()
+            _lib.check(_lib.load().iron_asset_shade_env_indirect(C.byref(mesh), self.bvh.workspace.data_ptr(), C.byref(env),
+                                                                 tables[0].data_ptr(), tables[1].data_ptr(), ray_o.data_ptr(),
+                                                                 ray_d.data_ptr(), t.data_ptr(), face_idx.data_ptr(), bary.data_ptr(),
+                                                                 _lib.ptr(pix), n, P, D, int(seed) & 0xFFFFFFFF, float(shadow_eps),
+                                                                 out["indirect_diffuse"].data_ptr(), out["indirect_specular"].data_ptr(),
+                                                                 C.byref(d), _lib.stream_ptr(dev)))
+        out["indirect_color"] = out["indirect_diffuse"] + out["indirect_specular"]
+        return out
+
+
+def check_path_args(max_depth, n_paths, indirect=False):
+    """The host-side refusal of the path integrator's two counts: max_depth 1 .. 8 (2 .. 8 for the indirect kernel itself, which does
+    not run at 1), n_paths 1 .. 2^16."""
+    lo = 2 if indirect else 1
+    if int(max_depth) != max_depth or not lo <= max_depth <= 8:
+        raise _lib.IronError("max_depth must be an integer in %d .. 8, got %r" % (lo, max_depth))
+    if int(n_paths) != n_paths or not 1 <= n_paths <= 1 << 16:
+        raise _lib.IronError("n_paths must be an integer in 1 .. 2^16, got %r" % (n_paths,))
+
 
 _tables = {}
 
@@ -228,7 +276,8 @@ def _mts_tables(dev):
 def render_asset_uv(camera, asset, light, uv, env=None):
     """One ray per entry of uv [H, W, 2] (pixel coordinates of `camera`): the dictionary of render_asset_camera for one sample
     per pixel.  Pixels go to the ray cast's lanes row-major: one 8x8 pixel tile per 64-lane wave measured slower.
-    env: None for the flash of intensity `light`, else the keywords of MeshAsset.shade_env plus `background` (render_asset_env)."""
+    env: None for the flash of intensity `light`, else the keywords of MeshAsset.shade_env plus `background`, `max_depth` and
+    `n_paths` (render_asset_env); max_depth > 1 adds the key indirect_color."""
     _args.refuse_cpu(WHAT, uv, camera.K)
     dev = asset.device
     H, W = int(uv.shape[0]), int(uv.shape[1])
@@ -241,12 +290,22 @@ def render_asset_uv(camera, asset, light, uv, env=None):
         else:
             env = dict(env)
             background = env.pop("background", False)
+            max_depth, n_paths = env.pop("max_depth", 1), env.pop("n_paths", 64)
             s = asset.shade_env(o, d, t, face, bary, tables=_mts_tables(dev), **env)
+            if max_depth > 1:  # the interreflections, lobe by lobe; the direct term above is untouched
+                ind = asset.shade_env_indirect(o, d, t, face, bary, env["envmap"], _mts_tables(dev), n_paths=n_paths, max_depth=max_depth,
+                                               seed=env.get("seed", 0), shadow_eps=env.get("shadow_eps", 1e-4))
+                s["indirect_color"] = ind["indirect_color"]
+                s["diffuse_color"] = s["diffuse_color"] + ind["indirect_diffuse"]
+                s["specular_color"] = s["specular_color"] + ind["indirect_specular"]
+                s["color"] = s["diffuse_color"] + s["specular_color"]
             if background:  # the map itself behind the asset
                 s["color"] = torch.where((face < 0)[:, None], env["envmap"].lookup(d), s["color"])
     img = lambda x: x.reshape([H, W] + list(x.shape[1:]))  # noqa: E731
     res = {k: img(s[k]) for k in ("color", "diffuse_color", "specular_color", "normal", "diffuse_albedo", "specular_albedo",
                                   "specular_roughness", "distance", "points")}
+    if "indirect_color" in s:
+        res["indirect_color"] = img(s["indirect_color"])
     res["convergent_mask"] = img(face >= 0)
     res["depth"] = res["distance"] / ray_d_norm
     res.update({"uv": uv, "ray_o": ray_o, "ray_d": ray_d, "ray_d_norm": ray_d_norm, "face_idx": img(face), "barycentric": img(bary),
@@ -272,7 +331,8 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1, _env=None):
     """Render `asset` (MeshAsset) from `camera` (raytracer.Camera, on the asset's device) under a point light of intensity `light`
     at the camera origin.  Returns render_camera's keys, all [H, W, ...] device tensors: color, diffuse_color, specular_color,
     normal, diffuse_albedo, specular_albedo, specular_roughness, convergent_mask, distance, depth, points, uv, ray_o, ray_d, plus
-    face_idx (-1: miss), barycentric, tex_uv, texture_hole, and t, ray_d_norm, coverage.  Direct illumination only.
+    face_idx (-1: miss), barycentric, tex_uv, texture_hole, and t, ray_d_norm, coverage.  Direct illumination only (render_asset_env
+    has the interreflections).
     samples_per_axis = s > 1 casts s^2 rays per pixel on a regular sub-pixel grid (subpixel_uvs): the AVERAGED maps are the sum of
     the s^2 frames in that order, divided by s^2 (torch, fixed order: bitwise reproducible); convergent_mask is coverage >= 1/2
     (`coverage` is returned too); texture_hole is the union; the per-ray keys (t, face_idx, barycentric, tex_uv, ray_o, ray_d) are
@@ -290,13 +350,14 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1, _env=None):
         f = render_asset_uv(camera, asset, light, uv, env=_env and _env(k))
         if res is None:
             res = f
+            averaged = AVERAGED + tuple(k for k in ("indirect_color",) if k in f)
             res["coverage"] = f["convergent_mask"].float()
         else:
-            for k in AVERAGED:
+            for k in averaged:
                 res[k] = res[k] + f[k]
             res["coverage"] = res["coverage"] + f["convergent_mask"].float()
             res["texture_hole"] = res["texture_hole"] | f["texture_hole"]
-    for k in AVERAGED + ("coverage",):
+    for k in averaged + ("coverage",):
         res[k] = res[k] / float(s * s)
     res["convergent_mask"] = res["coverage"] >= 0.5
     res["uv"] = camera.get_uv()
@@ -304,12 +365,26 @@ def render_asset_camera(camera, asset, light, samples_per_axis=1, _env=None):
 
 
 @torch.no_grad()
-def render_asset_env(camera, asset, envmap, n_light=64, n_brdf=64, seed=0, samples_per_axis=1, background=False, shadow_eps=1e-4):
+def render_asset_env(camera, asset, envmap, n_light=64, n_brdf=64, seed=0, samples_per_axis=1, background=False, shadow_eps=1e-4,
+                     max_depth=1, n_paths=64):
     """Render `asset` from `camera` under the environment map `envmap` (EnvMap on the asset's device): direct illumination with
     visibility, n_light environment samples and n_brdf BRDF samples per ray combined by the balance heuristic (csrc/envlight.hip,
     DESIGN.md §16).  Returns render_asset_camera's dictionary with the same keys; distance and depth keep their meaning.  Sub-pixel
     frames are averaged exactly as there, sample k of the sub-pixel grid with seed + k.  background=True fills `color` of every
-    ray that misses with envmap.lookup(ray_d) (before the averaging); the default leaves zeros there, like the flash render."""
-    return render_asset_camera(camera, asset, 0.0, samples_per_axis=samples_per_axis,
-                               _env=lambda k: {"envmap": envmap, "n_light": n_light, "n_brdf": n_brdf, "seed": int(seed) + k,
-                                               "shadow_eps": shadow_eps, "background": background})
+    ray that misses with envmap.lookup(ray_d) (before the averaging); the default leaves zeros there, like the flash render.
+    max_depth (1 .. 8): the largest number of surface vertices on a light path, the primary hit included.  1 is direct illumination
+    alone.  Above 1, n_paths (1 .. 2^16) paths per ray add the interreflections (MeshAsset.shade_env_indirect; the
+    direct term is unchanged): the dictionary gains indirect_color, diffuse_color and specular_color are direct + indirect of that
+    lobe (averaged over the sub-pixel frames like every map), and color = diffuse_color + specular_color of the averaged maps; under
+    background=True a pixel with a ray that misses keeps the mean of its frames' colours, which holds the map."""
+    check_path_args(max_depth, n_paths)
+    env = lambda k: {"envmap": envmap, "n_light": n_light, "n_brdf": n_brdf, "seed": int(seed) + k,  # noqa: E731
+                     "shadow_eps": shadow_eps, "background": background}
+    if max_depth == 1:
+        return render_asset_camera(camera, asset, 0.0, samples_per_axis=samples_per_axis, _env=env)
+    res = render_asset_camera(camera, asset, 0.0, samples_per_axis=samples_per_axis,
+                              _env=lambda k: dict(env(k), max_depth=int(max_depth), n_paths=int(n_paths)))
+    lobes = res["diffuse_color"] + res["specular_color"]
+    # a pixel with a ray that misses under background=True keeps the mean of its frames' colours, which holds the map
+    res["color"] = torch.where((res["coverage"] >= 1.0)[..., None], lobes, res["color"]) if background else lobes
+    return res

@@ -2,8 +2,9 @@
 S0's 512^3 extract_geometry mesh at 800x800 from the fixture camera, by device events (median of --reps after a warm-up run): the
 distribution build of a 512 x 1024 map, `occluded` against `raycast` on the camera's primary rays (alternating in one run), the
 integrator at 64 + 64 and 256 + 256 samples per pixel with its shadow rays per second (the shadow rays are counted from the
-visibility dump of a separate, untimed run: a sample below the horizon casts none), and whole render_asset_env frames.  The map
-and the material texture are synthetic (a smooth sky with a small sun; random materials): the timing depends on them only through
+visibility dump of a separate, untimed run: a sample below the horizon casts none), the path integrator for interreflections
+ at 64 paths per pixel and depth 2 and 4 with the rays it casts per second (bounce rays and shadow rays, counted from
+its dumps likewise), and whole render_asset_env frames.  The map and the material texture are synthetic (a smooth sky with a small sun; random materials): the timing depends on them only through
 where the samples go.  Writes one JSON line to profiles/envlight_bench.json and prints it.
 
     python tools/bench_envlight.py [--reps 5] [--res 512] [--size 800]
@@ -116,6 +117,36 @@ def main() -> None:
             visible += int(out["dump_vis"].sum())
         res["integrator"]["%d+%d" % (nl, nb)] = {"ms": ms, "samples": int((fi >= 0).sum()) * (nl + nb), "shadow_rays": rays,
                                                 "visible": visible, "shadow_mrays_per_s": round(rays / (ms * 1e-3) / 1e6, 1)}
+    # the interreflections: 64 paths per pixel, at most 2 and 4 surface vertices per path (incoherent secondary rays)
+    res["indirect"] = {}
+    vf = v[f.long()]
+    face_n = torch.nn.functional.normalize(torch.cross(vf[:, 1] - vf[:, 0], vf[:, 2] - vf[:, 0], dim=-1), dim=-1)
+    for depth in (2, 4):
+        ms = timed(lambda: asset.shade_env_indirect(o, d, t, fi, b, env, tables, n_paths=64, max_depth=depth), a.reps)
+        bounce, bounce_hits, shadow, visible, reached = 0, 0, 0, 0, [0] * depth
+        rows = max(1, (1 << 21) // (64 * depth * a.size))
+        for y0 in range(0, a.size, rows):
+            s = slice(y0 * a.size, min(y0 + rows, a.size) * a.size)
+            out = asset.shade_env_indirect(o[s], d[s], t[s], fi[s], b[s], env, tables, n_paths=64, max_depth=depth, dump=True,
+                                           pixel_idx=torch.arange(s.start, s.stop, device=dev, dtype=torch.int32))
+            face, wl = out["dump_face"], out["dump_light_dir"]
+            bounce += int((face != -2).sum())  # every vertex whose BRDF sample counts casts one closest-hit ray
+            bounce_hits += int((face >= 0).sum())
+            # a shadow ray is cast for a light sample above the shading horizon on the front side of the vertex's face; count the
+            # second condition, which the dump allows (the face is the one the bounce ray of the vertex before reached)
+            own = face[:, :, :-1].clamp(min=0).long()
+            shadow += int((((wl[:, :, 1:] * face_n[own]).sum(-1) > 0) & (wl[:, :, 1:] != 0).any(-1)).sum())
+            visible += int(out["dump_light_vis"].sum())
+            live = torch.cat([(fi[s] >= 0)[:, None, None].expand(-1, 64, 1), (out["dump_throughput"][:, :, :-1] != 0).any(-1)], 2)
+            for j in range(depth):
+                reached[j] += int(live[:, :, j].sum())
+        paths = int((fi >= 0).sum()) * 64
+        res["indirect"]["64x%d" % depth] = {"ms": ms, "paths": paths, "bounce_rays": bounce, "bounce_hits": bounce_hits, "shadow_rays": shadow,
+                                            "visible": visible, "mrays_per_s": round((bounce + shadow) / (ms * 1e-3) / 1e6, 1),
+                                            # the share of a hit pixel's path slots still under way at vertex j: the rest idle
+                                            "live_share_per_vertex": [round(r / max(paths, 1), 4) for r in reached]}
+    res["frame_64+64_depth2_64_ms"] = timed(lambda: render_asset_env(cam, asset, env, max_depth=2, n_paths=64), a.reps)
+    res["frame_64+64_depth4_64_ms"] = timed(lambda: render_asset_env(cam, asset, env, max_depth=4, n_paths=64), a.reps)
     res["frame_64+64_ms"] = timed(lambda: render_asset_env(cam, asset, env), a.reps)
     res["frame_256+256_ms"] = timed(lambda: render_asset_env(cam, asset, env, n_light=256, n_brdf=256), a.reps)
     res["frame_64+64_2x2_ms"] = timed(lambda: render_asset_env(cam, asset, env, samples_per_axis=2), a.reps)
