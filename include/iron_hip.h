@@ -816,8 +816,12 @@ int iron_trace_screen_counts(const void* workspace, double* out, void* stream);
  *                             (8 samples of one ray), out[1] those at a stride above 1, out[2] the largest watched slope relative
  *                             to L (after an allowance of delta / 2 for the screen's own error), out[3] 1 if the call marched
  *                             adaptively, 0 if it ran stride 1 throughout.  out[2] is the largest over the guard's three sources.
- *   iron_sampler_screen_debug what 4: value != 0 keeps rays with listed samples on stride 1 (the march before such rays strode);
- *                             what 5: value != 0 mutes the guard's stride-1-pass source (tests of the resolve's sources).
+ *   iron_sampler_screen_debug what 4: value != 0 keeps rays with listed samples on stride 1 (the march before such rays strode,
+ *                             which chose a block's stride one-sided: what 6 is implied);
+ *                             what 5: value != 0 mutes the guard's stride-1-pass source (tests of the resolve's sources);
+ *                             what 6: value != 0 makes a block's stride the gap in front of it, 1 + what the previous block's last
+ *                             sample certifies.  (The default is two-sided: up to twice that where the previous block's last two
+ *                             values rise, since a gap inside a block has an evaluated sample at each end.)
  *   iron_trace_stride_detail: synchronises `stream`; out[9] from the workspace of the last traced call: out[0] stride-1 passes of
  *                             rays that had already listed samples and whose 8 samples were all certainly positive, out[1]
  *                             stride-1 passes of rays that had listed none when the pass began, out[2] strided blocks discarded

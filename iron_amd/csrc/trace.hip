@@ -117,7 +117,7 @@ struct ScreenWs {
     int* flag;               // per network, pinned host words, may be null: [0] the screen's guard flag, [1] the slope guard's
     float delta_override;    // test hook (> 0: this delta)
     int stride;              // kStrideOn: the adaptive march may run (switch on, guard not raised, n_steps <= kStrideMaxSteps,
-                             // continuation items) | test hooks kStridePendingOff, kStrideMuteMarch
+                             // continuation items) | test hooks kStridePendingOff, kStrideMuteMarch, kStrideOneSided
     float l_override;        // test hook (> 0: this slope bound L)
     ResolveEntry* ent;       // [cap]
     int cap;
@@ -147,6 +147,9 @@ constexpr size_t kScreenCalibBytes = (kScreenCalibF1 + kScreenCalibPoints) * 4;
 constexpr float kStrideK = 2.0f;
 constexpr float kStrideGuard = 0.75f;
 constexpr float kStrideCalibH = 1.0f / 128.0f;
+// A block's stride is doubled over its first gap when its predecessor's last two samples rise by at least this slope, relative to L
+// (k_sampler_screen, *two-sided stride*): a flat tail is no evidence that the values behind it go on rising.
+constexpr float kStrideRise = 1.0f / 12.0f;
 constexpr int kScreenCalibG = 1;
 #ifndef IRON_SAMPLER_STRIDE_MAX
 #define IRON_SAMPLER_STRIDE_MAX 16   // 8: 0.2 ms more per C1 frame
@@ -154,8 +157,9 @@ constexpr int kScreenCalibG = 1;
 constexpr int kStrideMax = IRON_SAMPLER_STRIDE_MAX;
 constexpr int kStrideMaxSteps = 256;   // the continuation word carries a sample index in 8 bits
 constexpr int kStrideOn = 1;           // ScreenWs::stride
-constexpr int kStridePendingOff = 2;   // test hook: a pending ray keeps stride 1 (the march before pending rays strode)
+constexpr int kStridePendingOff = 2;   // test hook: a pending ray keeps stride 1 (the march before pending rays strode; one-sided)
 constexpr int kStrideMuteMarch = 4;    // test hook: k_sampler_screen's stride-1 passes do not feed the slope guard
+constexpr int kStrideOneSided = 8;     // test hook: a block's stride is its first gap (the choice before the two-sided one)
 static_assert(kStrideMax >= 1 && kStrideMax <= 16, "stride field of the slot's packed position");
 constexpr int kResolvePerRay = 2;   // resolve list capacity: entries per ray of the call
 constexpr uint8_t kRayPending = 2;     // ray_state: the ray has listed uncertain samples (carried across its continuation items)
@@ -536,7 +540,8 @@ __device__ __forceinline__ int sampler_draw(int tbase, unsigned need_slots, int 
 }
 
 // A held ticket: the list's ray (item position 0), or the continuation item once it is there (false: not yet).  item_pos is the
-// word's position field as published.
+// word's position field as published.  The word carries the value of the item's last sample and no slope: k_sampler_screen's taker
+// cannot tell whether the values rose, and its first block keeps the one-sided stride (1 + reach, the first gap's size).
 __device__ __forceinline__ bool sampler_take(const TraceWs& w, int n_list, int ticket, int& ray, int& item_pos, float& prev_f) {
     if (ticket < n_list) {
         ray = w.sampler_list[ticket];
@@ -718,7 +723,9 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler(IRON_TRACE_KERNEL_A
 // strd > 1 discards the rest of the block and the slot resumes behind its last good sample at stride 1.  So a ray's first sample that
 // is not certainly positive is always reached at stride 1, next to its evaluated predecessor, and everything that is made of it --
 // brackets, resolve entries, PendRec, overflow -- is the stride-1 code.  After a good block the next one starts 1 + stride_reach(f1(e_7))
-// (at most kStrideMax) behind e_7.  A pending ray (one that has listed uncertain samples) strides by the same rules: most pending rays
+// (at most kStrideMax) behind e_7, and its own stride is that gap, or up to twice as wide where the values rise (*two-sided stride*,
+// at the follow-up below; iron_sampler_screen_debug(6, 1): always that gap).
+// A pending ray (one that has listed uncertain samples) strides by the same rules: most pending rays
 // graze the surface, list a few samples at their closest approach and then climb far above delta + ld * m, and a strided block only
 // ever accepts certainly positive samples, so every later uncertain or negative sample of the ray is still met at stride 1 and listed
 // or bracketed by the stride-1 code (per C1 frame 288 k of the 551 k stride-1 passes were such rays' passes through certainly
@@ -792,6 +799,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
     const int unit = stride_on ? 1 : kSamplerBlock;   // what the continuation word's position counts: samples | blocks
     if (stride_on && blockIdx.x == 0 && threadIdx.x == 0) w.cnt->stride_mode = 1;
     const bool pend_strides = !(w.scr.stride & kStridePendingOff), watch_march = !(w.scr.stride & kStrideMuteMarch);
+    // (inf: no rise is enough.  kStridePendingOff is the march of a build that chose one-sided, and restores that too)
+    const float rise_min = (w.scr.stride & (kStrideOneSided | kStridePendingOff)) ? __builtin_inff() : kStrideRise;
     // per lane: s_in 0: k_sampler's evaluations of the rays decided here, s_in 1: the slot's passes, s_in 2: those at a stride above 1,
     // s_in 3 / 4: the stride-1 passes of a ray already pending whose samples were all certainly positive / of a ray not yet pending,
     // s_in 5: discarded strided blocks, s_in 6: the slot's slope observations (screen_flush_counts)
@@ -832,7 +841,8 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             }
             ray_origin_dir(a, ray, ox, oy, oz, dx, dy, dz);
             ray_interval(a, ray, smin, width);
-            // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it
+            // a continuation starts 1 + stride_reach(f of the item's last sample) behind that sample, as the publisher computed it;
+            // the item carries no slope, so that first gap is the block's stride too and prev_z below is the sample strd in front of pos
             strd = 1;
             if (stride_on && pos > 0 && (pend_strides || !pend)) {
                 const float ld = stride_ld(Lg, lin_step, width, dx, dy, dz);
@@ -896,6 +906,7 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const int reach = ld > 0.0f ? stride_reach(f, delta, ld) : 0;
         const int reach_next = __shfl(reach, me < 63 ? me + 1 : 63, 64);
         const float f_up = __shfl(f, me > 0 ? me - 1 : 0, 64);
+        const unsigned long long rise = __ballot(f - f_up >= rise_min * (ld * (float)strd));   // (false with a NaN on either side)
         // a block at a stride above 1, walked in order: its first sample that is not certainly positive (the last good one is the
         // sample before it) or its first gap that is not certified from either end (the last good one is the sample in front of it)
         const bool strided = has_ray && strd > 1;
@@ -961,8 +972,16 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
         const bool to_ovf = has_ray && overflow;
         // where a good block is followed up: behind its last sample by what that sample certifies, for a pending ray too
         const bool last_in = pos + strd * (kSamplerBlock - 1) < a.n_steps;
-        const int next_strd = (ld > 0.0f && (pend_strides || !pend_now) && last_in && f_last > delta) ? 1 + reach_last : 1;
-        const int next_pos = pos + strd * (kSamplerBlock - 1) + next_strd;
+        // The first gap has only e_7 to vouch for it: 1 + reach(e_7).  The gaps inside the next block have a sample at each end, and
+        // where the values rise (behind a grazing ray's closest approach) each end certifies at least what e_7 did: the stride is
+        // 1 + 2 * reach(e_7) when e_7 stands above e_6 by a slope of kStrideRise * L or more.  The choice is a guess about values not
+        // yet seen; the walk above certifies every gap of the block from its evaluated ends, or discards it.
+        const bool follow = ld > 0.0f && (pend_strides || !pend_now) && last_in && f_last > delta;
+        const bool rising = (rise >> (sl0 + kSamplerBlock - 1)) & 1ull;
+        const int next_gap = follow ? 1 + reach_last : 1;
+        const int next_wide = 1 + 2 * reach_last < kStrideMax ? 1 + 2 * reach_last : kStrideMax;
+        const int next_strd = (follow && rising) ? next_wide : next_gap;
+        const int next_pos = pos + strd * (kSamplerBlock - 1) + next_gap;
         const bool done = has_ray && !restart && (found_neg || next_pos >= a.n_steps);
         if (has_ray && me == sl0 + 1) ++ev_ref;                 // the slot's passes
         if (strided && me == sl0 + 2) ++ev_ref;                 // ... at a stride above 1
@@ -999,9 +1018,19 @@ __global__ __launch_bounds__(BE::kThreads, 1) void k_sampler_screen(IRON_TRACE_K
             atomicAdd(&q->n_done, 1);
         }
         pend = pend_now && !to_ovf;
-        if (restart) {   // behind the last good sample, at stride 1 (last_good < 0: the block's predecessor stays the previous sample)
-            if (last_good >= 0) { prev_z = z_good; prev_f = f_good; }
-            pos = pos + strd * last_good + 1;
+        if (restart) {   // behind the last good sample, at stride 1
+            // last_good < 0: the block's predecessor stays the previous sample.  It sits one first gap in front of pos, and the gap
+            // was 1 + stride_reach of its value (the follow-up above or the taker; ld is the same product both times), whatever strd is.
+            // Progress: the slot resumes one sample behind an evaluated, certainly positive sample -- of this block, or the previous
+            // one -- at stride 1.  A stride-1 block never restarts (`strided` is false): it ends the ray or is followed up at least
+            // one sample behind its last.  So pos exceeds the ray's last accepted sample after every pass, that sample moves forward
+            // at least every second pass, and a ray ends after at most 2 * n_steps passes.
+            if (last_good >= 0) {
+                prev_z = z_good; prev_f = f_good;
+                pos = pos + strd * last_good + 1;
+            } else {
+                pos = pos - stride_reach(prev_f, delta, ld);
+            }
             strd = 1;
         } else {
             prev_z = z_last;
@@ -1680,7 +1709,7 @@ std::atomic<float> g_screen_delta_override{0.0f};   // test hooks (iron_sampler_
 std::atomic<int> g_screen_cap_override{0};
 std::atomic<int> g_stride_switch{-1};           // iron_set_sampler_stride; -1 = the environment's (IRON_SAMPLER_STRIDE=0: off) / default on
 std::atomic<float> g_stride_l_override{0.0f};   // test hook (iron_sampler_screen_debug 3)
-std::atomic<int> g_stride_hooks{0};             // test hooks (iron_sampler_screen_debug 4, 5): kStridePendingOff | kStrideMuteMarch
+std::atomic<int> g_stride_hooks{0};             // test hooks (iron_sampler_screen_debug 4, 5, 6): kStridePendingOff | kStrideMuteMarch | kStrideOneSided
 std::atomic<int> g_defer_switch{-1};            // iron_set_resolve_defer; -1 = the environment's (IRON_RESOLVE_DEFER=0: off) / default on
 void set_screen_forward_tiles(int point_tiles);   // h2_kernels.hip
 
@@ -1828,8 +1857,8 @@ extern "C" int iron_sampler_screen_debug(int32_t what, double value) {
     if (what == 1) { g_screen_cap_override.store(value >= 1.0 ? (int)value : 0, std::memory_order_relaxed); return IRON_OK; }
     if (what == 2) { set_screen_forward_tiles(value == 1.0 ? 1 : 0); return IRON_OK; }
     if (what == 3) { g_stride_l_override.store(value > 0.0 ? (float)value : 0.0f, std::memory_order_relaxed); return IRON_OK; }
-    if (what == 4 || what == 5) {
-        const int bit = what == 4 ? kStridePendingOff : kStrideMuteMarch;
+    if (what == 4 || what == 5 || what == 6) {
+        const int bit = what == 4 ? kStridePendingOff : what == 5 ? kStrideMuteMarch : kStrideOneSided;
         if (value != 0.0) g_stride_hooks.fetch_or(bit, std::memory_order_relaxed);
         else g_stride_hooks.fetch_and(~bit, std::memory_order_relaxed);
         return IRON_OK;

@@ -20,6 +20,10 @@ rays, and the slope guard's ratio and number of observations from each of its th
 exact value against the screened predecessor, the exact values of adjacent listed samples).  L is empirical, not a
 certified bound; tests/test_sampler_stride_margin.py and tests/test_sampler_stride_pending.py pin the figures.
 
+How a good block is followed up is a parameter of both marches (`rule`, see RULES: the kernel's two-sided choice by default, the
+one-sided choice it replaced, and the variants that were emulated and not built); stride_report() / pending_report() give passes and
+restarts under each, tests/test_sampler_stride_two_sided.py holds the two-sided rule to the one-sided one.
+
     python3 tools/sampler_stride_margin.py [--res 200] [--scenes S0,S1,S3] [--gen 2] [--stride-max 16] [--l-scale 1.0]
 """
 import argparse
@@ -92,13 +96,40 @@ def _reach(v, delta, ld, smax):
     return c
 
 
-def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
+# How a good block is followed up (k_sampler_screen).  The next block's first sample sits 1 + reach(e_7) behind e_7
+# under every rule: that gap has only e_7 to vouch for it.  The rules differ in the stride inside the next block, whose gaps have an
+# evaluated sample at each end:
+#   one_sided       1 + reach(e_7), the first gap's size (the kernel before the two-sided choice; iron_sampler_screen_debug(6, 1));
+#   two_sided_any   min(smax, 1 + 2 * reach(e_7)) when f1(e_7) >= f1(e_6) -- behind a grazing ray's closest approach the values rise,
+#                   so each end of a gap certifies at least what e_7 did -- and the first gap's size otherwise;
+#   two_sided       the same, but the rise must be a slope worth the name: f1(e_7) - f1(e_6) >= RISE * L * (distance e_6 .. e_7).  A
+#                   flat tail (a bumpy field at a local maximum) is no evidence that the values go on rising (the kernel's rule);
+#   two_sided_calm  two_sided_any, but one_sided for the block that follows a restart's stride-1 block (a gate that was tried, not built).
+# Whatever is chosen is certified after the evaluation, gap by gap, or the block is discarded: the rule decides passes, never results.
+RULES = ("one_sided", "two_sided", "two_sided_any", "two_sided_calm")
+RULE = "two_sided"
+RISE = 1.0 / 12.0   # kStrideRise of csrc/trace.hip
+
+
+def _follow_up(rule, reach_last, rise, ld_block, smax, after_restart=False):
+    """(first gap, stride inside the block) behind a block whose last sample certifies reach_last skipped samples and stands `rise`
+    above the sample before it; ld_block = L * the distance between the two."""
+    if rule not in RULES:
+        raise ValueError("stride rule %r: one of %s" % (rule, ", ".join(RULES)))
+    gap = 1 + reach_last
+    rising = rise >= RISE * ld_block if rule == "two_sided" else rise >= 0.0
+    if rule == "one_sided" or not rising or (rule == "two_sided_calm" and after_restart):
+        return gap, gap
+    return gap, min(smax, 1 + 2 * reach_last)
+
+
+def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, rule=RULE):
     """The adaptive march over every ray.  Returns passes, strided passes, the stride-1 march's passes, the smallest exact value of a
     skipped sample, the skipped samples <= 0, and the guard ratio from screened (with allowance) and exact values."""
     n_rays, n = fe.shape
     fe_l, f1_l = fe.tolist(), f1.tolist()
     dz_l, w_l = dz.tolist(), width.tolist()
-    passes = strided = base = nonpos = 0
+    passes = strided = base = nonpos = restarts = 0
     worst = math.inf
     guard1 = guard_ex = 0.0
     for r in range(n_rays):
@@ -109,7 +140,7 @@ def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
         first = next((i for i in range(n) if b[i] < 0), n)
         base += min(first // BLOCK + 1, (n + BLOCK - 1) // BLOCK)
         seen = [False] * n
-        pos, s, pend = 0, 1, False
+        pos, s, pend, prev, calm = 0, 1, False, -1, False
         while pos < n:
             idx = [pos + s * k for k in range(BLOCK) if pos + s * k < n]
             passes += 1
@@ -131,7 +162,14 @@ def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
                 if last_good is not None:   # the rest of the block is discarded
                     for e in idx[last_good + 1:]:
                         seen[e] = False
-                    pos, s = pos + s * last_good + 1, 1
+                    restarts += 1
+                    if last_good < 0:   # as the kernel: the previous sample is 1 + reach(its value) in front of pos
+                        pos = pos - _reach(a[prev], delta, ld, smax)
+                        assert pos == prev + 1, (r, pos, prev)
+                    else:
+                        prev = idx[last_good]
+                        pos = prev + 1
+                    s, calm = 1, True
                     continue
             else:
                 ended, watch = False, True
@@ -148,19 +186,22 @@ def march(fe, f1, dz, width, delta, L, smax=STRIDE_MAX):
                     break
             if len(idx) < BLOCK:
                 break
-            last = idx[-1]
-            s = 1 + reach[-1] if (ld > 0.0 and not pend and a[last] > delta) else 1
-            pos = last + s
+            last = prev = idx[-1]
+            sb, gap, s = s, 1, 1
+            if ld > 0.0 and not pend and a[last] > delta:
+                gap, s = _follow_up(rule, reach[-1], a[last] - a[idx[-2]], ld * sb, smax, calm)
+            calm = False
+            pos = last + gap
         for i in range(first):
             if not seen[i]:
                 v = b[i]
                 worst = min(worst, v)
                 nonpos += not v > 0
-    return {"passes": passes, "strided_passes": strided, "baseline_passes": base, "min_exact_skipped": worst,
+    return {"passes": passes, "strided_passes": strided, "restarts": restarts, "baseline_passes": base, "min_exact_skipped": worst,
             "skipped_nonpositive": nonpos, "guard": guard1, "guard_exact": guard_ex}
 
 
-def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True):
+def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True, rule=RULE):
     """The march of k_sampler_screen ray by ray, to each ray's first certainly-negative screened sample or its end, pending rays
     (those that have listed an uncertain sample) included: with `pending_stride` they stride by the rules of the others, without
     it they keep stride 1 (the march before they strode); L = 0 is the all-stride-1 march.  Returns the pass counts, per ray what
@@ -168,11 +209,15 @@ def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True
     sources as the kernels take them, each with its number of observations:
       march    adjacent screened samples of stride-1 passes up to the first that is not certainly positive, delta / 2 allowed;
       resolve  the exact value of a listed sample against the screened value of its predecessor, delta / 2 allowed;
-      pair     the exact values of two adjacent samples listed by one pass, no allowance."""
+      pair     the exact values of two adjacent samples listed by one pass, no allowance.
+    `rule` is how a good block is followed up (RULES).  Progress is counted as the kernel's termination needs it: a pass that is not a
+    restart must end the ray or leave pos behind where it was; a restart must leave pos one sample behind an evaluated good sample
+    (the one the pass accepted last, or the ray's previous one: `restarts_first`, the case last_good < 0) at stride 1, where the
+    next pass cannot restart.  `stalls` counts the passes that did neither (must be none)."""
     n_rays, n = fe.shape
     fe_l, f1_l = fe.tolist(), f1.tolist()
     dz_l, w_l = dz.tolist(), width.tolist()
-    c = {"passes": 0, "strided_passes": 0, "restarts": 0, "stride1_behind": 0, "stride1_fresh": 0,
+    c = {"passes": 0, "strided_passes": 0, "restarts": 0, "restarts_first": 0, "stalls": 0, "stride1_behind": 0, "stride1_fresh": 0,
          "obs_march": 0, "obs_resolve": 0, "obs_pair": 0, "guard_march": 0.0, "guard_resolve": 0.0, "guard_pair": 0.0, "pending_rays": 0}
     classified = []
     for r in range(n_rays):
@@ -181,10 +226,11 @@ def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True
         if not (w_l[r] > 0.0 and 0.0 < ld < math.inf):
             ld = 0.0
         listed, first_neg = [], n
-        pos, s, pend = 0, 1, False
+        pos, s, pend, prev, calm = 0, 1, False, -1, False   # prev: the ray's last accepted sample
         while pos < n:
             idx = [pos + s * k for k in range(BLOCK) if pos + s * k < n]
             c["passes"] += 1
+            c["stalls"] += not pos > prev
             reach = [_reach(a[e], delta, ld, smax) if ld > 0.0 else 0 for e in idx]
             if s > 1:
                 c["strided_passes"] += 1
@@ -200,7 +246,14 @@ def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True
                             break
                 if last_good is not None:   # the rest of the block is discarded
                     c["restarts"] += 1
-                    pos, s = pos + s * last_good + 1, 1
+                    if last_good < 0:   # as the kernel: the previous sample is 1 + reach(its value) in front of pos, whatever s is
+                        c["restarts_first"] += 1
+                        pos = pos - _reach(a[prev], delta, ld, smax)
+                    else:
+                        prev = idx[last_good]
+                        pos = prev + 1
+                    c["stalls"] += pos != prev + 1 or not a[prev] > delta
+                    s, calm = 1, True
                     continue
             else:
                 ngood = [k for k, e in enumerate(idx) if not a[e] > delta]
@@ -229,8 +282,12 @@ def march_rays(fe, f1, dz, width, delta, L, smax=STRIDE_MAX, pending_stride=True
                     first_neg = idx[neg]
                     break
             last = pos + s * (BLOCK - 1)
-            s = 1 + reach[-1] if (ld > 0.0 and (pending_stride or not pend) and last < n and a[last] > delta) else 1
-            pos = last + s
+            sb, gap, s = s, 1, 1
+            if ld > 0.0 and (pending_stride or not pend) and last < n and a[last] > delta:
+                gap, s = _follow_up(rule, reach[-1], a[last] - a[last - sb], ld * sb, smax, calm)
+            c["stalls"] += not last + gap > pos
+            calm = False
+            prev, pos = idx[-1], last + gap
         c["pending_rays"] += pend
         classified.append((tuple(listed), first_neg))
     c["classified"] = classified
@@ -258,6 +315,12 @@ def pending_report(sd, spec, res, smax=STRIDE_MAX, l_scale=1.0, samples=None):
         for k, v in m.items():
             if k not in ("classified", "pending_rays"):
                 out["%s_%s" % (k, tag)] = v
+    # how a good block is followed up: the kernel's rule ("after" above) against the others
+    for rule in RULES:
+        m = new if rule == RULE else march_rays(fe, f1, dz, width, delta, L, smax, rule=rule)
+        out["rule_" + rule] = {"passes": m["passes"], "strided_passes": m["strided_passes"], "restarts": m["restarts"],
+                               "restarts_first": m["restarts_first"], "stalls": m["stalls"],
+                               "class_mismatch_rays": sum(x != y for x, y in zip(m["classified"], one["classified"]))}
     return out
 
 
@@ -274,6 +337,9 @@ def stride_report(sd, spec, res, smax=STRIDE_MAX, l_scale=1.0, samples=None):
         L = 0.0   # the kernel's rule: stride 1
     m = march(fe, f1, dz, width, delta, L, smax)
     out.update(m)
+    for rule in RULES:
+        o = m if rule == RULE else march(fe, f1, dz, width, delta, L, smax, rule)
+        out["rule_" + rule] = {k: o[k] for k in ("passes", "strided_passes", "restarts", "skipped_nonpositive")}
     out["lane_evals"] = m["passes"] * BLOCK
     out["baseline_lane_evals"] = m["baseline_passes"] * BLOCK
     out["ratio"] = m["passes"] / max(m["baseline_passes"], 1)
