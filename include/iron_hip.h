@@ -696,6 +696,60 @@ int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron_trace_para
                      iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Callable tracer (trace_any.hip).  RayTracer.forward on an SDF the library cannot evaluate itself: the caller's function
+ * supplies the values, batch by batch, and these entries do everything between two evaluations -- the per-ray state machine of
+ * models/raytracer.py:45-220 with the reference's formulas (one rounding per product and sum) and its own comparisons (NaN and
+ * zero fall where torch puts them).  The caller drives the loop:
+ *
+ *   start                      -> points = o + d * near, dist = near            evaluate points [n]
+ *   sphere_step(list_in = -1)  -> values land in sdf, termination tests, unfinished rays step and are listed in ascending
+ *     read, evaluate pts_out      ray order (pair_scan: deterministic); pts_out [count, 3] holds their new points, word 0 the
+ *     sphere_step(list_in = l)    count.  Lists alternate: a step that read list l (-1: all rays) wrote list 1 - l (0).
+ *     ...                         advance = 0 (the iteration limit is reached): tests and list only, no ray moves.
+ *   sphere_finish              -> conv (and, optionally, the unfinished mask) as raytracer.py:132-137
+ *   sampler_interval           -> [min, max] of every listed ray (raytracer.py:56-63); list_sel = -1: a = min_dis, b = max_dis
+ *                                 of rays 0..m-1 taken as given (ray_sampler as a stage)
+ *   sampler_points / evaluate / sampler_reduce, for blocks [k0, k0 + nk) of the list: nk * n_steps points, row-major;
+ *                                 the reduce keeps no-root / first-negative index and the bracket (z, f) pairs per ray (a NaN
+ *                                 sample is neither sign there: torch.sign gives 0 for it)
+ *   sampler_gather             -> rootless rays zeroed, bracketed ones listed in order (word 0: their count), their first mid
+ *                                 points in pts_out, word 1: whether any bracket is open (f_low > 0 > f_high)
+ *   bisect_load                -> the same start from explicit brackets of rays 0..n-1 (rootfind as a stage)
+ *   evaluate / bisect_step / read, while word 1 is set: every slot moves, word 1 = any open bracket wider than 2 * threshold
+ *   evaluate / finish          -> final mid point, value and distance scattered to the rays (conv = 1 when conv != NULL)
+ *
+ * `n` is the capacity the workspace was sized for (iron_trace_any_workspace_bytes(n)): the rays of the call; every list length
+ * m, block and slot count is checked against it, pts_out against pts_capacity (points), and every kernel is bounded by the count
+ * it was launched with.  `values` must hold one float per point of the batch just evaluated: the caller checks that before the
+ * call.  All work goes on `stream`; only iron_trace_any_read waits for it (out2[0] = word 0, out2[1] = word 1, HOST).
+ * ------------------------------------------------------------------------------------------- */
+size_t iron_trace_any_workspace_bytes(int64_t n);
+int iron_trace_any_start(const float* ray_o, const float* ray_d, const float* near, int64_t n, float* points, float* dist, void* stream);
+int iron_trace_any_sphere_step(const float* values, int64_t m, int32_t list_in, int32_t advance, float sdf_threshold, const float* ray_d,
+                               const float* far, const uint8_t* work, int64_t n, float* points, float* sdf, float* dist, float* pts_out,
+                               int64_t pts_capacity, void* workspace, size_t workspace_bytes, void* stream);
+int iron_trace_any_read(const void* workspace, size_t workspace_bytes, int64_t n, int64_t* out2, void* stream);
+int iron_trace_any_sphere_finish(const uint8_t* work, const float* far, float sdf_threshold, int64_t n, const float* sdf, const float* dist,
+                                 uint8_t* conv, uint8_t* unfinished_out, void* workspace, size_t workspace_bytes, void* stream);
+int iron_trace_any_sampler_interval(int32_t list_sel, int64_t m, const float* a, const float* b, const float* sdf, const float* dist, int64_t n,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int iron_trace_any_sampler_points(int32_t list_sel, int64_t m, int64_t k0, int64_t nk, int32_t n_steps, const float* lin_steps,
+                                  const float* ray_o, const float* ray_d, int64_t n, float* pts_out, int64_t pts_capacity, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int iron_trace_any_sampler_reduce(int64_t m, int64_t k0, int64_t nk, int32_t n_steps, const float* lin_steps, const float* values, int64_t n,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int iron_trace_any_sampler_gather(int32_t list_sel, int64_t m, const float* ray_o, const float* ray_d, int64_t n, uint8_t* conv, float* points,
+                                  float* sdf, float* dist, float* pts_out, int64_t pts_capacity, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int iron_trace_any_bisect_load(const float* f_low, const float* f_high, const float* d_low, const float* d_high, const float* ray_o,
+                               const float* ray_d, int64_t n, float* pts_out, int64_t pts_capacity, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int iron_trace_any_bisect_step(const float* values, int64_t nb, float sdf_threshold, const float* ray_o, const float* ray_d, int64_t n,
+                               float* pts_out, int64_t pts_capacity, void* workspace, size_t workspace_bytes, void* stream);
+int iron_trace_any_finish(const float* values, int64_t nb, const float* ray_o, const float* ray_d, int64_t n, uint8_t* conv, float* points,
+                          float* sdf, float* dist, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Shading.  Replaces render_normal_and_color (models/raytracer.py:593-662) with the driver's GGX
  * render_fn (render_surface.py:117-156): for every ray with conv != 0: get_all -> normalise ->
  * get_materials (models/rendering_func.py:5-16) -> GGXColocatedRenderer; other rays get zeros.

@@ -20,14 +20,26 @@ __version__ = "0.1.0"
 
 
 def install_as_models() -> None:
-    """Make `from models.raytracer import ...` (and friends) resolve to this package."""
+    """Make `from models.raytracer import ...` (and friends) resolve to this package.
+
+    The mirrored modules are laid over the caller's own `models` package when there is one -- already imported, or importable from
+    sys.path -- so that `models.dataset`, `models.helper` and whatever else it holds keep resolving to the caller's files.  Only
+    when no `models` package exists is an empty one made up."""
     import importlib
+    import importlib.util
 
     pkg = sys.modules.get("models")
     if pkg is None:
-        pkg = types.ModuleType("models")
-        pkg.__path__ = []  # mark as package
-        sys.modules["models"] = pkg
+        try:
+            found = importlib.util.find_spec("models") is not None
+        except (ImportError, ValueError):
+            found = False
+        if found:
+            pkg = importlib.import_module("models")
+        else:
+            pkg = types.ModuleType("models")
+            pkg.__path__ = []  # mark as package
+            sys.modules["models"] = pkg
     for name in ("raytracer", "renderer_ggx", "rendering_func", "fields", "embedder", "renderer", "network_conf", "image_losses",
                  "export_materials", "export_mesh"):
         mod = importlib.import_module("iron_amd." + name)

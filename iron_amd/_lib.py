@@ -207,6 +207,18 @@ SYMBOLS = {
                                    _P, _SZ, _P]),
     "iron_trace_phase": (C.c_int, [_I32, _P, C.POINTER(iron_trace_params), _P, _P, _P, _P, _P, _P, _P, _I64, _P,
                                    _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_trace_any_workspace_bytes": (_SZ, [_I64]),
+    "iron_trace_any_start": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
+    "iron_trace_any_sphere_step": (C.c_int, [_P, _I64, _I32, _I32, _F, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_read": (C.c_int, [_P, _SZ, _I64, C.POINTER(_I64), _P]),
+    "iron_trace_any_sphere_finish": (C.c_int, [_P, _P, _F, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_trace_any_sampler_interval": (C.c_int, [_I32, _I64, _P, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_sampler_points": (C.c_int, [_I32, _I64, _I64, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_sampler_reduce": (C.c_int, [_I64, _I64, _I64, _I32, _P, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_sampler_gather": (C.c_int, [_I32, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_bisect_load": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_bisect_step": (C.c_int, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "iron_trace_any_finish": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "iron_net_numeric_status": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
     "iron_net_force_exact": (C.c_int, [_P, _I32]),
     "iron_set_cu_limit": (_I32, [_I32]),

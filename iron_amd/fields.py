@@ -456,6 +456,41 @@ class NeRF(_HipNet):
         return alpha.reshape(sh + [1]), rgb.reshape(sh + [3])
 
 
+class NeRFdual(nn.Module):
+    """The fork's RGB + NIR background field (models/fields.py:329-412): NeRF's stack with one more head, nir_linear, beside
+    rgb_linear.  The reference's callers import the name (model_volume.py, model_bed.py) and none of its renderers calls it, so
+    this class carries the constructor, the parameter names and the state_dict layout -- a reference checkpoint loads -- and no
+    kernel: forward says so with IronError."""
+
+    def __init__(self, D=8, W=256, d_in=3, d_in_view=3, multires=0, multires_view=0, output_ch=5, skips=[4], use_viewdirs=False):
+        super().__init__()
+        self.D, self.W, self.d_in, self.d_in_view = D, W, d_in, d_in_view
+        self.multires, self.multires_view = multires, multires_view
+        self.input_ch, self.input_ch_view = 3, 3
+        self.embed_fn = self.embed_fn_view = None
+        if multires > 0:
+            self.embed_fn, self.input_ch = get_embedder(multires, input_dims=d_in)
+        if multires_view > 0:
+            self.embed_fn_view, self.input_ch_view = get_embedder(multires_view, input_dims=d_in_view)
+        self.skips = skips
+        self.use_viewdirs = use_viewdirs
+        # layer i + 1 takes the embedded input again when i is a skip; creation order = the reference's RNG consumption
+        widths = [self.input_ch] + [W + self.input_ch if i in self.skips else W for i in range(D - 1)]
+        self.pts_linears = nn.ModuleList([nn.Linear(w_in, W) for w_in in widths])
+        self.views_linears = nn.ModuleList([nn.Linear(self.input_ch_view + W, W // 2)])
+        if use_viewdirs:
+            self.feature_linear = nn.Linear(W, W)
+            self.alpha_linear = nn.Linear(W, 1)
+            self.rgb_linear = nn.Linear(W // 2, 3)
+            self.nir_linear = nn.Linear(W // 2, 1)
+        else:
+            self.output_linear = nn.Linear(W, output_ch)
+
+    def forward(self, input_pts, input_views):
+        raise _lib.IronError("NeRFdual.forward is not built: no renderer of the reference calls it (the class is only imported); "
+                             "its parameters and state_dict are the reference's")
+
+
 class SingleVarianceNetwork(nn.Module):
     """models/fields.py:415-421."""
 

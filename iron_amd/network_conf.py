@@ -93,6 +93,41 @@ def init_rendering_network_dict(renderer_name="comp", device="cuda"):
     }
 
 
+GGX_OPTIMIZED = ("color_network", "diffuse_albedo_network", "specular_albedo_network", "specular_roughness_network",
+                 "point_light_network")
+COMP_OPTIMIZED = GGX_OPTIMIZED + ("metallic_network", "dielectric_network", "metallic_eta_network", "metallic_k_network",
+                                  "dielectric_eta_network")
+
+
+def choose_optmizer(renderer_name='comp', network_name_list=[], network_dict={}):
+    """models/network_conf.py:707-745 (the name is the reference's spelling): one Adam per network of `network_dict`, 1e-4 for the
+    material networks and 1e-2 for the light.  Every network the branch lists must be in the dictionary (KeyError otherwise, as in
+    the reference); `comp` / `comp2` keep only `network_name_list` when it is not empty.  Host only."""
+    if renderer_name == "ggx":
+        names = GGX_OPTIMIZED
+    elif renderer_name in ("comp", "comp2"):
+        names = COMP_OPTIMIZED
+    else:
+        raise NotImplementedError("renderer %r: only 'ggx' and 'comp'/'comp2' are built" % renderer_name)
+    optimizers = {name: torch.optim.Adam(network_dict[name].parameters(), lr=1e-2 if name == "point_light_network" else 1e-4)
+                  for name in names}
+    if renderer_name != "ggx" and len(network_name_list) > 0:
+        optimizers = {name: optimizers[name] for name in network_name_list}
+    return optimizers
+
+
+def choose_renderer_func(renderer_name='comp', renderer=None, device='cuda:0'):
+    """models/network_conf.py:913-1060: the render_fn(interior_mask, network_dict, ray_o, ray_d, points, normals, features) of a
+    renderer.  The reference ignores its `renderer` argument and builds a new one; so does this (`device` is unused there too).
+    Returns the live callables of iron_amd.rendering_func: the GGX one for `ggx`, the composite one for `comp` / `comp2`."""
+    from .rendering_func import make_render_fn, make_render_fn_comp
+
+    renderer = choose_renderer(renderer_name)
+    if renderer_name in ("comp", "comp2"):
+        return make_render_fn_comp(renderer)
+    return make_render_fn(renderer)
+
+
 def choose_renderer(renderer_name="comp"):
     """models/network_conf.py:748-764."""
     from .renderer_ggx import CompositeRenderer, GGXColocatedRenderer

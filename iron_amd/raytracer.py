@@ -11,6 +11,8 @@ is the GGX one from iron_amd.rendering_func.
 Built: the forward path including hole filling and silhouette edge sampling (locate_edge_points :421-506,
 render_edge_pixels :665-729), and is_training=True (reparam_points :17-24, shading and edge blending
 attached to the parameters through the differentiable HIP operators of iron_amd.autograd).
+An SDF the library cannot evaluate itself is traced through SDFCallable(fn): the reference's evaluation schedule with fn supplying
+the values, the per-ray bookkeeping between two calls in csrc/trace_any.hip.
 There is no CPU path: tensors must be CUDA (ROCm) fp32.
 """
 from __future__ import annotations
@@ -38,6 +40,127 @@ class SDFHandle:
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return self.sdf_network.sdf(x)[..., 0]
+
+
+class SDFCallable:
+    """Marks `fn: Tensor[m,3] (CUDA, fp32, contiguous) -> Tensor[m]` as an SDF to be traced AS GIVEN: an analytic distance, a network
+    of a shape the fused tracer refuses, a hash-grid field, a post-processed distance.  RayTracer.forward / sphere_tracing /
+    ray_sampler / rootfind then make every evaluation the reference makes (raytracer.py:45-220), on the same points, by calling
+    `fn` under torch.no_grad() on the current stream; the per-ray state machine between two evaluations runs in the HIP kernels of
+    csrc/trace_any.hip.  The multi-rank form (phase_begin / forward_phased) does not take one."""
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise _lib.IronError("SDFCallable needs a callable, got %s" % type(fn).__name__)
+        self.fn = fn
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fn(x)
+
+
+class _AnyTrace:
+    """One reference call on an SDFCallable: the workspace, the evaluation buffer and the argument plumbing of iron_trace_any_*."""
+
+    def __init__(self, tracer, sdf, o, d, stats):
+        self.fn = sdf.fn
+        self.o, self.d = o, d
+        self.n, self.dev = o.shape[0], o.device
+        self.thr = float(tracer.sdf_threshold)
+        self.iters = int(tracer.sphere_tracing_iters)
+        self.n_steps = int(tracer.n_steps)
+        self.max_num_pts = int(tracer.max_num_pts)
+        self.rays_per_call = self.max_num_pts // self.n_steps
+        self.stats = stats
+        self.lib = _lib.load()
+        self.st = _lib.stream_ptr(self.dev)
+        self.ws_bytes = self.lib.iron_trace_any_workspace_bytes(self.n)
+        if self.n > 0 and self.ws_bytes == 0:
+            raise _lib.IronError("the callable tracer takes fewer than 2^31 - 1 rays per call; pass chunk=")
+        self.ws = _lib.workspace(self.ws_bytes, self.dev, "trace_any")
+        self.wsp = self.ws.data_ptr()
+        self.buf = torch.empty((max(self.n, 1), 3), dtype=torch.float32, device=self.dev)   # the next batch of the list stages
+        self.words = (C.c_int64 * 2)()
+
+    def evaluate(self, x, m):
+        """fn on the first m points of x; its result is checked here, on the host, before any kernel reads it."""
+        x = x[:m]
+        with torch.no_grad():
+            v = self.fn(x)
+        if not torch.is_tensor(v) or not v.is_cuda or v.device != x.device:
+            raise _lib.IronError("the sdf callable must return a CUDA tensor on the device of its argument")
+        if v.dtype != torch.float32:
+            raise _lib.IronError("the sdf callable must return float32, got %s" % (v.dtype,))
+        if v.numel() != m:
+            raise _lib.IronError("the sdf callable returned %d values for %d points" % (v.numel(), m))
+        if self.stats is not None:
+            self.stats["n_evals"] += m
+            self.stats["n_calls"] += 1
+        return v.reshape(-1).contiguous()
+
+    def read(self):
+        _lib.check(self.lib.iron_trace_any_read(self.wsp, self.ws_bytes, self.n, self.words, self.st))
+        return int(self.words[0]), int(self.words[1])
+
+    def sphere(self, near, far, work, points, sdf_out, dist):
+        """raytracer.py:105-130 -> (list holding the unfinished rays, their count)."""
+        lib, n = self.lib, self.n
+        _lib.check(lib.iron_trace_any_start(self.o.data_ptr(), self.d.data_ptr(), near.data_ptr(), n, points.data_ptr(), dist.data_ptr(), self.st))
+        values, m, cur, it = self.evaluate(points, n), n, -1, 0
+        while True:
+            advance = it < self.iters
+            _lib.check(lib.iron_trace_any_sphere_step(values.data_ptr(), m, cur, int(advance), self.thr, self.d.data_ptr(), far.data_ptr(),
+                                                      work.data_ptr(), n, points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(),
+                                                      self.buf.data_ptr(), self.buf.shape[0], self.wsp, self.ws_bytes, self.st))
+            cur = 0 if cur < 0 else 1 - cur
+            m, _ = self.read()
+            if not advance or m == 0:
+                return cur, m
+            it += 1
+            values = self.evaluate(self.buf, m)
+
+    def sphere_finish(self, far, work, sdf_out, dist, conv, unfinished=None):
+        _lib.check(self.lib.iron_trace_any_sphere_finish(work.data_ptr(), far.data_ptr(), self.thr, self.n, sdf_out.data_ptr(), dist.data_ptr(),
+                                                         conv.data_ptr(), _lib.ptr(unfinished), self.wsp, self.ws_bytes, self.st))
+
+    def sampler(self, sel, m, a, b, lin, conv, points, sdf_out, dist):
+        """raytracer.py:142-197 on the m rays of list `sel` (-1: rays 0..m-1 on [a, b] as given) -> (sampled rays, bisected rays,
+        bisection iterations)."""
+        lib, n, ns = self.lib, self.n, self.n_steps
+        if self.rays_per_call < 1:
+            raise _lib.IronError("the callable tracer samples whole rays per call: max_num_pts (%d) must be at least n_steps (%d)"
+                                 % (self.max_num_pts, ns))
+        _lib.check(lib.iron_trace_any_sampler_interval(sel, m, a.data_ptr(), b.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(), n,
+                                                       self.wsp, self.ws_bytes, self.st))
+        block = min(m, self.rays_per_call)
+        pts = torch.empty((block * ns, 3), dtype=torch.float32, device=self.dev)
+        for k0 in range(0, m, block):
+            nk = min(block, m - k0)
+            _lib.check(lib.iron_trace_any_sampler_points(sel, m, k0, nk, ns, lin.data_ptr(), self.o.data_ptr(), self.d.data_ptr(), n,
+                                                         pts.data_ptr(), pts.shape[0], self.wsp, self.ws_bytes, self.st))
+            values = self.evaluate(pts, nk * ns)
+            _lib.check(lib.iron_trace_any_sampler_reduce(m, k0, nk, ns, lin.data_ptr(), values.data_ptr(), n, self.wsp, self.ws_bytes, self.st))
+        _lib.check(lib.iron_trace_any_sampler_gather(sel, m, self.o.data_ptr(), self.d.data_ptr(), n, conv.data_ptr(), points.data_ptr(),
+                                                     sdf_out.data_ptr(), dist.data_ptr(), self.buf.data_ptr(), self.buf.shape[0], self.wsp,
+                                                     self.ws_bytes, self.st))
+        nb, wide = self.read()
+        return m, nb, (self.bisect(nb, wide, conv, points, sdf_out, dist) if nb > 0 else 0)
+
+    def bisect(self, nb, wide, conv, points, sdf_out, dist):
+        """raytracer.py:204-220 on the nb slots the gather (or bisect_load) opened -> iterations."""
+        lib, n = self.lib, self.n
+        it = 0
+        while wide:
+            if it >= 256:   # fp32 brackets halve to nothing long before; the reference's loop would never end here
+                raise _lib.IronError("the bisection does not close: the sdf callable returns NaN inside an open bracket, or a bracket is not finite")
+            values = self.evaluate(self.buf, nb)
+            _lib.check(lib.iron_trace_any_bisect_step(values.data_ptr(), nb, self.thr, self.o.data_ptr(), self.d.data_ptr(), n,
+                                                      self.buf.data_ptr(), self.buf.shape[0], self.wsp, self.ws_bytes, self.st))
+            _, wide = self.read()
+            it += 1
+        values = self.evaluate(self.buf, nb)
+        _lib.check(lib.iron_trace_any_finish(values.data_ptr(), nb, self.o.data_ptr(), self.d.data_ptr(), n, _lib.ptr(conv), points.data_ptr(),
+                                             sdf_out.data_ptr(), dist.data_ptr(), self.wsp, self.ws_bytes, self.st))
+        return it
 
 
 def _resolve_sdf_network(sdf, device):
@@ -68,7 +191,8 @@ def _resolve_sdf_network(sdf, device):
     cands = list({id(c): c for c in cands}.values())
     if len(cands) != 1:
         raise _lib.IronError("RayTracer.forward needs the sdf handle made by raytrace_pixels / SDFHandle(sdf_network), or a "
-                             "callable that wraps exactly one iron_amd SDFNetwork; opaque sdf callables cannot run on the HIP tracer")
+                             "callable that wraps exactly one iron_amd SDFNetwork; opaque sdf callables cannot run on the fused HIP tracer. "
+                             "Wrap any other callable in SDFCallable(fn) to trace it as given.")
     net = cands[0]
     g = torch.Generator().manual_seed(0)
     x = (torch.rand(64, 3, generator=g) * 1.6 - 0.8).to(device)
@@ -116,6 +240,8 @@ class RayTracer(nn.Module):
         `chunk` (extension): rays [k*chunk,(k+1)*chunk) are treated as separate reference calls
         (they share the bisection iteration count, raytracer.py:204-217); 0 = the whole batch."""
         o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        if isinstance(sdf, SDFCallable):
+            return self._forward_callable(sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
         near = _lib.require_cuda_f32(min_dis, "min_dis").reshape(-1)
@@ -145,10 +271,89 @@ class RayTracer(nn.Module):
             _check_stats(self.last_stats)
         return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
 
+    # ---- an opaque callable (SDFCallable): the same reference call, its evaluations made by the caller's function and everything
+    # between them by the kernels of csrc/trace_any.hip
+    @staticmethod
+    def _ray_args(o, ray_d, *scalars):
+        d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
+        rest = [_lib.require_cuda_f32(t, "argument").reshape(-1) for t in scalars]
+        for t in [d] + rest:
+            if t.shape[0] != o.shape[0] or t.device != o.device:
+                raise _lib.IronError("the ray arguments must have one entry per ray, on one device")
+        return [d] + rest
+
+    @staticmethod
+    def _work_arg(work_mask, n):
+        if work_mask.dtype != torch.bool or not work_mask.is_cuda:
+            raise _lib.IronError("work_mask must be a CUDA bool tensor")
+        work = work_mask.reshape(-1).contiguous()
+        if work.shape[0] != n:
+            raise _lib.IronError("work_mask must have one entry per ray")
+        return work
+
+    def _forward_callable(self, sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats):
+        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
+        n, dev = o.shape[0], o.device
+        work = self._work_arg(work_mask, n)
+        conv = torch.empty(n, dtype=torch.bool, device=dev)
+        points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        sdf_out = torch.empty(n, dtype=torch.float32, device=dev)
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        stats = {"n_evals": 0, "n_calls": 0, "n_sampler": 0, "n_bisect": 0, "n_bisect_iters": 0} if collect_stats else None
+        lin = _linspace_steps(self.n_steps, dev)
+        step = n if chunk is None or int(chunk) <= 0 else int(chunk)
+        with torch.cuda.device(dev):
+            for a in range(0, n, max(step, 1)):   # each chunk is a reference call of its own; slices of dim 0 stay contiguous
+                b = min(n, a + step)
+                run = _AnyTrace(self, sdf, o[a:b], d[a:b], stats)
+                c_near, c_far, c_work = near[a:b], far[a:b], work[a:b]
+                c_conv, c_points, c_sdf, c_dist = conv[a:b], points[a:b], sdf_out[a:b], dist[a:b]
+                sel, m = run.sphere(c_near, c_far, c_work, c_points, c_sdf, c_dist)
+                run.sphere_finish(c_far, c_work, c_sdf, c_dist, c_conv)
+                if m > 0:
+                    _, nb, it = run.sampler(sel, m, c_near, c_far, lin, c_conv, c_points, c_sdf, c_dist)
+                    if stats is not None:
+                        stats["n_sampler"] += m
+                        stats["n_bisect"] += nb
+                        stats["n_bisect_iters"] += it
+        if collect_stats:
+            self.last_stats = stats
+        return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
+
+    def _stage_callable(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
+        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        args = self._ray_args(o, ray_d, *[t for t in (in0, in1, in2, in3) if t is not None])
+        d, ins = args[0], args[1:]
+        n, dev = o.shape[0], o.device
+        mask = torch.zeros(n, dtype=torch.bool, device=dev)
+        unfinished = torch.zeros(n, dtype=torch.bool, device=dev)
+        points = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        sdf_out = torch.zeros(n, dtype=torch.float32, device=dev)
+        dist = torch.zeros(n, dtype=torch.float32, device=dev)
+        if n > 0:
+            with torch.cuda.device(dev):
+                run = _AnyTrace(self, sdf, o, d, None)
+                if stage == 0:
+                    work = self._work_arg(work_mask, n)
+                    run.sphere(ins[0], ins[1], work, points, sdf_out, dist)
+                    run.sphere_finish(ins[1], work, sdf_out, dist, mask, unfinished)
+                elif stage == 1:
+                    run.sampler(-1, n, ins[0], ins[1], _linspace_steps(self.n_steps, dev), mask, points, sdf_out, dist)
+                    # the gather clears the rootless rays and the finish raises the bracketed ones: `mask` started as zeros
+                else:
+                    _lib.check(run.lib.iron_trace_any_bisect_load(ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(),
+                                                                  o.data_ptr(), d.data_ptr(), n, run.buf.data_ptr(), run.buf.shape[0],
+                                                                  run.wsp, run.ws_bytes, run.st))
+                    _, wide = run.read()
+                    run.bisect(n, wide, None, points, sdf_out, dist)
+        return mask, unfinished, points, sdf_out, dist
+
 
     # ---- the three stages as the reference exposes them (raytracer.py:105-220; tests/test_raytracer.py drives forward(), the
     # methods are public API of the class): each is one iron_trace_stage call, i.e. the same persistent kernels forward() chains
     def _stage(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
+        if isinstance(sdf, SDFCallable):
+            return self._stage_callable(stage, sdf, ray_o, ray_d, in0, in1, in2, in3, work_mask)
         o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
@@ -205,6 +410,8 @@ class RayTracer(nn.Module):
         (raytracer.py:204-217) has to be MAX-reduced over the ranks before the second half runs.  `ray_index` [n] int64 =
         position of each ray in the whole job (chunk id = ray_index // chunk).  Returns the state phase_finish() takes;
         state["chunk_iters"] (int32 [n_chunks], device) is the table to reduce in place."""
+        if isinstance(sdf, SDFCallable):
+            raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take an SDFCallable: call forward() per rank")
         o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
@@ -422,7 +629,10 @@ def raytrace_pixels(sdf_network, raytracer, uv, camera, mask=None, max_num_rays=
         mask = torch.ones_like(uv[..., 0]).bool()
     dots_sh = list(uv.shape[:-1])
     ray_o, ray_d, ray_d_norm = camera.get_rays(uv)
-    sdf = SDFHandle(sdf_network)
+    if hasattr(sdf_network, "hip_net"):
+        sdf = SDFHandle(sdf_network)
+    else:  # a foreign network: traced through its own forward, as the reference does (raytracer.py:375)
+        sdf = SDFCallable(lambda x: sdf_network(x)[..., 0])
     o, d = ray_o.reshape(-1, 3), ray_d.reshape(-1, 3)
     hit, near, far = intersect_sphere(o, d, r=1.0)
     results = raytracer(sdf, o, d, near, far, hit & mask.reshape(-1), chunk=max_num_rays,
@@ -434,6 +644,14 @@ def raytrace_pixels(sdf_network, raytracer, uv, camera, mask=None, max_num_rays=
         merged[k] = v[..., 0] if v.shape[-1] == 1 else v
     merged.update({"uv": uv, "ray_o": ray_o, "ray_d": ray_d, "ray_d_norm": ray_d_norm})
     return merged
+
+
+def _require_iron_network(sdf_network, what, attr=None):
+    """Tracing takes any network (raytrace_pixels falls back to SDFCallable); the edge walk and the shading need the gradient and
+    feature kernels of an iron_amd SDFNetwork."""
+    if not hasattr(sdf_network, "hip_net" if attr is None else attr):
+        raise _lib.IronError("%s needs an iron_amd SDFNetwork, got %s: a foreign network can be traced "
+                             "(raytrace_pixels, raytrace_camera(detect_edges=False)) but not walked or shaded" % (what, type(sdf_network).__name__))
 
 
 def unique(x, dim=-1):
@@ -492,6 +710,7 @@ def locate_edge_points(camera, walk_start_points, sdf_network, max_step, step_si
     Every point is an independent state machine (a found point is never moved again), so all candidates
     advance together through <= max_step+1 get_all launches; `max_num_rays` has no effect on the result
     (the reference only uses it to bound memory) and is accepted for signature parity."""
+    _require_iron_network(sdf_network, "locate_edge_points (detect_edges=True)")
     if mask is None:
         mask = torch.ones_like(walk_start_points[..., 0]).bool()
     dev = walk_start_points.device
@@ -625,6 +844,7 @@ def render_normal_and_color(results, sdf_network, color_network_dict, render_fn,
     gets the reference's generic gather / get_all / render_fn / reshape flow (chunked by max_num_pts).
     is_training=True takes the generic flow under grad mode: get_all attached to the SDF parameters,
     reparam_points, render_fn over the differentiable HIP operators (iron_amd.autograd)."""
+    _require_iron_network(sdf_network, "render_normal_and_color", "get_all")
     dots_sh = list(results["convergent_mask"].shape)
     fused = getattr(render_fn, "iron_fused_ggx", None)
     if fused is not None and not is_training:
