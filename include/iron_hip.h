@@ -401,6 +401,35 @@ int iron_asset_shade_env_indirect(const iron_asset_mesh* mesh, const void* bvh_w
                                   const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_paths,
                                   int32_t max_depth, uint32_t seed, float shadow_eps, float* indirect_diffuse, float* indirect_specular,
                                   const iron_env_path_dump* dump, void* stream);
+/* Environment-map relighting of the neural scene, csrc/envlight.hip; DESIGN.md §19.  iron_asset_shade_env's integrator on a
+ * G-buffer of n pixels -- hit [n] uint8, points, normal (unit), ray_d, diffuse_albedo, specular_albedo [n,3], specular_roughness
+ * [n], pixel_idx [n] int32 (may be NULL: the pixel's position) -- with the shadow rays answered by iron_trace_occluded.  The
+ * samples, random numbers, densities, denominator, terms and the order of every sum are iron_asset_shade_env's, with v = -ray_d
+ * and the shading normal in the geometric normal's place: a sample counts when n.w > 0, n.v > 0 and w is finite.  One block of
+ * pixels [p0, p0 + nb) per call pair, nb (n_light + n_brdf) <= capacity, the number of samples `workspace`
+ * (iron_neural_env_workspace_bytes(capacity)) was sized for; all work goes on `stream`, no entry waits.
+ *   iron_neural_env_emit     the shadow rays of the block's counting samples with a denominator > 0, in ascending (pixel, sample)
+ *                            order: ray_o [capacity,3] = x + shadow_eps n (each product and sum rounded on its own), ray_d
+ *                            [capacity,3] = w, sample_idx [capacity] int32 = (pixel - p0) N + sample, count [1] int64 (DEVICE)
+ *                            their number.  Entries behind count are not written.
+ *   iron_neural_env_resolve  occluded [n_rays] uint8 for the first n_rays = count listed rays (the caller: iron_intersect_sphere
+ *                            with r = 1, then iron_trace_occluded; a ray that misses the sphere is not occluded) -> color,
+ *                            diffuse_color, specular_color [n,3] at the block's pixels (any may be NULL; zeros on a miss), and
+ *                            `dump` as in iron_asset_shade_env, [n,N(,3)].  The same seed, counts and workspace as the emit. */
+typedef struct iron_neural_gbuffer {
+    const uint8_t* hit;
+    const float *points, *normal, *ray_d, *diffuse_albedo, *specular_albedo, *specular_roughness;
+    const int32_t* pixel_idx;
+    int64_t n;
+} iron_neural_gbuffer;
+int iron_neural_env_workspace_bytes(int64_t capacity, size_t* bytes);
+int iron_neural_env_emit(const iron_neural_gbuffer* g, const iron_envmap* env, int64_t p0, int64_t nb, int32_t n_light, int32_t n_brdf,
+                         uint32_t seed, float shadow_eps, int64_t capacity, void* workspace, size_t workspace_bytes, float* ray_o,
+                         float* ray_d, int32_t* sample_idx, int64_t* count, void* stream);
+int iron_neural_env_resolve(const iron_neural_gbuffer* g, const iron_envmap* env, const float* tab_trans, const float* tab_diff_trans,
+                            int64_t p0, int64_t nb, int32_t n_light, int32_t n_brdf, uint32_t seed, int64_t capacity, void* workspace,
+                            size_t workspace_bytes, const uint8_t* occluded, const int32_t* sample_idx, int64_t n_rays, float* color,
+                            float* diffuse_color, float* specular_color, const iron_env_dump* dump, void* stream);
 /* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
  * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
  *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte
@@ -669,6 +698,17 @@ int iron_trace(const iron_net_t* sdf, const iron_trace_params* p, const float* l
                const float* ray_d, const float* near, const float* far, const uint8_t* work, int64_t n,
                uint8_t* conv, float* points, float* sdf_out, float* dist, iron_trace_stats* stats,
                void* workspace, size_t workspace_bytes, void* stream);
+
+/* The occlusion query: occluded [n] (uint8) is, bit for bit, the `conv` iron_trace writes for the same rays, segments and work
+ * mask -- the reference tracer's answer to "does this ray meet the surface in [near, far)".  The mask is final once the dense
+ * sampler has found, or not found, a first negative sample (models/raytracer.py:162-167), so the call runs iron_trace's sphere and
+ * sampler kernels and no bisection, and returns no points, sdf or distance.  The screen, the stride and the deferred resolve
+ * apply as in iron_trace.  `workspace`: iron_trace_occluded_workspace_bytes(n, p) (the tracer's workspace and 20 bytes per ray
+ * for the state the kernels keep).  stats may be NULL; n_bisect then counts the bracketed rays, none of which was bisected. */
+size_t iron_trace_occluded_workspace_bytes(int64_t n, const iron_trace_params* p);
+int iron_trace_occluded(const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps, const float* ray_o,
+                        const float* ray_d, const float* near, const float* far, const uint8_t* work, int64_t n,
+                        uint8_t* occluded, iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The three stages of RayTracer.forward as separate calls, for callers that use the reference's methods directly (models/raytracer.py
  * :105-140 sphere_tracing, :142-197 ray_sampler, :199-220 rootfind; tests/test_raytracer.py).  One call = one reference call: the

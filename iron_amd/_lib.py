@@ -100,6 +100,11 @@ class iron_env_dump(C.Structure):
     _fields_ = [("dir", C.c_void_p), ("denom", C.c_void_p), ("vis", C.c_void_p), ("contrib", C.c_void_p)]
 
 
+class iron_neural_gbuffer(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("hit", "points", "normal", "ray_d", "diffuse_albedo", "specular_albedo", "specular_roughness",
+                                          "pixel_idx")] + [("n", C.c_int64)]
+
+
 ENV_PATH_DUMP_FIELDS = ("bounce_dir", "bounce_org", "face", "t", "light_dir", "light_vis", "denom_light", "denom_brdf", "light_term",
                         "escape_term", "throughput", "lobe_diffuse", "lobe_specular")
 
@@ -163,6 +168,11 @@ SYMBOLS = {
                                        C.c_uint32, _F, C.POINTER(iron_asset_out), C.POINTER(iron_env_dump), _P]),
     "iron_asset_shade_env_indirect": (C.c_int, [C.POINTER(iron_asset_mesh), _P, C.POINTER(iron_envmap), _P, _P, _P, _P, _P, _P, _P, _P, _I64,
                                                 _I32, _I32, C.c_uint32, _F, _P, _P, C.POINTER(iron_env_path_dump), _P]),
+    "iron_neural_env_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_neural_env_emit": (C.c_int, [C.POINTER(iron_neural_gbuffer), C.POINTER(iron_envmap), _I64, _I64, _I32, _I32, C.c_uint32, _F, _I64,
+                                       _P, _SZ, _P, _P, _P, _P, _P]),
+    "iron_neural_env_resolve": (C.c_int, [C.POINTER(iron_neural_gbuffer), C.POINTER(iron_envmap), _P, _P, _I64, _I64, _I32, _I32, C.c_uint32,
+                                          _I64, _P, _SZ, _P, _P, _I64, _P, _P, _P, C.POINTER(iron_env_dump), _P]),
     "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
     "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
@@ -203,6 +213,8 @@ SYMBOLS = {
     "iron_trace_workspace_bytes": (_SZ, [_I64, C.POINTER(iron_trace_params)]),
     "iron_trace": (C.c_int, [_P, C.POINTER(iron_trace_params), _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                              _P, _SZ, _P]),
+    "iron_trace_occluded_workspace_bytes": (_SZ, [_I64, C.POINTER(iron_trace_params)]),
+    "iron_trace_occluded": (C.c_int, [_P, C.POINTER(iron_trace_params), _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
     "iron_trace_stage": (C.c_int, [_I32, _P, C.POINTER(iron_trace_params), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                                    _P, _SZ, _P]),
     "iron_trace_phase": (C.c_int, [_I32, _P, C.POINTER(iron_trace_params), _P, _P, _P, _P, _P, _P, _P, _I64, _P,

@@ -23,6 +23,7 @@
 // ray_walk.h (k_raycast's walk), the shadow rays bvh_any_hit, both on the one LDS stack in turn.  The direct term stays k_shade_env's.
 #include "asset_common.h"
 #include "ggx_core.h"
+#include "pair_scan.h"
 #include "ray_walk.h"
 
 namespace iron {
@@ -649,6 +650,194 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArg
     st3(a.indirect_specular, i, accs[0] / np, accs[1] / np, accs[2] / np);
 }
 
+// ---- the neural scene ----
+// The direct integrator of k_shade_env on a G-buffer of the neural scene (iron_amd/neural_relight.py), its shadow rays answered
+// by the sphere tracer (iron_trace_occluded) instead of a BVH walk, in three steps on one stream:
+//   k_nenv_emit     sample k of pixel i on lane k % kEnvGroup of the pixel's group, as in k_shade_env; the direction of every
+//                   sample goes to a dense [pixels, N, 3] array and a 0/1 flag -- the sample counts and its denominator is > 0 -- to
+//                   level 0 of a pair_scan; k_nenv_compact then lists the flagged samples' rays in ascending (pixel, sample) order;
+//   (the caller)    intersect_sphere and iron_trace_occluded on the list;
+//   k_nenv_scatter  the answers back to a [pixels, N] byte array of visibilities, and k_nenv_resolve draws every sample again
+//                   from the hash (nenv_sample: the one function both kernels run) and adds the visible ones' terms in k_shade_env's
+//                   order.
+// There is no geometric normal: the shading normal stands in dir_counts's second place, so a sample counts when n.w > 0, n.v > 0
+// and w is finite.  A block of pixels [p0, p0 + nb) is worked per call; nothing a pixel gets depends on the block it is in.
+struct NeuralEnvArgs {
+    iron_neural_gbuffer g;
+    iron_env_dump dump;
+    EnvDev env;
+    const float *tab_trans, *tab_diff;
+    int64_t p0, nb;          // the block of pixels
+    int32_t n_light, n_brdf;
+    uint32_t seed;
+    float shadow_eps;
+    Pair64* flags;           // [nb N] (emit)
+    float* dir;              // [nb N, 3] (emit)
+    const uint8_t* vis;      // [nb N] (resolve)
+    float *color, *diffuse_color, *specular_color;
+};
+
+struct NeuralEnvLayout {
+    ScanLevels scan;
+    size_t dir_off, vis_off, bytes;
+};
+
+inline NeuralEnvLayout nenv_layout(int64_t n_samples) {
+    NeuralEnvLayout L{};
+    Carver c;
+    L.scan = scan_levels(n_samples, c);
+    L.dir_off = c.take(sizeof(float) * 3 * (size_t)n_samples);
+    L.vis_off = c.take((size_t)n_samples);
+    L.bytes = c.off;
+    return L;
+}
+
+struct NeuralPixel {
+    bool hit;
+    float3 x, n, v;
+    float nv, alpha, mat[7];
+    uint32_t pixel;
+};
+
+__device__ __forceinline__ void nenv_pixel(const iron_neural_gbuffer& g, int64_t i, NeuralPixel& px) {
+    px.hit = g.hit[i] != 0;
+    px.x = px.n = px.v = make_float3(0.f, 0.f, 0.f);
+    px.nv = px.alpha = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) px.mat[c] = 0.0f;
+    px.pixel = g.pixel_idx ? (uint32_t)g.pixel_idx[i] : (uint32_t)i;
+    if (!px.hit) return;
+    px.x = ld3(g.points, i);
+    px.n = ld3(g.normal, i);
+    const float3 d = ld3(g.ray_d, i);
+    px.v = make_float3(-d.x, -d.y, -d.z);
+    px.nv = dot3(px.n, px.v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { px.mat[c] = g.diffuse_albedo[3 * i + c]; px.mat[3 + c] = g.specular_albedo[3 * i + c]; }
+    px.mat[6] = g.specular_roughness[i];
+    px.alpha = fmaxf(px.mat[6], 0.0001f);
+}
+
+// sample k of a hit pixel, as k_shade_env draws it: the direction (zero: no sample), the balance heuristic's denominator, the
+// map's radiance along it; true when the sample counts
+__device__ __forceinline__ bool nenv_sample(const NeuralEnvArgs& a, const NeuralPixel& px, int32_t k, float3& w, float& denom, float L[3]) {
+    float pl;
+    bool ok;
+    if (k < a.n_light) {
+        int r, c;
+        pl = env_sample(a.env, env_rand(a.seed, px.pixel, k, 0), env_rand(a.seed, px.pixel, k, 1), r, c, w);
+        const float* p = a.env.image + 3 * ((int64_t)r * a.env.We + c);
+        L[0] = p[0]; L[1] = p[1]; L[2] = p[2];
+        ok = true;
+    } else {
+        ok = brdf_sample(px.n, px.v, px.alpha, env_rand(a.seed, px.pixel, k, 0), env_rand(a.seed, px.pixel, k, 1), env_rand(a.seed, px.pixel, k, 2), w);
+        if (!ok) w = make_float3(0.f, 0.f, 0.f);
+        pl = env_eval(a.env, w, L);
+    }
+    const float pb = ok ? brdf_pdf(px.n, px.v, w, px.alpha) : 0.0f;
+    denom = (a.n_light > 0 ? (float)a.n_light * pl : 0.0f) + (a.n_brdf > 0 ? (float)a.n_brdf * pb : 0.0f);
+    return ok && dir_counts(px.n, px.n, px.nv, w);
+}
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_nenv_emit(NeuralEnvArgs a) {
+    const int lane = threadIdx.x, sl = lane % kEnvGroup;
+    const int64_t j = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;   // the pixel's place in the block
+    if (j >= a.nb) return;
+    NeuralPixel px;
+    nenv_pixel(a.g, a.p0 + j, px);
+    const int32_t N = a.n_light + a.n_brdf;
+    for (int32_t base = 0; base < N; base += kEnvGroup) {
+        const int32_t k = base + sl;
+        if (k >= N) break;
+        float3 w = make_float3(0.f, 0.f, 0.f);
+        float denom = 0.0f, L[3];
+        bool cast = false;
+        if (px.hit) cast = nenv_sample(a, px, k, w, denom, L) && denom > 0.0f;
+        const int64_t at = j * N + k;
+        st3(a.dir, at, w.x, w.y, w.z);
+        a.flags[at] = Pair64{cast ? 1 : 0, 0};
+    }
+}
+
+// the flagged samples' shadow rays, in the order of their flags: origin x + shadow_eps n (each product and sum rounded on its
+// own: -ffp-contract=off), direction w.  count[0] = their number.
+__global__ __launch_bounds__(256) void k_nenv_compact(NeuralEnvArgs a, const Pair64* __restrict__ prefix, const Pair64* __restrict__ total,
+                                                      int64_t capacity, float* __restrict__ ray_o, float* __restrict__ ray_d,
+                                                      int32_t* __restrict__ sample_idx, int64_t* __restrict__ count) {
+    const int32_t N = a.n_light + a.n_brdf;
+    const int64_t M = a.nb * N, at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at == 0) count[0] = total[0].a;
+    if (at >= M) return;
+    const int64_t pos = prefix[at].a, next = at + 1 < M ? prefix[at + 1].a : total[0].a;
+    if (next == pos || pos >= capacity) return;   // not flagged (the capacity holds every sample: the second test never fires)
+    const int64_t i = a.p0 + at / N;
+    const float3 x = ld3(a.g.points, i), n = ld3(a.g.normal, i), w = ld3(a.dir, at);
+    const float ex = a.shadow_eps * n.x, ey = a.shadow_eps * n.y, ez = a.shadow_eps * n.z;
+    st3(ray_o, pos, x.x + ex, x.y + ey, x.z + ez);
+    st3(ray_d, pos, w.x, w.y, w.z);
+    sample_idx[pos] = (int32_t)at;
+}
+
+__global__ __launch_bounds__(256) void k_nenv_scatter(const uint8_t* __restrict__ occluded, const int32_t* __restrict__ sample_idx,
+                                                      int64_t n_rays, int64_t M, uint8_t* __restrict__ vis) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_rays) return;
+    const int64_t at = sample_idx[q];
+    if (at >= 0 && at < M) vis[at] = occluded[q] ? 0 : 1;
+}
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_nenv_resolve(NeuralEnvArgs a) {
+    const int lane = threadIdx.x, sl = lane % kEnvGroup;
+    const int64_t j = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;
+    if (j >= a.nb) return;  // a whole group leaves together
+    const int64_t i = a.p0 + j;
+    NeuralPixel px;
+    nenv_pixel(a.g, i, px);
+    const int32_t N = a.n_light + a.n_brdf;
+    const float nn[3] = {px.n.x, px.n.y, px.n.z}, vv[3] = {px.v.x, px.v.y, px.v.z};
+    float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
+    for (int32_t base = 0; base < N; base += kEnvGroup) {
+        const int32_t k = base + sl;
+        if (k >= N) break;  // the ragged tail of the last round
+        float3 w = make_float3(0.f, 0.f, 0.f);
+        float denom = 0.0f, cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
+        bool vis = false;
+        if (px.hit) {
+            float L[3];
+            const bool counts = nenv_sample(a, px, k, w, denom, L);
+            vis = counts && denom > 0.0f && a.vis[j * N + k] != 0;
+            if (vis) {
+                PlasticOut f;
+                const float ww[3] = {w.x, w.y, w.z};
+                roughplastic_point(nn, vv, ww, px.mat, px.mat + 3, px.mat[6], a.tab_trans, a.tab_diff, f);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    cd[c] = L[c] * f.diffuse[c] / denom;  // an infinite density (the map's poles) gives 0
+                    cs[c] = L[c] * f.specular[c] / denom;
+                    accd[c] += cd[c];
+                    accs[c] += cs[c];
+                }
+            }
+        }
+        const int64_t at = i * N + k;
+        st3(a.dump.dir, at, w.x, w.y, w.z);
+        if (a.dump.denom) a.dump.denom[at] = denom;
+        if (a.dump.vis) a.dump.vis[at] = vis ? 1 : 0;
+        st3(a.dump.contrib, at, cd[0] + cs[0], cd[1] + cs[1], cd[2] + cs[2]);
+    }
+#pragma unroll
+    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
+            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
+        }
+    if (sl != 0) return;
+    st3(a.color, i, accd[0] + accs[0], accd[1] + accs[1], accd[2] + accs[2]);
+    st3(a.diffuse_color, i, accd[0], accd[1], accd[2]);
+    st3(a.specular_color, i, accs[0], accs[1], accs[2]);
+}
+
 static bool env_dev(const iron_envmap* env, EnvDev& E) {
     if (!env || !env->image || !env->dist || env->h <= 0 || env->w <= 0 || (int64_t)env->h * env->w > (1 << 24)) return false;
     const EnvLayout L = env_layout(env->h, env->w);
@@ -782,5 +971,80 @@ extern "C" int iron_asset_shade_env_indirect(const iron_asset_mesh* mesh, const 
     a.pixel_idx = pixel_idx; a.indirect_diffuse = indirect_diffuse; a.indirect_specular = indirect_specular; a.n = n_rays;
     a.n_paths = n_paths; a.max_depth = max_depth; a.seed = seed; a.shadow_eps = shadow_eps;
     IRON_LAUNCH(k_shade_env_indirect, blocks_for(n_rays, kEnvPixels), kBvQueryBlock, (hipStream_t)stream, a);
+    return IRON_OK;
+}
+
+// ---- the neural scene ----
+// what the three entries check alike, and the argument block of a pixel block
+static int nenv_args(const iron_neural_gbuffer* g, const iron_envmap* env, int64_t p0, int64_t nb, int32_t n_light, int32_t n_brdf,
+                     int64_t capacity, const void* workspace, size_t workspace_bytes, NeuralEnvArgs& a, NeuralEnvLayout& L) {
+    if (!g || g->n < 0 || n_light < 0 || n_brdf < 0 || (int64_t)n_light + n_brdf < 1 || (int64_t)n_light + n_brdf > (1 << 20)) return IRON_ERR_BAD_ARG;
+    if (p0 < 0 || nb < 1 || p0 + nb > g->n || capacity < 1) return IRON_ERR_BAD_ARG;
+    const int64_t N = (int64_t)n_light + n_brdf;
+    if (nb * N > capacity || capacity > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;   // the samples of a block: int32 list entries
+    if (!g->hit || !g->points || !g->normal || !g->ray_d || !g->diffuse_albedo || !g->specular_albedo || !g->specular_roughness)
+        return IRON_ERR_BAD_ARG;
+    if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
+    L = nenv_layout(capacity);
+    if (!workspace || ((uintptr_t)workspace & 15) != 0) return IRON_ERR_BAD_ARG;
+    if (workspace_bytes < L.bytes) return IRON_ERR_WORKSPACE;
+    a.g = *g;
+    a.dump = iron_env_dump{nullptr, nullptr, nullptr, nullptr};
+    a.tab_trans = a.tab_diff = nullptr;
+    a.p0 = p0; a.nb = nb; a.n_light = n_light; a.n_brdf = n_brdf; a.seed = 0; a.shadow_eps = 0.0f;
+    a.flags = nullptr; a.dir = nullptr; a.vis = nullptr;
+    a.color = a.diffuse_color = a.specular_color = nullptr;
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_env_workspace_bytes(int64_t capacity, size_t* bytes) {
+    if (!bytes || capacity < 1 || capacity > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
+    *bytes = nenv_layout(capacity).bytes;
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_env_emit(const iron_neural_gbuffer* g, const iron_envmap* env, int64_t p0, int64_t nb, int32_t n_light,
+                                    int32_t n_brdf, uint32_t seed, float shadow_eps, int64_t capacity, void* workspace, size_t workspace_bytes,
+                                    float* ray_o, float* ray_d, int32_t* sample_idx, int64_t* count, void* stream) {
+    NeuralEnvArgs a;
+    NeuralEnvLayout L;
+    const int rc = nenv_args(g, env, p0, nb, n_light, n_brdf, capacity, workspace, workspace_bytes, a, L);
+    if (rc != IRON_OK) return rc;
+    if (!ray_o || !ray_d || !sample_idx || !count) return IRON_ERR_BAD_ARG;
+    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = nb * ((int64_t)n_light + n_brdf);
+    a.seed = seed; a.shadow_eps = shadow_eps;
+    a.flags = L.scan.level(workspace, 0);
+    a.dir = ws_ptr<float>(workspace, L.dir_off);
+    // the scan runs over the whole capacity: the entries behind this block's samples are zero
+    if (capacity > M) IRON_HIP_TRY(hipMemsetAsync(a.flags + M, 0, sizeof(Pair64) * (size_t)(capacity - M), st));
+    IRON_LAUNCH(k_nenv_emit, blocks_for(nb, kEnvPixels), kBvQueryBlock, st, a);
+    const int rs = pair_scan(L.scan, workspace, st);
+    if (rs != IRON_OK) return rs;
+    IRON_LAUNCH(k_nenv_compact, blocks_for(M, 256), 256, st, a, (const Pair64*)L.scan.level(workspace, 0),
+                (const Pair64*)L.scan.level(workspace, L.scan.levels), capacity, ray_o, ray_d, sample_idx, count);
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_env_resolve(const iron_neural_gbuffer* g, const iron_envmap* env, const float* tab_trans, const float* tab_diff_trans,
+                                       int64_t p0, int64_t nb, int32_t n_light, int32_t n_brdf, uint32_t seed, int64_t capacity,
+                                       void* workspace, size_t workspace_bytes, const uint8_t* occluded, const int32_t* sample_idx,
+                                       int64_t n_rays, float* color, float* diffuse_color, float* specular_color, const iron_env_dump* dump,
+                                       void* stream) {
+    NeuralEnvArgs a;
+    NeuralEnvLayout L;
+    const int rc = nenv_args(g, env, p0, nb, n_light, n_brdf, capacity, workspace, workspace_bytes, a, L);
+    if (rc != IRON_OK) return rc;
+    const int64_t M = nb * ((int64_t)n_light + n_brdf);
+    if (!tab_trans || !tab_diff_trans || n_rays < 0 || n_rays > M || (n_rays > 0 && (!occluded || !sample_idx))) return IRON_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* vis = ws_ptr<uint8_t>(workspace, L.vis_off);
+    IRON_HIP_TRY(hipMemsetAsync(vis, 0, (size_t)M, st));
+    if (n_rays > 0) IRON_LAUNCH(k_nenv_scatter, blocks_for(n_rays, 256), 256, st, occluded, sample_idx, n_rays, M, vis);
+    a.seed = seed; a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans; a.vis = vis;
+    a.dump = dump ? *dump : iron_env_dump{nullptr, nullptr, nullptr, nullptr};
+    a.color = color; a.diffuse_color = diffuse_color; a.specular_color = specular_color;
+    IRON_LAUNCH(k_nenv_resolve, blocks_for(nb, kEnvPixels), kBvQueryBlock, st, a);
     return IRON_OK;
 }

@@ -1993,11 +1993,12 @@ extern "C" int32_t iron_set_trace_split(int32_t parts) {
     return g_trace_split.exchange(parts > 0 ? (parts > kMaxTraceSplits ? kMaxTraceSplits : parts) : 0, std::memory_order_relaxed);
 }
 
-extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps,
-                                const float* ray_o, const float* ray_d, const float* near, const float* far,
-                                const uint8_t* work, const int64_t* ray_index, int64_t n, int32_t* chunk_iters,
-                                int64_t n_chunks, uint8_t* conv, float* points, float* sdf_out, float* dist,
-                                iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
+// `mask_only` (iron_trace_occluded): phase 0 without the bisection; every bracketed ray is marked convergent instead
+static int trace_phase(int32_t phase, const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps,
+                       const float* ray_o, const float* ray_d, const float* near, const float* far,
+                       const uint8_t* work, const int64_t* ray_index, int64_t n, int32_t* chunk_iters,
+                       int64_t n_chunks, uint8_t* conv, float* points, float* sdf_out, float* dist,
+                       iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream, bool mask_only) {
     if (phase != 0 && phase != 1) return IRON_ERR_BAD_ARG;
     const bool args_ok = lin_steps && ray_o && ray_d && near && far && work && conv && points && sdf_out && dist;
     WsLayout L;
@@ -2072,7 +2073,10 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
                 ProfScope ps(IRON_PROF_SAMPLER, sk);
                 run_sampler(h2, screen, sdf, a, w, nk, sk);
             }
-            {
+            if (mask_only) {
+                const unsigned gb = (unsigned)((nk + 255) / 256 < 1024 ? (nk + 255) / 256 : 1024);
+                hipLaunchKernelGGL(k_stage_mark_list, dim3(gb), dim3(256), 0, sk, w.root_list, &w.cnt->n_root, a.conv);
+            } else {
                 ProfScope ps(IRON_PROF_BISECT_A, sk);
                 launch_trace_kernel(kBisectA, h2, sdf, a, w, tiles, sk);
             }
@@ -2085,10 +2089,44 @@ extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron
     }
     for (int k = 1; k < parts; ++k)   // join: everything behind this call on the caller's stream sees all parts finished
         if (bnd[k + 1] > bnd[k]) IRON_HIP_TRY(hipStreamWaitEvent(st, S->join[k - 1], 0));
-    if (phase == 1 && h2) envelope_scan(sdf, sdf_out, n, nullptr, 1, st);   // envelope guard (envelope.hip): every ray's last sdf value
-    if (phase == 1 && stats) hipLaunchKernelGGL(k_trace_stats, dim3(1), dim3(64), 0, st, w0, parts, p->n_steps, stats);
+    const bool last = phase == 1 || mask_only;
+    if (last && h2) envelope_scan(sdf, sdf_out, n, nullptr, 1, st);   // envelope guard (envelope.hip): every ray's last sdf value
+    if (last && stats) hipLaunchKernelGGL(k_trace_stats, dim3(1), dim3(64), 0, st, w0, parts, p->n_steps, stats);
     IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
+}
+
+extern "C" int iron_trace_phase(int32_t phase, const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps,
+                                const float* ray_o, const float* ray_d, const float* near, const float* far,
+                                const uint8_t* work, const int64_t* ray_index, int64_t n, int32_t* chunk_iters,
+                                int64_t n_chunks, uint8_t* conv, float* points, float* sdf_out, float* dist,
+                                iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    return trace_phase(phase, sdf, p, lin_steps, ray_o, ray_d, near, far, work, ray_index, n, chunk_iters, n_chunks, conv, points, sdf_out,
+                       dist, stats, workspace, workspace_bytes, stream, false);
+}
+
+// the per-ray scratch behind the tracer's own workspace: the points, sdf and distance the sphere and sampler kernels keep per ray
+static size_t occluded_scratch(int64_t n) { return align256(sizeof(float) * 3 * (size_t)n) + 2 * align256(sizeof(float) * (size_t)n); }
+
+extern "C" size_t iron_trace_occluded_workspace_bytes(int64_t n, const iron_trace_params* p) {
+    if (n <= 0) return 0;
+    return align256(iron_trace_workspace_bytes(n, p)) + occluded_scratch(n);
+}
+
+extern "C" int iron_trace_occluded(const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps, const float* ray_o,
+                                   const float* ray_d, const float* near, const float* far, const uint8_t* work, int64_t n,
+                                   uint8_t* occluded, iron_trace_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n < 0 || !p) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!workspace) return IRON_ERR_BAD_ARG;
+    const size_t head = align256(iron_trace_workspace_bytes(n, p));
+    if (workspace_bytes < head + occluded_scratch(n)) return IRON_ERR_WORKSPACE;
+    char* s = (char*)workspace + head;
+    float* points = (float*)s;
+    float* sdf_out = (float*)(s + align256(sizeof(float) * 3 * (size_t)n));
+    float* dist = (float*)((char*)sdf_out + align256(sizeof(float) * (size_t)n));
+    return trace_phase(0, sdf, p, lin_steps, ray_o, ray_d, near, far, work, nullptr, n, nullptr, 0, occluded, points, sdf_out, dist, stats,
+                       workspace, head, stream, true);
 }
 
 extern "C" int iron_trace_stage(int32_t stage, const iron_net_t* sdf, const iron_trace_params* p, const float* lin_steps,

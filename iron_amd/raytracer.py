@@ -271,6 +271,41 @@ class RayTracer(nn.Module):
             _check_stats(self.last_stats)
         return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
 
+    @torch.no_grad()
+    def occluded(self, sdf, ray_o, ray_d, min_dis, max_dis, work_mask=None, collect_stats: bool = False):
+        """Does each ray meet the surface in [min_dis, max_dis)?  bool [n], bit for bit forward(...)["convergent_mask"] for the same
+        arguments: the reference tracer's own answer.  For an SDFNetwork (SDFHandle, or a callable forward() accepts) it is computed
+        by the sphere and sampler kernels alone (iron_trace_occluded): the mask is final once the dense sampler has found, or not
+        found, a first negative sample (raytracer.py:162-167), so no ray is bisected and no point, sdf or distance is returned.
+        An SDFCallable is traced by forward() itself and its mask returned: that form is not shortened.  work_mask None: every ray.
+        Bare callables and CPU tensors are refused as forward() refuses them."""
+        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        n, dev = o.shape[0], o.device
+        if work_mask is None:
+            work_mask = torch.ones(n, dtype=torch.bool, device=dev)
+        if isinstance(sdf, SDFCallable):
+            return self.forward(sdf, o, ray_d, min_dis, max_dis, work_mask, collect_stats=collect_stats)["convergent_mask"]
+        net = _resolve_sdf_network(sdf, dev)
+        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
+        work = self._work_arg(work_mask, n)
+        occ = torch.empty(n, dtype=torch.bool, device=dev)
+        if n == 0:
+            return occ
+        lib = _lib.load()
+        prm = self._params(0)
+        ws_bytes = lib.iron_trace_occluded_workspace_bytes(n, C.byref(prm))
+        ws = _lib.workspace(ws_bytes, dev, "trace")
+        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
+        lin = _linspace_steps(self.n_steps, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.iron_trace_occluded(net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(),
+                                               near.data_ptr(), far.data_ptr(), work.data_ptr(), n, occ.data_ptr(), _lib.ptr(stats),
+                                               ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
+        if collect_stats:
+            self.last_stats = dict(zip(_lib.TRACE_STATS_FIELDS, stats.cpu().tolist()))
+            _check_stats(self.last_stats)
+        return occ
+
     # ---- an opaque callable (SDFCallable): the same reference call, its evaluations made by the caller's function and everything
     # between them by the kernels of csrc/trace_any.hip
     @staticmethod
