@@ -430,6 +430,60 @@ int iron_neural_env_resolve(const iron_neural_gbuffer* g, const iron_envmap* env
                             int64_t p0, int64_t nb, int32_t n_light, int32_t n_brdf, uint32_t seed, int64_t capacity, void* workspace,
                             size_t workspace_bytes, const uint8_t* occluded, const int32_t* sample_idx, int64_t n_rays, float* color,
                             float* diffuse_color, float* specular_color, const iron_env_dump* dump, void* stream);
+/* Interreflections on the neural scene, csrc/envlight.hip; DESIGN.md §20.  iron_asset_shade_env_indirect's paths (vertex, samples,
+ * random numbers env_rand(seed, pixel, path, 8 (j + 1) + c), terms, lobe weights, the order of every sum) on the G-buffer above,
+ * with the shading normal in the geometric normal's place, both rays of a vertex leaving x + shadow_eps n (each product and sum
+ * rounded on its own), shadow rays answered by iron_trace_occluded and bounce rays by iron_trace with chunk = 1.  A wavefront over
+ * depth: one block of pixels [p0, p0 + nb) at a time, slot = (pixel - p0) n_paths + path, nb n_paths <= capacity, the number of
+ * slots `workspace` (iron_neural_path_workspace_bytes(capacity), about 150 bytes per slot) was sized for; the workspace carries the
+ * paths' state from call to call.  n_paths 1 .. 2^16, max_depth 2 .. 8, else IRON_ERR_BAD_ARG.  All work goes on `stream`, no entry
+ * waits.  Per block: begin, then for depth = 0 .. max_depth - 1 emit and resolve, then finish.
+ *   iron_neural_path_begin    every slot's state from the G-buffer: alive on a hit, vertex 0, T = 1, C = b_d = b_s = 0.
+ *   iron_neural_path_emit     the two samples of every alive slot at vertex `depth`.  Lists in ascending slot order: the shadow rays
+ *                             of the environment samples that count with dl > 0 (depth >= 1) in shadow_o, shadow_d [capacity,3],
+ *                             shadow_idx [capacity] int32 (the slot); the bounce rays of the BRDF samples that count and whose ray is
+ *                             valid in bounce_o, bounce_d, bounce_idx likewise.  counts [3] int64 (DEVICE): shadow rays, bounce
+ *                             rays, alive slots.  Entries behind a count are not written.
+ *   iron_neural_path_resolve  occluded [n_shadow] uint8 for the listed shadow rays (iron_intersect_sphere with r = 1, then
+ *                             iron_trace_occluded; a ray that misses the sphere is not occluded) and `bounce`, one row per listed
+ *                             bounce ray [n_bounce]: hit uint8 (the tracer converged inside the sphere), distance, points, and the
+ *                             surface record there -- normal (unit), diffuse_albedo, specular_albedo [.,3], specular_roughness;
+ *                             rows without a hit are not read.  n_shadow and n_bounce are the emit's counts, the other arguments the
+ *                             emit's.  Adds T L (f_d + f_s) / dl for a visible environment sample, then, for a bounce ray that
+ *                             does not hit, T L(w_b) (f_d + f_s) / db (depth >= 1).  A hit with n'.(-w_b) > 0 and p_brdf > 0 becomes
+ *                             vertex depth + 1 with v = -w_b and T <- T (f_d + f_s) / p_brdf (at depth 0: b_d = f_d / p_brdf,
+ *                             b_s = f_s / p_brdf, T stays 1); anything else ends the path.
+ *   iron_neural_path_finish   indirect_diffuse, indirect_specular [n,3] at the block's pixels (either may be NULL; zeros on a
+ *                             miss): the sum over paths of b_d C / n_paths and b_s C / n_paths in iron_asset_shade_env_indirect's order.
+ *   dump (may be NULL, and each pointer in it), per (pixel, path, vertex) [n,n_paths,max_depth,...] written by the resolve of that
+ *   depth for every slot of the block: iron_env_path_dump's fields with `reached` int32 (1 hit, -1 escaped, -2 no ray) for face and
+ *   `distance` (the tracer's; inf when escaped) for t, and the surface record of a hit, vertex_*; a slot that is not alive writes
+ *   -2 and zeros.  Per (pixel, path) [n,n_paths,3], written by the finish: lobe_diffuse, lobe_specular, path_value = (b_d + b_s) C. */
+typedef struct iron_neural_path_dump {
+    float* bounce_dir; float* bounce_org; int32_t* reached; float* distance;
+    float* vertex_points; float* vertex_normal; float* vertex_diffuse_albedo; float* vertex_specular_albedo; float* vertex_roughness;
+    float* light_dir; uint8_t* light_vis; float* denom_light; float* denom_brdf; float* light_term; float* escape_term;
+    float* throughput;                                                            /* per (pixel, path, vertex) */
+    float* lobe_diffuse; float* lobe_specular; float* path_value;                  /* per (pixel, path) */
+} iron_neural_path_dump;
+typedef struct iron_neural_bounce {
+    const uint8_t* hit;
+    const float *distance, *points, *normal, *diffuse_albedo, *specular_albedo, *specular_roughness;
+} iron_neural_bounce;
+int iron_neural_path_workspace_bytes(int64_t capacity, size_t* bytes);
+int iron_neural_path_begin(const iron_neural_gbuffer* g, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int64_t capacity,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int iron_neural_path_emit(const iron_neural_gbuffer* g, const iron_envmap* env, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth,
+                          int32_t depth, uint32_t seed, float shadow_eps, int64_t capacity, void* workspace, size_t workspace_bytes,
+                          float* shadow_o, float* shadow_d, int32_t* shadow_idx, float* bounce_o, float* bounce_d, int32_t* bounce_idx,
+                          int64_t* counts, void* stream);
+int iron_neural_path_resolve(const iron_neural_gbuffer* g, const iron_envmap* env, const float* tab_trans, const float* tab_diff_trans,
+                             int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int32_t depth, uint32_t seed, float shadow_eps,
+                             int64_t capacity, void* workspace, size_t workspace_bytes, const uint8_t* occluded, int64_t n_shadow,
+                             const iron_neural_bounce* bounce, int64_t n_bounce, const iron_neural_path_dump* dump, void* stream);
+int iron_neural_path_finish(const iron_neural_gbuffer* g, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int64_t capacity,
+                            void* workspace, size_t workspace_bytes, float* indirect_diffuse, float* indirect_specular,
+                            const iron_neural_path_dump* dump, void* stream);
 /* Face connectivity and Smart UV project (models/export_mesh.py's largest component, models/export_uv.py's Blender smart_project),
  * csrc/uvunwrap.hip; the algorithm and its contract are in iron_amd/uv_unwrap.py and DESIGN.md §13.
  *   Mesh: verts fp32 [n_verts,3], faces int32 [n_faces,3], 0 < n_faces < 2^31 - 1.  `state` is 16 bytes of device scratch (8-byte

@@ -113,6 +113,19 @@ class iron_env_path_dump(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ENV_PATH_DUMP_FIELDS]
 
 
+NEURAL_PATH_DUMP_FIELDS = ("bounce_dir", "bounce_org", "reached", "distance", "vertex_points", "vertex_normal", "vertex_diffuse_albedo",
+                           "vertex_specular_albedo", "vertex_roughness", "light_dir", "light_vis", "denom_light", "denom_brdf", "light_term",
+                           "escape_term", "throughput", "lobe_diffuse", "lobe_specular", "path_value")
+
+
+class iron_neural_path_dump(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in NEURAL_PATH_DUMP_FIELDS]
+
+
+class iron_neural_bounce(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("hit", "distance", "points", "normal", "diffuse_albedo", "specular_albedo", "specular_roughness")]
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -173,6 +186,15 @@ SYMBOLS = {
                                        _P, _SZ, _P, _P, _P, _P, _P]),
     "iron_neural_env_resolve": (C.c_int, [C.POINTER(iron_neural_gbuffer), C.POINTER(iron_envmap), _P, _P, _I64, _I64, _I32, _I32, C.c_uint32,
                                           _I64, _P, _SZ, _P, _P, _I64, _P, _P, _P, C.POINTER(iron_env_dump), _P]),
+    "iron_neural_path_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),
+    "iron_neural_path_begin": (C.c_int, [C.POINTER(iron_neural_gbuffer), _I64, _I64, _I32, _I32, _I64, _P, _SZ, _P]),
+    "iron_neural_path_emit": (C.c_int, [C.POINTER(iron_neural_gbuffer), C.POINTER(iron_envmap), _I64, _I64, _I32, _I32, _I32, C.c_uint32, _F,
+                                        _I64, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iron_neural_path_resolve": (C.c_int, [C.POINTER(iron_neural_gbuffer), C.POINTER(iron_envmap), _P, _P, _I64, _I64, _I32, _I32, _I32,
+                                           C.c_uint32, _F, _I64, _P, _SZ, _P, _I64, C.POINTER(iron_neural_bounce), _I64,
+                                           C.POINTER(iron_neural_path_dump), _P]),
+    "iron_neural_path_finish": (C.c_int, [C.POINTER(iron_neural_gbuffer), _I64, _I64, _I32, _I32, _I64, _P, _SZ, _P, _P,
+                                          C.POINTER(iron_neural_path_dump), _P]),
     "iron_mesh_edge_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "iron_mesh_components": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I32, C.POINTER(_I32), _P]),
     "iron_uv_workspace_bytes": (C.c_int, [_I64, C.POINTER(_SZ)]),

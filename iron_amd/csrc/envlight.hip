@@ -838,6 +838,336 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_nenv_resolve(NeuralEnvArgs a)
     st3(a.specular_color, i, accs[0], accs[1], accs[2]);
 }
 
+// ---- interreflections on the neural scene ----
+// k_shade_env_indirect's paths on the neural scene, as a wavefront over depth: a path's closest hit is the sphere tracer's, which
+// is a call of its own, so a path's state lives in a workspace between two tracer calls.  Per block of pixels [p0, p0 + nb), slot
+// s = (pixel - p0) n_paths + path, on one stream:
+//   k_npath_begin    the state of every slot from the G-buffer: alive, the vertex (x, n, v, the seven material channels), T = 1,
+//                    C = b_d = b_s = 0;
+//   k_npath_emit     depth j: per alive slot the two samples of npath_sample (the one function emit and resolve run); their
+//                    directions to the workspace, the two flags -- the light sample counts with dl > 0; the BRDF sample counts and
+//                    its ray is valid -- to level 0 of one pair_scan (Pair64 carries both); k_npath_compact then lists the shadow
+//                    rays and the bounce rays (origin x + shadow_eps n, direction, slot) in ascending slot order;
+//   (the caller)     intersect_sphere with occluded on the shadow list, with forward(chunk = 1) and the surface record on the
+//                    bounce list;
+//   k_npath_resolve  depth j: draws both samples again, adds the visible light term and the escape term to C, forms the next vertex
+//                    and T (b_d, b_s at j = 0) or ends the path, writes the dumps.  A slot finds its rays' answers through the
+//                    scan's prefixes, which stay in the workspace;
+//   k_npath_finish   the pixel's sums of b_d C and b_s C in k_shade_env_indirect's order: path p on lane p % 16 in round p / 16, the
+//                    butterfly, one division by n_paths.
+// Vertex, samples, random numbers, terms and their order are k_shade_env_indirect's with the shading normal in the geometric
+// normal's place (dir_counts(n, n, n.v, w)) and both rays leaving x + shadow_eps n.
+constexpr int kPathState = 28;  // floats per slot: x 0-2, n 3-5, v 6-8, material 9-15, T 16-18, C 19-21, b_d 22-24, b_s 25-27
+constexpr int kPathBlock = 256;
+
+struct NeuralPathLayout {
+    ScanLevels scan;
+    size_t state_off, dir_off, alive_off, cast_off, bytes;
+};
+
+inline NeuralPathLayout npath_layout(int64_t capacity) {
+    NeuralPathLayout L{};
+    Carver c;
+    L.scan = scan_levels(capacity, c);
+    L.state_off = c.take(sizeof(float) * kPathState * (size_t)capacity);
+    L.dir_off = c.take(sizeof(float) * 6 * (size_t)capacity);
+    L.alive_off = c.take((size_t)capacity);
+    L.cast_off = c.take((size_t)capacity);
+    L.bytes = c.off;
+    return L;
+}
+
+struct NeuralPathArgs {
+    iron_neural_gbuffer g;
+    iron_neural_path_dump dump;
+    EnvDev env;
+    const float *tab_trans, *tab_diff;
+    int64_t p0, nb, capacity;
+    int32_t n_paths, max_depth, depth;
+    uint32_t seed;
+    float shadow_eps;
+    float* state;    // [kPathState][capacity]
+    float* dir;      // [capacity, 6]: w_l, w_b of the depth under way
+    uint8_t* alive;  // [capacity]
+    uint8_t* cast;   // [capacity]: bit 0 a shadow ray is listed, bit 1 a bounce ray
+    Pair64* flags;   // level 0 of the scan: the flags (emit), then their exclusive prefixes
+    // the caller's answers (resolve)
+    const uint8_t *occluded, *bounce_hit;
+    const float *bounce_dist, *bounce_points, *bounce_normal, *bounce_kd, *bounce_ks, *bounce_rough;
+    int64_t n_shadow, n_bounce;
+    float *indirect_diffuse, *indirect_specular;  // finish
+};
+
+// what a slot keeps of its vertex
+struct NeuralVertex {
+    float3 x, n, v;
+    float mat[7];
+};
+
+__device__ __forceinline__ float3 npath_ld3(const float* __restrict__ state, int64_t cap, int f, int64_t s) {
+    return make_float3(state[(int64_t)f * cap + s], state[(int64_t)(f + 1) * cap + s], state[(int64_t)(f + 2) * cap + s]);
+}
+__device__ __forceinline__ void npath_st3(float* __restrict__ state, int64_t cap, int f, int64_t s, float a, float b, float c) {
+    state[(int64_t)f * cap + s] = a; state[(int64_t)(f + 1) * cap + s] = b; state[(int64_t)(f + 2) * cap + s] = c;
+}
+__device__ __forceinline__ void npath_load_vertex(const float* __restrict__ state, int64_t cap, int64_t s, NeuralVertex& x) {
+    x.x = npath_ld3(state, cap, 0, s); x.n = npath_ld3(state, cap, 3, s); x.v = npath_ld3(state, cap, 6, s);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) x.mat[c] = state[(int64_t)(9 + c) * cap + s];
+}
+__device__ __forceinline__ void npath_store_vertex(float* __restrict__ state, int64_t cap, int64_t s, const NeuralVertex& x) {
+    npath_st3(state, cap, 0, s, x.x.x, x.x.y, x.x.z);
+    npath_st3(state, cap, 3, s, x.n.x, x.n.y, x.n.z);
+    npath_st3(state, cap, 6, s, x.v.x, x.v.y, x.v.z);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) state[(int64_t)(9 + c) * cap + s] = x.mat[c];
+}
+
+// the two samples of vertex j of path p, as k_shade_env_indirect draws them
+struct PathSample {
+    float3 wl, wb, org;     // light direction, bounce direction (zero: no sample), the origin of both rays
+    float dl, db, pb;       // the two denominators, p_brdf(w_b)
+    float Ll[3], Lb[3];     // the map's radiance along the two
+    bool lcast, bcast;      // a shadow ray / a bounce ray is cast
+};
+
+__device__ __forceinline__ void npath_sample(const EnvDev& env, uint32_t seed, uint32_t pixel, int32_t p, int32_t j, const NeuralVertex& x,
+                                             float shadow_eps, PathSample& s) {
+    const uint32_t dim = 8u * (uint32_t)(j + 1);
+    const float alpha = fmaxf(x.mat[6], 0.0001f), nv = dot3(x.n, x.v);
+    s.wl = s.wb = make_float3(0.f, 0.f, 0.f);
+    s.dl = s.db = s.pb = 0.0f;
+    s.lcast = s.bcast = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s.Ll[c] = s.Lb[c] = 0.0f;
+    const float ex = shadow_eps * x.n.x, ey = shadow_eps * x.n.y, ez = shadow_eps * x.n.z;  // each product and sum rounded on its own
+    s.org = make_float3(x.x.x + ex, x.x.y + ey, x.x.z + ez);
+    if (j >= 1) {  // the environment sample
+        int r, c;
+        const float pl = env_sample(env, env_rand(seed, pixel, p, dim + 3u), env_rand(seed, pixel, p, dim + 4u), r, c, s.wl);
+        const float* L = env.image + 3 * ((int64_t)r * env.We + c);
+        s.Ll[0] = L[0]; s.Ll[1] = L[1]; s.Ll[2] = L[2];
+        s.dl = pl + brdf_pdf(x.n, x.v, s.wl, alpha);
+        s.lcast = dir_counts(x.n, x.n, nv, s.wl) && s.dl > 0.0f;
+    }
+    const bool ok = brdf_sample(x.n, x.v, alpha, env_rand(seed, pixel, p, dim), env_rand(seed, pixel, p, dim + 1u),
+                                env_rand(seed, pixel, p, dim + 2u), s.wb);
+    if (!ok) s.wb = make_float3(0.f, 0.f, 0.f);
+    if (ok && dir_counts(x.n, x.n, nv, s.wb)) {
+        const float pl = env_eval(env, s.wb, s.Lb);
+        s.pb = brdf_pdf(x.n, x.v, s.wb, alpha);
+        s.db = pl + s.pb;
+        s.bcast = ray_valid(s.org, s.wb);
+    }
+}
+
+__device__ __forceinline__ uint32_t npath_pixel(const iron_neural_gbuffer& g, int64_t i) {
+    return g.pixel_idx ? (uint32_t)g.pixel_idx[i] : (uint32_t)i;
+}
+
+__global__ __launch_bounds__(kPathBlock) void k_npath_begin(NeuralPathArgs a) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.nb * a.n_paths) return;
+    NeuralPixel px;
+    nenv_pixel(a.g, a.p0 + s / a.n_paths, px);
+    NeuralVertex x;
+    x.x = px.x; x.n = px.n; x.v = px.v;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) x.mat[c] = px.mat[c];
+    npath_store_vertex(a.state, a.capacity, s, x);
+    npath_st3(a.state, a.capacity, 16, s, 1.f, 1.f, 1.f);
+    npath_st3(a.state, a.capacity, 19, s, 0.f, 0.f, 0.f);
+    npath_st3(a.state, a.capacity, 22, s, 0.f, 0.f, 0.f);
+    npath_st3(a.state, a.capacity, 25, s, 0.f, 0.f, 0.f);
+    a.alive[s] = px.hit ? 1 : 0;
+}
+
+// counts[2] += the alive slots (one atomic per wave: integer, so the order does not matter)
+__global__ __launch_bounds__(kPathBlock) void k_npath_emit(NeuralPathArgs a, unsigned long long* __restrict__ counts) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = s < a.nb * a.n_paths;
+    const bool alive = in && a.alive[s] != 0;
+    PathSample q;
+    q.wl = q.wb = make_float3(0.f, 0.f, 0.f);
+    q.lcast = q.bcast = false;
+    if (alive) {
+        NeuralVertex x;
+        npath_load_vertex(a.state, a.capacity, s, x);
+        npath_sample(a.env, a.seed, npath_pixel(a.g, a.p0 + s / a.n_paths), (int32_t)(s % a.n_paths), a.depth, x, a.shadow_eps, q);
+    }
+    if (in) {
+        float* d = a.dir + 6 * s;
+        d[0] = q.wl.x; d[1] = q.wl.y; d[2] = q.wl.z; d[3] = q.wb.x; d[4] = q.wb.y; d[5] = q.wb.z;
+        a.flags[s] = Pair64{q.lcast ? 1 : 0, q.bcast ? 1 : 0};
+        a.cast[s] = (uint8_t)((q.lcast ? 1 : 0) | (q.bcast ? 2 : 0));
+    }
+    const unsigned long long wave = __ballot(alive);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && wave != 0) atomicAdd(counts + 2, (unsigned long long)__popcll(wave));
+}
+
+__global__ __launch_bounds__(kPathBlock) void k_npath_compact(NeuralPathArgs a, const Pair64* __restrict__ prefix, const Pair64* __restrict__ total,
+                                                              float* __restrict__ shadow_o, float* __restrict__ shadow_d,
+                                                              int32_t* __restrict__ shadow_idx, float* __restrict__ bounce_o,
+                                                              float* __restrict__ bounce_d, int32_t* __restrict__ bounce_idx,
+                                                              unsigned long long* __restrict__ counts) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s == 0) { counts[0] = (unsigned long long)total[0].a; counts[1] = (unsigned long long)total[0].b; }
+    if (s >= a.nb * a.n_paths) return;
+    const uint8_t cast = a.cast[s];
+    if (cast == 0) return;
+    const float3 x = npath_ld3(a.state, a.capacity, 0, s), n = npath_ld3(a.state, a.capacity, 3, s);
+    const float ex = a.shadow_eps * n.x, ey = a.shadow_eps * n.y, ez = a.shadow_eps * n.z;
+    const float* d = a.dir + 6 * s;
+    const Pair64 at = prefix[s];
+    if ((cast & 1) && at.a < a.capacity) {
+        st3(shadow_o, at.a, x.x + ex, x.y + ey, x.z + ez);
+        st3(shadow_d, at.a, d[0], d[1], d[2]);
+        shadow_idx[at.a] = (int32_t)s;
+    }
+    if ((cast & 2) && at.b < a.capacity) {
+        st3(bounce_o, at.b, x.x + ex, x.y + ey, x.z + ez);
+        st3(bounce_d, at.b, d[3], d[4], d[5]);
+        bounce_idx[at.b] = (int32_t)s;
+    }
+}
+
+__global__ __launch_bounds__(kPathBlock) void k_npath_resolve(NeuralPathArgs a) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.nb * a.n_paths) return;
+    const int64_t i = a.p0 + s / a.n_paths;
+    const int32_t p = (int32_t)(s % a.n_paths), j = a.depth;
+    const int64_t cap = a.capacity;
+    float3 wl = make_float3(0.f, 0.f, 0.f), wb = wl, org = wl;
+    float dl = 0.0f, db = 0.0f, th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
+    float rx[3] = {0.f, 0.f, 0.f}, rn[3] = {0.f, 0.f, 0.f}, rkd[3] = {0.f, 0.f, 0.f}, rks[3] = {0.f, 0.f, 0.f}, rr = 0.0f;
+    bool lvis = false;
+    int32_t reached = -2;
+    if (a.alive[s] != 0) {
+        bool alive = false;  // until the vertex hands the path on
+        NeuralVertex x;
+        npath_load_vertex(a.state, cap, s, x);
+        float3 T = npath_ld3(a.state, cap, 16, s), Cs = npath_ld3(a.state, cap, 19, s);
+        float Tv[3] = {T.x, T.y, T.z}, C[3] = {Cs.x, Cs.y, Cs.z};
+        PathSample q;
+        npath_sample(a.env, a.seed, npath_pixel(a.g, i), p, j, x, a.shadow_eps, q);
+        wl = q.wl; wb = q.wb; dl = q.dl; db = q.db;
+        const uint8_t cast = a.cast[s];
+        const Pair64 at = a.flags[s];
+        const float nn[3] = {x.n.x, x.n.y, x.n.z}, vv[3] = {x.v.x, x.v.y, x.v.z};
+        if ((cast & 1) && at.a < a.n_shadow) {  // the environment sample: listed means it counts and dl > 0
+            lvis = a.occluded[at.a] == 0;
+            if (lvis) {
+                PlasticOut f;
+                const float ww[3] = {wl.x, wl.y, wl.z};
+                roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    lt[c] = (Tv[c] * q.Ll[c]) * (f.diffuse[c] + f.specular[c]) / dl;  // an infinite density gives 0
+                    C[c] += lt[c];
+                }
+            }
+        }
+        if ((cast & 2) && at.b < a.n_bounce) {  // the BRDF sample and its ray
+            org = q.org;
+            const bool hit = a.bounce_hit[at.b] != 0;
+            reached = hit ? 1 : -1;
+            th = hit ? a.bounce_dist[at.b] : kInfF;
+            PlasticOut f;
+            const float ww[3] = {wb.x, wb.y, wb.z};
+            roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+            if (!hit) {
+                if (j >= 1 && db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        et[c] = (Tv[c] * q.Lb[c]) * (f.diffuse[c] + f.specular[c]) / db;
+                        C[c] += et[c];
+                    }
+                }
+            } else {
+                const float3 x2 = ld3(a.bounce_points, at.b), n2 = ld3(a.bounce_normal, at.b);
+                rx[0] = x2.x; rx[1] = x2.y; rx[2] = x2.z; rn[0] = n2.x; rn[1] = n2.y; rn[2] = n2.z;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { rkd[c] = a.bounce_kd[3 * at.b + c]; rks[c] = a.bounce_ks[3 * at.b + c]; }
+                rr = a.bounce_rough[at.b];
+                // a surface met from behind is black, like a back-facing primary hit
+                if (-dot3(n2, wb) > 0.0f && q.pb > 0.0f) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        if (j == 0) {
+                            a.state[(int64_t)(22 + c) * cap + s] = f.diffuse[c] / q.pb;
+                            a.state[(int64_t)(25 + c) * cap + s] = f.specular[c] / q.pb;
+                        } else {
+                            Tv[c] = Tv[c] * (f.diffuse[c] + f.specular[c]) / q.pb;
+                        }
+                        tp[c] = Tv[c];
+                    }
+                    NeuralVertex y;
+                    y.x = x2; y.n = n2; y.v = make_float3(-wb.x, -wb.y, -wb.z);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { y.mat[c] = rkd[c]; y.mat[3 + c] = rks[c]; }
+                    y.mat[6] = rr;
+                    npath_store_vertex(a.state, cap, s, y);
+                    npath_st3(a.state, cap, 16, s, Tv[0], Tv[1], Tv[2]);
+                    alive = true;
+                }
+            }
+        }
+        npath_st3(a.state, cap, 19, s, C[0], C[1], C[2]);
+        a.alive[s] = alive ? 1 : 0;
+    }
+    const int64_t at = ((int64_t)i * a.n_paths + p) * a.max_depth + j;
+    st3(a.dump.bounce_dir, at, wb.x, wb.y, wb.z);
+    st3(a.dump.bounce_org, at, org.x, org.y, org.z);
+    if (a.dump.reached) a.dump.reached[at] = reached;
+    if (a.dump.distance) a.dump.distance[at] = th;
+    st3(a.dump.vertex_points, at, rx[0], rx[1], rx[2]);
+    st3(a.dump.vertex_normal, at, rn[0], rn[1], rn[2]);
+    st3(a.dump.vertex_diffuse_albedo, at, rkd[0], rkd[1], rkd[2]);
+    st3(a.dump.vertex_specular_albedo, at, rks[0], rks[1], rks[2]);
+    if (a.dump.vertex_roughness) a.dump.vertex_roughness[at] = rr;
+    st3(a.dump.light_dir, at, wl.x, wl.y, wl.z);
+    if (a.dump.light_vis) a.dump.light_vis[at] = lvis ? 1 : 0;
+    if (a.dump.denom_light) a.dump.denom_light[at] = dl;
+    if (a.dump.denom_brdf) a.dump.denom_brdf[at] = db;
+    st3(a.dump.light_term, at, lt[0], lt[1], lt[2]);
+    st3(a.dump.escape_term, at, et[0], et[1], et[2]);
+    st3(a.dump.throughput, at, tp[0], tp[1], tp[2]);
+}
+
+__global__ __launch_bounds__(kBvQueryBlock) void k_npath_finish(NeuralPathArgs a) {
+    const int lane = threadIdx.x, sl = lane % kEnvGroup;
+    const int64_t k = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;  // the pixel's place in the block
+    if (k >= a.nb) return;  // a whole group leaves together
+    const int64_t i = a.p0 + k, cap = a.capacity;
+    float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
+    for (int32_t base = 0; base < a.n_paths; base += kEnvGroup) {
+        const int32_t p = base + sl;
+        if (p >= a.n_paths) break;  // the ragged tail of the last round
+        const int64_t s = k * a.n_paths + p;
+        const float3 C = npath_ld3(a.state, cap, 19, s), bd = npath_ld3(a.state, cap, 22, s), bs = npath_ld3(a.state, cap, 25, s);
+        const float Cv[3] = {C.x, C.y, C.z}, bdv[3] = {bd.x, bd.y, bd.z}, bsv[3] = {bs.x, bs.y, bs.z};
+        st3(a.dump.lobe_diffuse, i * a.n_paths + p, bdv[0], bdv[1], bdv[2]);
+        st3(a.dump.lobe_specular, i * a.n_paths + p, bsv[0], bsv[1], bsv[2]);
+        st3(a.dump.path_value, i * a.n_paths + p, (bdv[0] + bsv[0]) * Cv[0], (bdv[1] + bsv[1]) * Cv[1], (bdv[2] + bsv[2]) * Cv[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += bdv[c] * Cv[c];
+            accs[c] += bsv[c] * Cv[c];
+        }
+    }
+#pragma unroll
+    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
+            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
+        }
+    if (sl != 0) return;
+    const float np = (float)a.n_paths;
+    st3(a.indirect_diffuse, i, accd[0] / np, accd[1] / np, accd[2] / np);
+    st3(a.indirect_specular, i, accs[0] / np, accs[1] / np, accs[2] / np);
+}
+
 static bool env_dev(const iron_envmap* env, EnvDev& E) {
     if (!env || !env->image || !env->dist || env->h <= 0 || env->w <= 0 || (int64_t)env->h * env->w > (1 << 24)) return false;
     const EnvLayout L = env_layout(env->h, env->w);
@@ -1046,5 +1376,107 @@ extern "C" int iron_neural_env_resolve(const iron_neural_gbuffer* g, const iron_
     a.dump = dump ? *dump : iron_env_dump{nullptr, nullptr, nullptr, nullptr};
     a.color = color; a.diffuse_color = diffuse_color; a.specular_color = specular_color;
     IRON_LAUNCH(k_nenv_resolve, blocks_for(nb, kEnvPixels), kBvQueryBlock, st, a);
+    return IRON_OK;
+}
+
+// ---- interreflections on the neural scene ----
+// what the entries of a block check alike, and the argument block
+static int npath_args(const iron_neural_gbuffer* g, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int64_t capacity,
+                      void* workspace, size_t workspace_bytes, NeuralPathArgs& a) {
+    if (!g || g->n < 0 || n_paths < 1 || n_paths > (1 << 16) || max_depth < 2 || max_depth > 8) return IRON_ERR_BAD_ARG;
+    if (p0 < 0 || nb < 1 || p0 + nb > g->n || capacity < 1 || capacity > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
+    if (nb > capacity / n_paths) return IRON_ERR_BAD_ARG;   // the slots of a block: int32 list entries
+    if (!g->hit || !g->points || !g->normal || !g->ray_d || !g->diffuse_albedo || !g->specular_albedo || !g->specular_roughness)
+        return IRON_ERR_BAD_ARG;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0) return IRON_ERR_BAD_ARG;
+    const NeuralPathLayout L = npath_layout(capacity);
+    if (workspace_bytes < L.bytes) return IRON_ERR_WORKSPACE;
+    a = NeuralPathArgs{};
+    a.g = *g;
+    a.p0 = p0; a.nb = nb; a.capacity = capacity; a.n_paths = n_paths; a.max_depth = max_depth;
+    a.state = ws_ptr<float>(workspace, L.state_off);
+    a.dir = ws_ptr<float>(workspace, L.dir_off);
+    a.alive = ws_ptr<uint8_t>(workspace, L.alive_off);
+    a.cast = ws_ptr<uint8_t>(workspace, L.cast_off);
+    a.flags = L.scan.level(workspace, 0);
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_path_workspace_bytes(int64_t capacity, size_t* bytes) {
+    if (!bytes || capacity < 1 || capacity > 0x7fffffffLL - 64) return IRON_ERR_BAD_ARG;
+    *bytes = npath_layout(capacity).bytes;
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_path_begin(const iron_neural_gbuffer* g, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int64_t capacity,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    NeuralPathArgs a;
+    const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
+    if (rc != IRON_OK) return rc;
+    IRON_LAUNCH(k_npath_begin, blocks_for(nb * n_paths, kPathBlock), kPathBlock, (hipStream_t)stream, a);
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_path_emit(const iron_neural_gbuffer* g, const iron_envmap* env, int64_t p0, int64_t nb, int32_t n_paths,
+                                     int32_t max_depth, int32_t depth, uint32_t seed, float shadow_eps, int64_t capacity, void* workspace,
+                                     size_t workspace_bytes, float* shadow_o, float* shadow_d, int32_t* shadow_idx, float* bounce_o,
+                                     float* bounce_d, int32_t* bounce_idx, int64_t* counts, void* stream) {
+    NeuralPathArgs a;
+    const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
+    if (rc != IRON_OK) return rc;
+    if (depth < 0 || depth >= max_depth || !(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    if (!shadow_o || !shadow_d || !shadow_idx || !bounce_o || !bounce_d || !bounce_idx || !counts) return IRON_ERR_BAD_ARG;
+    if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const NeuralPathLayout L = npath_layout(capacity);
+    const int64_t M = nb * n_paths;
+    a.depth = depth; a.seed = seed; a.shadow_eps = shadow_eps;
+    // the scan runs over the whole capacity: the entries behind this block's slots are zero
+    if (capacity > M) IRON_HIP_TRY(hipMemsetAsync(a.flags + M, 0, sizeof(Pair64) * (size_t)(capacity - M), st));
+    IRON_HIP_TRY(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st));
+    IRON_LAUNCH(k_npath_emit, blocks_for(M, kPathBlock), kPathBlock, st, a, (unsigned long long*)counts);
+    const int rs = pair_scan(L.scan, workspace, st);
+    if (rs != IRON_OK) return rs;
+    IRON_LAUNCH(k_npath_compact, blocks_for(M, kPathBlock), kPathBlock, st, a, (const Pair64*)L.scan.level(workspace, 0),
+                (const Pair64*)L.scan.level(workspace, L.scan.levels), shadow_o, shadow_d, shadow_idx, bounce_o, bounce_d, bounce_idx,
+                (unsigned long long*)counts);
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_path_resolve(const iron_neural_gbuffer* g, const iron_envmap* env, const float* tab_trans, const float* tab_diff_trans,
+                                        int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int32_t depth, uint32_t seed,
+                                        float shadow_eps, int64_t capacity, void* workspace, size_t workspace_bytes, const uint8_t* occluded,
+                                        int64_t n_shadow, const iron_neural_bounce* bounce, int64_t n_bounce,
+                                        const iron_neural_path_dump* dump, void* stream) {
+    NeuralPathArgs a;
+    const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
+    if (rc != IRON_OK) return rc;
+    const int64_t M = nb * n_paths;
+    if (depth < 0 || depth >= max_depth || !(shadow_eps >= 0.0f) || !(shadow_eps < kInfF) || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
+    if (n_shadow < 0 || n_shadow > M || n_bounce < 0 || n_bounce > M || (n_shadow > 0 && !occluded)) return IRON_ERR_BAD_ARG;
+    if (n_bounce > 0 && (!bounce || !bounce->hit || !bounce->distance || !bounce->points || !bounce->normal || !bounce->diffuse_albedo ||
+                         !bounce->specular_albedo || !bounce->specular_roughness))
+        return IRON_ERR_BAD_ARG;
+    if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
+    a.depth = depth; a.seed = seed; a.shadow_eps = shadow_eps; a.tab_trans = tab_trans; a.tab_diff = tab_diff_trans;
+    a.occluded = occluded; a.n_shadow = n_shadow; a.n_bounce = n_bounce;
+    if (n_bounce > 0) {
+        a.bounce_hit = bounce->hit; a.bounce_dist = bounce->distance; a.bounce_points = bounce->points; a.bounce_normal = bounce->normal;
+        a.bounce_kd = bounce->diffuse_albedo; a.bounce_ks = bounce->specular_albedo; a.bounce_rough = bounce->specular_roughness;
+    }
+    if (dump) a.dump = *dump;
+    IRON_LAUNCH(k_npath_resolve, blocks_for(M, kPathBlock), kPathBlock, (hipStream_t)stream, a);
+    return IRON_OK;
+}
+
+extern "C" int iron_neural_path_finish(const iron_neural_gbuffer* g, int64_t p0, int64_t nb, int32_t n_paths, int32_t max_depth, int64_t capacity,
+                                       void* workspace, size_t workspace_bytes, float* indirect_diffuse, float* indirect_specular,
+                                       const iron_neural_path_dump* dump, void* stream) {
+    NeuralPathArgs a;
+    const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
+    if (rc != IRON_OK) return rc;
+    a.indirect_diffuse = indirect_diffuse; a.indirect_specular = indirect_specular;
+    if (dump) a.dump = *dump;
+    IRON_LAUNCH(k_npath_finish, blocks_for(nb, kEnvPixels), kBvQueryBlock, (hipStream_t)stream, a);
     return IRON_OK;
 }

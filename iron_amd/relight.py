@@ -2,13 +2,15 @@
 
     python -m iron_amd.relight --ckpt CKPT.pth --cam_dict cam_dict_norm.json --envmap FILE --out DIR
                                [--n-light N] [--n-brdf N] [--seed S] [--samples-per-axis A] [--background] [--shadow-eps E]
+                               [--max-depth D] [--n-paths P]
 
 CKPT.pth is a stage-2 checkpoint: a dictionary of state-dicts under the keys sdf_network, diffuse_albedo_network,
 specular_albedo_network and specular_roughness_network (render_surface.py:669-671; point_light_network and anything else in it is
 ignored), loaded into the `ggx` networks of iron_amd.network_conf.  FILE is a lat-long environment map (.npy, Radiance .hdr, or .exr
 when imageio reads it).  For every entry NAME of the camera JSON ({"K": 16 floats, "W2C": 16 floats, "img_size": [W, H]}) it writes
 what `python -m iron_amd.render_asset --envmap` writes, through the same writers: OUT/image/STEM.exr (a float32 STEM.npy when
-imageio has no EXR plugin) and the 8-bit OUT/image/STEM.png = clip(x^(1/2.2)).
+imageio has no EXR plugin) and the 8-bit OUT/image/STEM.png = clip(x^(1/2.2)).  --max-depth D > 1 adds the interreflections by
+P paths per ray of at most D surface vertices.
 """
 from __future__ import annotations
 
@@ -74,7 +76,12 @@ def parse_args(argv=None):
     ap.add_argument("--samples-per-axis", type=int, default=1, dest="samples_per_axis")
     ap.add_argument("--background", action="store_true", help="show the map where a ray misses the scene")
     ap.add_argument("--shadow-eps", type=float, default=1e-3, dest="shadow_eps", help="offset of a shadow ray's origin along the normal")
+    ap.add_argument("--max-depth", type=int, default=1, dest="max_depth",
+                    help="largest number of surface vertices on a light path, the primary hit included (1: direct light only)")
+    ap.add_argument("--n-paths", type=int, default=64, dest="n_paths", help="paths per ray for the interreflections (--max-depth > 1)")
     a = ap.parse_args(argv)
+    if not 1 <= a.max_depth <= 8 or not 1 <= a.n_paths <= 1 << 16:
+        ap.error("--max-depth must be in 1 .. 8 and --n-paths in 1 .. 65536")
     if a.n_light < 0 or a.n_brdf < 0 or a.n_light + a.n_brdf == 0:
         ap.error("--n-light and --n-brdf must be >= 0 and not both 0")
     if a.samples_per_axis < 1 or not a.shadow_eps >= 0:
@@ -92,7 +99,8 @@ def main(argv=None) -> None:
     sdf_network, nets = load_networks(a.ckpt, dev)
     envmap = EnvMap(read_envmap(a.envmap), device=dev)
     images = relight_cam_dict(sdf_network, nets, cam_dict, envmap, a.out, samples_per_axis=a.samples_per_axis, n_light=a.n_light,
-                              n_brdf=a.n_brdf, seed=a.seed, background=a.background, shadow_eps=a.shadow_eps)
+                              n_brdf=a.n_brdf, seed=a.seed, background=a.background, shadow_eps=a.shadow_eps, max_depth=a.max_depth,
+                              n_paths=a.n_paths)
     print("relit %d views into %s" % (len(images), os.path.join(a.out, "image")))
 
 

@@ -14,7 +14,15 @@ wound inwards (marching cubes' winding on an SDF that is positive outside) and t
 black, so the asset is compared with every face turned round; the mean colour of the asset as written is reported beside it.  Writes one JSON line to
 profiles/neural_relight_bench.json and prints it.
 
-    python tools/bench_neural_relight.py [--reps 3] [--export-res 256] [--sizes 400 800] [--no-export]
+--arm indirect measures the interreflections instead: the same two fields at the first of --sizes, 64 + 64 direct
+samples and 64 paths per pixel at max_depth 2 and 4.  Per frame (the median of --reps after a warm-up, device event pairs): ms per
+stage of the direct pass and of the path pass (path_emit includes the host's read of the two ray counts per block and depth), the
+direct stages' sum beside the whole frame, bounce rays per second of the bounce stage (forward with chunk = 1) and shadow rays per
+second of the path pass's occlusion stage beside the direct pass's, the alive share of the paths at every depth, and SDF evaluations
+per bounce ray from the tracer's counters (a separate, untimed run).  It writes its line as the second line of the same file and leaves
+the first as it is.
+
+    python tools/bench_neural_relight.py [--reps 3] [--export-res 256] [--sizes 400 800] [--no-export] [--arm direct|indirect]
 """
 from __future__ import annotations
 
@@ -59,8 +67,54 @@ def frame(cam, sdf, tr, nets, env, reps, **kw):
     return out, res["color"]
 
 
+DIRECT_STAGES = ("gbuffer", "emit", "trace", "resolve")
+
+
+def indirect_frame(cam, sdf, tr, nets, env, reps, depth, n_paths=64):
+    """relight_camera with the interreflections, `reps` times after a warm-up -> the median frame's figures"""
+    from iron_amd.neural_relight import relight_camera
+    kw = dict(max_depth=depth, n_paths=n_paths)
+    relight_camera(cam, sdf, tr, nets, env, **kw)
+    runs = []
+    for _ in range(reps):
+        stats = {}
+        res = relight_camera(cam, sdf, tr, nets, env, stats=stats, **kw)
+        runs.append(stats)
+    runs.sort(key=lambda s: sum(s["ms"].values()))
+    s = runs[len(runs) // 2]
+    total, direct = sum(s["ms"].values()), sum(s["ms"][k] for k in DIRECT_STAGES)
+    paths = max(s["alive"][0], 1)
+    counters = {"trace_stats": True}   # the tracer's counters, untimed
+    relight_camera(cam, sdf, tr, nets, env, stats=counters, **kw)
+    return {"ms": {k: round(v, 3) for k, v in s["ms"].items()}, "frame_ms": round(total, 3), "direct_ms": round(direct, 3),
+            "indirect_ms": round(total - direct, 3), "hits": int(res["convergent_mask"].sum()), "n_paths": n_paths, "max_depth": depth,
+            "bounce_rays": s["bounce_rays"], "bounce_hits": s["bounce_hits"], "indirect_shadow_rays": s["indirect_shadow_rays"],
+            "indirect_occluded": s["indirect_occluded"], "direct_shadow_rays": s["shadow_rays"],
+            "bounce_mrays_per_s": round(s["bounce_rays"] / max(s["ms"]["path_bounce"], 1e-9) / 1e3, 2),
+            "indirect_shadow_mrays_per_s": round(s["indirect_shadow_rays"] / max(s["ms"]["path_shadow"], 1e-9) / 1e3, 2),
+            "direct_shadow_mrays_per_s": round(s["shadow_rays"] / max(s["ms"]["trace"], 1e-9) / 1e3, 2),
+            "alive_share": [round(a / paths, 5) for a in s["alive"]],
+            "evals_per_bounce_ray": round(counters["bounce_tracer"]["n_evals"] / max(counters["bounce_rays"], 1), 3),
+            "mean_indirect": round(float(res["indirect_color"].mean()), 6), "mean_color": round(float(res["color"].mean()), 6)}
+
+
+def write_line(path, line, at):
+    """`line` as line `at` of the file, the other lines kept"""
+    lines = []
+    if os.path.exists(path):
+        with open(path) as fp:
+            lines = [x for x in fp.read().split("\n") if x]
+    while len(lines) <= at:
+        lines.append("{}")
+    lines[at] = line
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fp:
+        fp.write("\n".join(lines) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arm", choices=("direct", "indirect"), default="direct")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--export-res", type=int, default=256, dest="export_res")
     ap.add_argument("--sizes", type=int, nargs="+", default=[400, 800])
@@ -85,6 +139,17 @@ def main() -> None:
     def camera(size):
         K, W2C = scenes.fixture_camera_matrices(size, size)
         return Camera(size, size, K.to(dev), W2C.to(dev))
+
+    if a.arm == "indirect":
+        res = {"arm": "indirect", "device": res["device"], "reps": a.reps, "samples": [64, 64], "envmap": [512, 1024], "size": a.sizes[0],
+               "frames": {}}
+        for name, sdf in fields.items():
+            for depth in (2, 4):
+                res["frames"]["%s_%d_depth%d" % (name, a.sizes[0], depth)] = indirect_frame(camera(a.sizes[0]), sdf, tr, nets, env, a.reps, depth)
+        line = json.dumps(res, sort_keys=True)
+        write_line(a.out, line, 1)
+        print(line)
+        return
 
     for name, sdf in fields.items():
         for size in a.sizes:
@@ -140,9 +205,7 @@ def main() -> None:
                     "mean_color_asset": round(float(mesh_img["color"][both].mean()), 6)}
         res["export_loss_S0"] = loss
     line = json.dumps(res, sort_keys=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fp:
-        fp.write(line + "\n")
+    write_line(a.out, line, 0)
     print(line)
 
 
