@@ -220,6 +220,55 @@ int iron_ssim_backward(const float* x, const float* y, int32_t b, int32_t c, int
 int iron_gaussian_filter(const float* x, int64_t n_planes, int32_t h, int32_t w, const float* win, int32_t win_size, float* out,
                          void* stream);
 
+/* Multi-tensor Adam (csrc/optim.hip): torch.optim.Adam without weight decay or amsgrad over a HOST table of tensors,
+ *     m <- m + (1 - beta1)(g - m);  v <- beta2 v + (1 - beta2) g^2;  p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * with t = `step` (>= 1: the count AFTER this update, as torch keeps it) per tensor and both bias corrections formed in fp64.  All
+ * four buffers of a tensor are fp32, `numel` long, 4-byte aligned (nothing more is assumed) and must not overlap another entry's.
+ * zero_grad != 0: every gradient is left exactly 0, in the same pass.  The table is cut into chunks of IRON_ADAM_CHUNK elements
+ * and travels in the kernels' argument block, IRON_ADAM_MAX_TENSORS tensors per launch: ceil(n_tensors / IRON_ADAM_MAX_TENSORS)
+ * launches, no upload, no allocation, no host synchronisation.  IRON_ERR_BAD_ARG: a null pointer (with numel > 0), a negative
+ * numel, step < 1, a beta outside [0, 1), a negative eps; nothing is enqueued then. */
+#define IRON_ADAM_CHUNK 2048
+#define IRON_ADAM_MAX_TENSORS 80
+typedef struct iron_adam_tensor {
+    float* param;
+    float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    int64_t step;
+    double lr;
+} iron_adam_tensor;
+int iron_adam_multi(const iron_adam_tensor* tensors, int64_t n_tensors, double beta1, double beta2, double eps, int32_t zero_grad,
+                    void* stream);
+
+/* The regularisers of the stage-2 step (render_surface.py:580-613, 639), csrc/optim.hip.  Three sets of 3-vectors -- eik_grad
+ * [m,3] (the uniform eikonal gradients), normal [n_pix,3] where mask [n_pix] (uint8, non-zero = kept) holds, edge_normal [e,3]
+ * (NULL with e = 0) -- and roughness [n_pix]:
+ *     eik_loss        = eik_weight * sum over the sets of (|g| - 1)^2 / cnt,  cnt = m + n_mask + e
+ *     roughrange_loss = roughrange_weight * mean(r - 0.5 over masked r > 0.5), 0 when nothing is selected
+ * As in the reference, the masked and the edge set enter only when the mask keeps at least one pixel (cnt = m otherwise).  Both
+ * losses are DEVICE scalars; counts (DEVICE int64 [3]) = cnt, n_mask, number of selected roughness values; state (DEVICE double
+ * [4]) carries the backward's scales.  Sums are per-workgroup partials in `workspace`, added in a fixed order in fp64 (no
+ * atomics: bitwise reproducible).  The backward reads the upstream gradients d_eik / d_roughrange from DEVICE scalars (NULL =
+ * zero) and WRITES every element of each non-NULL output: 2 (|g| - 1) g / |g| * eik_weight / cnt * d_eik on the vectors that
+ * entered (0 for a zero vector and outside the mask), roughrange_weight / n * d_roughrange on the selected roughness values (r
+ * == 0.5 is not selected), 0 elsewhere. */
+typedef struct iron_surface_reg_args {
+    const float* eik_grad;
+    const float* normal;
+    const uint8_t* mask;
+    const float* roughness;
+    const float* edge_normal;
+    int64_t m, n_pix, e;
+    float eik_weight, roughrange_weight;
+} iron_surface_reg_args;
+size_t iron_surface_reg_workspace_bytes(int64_t m, int64_t n_pix, int64_t e);
+int iron_surface_reg(const iron_surface_reg_args* a, float* eik_loss, float* roughrange_loss, int64_t* counts, double* state,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int iron_surface_reg_backward(const iron_surface_reg_args* a, const double* state, const float* d_eik, const float* d_roughrange,
+                              float* d_eik_grad, float* d_normal, float* d_roughness, float* d_edge_normal, void* stream);
+
 /* Diagnostics: last hipError_t seen by this library on the calling thread (iron_train_last_blas_status: kept for ABI
  * stability, always 0: the library links no BLAS). */
 int iron_train_last_hip_error(void);

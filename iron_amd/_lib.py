@@ -312,8 +312,28 @@ class iron_neus_composite_grads(C.Structure):
                                           "d_sample_color", "d_inv_s", "d_bg_density", "d_bg_color")]
 
 
+class iron_adam_tensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("step", C.c_int64), ("lr", C.c_double)]
+
+
+class iron_surface_reg_args(C.Structure):
+    _fields_ = [("eik_grad", C.c_void_p), ("normal", C.c_void_p), ("mask", C.c_void_p), ("roughness", C.c_void_p),
+                ("edge_normal", C.c_void_p), ("m", C.c_int64), ("n_pix", C.c_int64), ("e", C.c_int64),
+                ("eik_weight", C.c_float), ("roughrange_weight", C.c_float)]
+
+
+IRON_ERR_BAD_ARG = -1
+IRON_ADAM_CHUNK = 2048        # include/iron_train.h
+IRON_ADAM_MAX_TENSORS = 80
+
 TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libiron_train.so")
 TRAIN_SYMBOLS = {
+    "iron_adam_multi": (C.c_int, [C.POINTER(iron_adam_tensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "iron_surface_reg_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "iron_surface_reg": (C.c_int, [C.POINTER(iron_surface_reg_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
+    "iron_surface_reg_backward": (C.c_int, [C.POINTER(iron_surface_reg_args)] + [C.c_void_p] * 8),
     "iron_train_gemm_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "iron_train_gemm": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _F, _P, _I32, _P, _SZ, _P]),
     "iron_sdf_backward_workspace_bytes": (_SZ, [C.POINTER(iron_sdf_train_desc), _I64]),

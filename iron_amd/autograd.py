@@ -578,6 +578,53 @@ class SSIMFn(torch.autograd.Function):
         return dx, dy, None, None, None, None, None
 
 
+class SurfaceRegFn(torch.autograd.Function):
+    """(eik_loss, roughrange_loss, counts) = the regularisers of render_surface.py:580-613, 639 (include/iron_train.h:
+    iron_surface_reg).  eik_grad [M, 3], normal [P, 3], mask [P] uint8, roughness [P], edge_normal [E, 3] or None; counts is the
+    device int64 [3] (cnt, n_mask, n_selected).  Gradients go to eik_grad, normal, roughness and edge_normal."""
+
+    @staticmethod
+    def forward(ctx, eik_grad, normal, mask, roughness, edge_normal, eik_weight, roughrange_weight):
+        lib = _lib.load_train()
+        dev = eik_grad.device
+        a = _lib.iron_surface_reg_args()
+        a.eik_grad, a.normal, a.mask, a.roughness, a.edge_normal = (eik_grad.data_ptr(), normal.data_ptr(), mask.data_ptr(),
+                                                                    roughness.data_ptr(), _lib.ptr(edge_normal))
+        a.m, a.n_pix, a.e = eik_grad.shape[0], normal.shape[0], 0 if edge_normal is None else edge_normal.shape[0]
+        a.eik_weight, a.roughrange_weight = eik_weight, roughrange_weight
+        with torch.cuda.device(dev):
+            ws = _lib.workspace(lib.iron_surface_reg_workspace_bytes(a.m, a.n_pix, a.e), dev, "surface_reg")
+            eik = torch.empty((), dtype=torch.float32, device=dev)
+            rr = torch.empty((), dtype=torch.float32, device=dev)
+            counts = torch.empty(3, dtype=torch.int64, device=dev)
+            state = torch.empty(4, dtype=torch.float64, device=dev)
+            _lib.check_train(lib.iron_surface_reg(C.byref(a), eik.data_ptr(), rr.data_ptr(), counts.data_ptr(),
+                                                  state.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        ctx.args, ctx.state = a, state
+        ctx.save_for_backward(eik_grad, normal, mask, roughness, edge_normal)   # keeps the buffers `a` points to alive
+        ctx.mark_non_differentiable(counts)
+        return eik, rr, counts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_eik, g_rr, _g_counts):
+        eik_grad, normal, mask, roughness, edge_normal = ctx.saved_tensors
+        lib = _lib.load_train()
+        dev = eik_grad.device
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            g_eik = None if g_eik is None else _lib.require_cuda_f32(g_eik, "upstream gradient").reshape(1)
+            g_rr = None if g_rr is None else _lib.require_cuda_f32(g_rr, "upstream gradient").reshape(1)
+            d_eik = torch.empty_like(eik_grad) if need[0] else None
+            d_normal = torch.empty_like(normal) if need[1] else None
+            d_rough = torch.empty_like(roughness) if need[3] else None
+            d_edge = torch.empty_like(edge_normal) if edge_normal is not None and need[4] else None
+            _lib.check_train(lib.iron_surface_reg_backward(C.byref(ctx.args), ctx.state.data_ptr(), _lib.ptr(g_eik), _lib.ptr(g_rr),
+                                                           _lib.ptr(d_eik), _lib.ptr(d_normal), _lib.ptr(d_rough), _lib.ptr(d_edge),
+                                                           _lib.stream_ptr(dev)))
+        return d_eik, d_normal, None, d_rough, d_edge, None, None
+
+
 def numeric_status(reset: bool = True, device=None) -> bool:
     """True when a backward pass since the last reset met an operand outside the range of its split-fp16 layer products
     (|x| > 65 504 or non-finite: the gradients of that pass are inf / NaN where fp32 autograd has numbers; include/iron_train.h).

@@ -5,6 +5,9 @@ Same public names and signatures as the reference module, so `from models.image_
 (render_surface.py:24, after iron_amd.install_as_models()) resolves here.  Neither scipy (the pyramid filter) nor kornia (the
 erosion of the SSIM mask) is needed: the filter taps are computed in closed form below, the erosion runs in the SSIM kernel.
 Inputs are float32 CUDA tensors; there is no CPU path.
+
+`surface_regularisers` is the rest of the stage-2 loss (render_surface.py:580-613, 639: the eikonal and roughness-range terms), which
+the reference writes inline; csrc/optim.hip (iron_surface_reg), differentiable through iron_amd.autograd.SurfaceRegFn.
 """
 from __future__ import annotations
 
@@ -150,3 +153,43 @@ def ssim_loss_fn(X, Y, mask=None, data_range=1.0, win_size=11, win_sigma=1.5, K=
             m = m.float()
         m = m.contiguous()
     return SSIMFn.apply(X, Y, m, (C.c_float * win_size)(*win), win_size, float(C1), float(C2))
+
+
+def surface_regularisers(eik_grad, normal, mask, specular_roughness, edge_pos_neg_normal=None, eik_weight=0.1, roughrange_weight=0.1,
+                         return_counts=False):
+    r"""The regularisers of the stage-2 step (render_surface.py:580-613, 639) in one forward and one backward launch chain:
+
+        eik_loss        = eik_weight * (sum_uniform + sum_masked + sum_edge of (|g| - 1)^2) / (M + n_mask + E)
+        roughrange_loss = roughrange_weight * mean(r - 0.5 over masked r > 0.5), or 0 when no masked value exceeds 0.5
+
+    eik_grad [M, 3]: SDFNetwork.gradient at the uniform points; normal [H, W, 3], mask [H, W] (bool / uint8) and
+    specular_roughness ([H, W] from the ggx render_fn, [H, W, 1] from the comp one): the frame; edge_pos_neg_normal [E, 3] or None.
+    With an all-false mask only the uniform set counts, as in the reference.  Returns two device scalars attached to eik_grad,
+    normal, specular_roughness and edge_pos_neg_normal; return_counts=True adds the device int64 [3] (M + n_mask + E, n_mask,
+    number of selected roughness values)."""
+    from .autograd import SurfaceRegFn
+    if eik_grad.dim() != 2 or eik_grad.shape[-1] != 3:
+        raise _lib.IronError("surface_regularisers: eik_grad must be [M, 3], got %s" % (tuple(eik_grad.shape),))
+    if normal.dim() < 2 or normal.shape[-1] != 3:
+        raise _lib.IronError("surface_regularisers: normal must be [..., 3], got %s" % (tuple(normal.shape),))
+    lead = tuple(normal.shape[:-1])
+    if tuple(mask.shape) != lead:
+        raise _lib.IronError("surface_regularisers: mask must be %s, got %s" % (lead, tuple(mask.shape)))
+    if tuple(specular_roughness.shape) not in (lead, lead + (1,)):
+        raise _lib.IronError("surface_regularisers: specular_roughness must be %s or %s, got %s"
+                             % (lead, lead + (1,), tuple(specular_roughness.shape)))
+    if edge_pos_neg_normal is not None and (edge_pos_neg_normal.dim() != 2 or edge_pos_neg_normal.shape[-1] != 3):
+        raise _lib.IronError("surface_regularisers: edge_pos_neg_normal must be [E, 3], got %s" % (tuple(edge_pos_neg_normal.shape),))
+    if not mask.is_cuda or mask.device != eik_grad.device or mask.dtype not in (torch.bool, torch.uint8):
+        raise _lib.IronError("surface_regularisers: mask must be a bool / uint8 CUDA tensor on %s" % eik_grad.device)
+    g = _lib.require_cuda_f32(eik_grad, "eik_grad")
+    n = _lib.require_cuda_f32(normal, "normal").reshape(-1, 3)
+    r = _lib.require_cuda_f32(specular_roughness, "specular_roughness").reshape(-1)
+    e = None if edge_pos_neg_normal is None else _lib.require_cuda_f32(edge_pos_neg_normal, "edge_pos_neg_normal")
+    for t, name in ((n, "normal"), (r, "specular_roughness"), (e, "edge_pos_neg_normal")):
+        if t is not None and t.device != g.device:
+            raise _lib.IronError("surface_regularisers: %s must be on %s" % (name, g.device))
+    m = mask.detach().contiguous().reshape(-1)
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    eik, rr, counts = SurfaceRegFn.apply(g, n, m, r, e, float(eik_weight), float(roughrange_weight))
+    return (eik, rr, counts) if return_counts else (eik, rr)
