@@ -995,6 +995,34 @@ int32_t iron_set_resolve_defer(int32_t on);
 int iron_trace_resolve_counts(const void* workspace, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Stage-1 batches and validation frames (models/dataset.py:271-300, 335-361; render_volume.py:696-729), csrc/volume.hip.
+ * kinv44 / pose44: DEVICE row-major 4x4 fp32 matrices of one view -- inverse(K) and inverse(W2C); their upper 3x3 and 3x4 are
+ * read.  One thread per ray, the reference's arithmetic in its order:
+ *     p = Kinv (x, y, 1);  v = p / |p|;  d = R v;  o = t;  a = sum d^2;  b = 2 sum o d;  mid = 0.5 (-b) / a;  near, far = mid -+ 1
+ *   iron_volume_rays       random mode.  image: uint8 [h, w, c >= 3]; mask: uint8 [h, w, cm >= 1] or NULL (the mask is then 1);
+ *                          px, py: DEVICE int64 [n] pixel columns and rows (drawn by the caller: no random numbers are made here).
+ *                          Writes data [n, 10] = rays_o, rays_d, rgb / 255, mask[..., 0] / 255, and near [n], far [n].  A pixel
+ *                          outside the picture is not read: its colour and mask are NaN.
+ *   iron_volume_rays_grid  grid mode.  tx [cols], ty [rows]: DEVICE fp32 pixel coordinates (torch.linspace(0, W - 1, W // l) and
+ *                          linspace(0, H - 1, H // l) as torch makes them); ray (row, col) looks through (tx[col], ty[row]).
+ *                          Writes rays_o, rays_d [rows, cols, 3]: the reference's transpose(0, 1).  No colour gather.
+ *   iron_volume_frame_u8   n rays of a frame of frame_rays rays, written at ray `offset` (offset + n <= frame_rays).  rgb_frame
+ *                          (uint8 [frame_rays, 3] or NULL) = trunc(clip(color * 256, 0, 255)), color [n, 3].  normal_frame (uint8
+ *                          [frame_rays, 3] or NULL) = trunc(clip(rot33 . N * 128 + 128, 0, 255)) with N = sum over the first m
+ *                          columns j of gradients[r, j, :] * weights[r, j] * inside_sphere[r, j], summed in order in fp32;
+ *                          gradients [n, m, 3], weights [n, mw >= m] (the outside samples' columns are skipped), inside_sphere
+ *                          [n, m] or NULL, rot33: DEVICE row-major 3x3 (the inverse of the pose's rotation).
+ * ------------------------------------------------------------------------------------------- */
+int iron_volume_rays(const uint8_t* image, int32_t h, int32_t w, int32_t c, const uint8_t* mask, int32_t cm, const float* kinv44,
+                     const float* pose44, const int64_t* px, const int64_t* py, int64_t n, float* data, float* near, float* far,
+                     void* stream);
+int iron_volume_rays_grid(const float* kinv44, const float* pose44, const float* tx, const float* ty, int32_t rows, int32_t cols,
+                          float* rays_o, float* rays_d, void* stream);
+int iron_volume_frame_u8(const float* color, const float* gradients, const float* weights, const float* inside_sphere,
+                         const float* rot33, int64_t n, int32_t m, int32_t mw, int64_t offset, int64_t frame_rays, uint8_t* rgb_frame,
+                         uint8_t* normal_frame, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the
  * caller's stream around each compute kernel.  Off by default.  iron_profile_read blocks on the
  * recorded events, adds their elapsed milliseconds / launch counts into the caller's arrays

@@ -269,6 +269,44 @@ int iron_surface_reg(const iron_surface_reg_args* a, float* eik_loss, float* rou
 int iron_surface_reg_backward(const iron_surface_reg_args* a, const double* state, const float* d_eik, const float* d_roughrange,
                               float* d_eik_grad, float* d_normal, float* d_roughness, float* d_edge_normal, void* stream);
 
+/* The loss of the stage-1 step (render_volume.py:458-496) and the statistics it logs (:507-510), csrc/volume_loss.hip.  Per ray
+ * i < b: color_fine [b,3]; true_rgb (rows of rgb_stride >= 3 floats) and the RAW mask (rows of mask_stride >= 1 floats; NULL is
+ * allowed when mask_weight <= 0) -- both may point into the [b,10] batch; weight_sum [b]; weight_max [b]; cdf_fine (first
+ * column, rows of cdf_stride floats); gradient_error: DEVICE scalar (the renderer's eikonal statistic).
+ *     m = raw > 0.5 when mask_weight > 0, else 1;  mask_sum = sum m + 1e-5
+ *     color_fine_loss = sum |(c - t) m| / mask_sum;  psnr = 20 log10(1 / sqrt(sum (c - t)^2 m / (3 mask_sum)))  (+inf at c == t)
+ *     mask_loss = mean over b of BCE(clip(weight_sum, 1e-3, 1 - 1e-3), m)  (torch's binary_cross_entropy)
+ *     loss = color_fine_loss + igr_weight gradient_error + mask_weight mask_loss
+ * `loss` is a DEVICE scalar; `record` (DEVICE fp32 [IRON_VL_RECORD]) holds the scalars at the IRON_VL_* indices; `state` (DEVICE
+ * double [4]) carries the backward's scales.  Per-ray values are fp32, formed as torch forms them; the sums are per-workgroup
+ * partials in `workspace`, added in a fixed order in fp64 by one final workgroup (no atomics: bitwise reproducible, and the cut
+ * into workgroups depends on b alone).  The backward reads the upstream gradient from the DEVICE scalar d_loss (NULL = 1) and
+ * WRITES every element of each non-NULL output:
+ *     d_color [b,3]      = sign((c - t) m) m / mask_sum * d_loss            (sign(0) = 0)
+ *     d_weight_sum [b]   = mask_weight / b * (-m / w + (1 - m) / (1 - w)) * d_loss where 1e-3 <= w <= 1 - 1e-3 (both fp32), else 0
+ *     d_gradient_error   = igr_weight * d_loss
+ * IRON_ERR_BAD_ARG: a null pointer, b < 1 or a stride too small; nothing is enqueued then. */
+enum {
+    IRON_VL_LOSS = 0, IRON_VL_COLOR = 1, IRON_VL_EIKONAL = 2, IRON_VL_MASK = 3, IRON_VL_PSNR = 4, IRON_VL_CDF = 5,
+    IRON_VL_WEIGHT_MAX = 6, IRON_VL_MASK_SUM = 7, IRON_VL_RECORD = 8
+};
+typedef struct iron_volume_loss_args {
+    const float* color_fine;
+    const float* true_rgb;
+    const float* mask;
+    const float* weight_sum;
+    const float* weight_max;
+    const float* cdf_fine;
+    const float* gradient_error;
+    int64_t b, rgb_stride, mask_stride, cdf_stride;
+    float igr_weight, mask_weight;
+} iron_volume_loss_args;
+size_t iron_volume_loss_workspace_bytes(int64_t b);
+int iron_volume_loss(const iron_volume_loss_args* a, float* loss, float* record, double* state, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int iron_volume_loss_backward(const iron_volume_loss_args* a, const double* state, const float* d_loss, float* d_color,
+                              float* d_weight_sum, float* d_gradient_error, void* stream);
+
 /* Diagnostics: last hipError_t seen by this library on the calling thread (iron_train_last_blas_status: kept for ABI
  * stability, always 0: the library links no BLAS). */
 int iron_train_last_hip_error(void);

@@ -266,6 +266,9 @@ SYMBOLS = {
     "iron_trace_stride_detail": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "iron_set_resolve_defer": (_I32, [_I32]),
     "iron_trace_resolve_counts": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "iron_volume_rays": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "iron_volume_rays_grid": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "iron_volume_frame_u8": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _P, _P, _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),
@@ -323,6 +326,15 @@ class iron_surface_reg_args(C.Structure):
                 ("eik_weight", C.c_float), ("roughrange_weight", C.c_float)]
 
 
+class iron_volume_loss_args(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("color_fine", "true_rgb", "mask", "weight_sum", "weight_max", "cdf_fine", "gradient_error")]
+                + [(k, C.c_int64) for k in ("b", "rgb_stride", "mask_stride", "cdf_stride")]
+                + [("igr_weight", C.c_float), ("mask_weight", C.c_float)])
+
+
+# the record of iron_volume_loss (include/iron_train.h: IRON_VL_*), in index order
+VOLUME_LOSS_RECORD = ("loss", "color_fine_loss", "eikonal_loss", "mask_loss", "psnr", "cdf", "weight_max", "mask_sum")
+
 IRON_ERR_BAD_ARG = -1
 IRON_ADAM_CHUNK = 2048        # include/iron_train.h
 IRON_ADAM_MAX_TENSORS = 80
@@ -334,6 +346,10 @@ TRAIN_SYMBOLS = {
     "iron_surface_reg": (C.c_int, [C.POINTER(iron_surface_reg_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
     "iron_surface_reg_backward": (C.c_int, [C.POINTER(iron_surface_reg_args)] + [C.c_void_p] * 8),
+    "iron_volume_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "iron_volume_loss": (C.c_int, [C.POINTER(iron_volume_loss_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "iron_volume_loss_backward": (C.c_int, [C.POINTER(iron_volume_loss_args)] + [C.c_void_p] * 6),
     "iron_train_gemm_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "iron_train_gemm": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _F, _P, _I32, _P, _SZ, _P]),
     "iron_sdf_backward_workspace_bytes": (_SZ, [C.POINTER(iron_sdf_train_desc), _I64]),

@@ -625,6 +625,51 @@ class SurfaceRegFn(torch.autograd.Function):
         return d_eik, d_normal, None, d_rough, d_edge, None, None
 
 
+class VolumeLossFn(torch.autograd.Function):
+    """(loss, record) = the stage-1 loss of render_volume.py:458-496 (include/iron_train.h: iron_volume_loss).  color_fine [B, 3],
+    true_rgb [B, >= 3 with a row stride], raw mask [B, >= 1 with a row stride] or None, weight_sum [B], weight_max [B], cdf_fine
+    [B, M], gradient_error: 0-d device tensor; record is the device fp32 [8] of _lib.VOLUME_LOSS_RECORD.  Gradients go to
+    color_fine, weight_sum and gradient_error."""
+
+    @staticmethod
+    def forward(ctx, color_fine, true_rgb, mask, weight_sum, weight_max, cdf_fine, gradient_error, igr_weight, mask_weight):
+        lib = _lib.load_train()
+        dev = color_fine.device
+        a = _lib.iron_volume_loss_args()
+        a.color_fine, a.true_rgb, a.mask, a.weight_sum = color_fine.data_ptr(), true_rgb.data_ptr(), _lib.ptr(mask), weight_sum.data_ptr()
+        a.weight_max, a.cdf_fine, a.gradient_error = weight_max.data_ptr(), cdf_fine.data_ptr(), gradient_error.data_ptr()
+        a.b, a.rgb_stride, a.cdf_stride = color_fine.shape[0], true_rgb.stride(0), cdf_fine.stride(0)
+        a.mask_stride = 1 if mask is None else mask.stride(0)
+        a.igr_weight, a.mask_weight = igr_weight, mask_weight
+        with torch.cuda.device(dev):
+            ws = _lib.workspace(lib.iron_volume_loss_workspace_bytes(a.b), dev, "volume_loss")
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            record = torch.empty(len(_lib.VOLUME_LOSS_RECORD), dtype=torch.float32, device=dev)
+            state = torch.empty(4, dtype=torch.float64, device=dev)
+            _lib.check_train(lib.iron_volume_loss(C.byref(a), loss.data_ptr(), record.data_ptr(), state.data_ptr(), ws.data_ptr(),
+                                                  ws.numel(), _lib.stream_ptr(dev)))
+        ctx.args, ctx.state = a, state
+        ctx.save_for_backward(color_fine, true_rgb, mask, weight_sum, weight_max, cdf_fine, gradient_error)   # keeps `a`'s buffers alive
+        ctx.mark_non_differentiable(record)
+        return loss, record
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _g_record):
+        color_fine, _, _, weight_sum, _, _, gradient_error = ctx.saved_tensors
+        lib = _lib.load_train()
+        dev = color_fine.device
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            g_loss = _lib.require_cuda_f32(g_loss, "upstream gradient").reshape(1)
+            d_color = torch.empty_like(color_fine) if need[0] else None
+            d_wsum = torch.empty_like(weight_sum) if need[3] else None
+            d_gerr = torch.empty_like(gradient_error) if need[6] else None
+            _lib.check_train(lib.iron_volume_loss_backward(C.byref(ctx.args), ctx.state.data_ptr(), g_loss.data_ptr(), _lib.ptr(d_color),
+                                                           _lib.ptr(d_wsum), _lib.ptr(d_gerr), _lib.stream_ptr(dev)))
+        return d_color, None, None, d_wsum, None, None, d_gerr, None, None
+
+
 def numeric_status(reset: bool = True, device=None) -> bool:
     """True when a backward pass since the last reset met an operand outside the range of its split-fp16 layer products
     (|x| > 65 504 or non-finite: the gradients of that pass are inf / NaN where fp32 autograd has numbers; include/iron_train.h).

@@ -19,8 +19,8 @@ LIB_TRAIN = os.path.join(CSRC, "libiron_train.so")  # backward passes (include/i
 OBJ_DIR = os.path.join(CSRC, "build")
 MANIFEST = os.path.join(OBJ_DIR, "manifest.json")  # which flag set every translation unit was compiled with (bench.py echoes it)
 
-SOURCES = ["pack.hip", "pack_h2.hip", "sdf_forward.hip", "h2_kernels.hip", "w16.hip", "pointwise.hip", "trace.hip", "trace_any.hip", "shade.hip", "getall_rev.hip", "envelope.hip", "nerf.hip", "neus.hip", "profile.hip", "pair_scan.hip", "mcubes.hip", "texbake.hip", "meshdist.hip", "meshrender.hip", "envlight.hip", "uvunwrap.hip", "imgmetrics.hip"]
-TRAIN_SOURCES = ["train.hip", "losses.hip", "optim.hip"]
+SOURCES = ["pack.hip", "pack_h2.hip", "sdf_forward.hip", "h2_kernels.hip", "w16.hip", "pointwise.hip", "trace.hip", "trace_any.hip", "shade.hip", "getall_rev.hip", "envelope.hip", "nerf.hip", "neus.hip", "profile.hip", "pair_scan.hip", "mcubes.hip", "texbake.hip", "meshdist.hip", "meshrender.hip", "envlight.hip", "uvunwrap.hip", "imgmetrics.hip", "volume.hip"]
+TRAIN_SOURCES = ["train.hip", "losses.hip", "optim.hip", "volume_loss.hip"]
 HEADERS = [os.path.join("..", "..", "include", "iron_train.h"), "gemm_h2.h", "lds_dma.h", "iron_common.h", "mlp_core.h", "mlp_h2.h", "mlp_h2_rev.h", "shade_args.h", "h2_setup.h", "pack_common.h", "ggx_core.h", "mc_table.h", "host_util.h", "pair_scan.h", "mesh_common.h", "bvh_common.h", "ray_core.h", "ray_walk.h", "asset_common.h", os.path.join("..", "..", "include", "iron_hip.h")]
 
 BASE_FLAGS = [
@@ -117,7 +117,8 @@ def build(force: bool = False, extra_flags=(), verbose: bool = True) -> str:
     if r.returncode != 0:
         raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
     # the training library: the backward passes (train.hip; layer products are the split-fp16 MFMA GEMM of gemm_h2.h, no BLAS
-    # library linked), the stage-2 image losses (losses.hip), the regularisers and the multi-tensor Adam (optim.hip)
+    # library linked), the stage-2 image losses (losses.hip), the regularisers and the multi-tensor Adam (optim.hip), the stage-1
+    # loss (volume_loss.hip)
     cmd = [hipcc] + BASE_FLAGS + extra_flags + ["-shared", "-o", LIB_TRAIN] + [os.path.join(CSRC, s) for s in TRAIN_SOURCES]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

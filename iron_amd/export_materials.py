@@ -124,6 +124,22 @@ def write_ply_points(path, points, colors_rgba):
         fp.write(rec.tobytes())
 
 
+def write_ply_mesh(path, vertices, triangles):
+    """Binary little-endian PLY triangle mesh: float x, y, z per vertex, `uchar 3` and three int vertex indices per face."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("write_ply_mesh: a face names a vertex outside 0 .. %d" % (len(v) - 1))
+    rec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", 3)])
+    rec["n"], rec["i"] = 3, f
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
+    with open(path, "wb") as fp:
+        fp.write(header.encode("ascii"))
+        fp.write(v.astype("<f4").tobytes())
+        fp.write(rec.tobytes())
+
+
 def _write_png(path, img8):
     from PIL import Image
     Image.fromarray(np.ascontiguousarray(img8)).save(path)

@@ -8,6 +8,9 @@ Inputs are float32 CUDA tensors; there is no CPU path.
 
 `surface_regularisers` is the rest of the stage-2 loss (render_surface.py:580-613, 639: the eikonal and roughness-range terms), which
 the reference writes inline; csrc/optim.hip (iron_surface_reg), differentiable through iron_amd.autograd.SurfaceRegFn.
+
+`volume_losses` is the loss of the stage-1 step (render_volume.py:458-496), which the reference writes inline as well;
+csrc/volume_loss.hip (iron_volume_loss), differentiable through iron_amd.autograd.VolumeLossFn.
 """
 from __future__ import annotations
 
@@ -193,3 +196,64 @@ def surface_regularisers(eik_grad, normal, mask, specular_roughness, edge_pos_ne
     m = m.view(torch.uint8) if m.dtype == torch.bool else m
     eik, rr, counts = SurfaceRegFn.apply(g, n, m, r, e, float(eik_weight), float(roughrange_weight))
     return (eik, rr, counts) if return_counts else (eik, rr)
+
+
+def volume_losses(color_fine, true_rgb, mask, weight_sum, weight_max, cdf_fine, gradient_error, igr_weight=0.1, mask_weight=0.0):
+    r"""The loss of the stage-1 step (render_volume.py:458-496) and the statistics it logs (:507-510) in one forward and one backward
+    launch chain (csrc/volume_loss.hip):
+
+        mask  = (raw mask > 0.5) when mask_weight > 0, else 1;   mask_sum = sum mask + 1e-5
+        color_fine_loss = sum |(color_fine - true_rgb) mask| / mask_sum
+        mask_loss       = binary_cross_entropy(weight_sum.clip(1e-3, 1 - 1e-3), mask)
+        loss            = color_fine_loss + igr_weight * gradient_error + mask_weight * mask_loss
+
+    color_fine [B, 3]; true_rgb [B, 3] and the raw mask [B, 1] (or [B]; None with mask_weight = 0) may be slices of the [B, 10] batch
+    (only their last dimension must be dense); weight_sum and weight_max [B, 1] or [B]; cdf_fine [B, M] (its first column is
+    used); gradient_error: the renderer's 0-d eikonal statistic.  Returns a dictionary of 0-d device tensors: "loss" (the only one
+    attached to the graph: gradients go to color_fine, weight_sum and gradient_error), "color_fine_loss", "eikonal_loss",
+    "mask_loss", "psnr" (+inf when prediction equals target), "cdf", "weight_max", "mask_sum".  Nothing waits for the host."""
+    from .autograd import VolumeLossFn
+    if color_fine.dim() != 2 or color_fine.shape[1] != 3 or color_fine.shape[0] < 1:
+        raise _lib.IronError("volume_losses: color_fine must be [B >= 1, 3], got %s" % (tuple(color_fine.shape),))
+    b = color_fine.shape[0]
+    c = _lib.require_cuda_f32(color_fine, "color_fine")
+    dev = c.device
+
+    def rows(t, name, width):
+        """[B, >= width] float32 on `dev` whose rows are dense (a slice of a wider batch stays where it is)."""
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != torch.float32:
+            raise _lib.IronError("volume_losses: %s must be a float32 CUDA tensor on %s" % (name, dev))
+        t = t.detach()
+        if t.dim() == 1:
+            t = t.unsqueeze(-1)
+        if t.dim() != 2 or t.shape[0] != b or t.shape[1] < width:
+            raise _lib.IronError("volume_losses: %s must be [%d, >= %d], got %s" % (name, b, width, tuple(t.shape)))
+        if t.stride(1) != 1 or (b > 1 and t.stride(0) < t.shape[1]):
+            t = t.contiguous()
+        return t
+
+    def column(t, name):
+        if not torch.is_tensor(t) or t.device != dev or t.numel() != b:
+            raise _lib.IronError("volume_losses: %s must hold %d values on %s" % (name, b, dev))
+        return _lib.require_cuda_f32(t, name).reshape(-1)
+
+    if true_rgb.dim() != 2 or true_rgb.shape[1] != 3:
+        raise _lib.IronError("volume_losses: true_rgb must be [B, 3], got %s" % (tuple(true_rgb.shape),))
+    t = rows(true_rgb, "true_rgb", 3)
+    if mask is None:
+        if mask_weight > 0:
+            raise _lib.IronError("volume_losses: mask_weight > 0 needs a mask")
+        m = None
+    else:
+        if mask.numel() != b:
+            raise _lib.IronError("volume_losses: mask must be [B, 1], got %s" % (tuple(mask.shape),))
+        m = rows(mask, "mask", 1)
+    cdf = rows(cdf_fine, "cdf_fine", 1)
+    if not torch.is_tensor(gradient_error) or gradient_error.numel() != 1 or gradient_error.device != dev:
+        raise _lib.IronError("volume_losses: gradient_error must be a device scalar on %s" % dev)
+    ge = _lib.require_cuda_f32(gradient_error, "gradient_error").reshape(())
+    loss, record = VolumeLossFn.apply(c, t, m, column(weight_sum, "weight_sum"), column(weight_max.detach(), "weight_max"), cdf, ge,
+                                      float(igr_weight), float(mask_weight))
+    out = {k: record[i] for i, k in enumerate(_lib.VOLUME_LOSS_RECORD)}
+    out["loss"] = loss
+    return out

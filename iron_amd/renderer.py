@@ -276,11 +276,13 @@ class NeuSRenderer:
                 params += list(net.parameters())
         return any_requires_grad(*params)
 
-    def render(self, rays_o, rays_d, near, far, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0) -> Dict[str, torch.Tensor]:
+    def render(self, rays_o, rays_d, near, far, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0,
+               generator=None) -> Dict[str, torch.Tensor]:
         """renderer.py:346-453.  The sample placement (linspace, optional stratified jitter, the four up-sampling rounds, merges)
         runs without grad exactly as in the reference (:387); under grad mode with trainable networks the two render cores are
         attached to the parameters -- get_all / colour net / NeRF / compositing are the differentiable operators of
-        iron_amd.autograd -- so render_volume.py's loss.backward() works; otherwise plain tensors come back."""
+        iron_amd.autograd -- so render_volume.py's loss.backward() works; otherwise plain tensors come back.  `generator`: the
+        device generator the sample jitter is drawn from (None: the device's default one, as before)."""
         from .autograd import NeusCompositeFn
         training = self._trainable()
         perturb = self.perturb if perturb_overwrite < 0 else perturb_overwrite
@@ -299,14 +301,14 @@ class NeuSRenderer:
                 _lib.check(lib.iron_neus_linspace(near.data_ptr(), far.data_ptr(), lin.data_ptr(), batch, self.n_samples, z_vals.data_ptr(), st))
                 z_out = None
                 if perturb > 0:  # :369-378 (random numbers come from torch's generator of this device)
-                    z_vals = z_vals + (torch.rand([batch, 1], device=dev) - 0.5) * 2.0 / self.n_samples
+                    z_vals = z_vals + (torch.rand([batch, 1], device=dev, generator=generator) - 0.5) * 2.0 / self.n_samples
                 if self.n_outside > 0:
                     z_out = torch.empty((batch, self.n_outside), dtype=torch.float32, device=dev)
                     if perturb > 0:
                         zo = torch.linspace(1e-3, 1.0 - 1.0 / (self.n_outside + 1.0), self.n_outside, device=dev)
                         mids = 0.5 * (zo[1:] + zo[:-1])
                         upper, lower = torch.cat([mids, zo[-1:]], -1), torch.cat([zo[:1], mids], -1)
-                        zo = lower[None, :] + (upper - lower)[None, :] * torch.rand([batch, self.n_outside], device=dev)
+                        zo = lower[None, :] + (upper - lower)[None, :] * torch.rand([batch, self.n_outside], device=dev, generator=generator)
                         z_out = far[:, None] / torch.flip(zo, dims=[-1]) + 1.0 / self.n_samples
                     else:
                         # far / flip(linspace(1e-3, 1 - 1/(n_outside+1))) + 1/n_samples: one ascending row per ray (:361-381)
