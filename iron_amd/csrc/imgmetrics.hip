@@ -1,8 +1,8 @@
 // Image evaluation metrics (evaluation/eval_image_folder.py: PSNR, skimage's uniform-window SSIM, LPIPS-AlexNet).
 // Conventions: include/iron_hip.h, iron_img_* / iron_lpips_* block.
 //
-// Every reduction here is a fixed-order sum: a kernel leaves one fp64 partial per workgroup (or per wave) in the caller's
-// workspace and k_reduce_f64 adds them in index order -- no float atomics, so every output is bitwise reproducible.
+// Every reduction here is a fixed-order sum (fixed_sum.h): a kernel leaves one fp64 partial per workgroup (or per wave) in the
+// caller's workspace and k_reduce_f64 / k_lpips_final add them -- no float atomics, so every output is bitwise reproducible.
 //
 //   iron_img_sqerr   k_sqerr<T>      uint8: integer differences, exact uint64 sums; fp32: difference and square in fp32, fp64 sums
 //   iron_img_ssim    k_ssim<T, Acc>  one workgroup = a 16 x 32 tile of S of one channel: the (16+10) x (32+10) input tile in LDS, the
@@ -17,9 +17,13 @@
 //                    k_lpips_tap     one wave per pixel: both channel norms, the squared difference of the unit vectors, the lin
 //                                    dot product (fp64), per-wave spatial sums
 //                    k_lpips_final   the five layer means added in order; NaN and a raised flag word if an operand left fp16 range
-#include "iron_common.h"
+#include "fixed_sum.h"
+#include "host_util.h"
 
 namespace iron {
+
+using fixed_sum::block_sum;
+using fixed_sum::slot_sum;
 
 typedef _Float16 im_half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 im_half2 __attribute__((ext_vector_type(2)));
@@ -31,26 +35,10 @@ constexpr int kImSqerrBlocks = 1024;   // partials of iron_img_sqerr
 constexpr int kImTapBlocks = 256;      // k_lpips_tap: 4 waves each, one partial per wave
 constexpr int kImTapPartials = kImTapBlocks * 4;
 
-// fixed-order block sum of one fp64 value per thread (256 threads); the result is valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = kImBlock / 2; off > 0; off >>= 1) {
-        if (t < off) s[t] += s[t + off];
-        __syncthreads();
-    }
-    return s[0];
-}
-
-// out[g] = scale * (sum of partials[g * n .. g * n + n) in a fixed order): thread t adds elements t, t + 256, ..., then the tree
+// out[g] = scale * (the fixed-order sum of partials[g * n .. g * n + n))
 __global__ __launch_bounds__(kImBlock) void k_reduce_f64(const double* __restrict__ partials, int n, double scale, double* __restrict__ out) {
     __shared__ double s[kImBlock];
-    const double* p = partials + (size_t)blockIdx.x * n;
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += kImBlock) a += p[i];
-    const double r = block_sum_f64(a, s);
+    const double r = slot_sum<kImBlock>(partials + (size_t)blockIdx.x * n, n, 1, s);
     if (threadIdx.x == 0) out[blockIdx.x] = r * scale;
 }
 
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(kImBlock) void k_sqerr(const T* __restrict__ a, con
             acc += (double)(d * d);  // the square rounded to fp32 as numpy's (pred - trgt) ** 2 on float32 arrays
         }
     }
-    const double r = block_sum_f64(acc, s);
+    const double r = block_sum<kImBlock>(acc, s);
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
@@ -144,7 +132,7 @@ __global__ __launch_bounds__(kImBlock) void k_ssim(const T* __restrict__ x, cons
             if (smap) smap[((size_t)ch * OH + oy) * OW + ox] = S;
         }
     }
-    const double rsum = block_sum_f64(local, red);
+    const double rsum = block_sum<kImBlock>(local, red);
     if (tid == 0) partials[(size_t)ch * gridDim.x * gridDim.y + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = rsum;
 }
 
@@ -402,13 +390,7 @@ __global__ __launch_bounds__(kImBlock) void k_lpips_final(const double* __restri
                                                          double* __restrict__ out) {
     __shared__ double s[kImBlock];
     double total = 0.0;
-    for (int l = 0; l < 5; ++l) {
-        const double* p = partials + (size_t)l * kImTapPartials;
-        double v = 0.0;
-        for (int i = threadIdx.x; i < kImTapPartials; i += kImBlock) v += p[i];
-        total += block_sum_f64(v, s) * a.inv_hw[l];
-        __syncthreads();
-    }
+    for (int l = 0; l < 5; ++l) total += slot_sum<kImBlock>(partials + (size_t)l * kImTapPartials, kImTapPartials, 1, s) * a.inv_hw[l];
     if (threadIdx.x == 0) {
         const bool bad = *flag != 0;
         out[0] = bad ? __longlong_as_double(0x7ff8000000000000LL) : total;
@@ -418,8 +400,6 @@ __global__ __launch_bounds__(kImBlock) void k_lpips_final(const double* __restri
 
 // ---- host side ----
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline int grid_for(int64_t n) { return (int)((n + kImBlock - 1) / kImBlock); }
 constexpr int kImMaxSide = 16384;
 
 static int launch_conv(const float* in, int B, int H, int W, int Cin, const float* weight, const float* bias, int Cout, int ks, int stride,
@@ -450,7 +430,7 @@ static int launch_pool(const float* in, int B, int H, int W, int C, float* out, 
     const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
     const int64_t total = (int64_t)B * Ho * Wo * C;
     if (total >= (1LL << 40)) return IRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_maxpool3s2, dim3(grid_for(total)), dim3(kImBlock), 0, st, in, H, W, C, Ho, Wo, total, out);
+    hipLaunchKernelGGL(k_maxpool3s2, dim3(blocks_for(total, kImBlock)), dim3(kImBlock), 0, st, in, H, W, C, Ho, Wo, total, out);
     IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
 }
@@ -465,8 +445,8 @@ static int launch_tap(const float* feat, int H, int W, int C, const float* lin, 
 static int launch_prepare(const void* pred, const void* trgt, int H, int W, int is_f32, float* out, hipStream_t st) {
     if (!pred || !trgt || !out || H <= 0 || W <= 0 || H > kImMaxSide || W > kImMaxSide) return IRON_ERR_BAD_ARG;
     const int64_t n = (int64_t)H * W * 3;
-    if (is_f32) hipLaunchKernelGGL(k_lpips_prepare<float>, dim3(grid_for(2 * n)), dim3(kImBlock), 0, st, (const float*)pred, (const float*)trgt, n, out);
-    else hipLaunchKernelGGL(k_lpips_prepare<uint8_t>, dim3(grid_for(2 * n)), dim3(kImBlock), 0, st, (const uint8_t*)pred, (const uint8_t*)trgt, n, out);
+    if (is_f32) hipLaunchKernelGGL(k_lpips_prepare<float>, dim3(blocks_for(2 * n, kImBlock)), dim3(kImBlock), 0, st, (const float*)pred, (const float*)trgt, n, out);
+    else hipLaunchKernelGGL(k_lpips_prepare<uint8_t>, dim3(blocks_for(2 * n, kImBlock)), dim3(kImBlock), 0, st, (const uint8_t*)pred, (const uint8_t*)trgt, n, out);
     IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
 }
@@ -487,7 +467,7 @@ static LpLayout lp_layout(int H, int W) {
     if (H <= 0 || W <= 0 || H > kImMaxSide || W > kImMaxSide) return L;
     size_t off = 0;
     L.in_off = off;
-    off += up256((size_t)2 * H * W * 3 * 4);
+    off += align256((size_t)2 * H * W * 3 * 4);
     int h = H, w = W, np = 0;
     for (int l = 0; l < 5; ++l) {
         const LpLayer& y = kLpLayers[l];
@@ -496,19 +476,19 @@ static LpLayout lp_layout(int H, int W) {
         w = (w + 2 * y.pad - y.ks) / y.stride + 1;
         L.th[l] = h; L.tw[l] = w;
         L.tap_off[l] = off;
-        off += up256((size_t)2 * h * w * y.cout * 4);
+        off += align256((size_t)2 * h * w * y.cout * 4);
         if (y.pool) {
             if (h < 3 || w < 3) return L;
             h = (h - 3) / 2 + 1;
             w = (w - 3) / 2 + 1;
             L.ph[np] = h; L.pw[np] = w;
             L.pool_off[np] = off;
-            off += up256((size_t)2 * h * w * y.cout * 4);
+            off += align256((size_t)2 * h * w * y.cout * 4);
             ++np;
         }
     }
     L.part_off = off;
-    off += up256((size_t)5 * kImTapPartials * 8);
+    off += align256((size_t)5 * kImTapPartials * 8);
     L.flag_off = off;
     off += 256;
     L.bytes = off;

@@ -4,8 +4,8 @@
 //
 // Conventions: images are [B, C, H, W] fp32 contiguous, processed as B*C independent planes (the pyramid filter is diagonal in
 // the channels).  Every reduction goes through per-workgroup partials written to fixed slots and one single-workgroup reduce
-// in a fixed order, in fp64; there are no atomics, so the loss and both gradients are bitwise reproducible.  The upstream
-// gradient is read on the device; nothing here synchronises the host.
+// in the fixed order of fixed_sum.h, in fp64; there are no atomics, so the loss and both gradients are bitwise reproducible.
+// The upstream gradient is read on the device; nothing here synchronises the host.
 //
 // Pyramid L2 (PyramidL2Loss.forward): d0 = X - Y, d_{k+1} = avgpool2(conv7x7(d_k)) (zero padding 3, floor pooling), loss =
 // sum_k |d_k|^2 / ((h/2^k)(w/2^k)), k = 0..4.
@@ -27,28 +27,15 @@
 //   k_ssim_reduce   one workgroup: N = |E| (or B*H'*W'), loss = 1 - (sum + band) / N
 //   k_ssim_adjoint  dX = G^T(dmu1) + 2X G^T(dsig) + Y G^T(dm12), dY the same with X, Y swapped; G^T is the "full" correlation
 //   k_blur_valid    gaussian_filter(): the valid separable blur alone (inference)
-#include <hip/hip_runtime.h>
+#include "fixed_sum.h"
+#include "train_common.h"
 
-#include "../../include/iron_train.h"
-
-namespace iron_train {
-extern thread_local int g_hip_error;
-}
+using namespace iron_train;
+using fixed_sum::block_sum;
+using fixed_sum::slot_sum;
 
 namespace {
 
-using iron_train::g_hip_error;
-
-#define LS_HIP(expr)                   \
-    do {                               \
-        hipError_t _e = (expr);        \
-        if (_e != hipSuccess) {        \
-            g_hip_error = (int)_e;     \
-            return IRON_ERR_HIP;       \
-        }                              \
-    } while (0)
-
-constexpr int kThreads = 256;
 constexpr int kLevels = 5;
 constexpr int kPyrTile = 32;              // level-k pixels per tile side
 constexpr int kPyrSpan = kPyrTile + 6;    // with the 3-px halo
@@ -62,21 +49,6 @@ struct Taps49 {
 struct Win {
     float w[kMaxWin];
 };
-
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
-
-// fixed-order block sum of one double per thread (kThreads threads); the result is valid in thread 0
-__device__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x + threadIdx.y * blockDim.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // ================================================= pyramid L2 =================================================================
 
@@ -109,8 +81,8 @@ PyrLayout pyr_layout(int64_t n, int h, int w) {
         off += align256(sizeof(float) * (size_t)n * L.h[k] * L.w[k]);
     }
     for (int k = 0; k < 4; ++k) {
-        L.nbx[k] = cdiv(L.w[k], kPyrTile);
-        L.nby[k] = cdiv(L.h[k], kPyrTile);
+        L.nbx[k] = cdiv64(L.w[k], kPyrTile);
+        L.nby[k] = cdiv64(L.h[k], kPyrTile);
         L.part_off[k] = off;
         off += align256(sizeof(double) * 2 * (size_t)L.nbx[k] * L.nby[k] * n);
     }
@@ -161,9 +133,8 @@ __global__ __launch_bounds__(kThreads) void k_pyr_down(const float* __restrict__
         out_sq = (double)v * v;
     }
     const size_t slot = ((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    const double a = block_sum(in_sq, red);
-    __syncthreads();
-    const double b = block_sum(out_sq, red);
+    const double a = block_sum<kThreads>(in_sq, red);
+    const double b = block_sum<kThreads>(out_sq, red);
     if (t == 0) {
         part[2 * slot] = a;
         part[2 * slot + 1] = b;
@@ -181,11 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_pyr_reduce(PyrSums P, float* __res
     double total = 0.0;
     for (int k = 0; k < kLevels; ++k) {
         const int launch = k < 4 ? k : 3, comp = k < 4 ? 0 : 1;
-        double v = 0.0;
-        for (int i = threadIdx.x; i < P.count[launch]; i += kThreads) v += P.part[launch][2 * i + comp];
-        const double sk = block_sum(v, red);
-        __syncthreads();
-        total += sk * P.inv[k];
+        total += slot_sum<kThreads>(P.part[launch] + comp, P.count[launch], 2, red) * P.inv[k];
     }
     if (threadIdx.x == 0) loss[0] = (float)total;
 }
@@ -250,10 +217,10 @@ struct SsimLayout {
 SsimLayout ssim_layout(const SsimGeom& g) {
     SsimLayout L{};
     size_t off = 0;
-    L.ebx = cdiv(g.w, kErodeTile);
-    L.eby = cdiv(g.h, kErodeTile);
-    L.sbx = cdiv(g.wv, kTx);
-    L.sby = cdiv(g.hv, kTy);
+    L.ebx = cdiv64(g.w, kErodeTile);
+    L.eby = cdiv64(g.h, kErodeTile);
+    L.sbx = cdiv64(g.wv, kTx);
+    L.sby = cdiv64(g.hv, kTy);
     L.stats_off = off;
     off += 256;
     L.e_off = off;
@@ -332,9 +299,8 @@ __global__ __launch_bounds__(kThreads) void k_erode(const void* __restrict__ mas
         }
     }
     const size_t slot = ((size_t)img * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    const double a = block_sum(n_all, red);
-    __syncthreads();
-    const double bsum = block_sum(n_band, red);
+    const double a = block_sum<kThreads>(n_all, red);
+    const double bsum = block_sum<kThreads>(n_band, red);
     if (t == 0) {
         part[2 * slot] = a;
         part[2 * slot + 1] = bsum;
@@ -463,7 +429,7 @@ __global__ __launch_bounds__(kThreads) void k_ssim_tile(SsimGeom g, Win wy, Win 
             const bool keep = !a.e || a.e[(size_t)img * hw + (size_t)(oy + g.r) * g.w + (ox + g.r)];
             if (keep) v += acc[k] / g.c;
         }
-        const double s = block_sum(v, red);
+        const double s = block_sum<kThreads>(v, red);
         if (t == 0) a.part[((size_t)img * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -471,19 +437,11 @@ __global__ __launch_bounds__(kThreads) void k_ssim_tile(SsimGeom g, Win wy, Win 
 __global__ __launch_bounds__(kThreads) void k_ssim_reduce(const double* __restrict__ spart, int ns, const double* __restrict__ epart,
                                                          int ne, double n_unmasked, double* __restrict__ stats, float* __restrict__ loss) {
     __shared__ double red[kThreads];
-    double v = 0.0;
-    for (int i = threadIdx.x; i < ns; i += kThreads) v += spart[i];
-    const double s = block_sum(v, red);
-    __syncthreads();
+    const double s = slot_sum<kThreads>(spart, ns, 1, red);
     double n = n_unmasked, band = 0.0;
     if (epart) {
-        v = 0.0;
-        for (int i = threadIdx.x; i < ne; i += kThreads) v += epart[2 * i];
-        n = block_sum(v, red);
-        __syncthreads();
-        v = 0.0;
-        for (int i = threadIdx.x; i < ne; i += kThreads) v += epart[2 * i + 1];
-        band = block_sum(v, red);
+        n = slot_sum<kThreads>(epart, ne, 2, red);
+        band = slot_sum<kThreads>(epart + 1, ne, 2, red);
     }
     if (threadIdx.x == 0) {
         stats[0] = n;
@@ -630,7 +588,7 @@ extern "C" int iron_pyramid_l2_forward(const float* x, const float* y, int64_t n
         P.inv[k] = 1.0 / ((h / s) * (w / s));  // the reference's h / 2.0 ... divisors, not the floor-pooled sizes
     }
     hipLaunchKernelGGL(k_pyr_reduce, dim3(1), dim3(kThreads), 0, st, P, loss);
-    LS_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -657,7 +615,7 @@ extern "C" int iron_pyramid_l2_backward(const float* x, const float* y, int64_t 
         hipLaunchKernelGGL(k_pyr_up, dim3(L.nbx[k], L.nby[k], (unsigned)n_planes), dim3(16, 16), 0, st, src, x, y, L.h[k], L.w[k], gnext,
                            k == 3 ? 1 : 0, L.h[k + 1], L.w[k + 1], T, coef[k], coef[k + 1], d_loss, gk, k == 0 ? dy : nullptr);
     }
-    LS_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -706,7 +664,7 @@ extern "C" int iron_ssim_forward(const float* x, const float* y, int32_t b, int3
     hipLaunchKernelGGL(k_ssim_reduce, dim3(1), dim3(kThreads), 0, st, (const double*)(ws + L.spart_off), L.sbx * L.sby * b,
                        mask ? (const double*)(ws + L.epart_off) : nullptr, L.ebx * L.eby * b, (double)b * g.hv * g.wv,
                        (double*)(ws + L.stats_off), loss);
-    LS_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -734,9 +692,9 @@ extern "C" int iron_ssim_backward(const float* x, const float* y, int32_t b, int
     a.d_loss = d_loss;
     a.adj = (float*)scratch;
     hipLaunchKernelGGL(k_ssim_tile<1>, dim3(L.sbx, L.sby, b), dim3(kThreads), ssim_tile_lds(g), st, g, wy, wx, a);
-    hipLaunchKernelGGL(k_ssim_adjoint, dim3(cdiv(w, kTx), cdiv(h, kTy), b * c), dim3(kThreads), ssim_adj_lds(g), st, g, wy, wx, x, y,
+    hipLaunchKernelGGL(k_ssim_adjoint, dim3(cdiv64(w, kTx), cdiv64(h, kTy), b * c), dim3(kThreads), ssim_adj_lds(g), st, g, wy, wx, x, y,
                        (const float*)scratch, dx, dy);
-    LS_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -751,8 +709,8 @@ extern "C" int iron_gaussian_filter(const float* x, int64_t n_planes, int32_t h,
     ssim_windows(win, win_size, g, &wy, &wx);
     const size_t ry = kTy + g.wy - 1, rx = kTx + g.wx - 1;
     const size_t lds = align256(ry * rx * sizeof(float)) + ry * kTx * sizeof(double);
-    hipLaunchKernelGGL(k_blur_valid, dim3(cdiv(g.wv, kTx), cdiv(g.hv, kTy), (unsigned)n_planes), dim3(kThreads), lds, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_blur_valid, dim3(cdiv64(g.wv, kTx), cdiv64(g.hv, kTy), (unsigned)n_planes), dim3(kThreads), lds, (hipStream_t)stream,
                        g, wy, wx, x, out);
-    LS_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }

@@ -15,35 +15,18 @@
 //
 // iron_surface_reg: the eikonal and roughness-range terms of render_surface.py:580-613, 639 over three sets of 3-vectors (the
 // uniform eikonal gradients, the frame's normals under the mask, the edge normals) and the masked roughness map.
-//   k_reg_partial   one workgroup per kRegSpan items of the concatenated index space: six fixed-order block sums -> one slot
-//   k_reg_final     one workgroup: the slots in a fixed order, then the two losses, the counts and the backward's scales
+//   k_reg_partial   one workgroup per kRegSpan items of the concatenated index space: six block sums -> one slot (fixed_sum.h)
+//   k_reg_final     one workgroup: the slots' totals (fixed_sum.h), then the two losses, the counts and the backward's scales
 //   k_reg_backward  one thread per item: 2 (|g| - 1) g / |g| w / cnt (0 for a zero vector), w / n on the selected roughness
 // No atomics anywhere: forward and backward are bitwise reproducible.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
 
-#include "../../include/iron_train.h"
+#include "fixed_sum.h"
+#include "train_common.h"
 
-namespace iron_train {
-extern thread_local int g_hip_error;
-}
+using namespace iron_train;
 
 namespace {
-
-using iron_train::g_hip_error;
-
-#define OP_HIP(expr)                   \
-    do {                               \
-        hipError_t _e = (expr);        \
-        if (_e != hipSuccess) {        \
-            g_hip_error = (int)_e;     \
-            return IRON_ERR_HIP;       \
-        }                              \
-    } while (0)
-
-constexpr int kThreads = 256;
 
 // ================================================= multi-tensor Adam ==========================================================
 
@@ -132,21 +115,6 @@ constexpr int kRegPerThread = 8;
 constexpr int kRegSpan = kThreads * kRegPerThread;   // items of the concatenated index space per workgroup
 constexpr int kRegVals = 6;                          // sum_uniform, sum_masked, sum_edge, sum_rough, n_mask, n_sel
 
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// fixed-order block sum of one double per thread; the result is valid in thread 0
-__device__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __device__ __forceinline__ float vec_norm(const float* __restrict__ g) {
     return sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
 }
@@ -179,10 +147,7 @@ __global__ __launch_bounds__(kThreads) void k_reg_partial(iron_surface_reg_args 
             acc[2] += (double)(d * d);
         }
     }
-    for (int j = 0; j < kRegVals; ++j) {
-        const double s = block_sum(acc[j], red);
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * kRegVals + j] = s;
-    }
+    fixed_sum::store_slot<kThreads>(acc, part, red);
 }
 
 // state: [0] eik_weight / cnt, [1] roughrange_weight / n_sel (0: none selected), [2] 1 when the masked and edge sets count
@@ -191,11 +156,7 @@ __global__ __launch_bounds__(kThreads) void k_reg_final(iron_surface_reg_args a,
                                                        int64_t* __restrict__ counts, double* __restrict__ state) {
     __shared__ double red[kThreads];
     double tot[kRegVals];
-    for (int j = 0; j < kRegVals; ++j) {
-        double s = 0.0;
-        for (int64_t b = threadIdx.x; b < nb; b += kThreads) s += part[(size_t)b * kRegVals + j];
-        tot[j] = block_sum(s, red);
-    }
+    fixed_sum::load_slots<kThreads>(part, nb, tot, red);
     if (threadIdx.x != 0) return;
     const int64_t n_mask = (int64_t)tot[4], n_sel = (int64_t)tot[5];
     const bool on = n_mask > 0;   // render_surface.py:591: the masked and the edge set enter only under mask.any()
@@ -279,8 +240,7 @@ int iron_adam_multi(const iron_adam_tensor* tensors, int64_t n_tensors, double b
     uint32_t chunks = 0;
     auto flush = [&]() -> int {
         if (L.n == 0) return IRON_OK;
-        hipLaunchKernelGGL(k_adam, dim3(chunks), dim3(kThreads), 0, (hipStream_t)stream, L);
-        OP_HIP(hipGetLastError());
+        IRON_TRAIN_LAUNCH(k_adam, chunks, kThreads, (hipStream_t)stream, L);
         L.n = 0;
         chunks = 0;
         return IRON_OK;
@@ -313,24 +273,18 @@ int iron_adam_multi(const iron_adam_tensor* tensors, int64_t n_tensors, double b
 
 size_t iron_surface_reg_workspace_bytes(int64_t m, int64_t n_pix, int64_t e) {
     if (m < 0 || n_pix < 0 || e < 0) return 0;
-    const int64_t nb = cdiv64(m + n_pix + e, kRegSpan);
-    return sizeof(double) * kRegVals * (size_t)(nb > 0 ? nb : 1);
+    return slot_bytes(slot_count(m + n_pix + e, kRegSpan), kRegVals);
 }
 
 int iron_surface_reg(const iron_surface_reg_args* a, float* eik_loss, float* roughrange_loss, int64_t* counts, double* state,
                      void* workspace, size_t workspace_bytes, void* stream) {
     if (!reg_args_ok(a) || !eik_loss || !roughrange_loss || !counts || !state || !workspace) return IRON_ERR_BAD_ARG;
     if (workspace_bytes < iron_surface_reg_workspace_bytes(a->m, a->n_pix, a->e)) return IRON_ERR_WORKSPACE;
-    const int64_t nb = cdiv64(a->m + a->n_pix + a->e, kRegSpan);
-    if (nb > 0x7fffffff) return IRON_ERR_UNSUPPORTED;
+    const int64_t nb = slot_count(a->m + a->n_pix + a->e, kRegSpan);
+    if (!grid_ok(nb)) return IRON_ERR_UNSUPPORTED;
     double* part = (double*)workspace;
-    if (nb > 0) {
-        hipLaunchKernelGGL(k_reg_partial, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, *a, part);
-        OP_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_reg_final, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, *a, part, nb, eik_loss, roughrange_loss, counts,
-                       state);
-    OP_HIP(hipGetLastError());
+    if (nb > 0) IRON_TRAIN_LAUNCH(k_reg_partial, (unsigned)nb, kThreads, (hipStream_t)stream, *a, part);
+    IRON_TRAIN_LAUNCH(k_reg_final, 1, kThreads, (hipStream_t)stream, *a, part, nb, eik_loss, roughrange_loss, counts, state);
     return IRON_OK;
 }
 
@@ -338,11 +292,10 @@ int iron_surface_reg_backward(const iron_surface_reg_args* a, const double* stat
                               float* d_eik_grad, float* d_normal, float* d_roughness, float* d_edge_normal, void* stream) {
     if (!reg_args_ok(a) || !state) return IRON_ERR_BAD_ARG;
     const int64_t nb = cdiv64(a->m + a->n_pix + a->e, kThreads);
-    if (nb > 0x7fffffff) return IRON_ERR_UNSUPPORTED;
+    if (!grid_ok(nb)) return IRON_ERR_UNSUPPORTED;
     if (nb == 0) return IRON_OK;
-    hipLaunchKernelGGL(k_reg_backward, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, *a, state, d_eik, d_roughrange,
-                       d_eik_grad, d_normal, d_roughness, d_edge_normal);
-    OP_HIP(hipGetLastError());
+    IRON_TRAIN_LAUNCH(k_reg_backward, (unsigned)nb, kThreads, (hipStream_t)stream, *a, state, d_eik, d_roughrange, d_eik_grad, d_normal,
+                      d_roughness, d_edge_normal);
     return IRON_OK;
 }
 

@@ -3,7 +3,7 @@
 //
 // Counts (iron_bake_count), one thread per face, 256-face blocks:
 //   k_bake_area     fp32 area |cross(v0 - v2, v1 - v2)| -> area[f]; fp64 partial sums per block -> part[b]
-//   k_bake_sum      one block sums the partials in a fixed order -> the normaliser (rounded to fp32 like the reference's sum)
+//   k_bake_sum      one block sums the partials (fixed_sum.h) -> the normaliser (rounded to fp32 like the reference's sum)
 //   k_bake_count    cnt[f] = ceil(n * (area / sum)) in fp32; pair[f] = (cnt, cnt > 0)
 //   pair_scan       exclusive scan of the pairs (pair_scan.h); the top level holds the totals: sum(cnt) and the number of faces
 //                   with a sample
@@ -17,6 +17,7 @@
 // (C + 1) int64.  The taps follow the reference's fp32 arithmetic; every term is w * value in fp64, rounded to an integer number
 // of 2^-24 units; integer adds are associative, so the accumulator is the same whatever order the atomics land in.
 // Resolve (iron_bake_resolve): fp32 texel values and acc / (w + 1e-10) in fp32, like the reference's float32 images.
+#include "fixed_sum.h"
 #include "mesh_common.h"
 #include "pair_scan.h"
 
@@ -68,26 +69,14 @@ __global__ __launch_bounds__(kBkBlock) void k_bake_area(const float* __restrict_
         }
         area[f] = a;
     }
-    s[threadIdx.x] = (double)a;
-    __syncthreads();
-    for (int h = kBkBlock / 2; h > 0; h >>= 1) {
-        if (threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = s[0];
+    const double r = fixed_sum::block_sum<kBkBlock>((double)a, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 __global__ __launch_bounds__(1024) void k_bake_sum(const double* __restrict__ part, int64_t n, float* __restrict__ sum) {
     __shared__ double s[1024];
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) acc += part[i];
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if (threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *sum = (float)s[0];
+    const double r = fixed_sum::slot_sum<1024>(part, n, 1, s);
+    if (threadIdx.x == 0) *sum = (float)r;
 }
 
 __global__ void k_bake_count(const float* __restrict__ area, const float* __restrict__ sum, int64_t nf, float n_samples,

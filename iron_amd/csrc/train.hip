@@ -8,7 +8,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "../../include/iron_train.h"
+#include "train_common.h"
 #include "gemm_h2.h"
 #include "ggx_core.h"
 
@@ -17,14 +17,6 @@ namespace iron_train {
 thread_local int g_hip_error = 0;
 thread_local int g_blas_status = 0;
 
-#define TR_HIP(expr)                                 \
-    do {                                             \
-        hipError_t _e = (expr);                      \
-        if (_e != hipSuccess) {                      \
-            g_hip_error = (int)_e;                   \
-            return IRON_ERR_HIP;                     \
-        }                                            \
-    } while (0)
 #define TR_TRY(expr)                \
     do {                            \
         int _r = (expr);            \
@@ -64,7 +56,7 @@ static int gemm_rm(const GemmCtx& h, bool ta, bool tb, int m, int n, int k, cons
     if (a_is_gradient && amax) {
         g.a_absmax = amax;
     } else if (a_is_gradient && k > 0) {
-        TR_HIP(hipMemsetAsync(h.scratch, 0, sizeof(float), h.st));
+        IRON_TRAIN_HIP(hipMemsetAsync(h.scratch, 0, sizeof(float), h.st));
         const int64_t count = (int64_t)(ta ? k : m) * lda;  // the rows in use are contiguous: lda == row length at every call site
         hipLaunchKernelGGL(k_absmax, dim3((unsigned)((count + 1023) / 1024 < 1024 ? (count + 1023) / 1024 : 1024)), dim3(256), 0, h.st, A, count, h.scratch);
         g.a_absmax = h.scratch;
@@ -90,7 +82,7 @@ static int gemm_rm(const GemmCtx& h, bool ta, bool tb, int m, int n, int k, cons
         } else {
             er = n_tiles <= 4 ? gemm_rows_launch<1>(r, h.st) : (n_tiles <= 8 ? gemm_rows_launch<2>(r, h.st) : gemm_rows_launch<3>(r, h.st));
         }
-        TR_HIP(er);
+        IRON_TRAIN_HIP(er);
         return IRON_OK;
     }
     hipError_t e;
@@ -98,7 +90,7 @@ static int gemm_rm(const GemmCtx& h, bool ta, bool tb, int m, int n, int k, cons
     else if (!ta && !tb) e = gemm_split_launch<false, true>(g, 1, h.st);
     else if (ta && !tb) e = gemm_split_launch<true, true>(g, 1, h.st);
     else return IRON_ERR_UNSUPPORTED;
-    TR_HIP(e);
+    IRON_TRAIN_HIP(e);
     return IRON_OK;
 }
 
@@ -136,12 +128,12 @@ static int gemm_dw(const GemmCtx& h, hipStream_t st, int out, int in, int R, con
     if (amax) {
         g.a_absmax = amax;
     } else {
-        TR_HIP(hipMemsetAsync(h.scratch, 0, sizeof(float), st));
+        IRON_TRAIN_HIP(hipMemsetAsync(h.scratch, 0, sizeof(float), st));
         const int64_t count = (int64_t)R * out;
         hipLaunchKernelGGL(k_absmax, dim3((unsigned)((count + 1023) / 1024 < 1024 ? (count + 1023) / 1024 : 1024)), dim3(256), 0, st, dZ, count, h.scratch);
         g.a_absmax = h.scratch;
     }
-    TR_HIP((gemm_split_launch<true, true>(g, S, st)));
+    IRON_TRAIN_HIP((gemm_split_launch<true, true>(g, S, st)));
     const int cnt = out * in;
     hipLaunchKernelGGL(k_reduce_partials, dim3((cnt + 255) / 256), dim3(256), 0, st, partial, S, cnt, beta, dW);
     return IRON_OK;
@@ -376,8 +368,8 @@ static int sdf_backward(const iron_sdf_train_desc* d, const float* x, int64_t n,
     const float rs2 = 0.70710678118654752440f;
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(k_wn_fold, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, ly[l].out_dim, ly[l].in_dim, P.W[l]);
-        TR_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
-        if (n == 0) TR_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
+        IRON_TRAIN_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
+        if (n == 0) IRON_TRAIN_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
     }
     const int tangent = d_grad ? 1 : 0;
     for (int64_t p0 = 0; p0 < n; p0 += P.m_max) {
@@ -409,7 +401,7 @@ static int sdf_backward(const iron_sdf_train_desc* d, const float* x, int64_t n,
         float* dz_max_nxt = h.scratch + 2;
         float* dz_cur = P.dZ;
         float* dz_nxt = P.dX;
-        TR_HIP(hipMemsetAsync(dz_max_cur, 0, sizeof(float), st));
+        IRON_TRAIN_HIP(hipMemsetAsync(dz_max_cur, 0, sizeof(float), st));
         hipLaunchKernelGGL(k_sdf_seed, strip_grid(m, out_last), dim3(256), 0, st, d_sdf ? d_sdf + p0 : nullptr,
                            d_feat ? d_feat + (size_t)p0 * (out_last - 1) : nullptr, m, out_last, tangent, dz_cur, P.db[L - 1], dz_max_cur);
         for (int l = L - 1; l >= 0; --l) {
@@ -418,7 +410,7 @@ static int sdf_backward(const iron_sdf_train_desc* d, const float* x, int64_t n,
             if (l == 0) break;
             const int outp = ly[l - 1].out_dim;
             const float sc = l == d->skip_layer ? rs2 : 1.0f;
-            TR_HIP(hipMemsetAsync(dz_max_nxt, 0, sizeof(float), st));
+            IRON_TRAIN_HIP(hipMemsetAsync(dz_max_nxt, 0, sizeof(float), st));
             RowsEpi eb;
             memset(&eb, 0, sizeof(eb));
             eb.paired = tangent; eb.m_pts = m; eb.n_act = outp; eb.sc = sc; eb.Z = P.Z[l - 1]; eb.ldz = outp;
@@ -438,9 +430,9 @@ static int sdf_backward(const iron_sdf_train_desc* d, const float* x, int64_t n,
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(k_wn_back, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, P.dW[l], ly[l].out_dim, ly[l].in_dim,
                            ly[l].d_weight_v, ly[l].d_weight_g);
-        TR_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
+        IRON_TRAIN_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
     }
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -596,8 +588,8 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
     const float rs2 = 0.70710678118654752440f;
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(k_wn_fold, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, ly[l].out_dim, ly[l].in_dim, P.W[l]);
-        TR_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
-        if (n == 0) TR_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
+        IRON_TRAIN_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
+        if (n == 0) IRON_TRAIN_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
     }
     for (int64_t p0 = 0; p0 < n; p0 += P.m_max) {
         const int m = (int)((n - p0) < P.m_max ? (n - p0) : P.m_max);
@@ -627,7 +619,7 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
         const int out_last = ly[L - 1].out_dim;
         hipLaunchKernelGGL(k_render_out_back, strip_grid(m, out_last), dim3(256), 0, st, P.Z[L - 1], ly[L - 1].bias, d_out + (size_t)p0 * out_last, m,
                            out_last, d->output_bias, d->output_scale, d->squeeze_out, d->squeeze_out_scale, P.dZ, P.db[L - 1]);
-        TR_HIP(hipMemsetAsync(P.dIN0, 0, sizeof(float) * (size_t)m * I.D0, st));
+        IRON_TRAIN_HIP(hipMemsetAsync(P.dIN0, 0, sizeof(float) * (size_t)m * I.D0, st));
         // |dZ|_max of the layer in flight, written by the kernel that writes its dZ (the 3-wide seed of the last layer: one tiny pass);
         // scalars and dZ buffers in turn as in sdf_backward
         float* dz_max_cur = h.scratch + 1;
@@ -645,7 +637,7 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
             }
             const int outp = ly[l - 1].out_dim;
             const bool is_skip = (l == d->skip_layer);
-            TR_HIP(hipMemsetAsync(dz_max_nxt, 0, sizeof(float), st));
+            IRON_TRAIN_HIP(hipMemsetAsync(dz_max_nxt, 0, sizeof(float), st));
             RowsEpi eb;
             memset(&eb, 0, sizeof(eb));
             eb.m_pts = m; eb.n_act = outp; eb.sc = 1.0f; eb.Z = P.Z[l - 1]; eb.ldz = outp; eb.out = dz_nxt; eb.ld_out = outp;
@@ -665,7 +657,7 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
         }
         hipLaunchKernelGGL(k_render_in_back, dim3((m + 255) / 256), dim3(256), 0, st, I, cp, cv, m, P.dIN0, d_pts ? d_pts + 3 * p0 : nullptr,
                            (d_view && I.nv) ? d_view + 3 * p0 : nullptr, d_nrm ? d_nrm + 3 * p0 : nullptr);
-        if (d_view && !I.nv) TR_HIP(hipMemsetAsync(d_view + 3 * p0, 0, sizeof(float) * 3 * m, st));
+        if (d_view && !I.nv) IRON_TRAIN_HIP(hipMemsetAsync(d_view + 3 * p0, 0, sizeof(float) * 3 * m, st));
         if (d_feat && I.nf)
             hipLaunchKernelGGL(k_copy_cols, grid1((int64_t)m * I.nf), dim3(256), 0, st, P.dIN0 + (I.np + I.nv + I.nn), I.D0, m, I.nf, 1.0f,
                                d_feat + (size_t)p0 * I.nf, I.nf, 0);
@@ -673,9 +665,9 @@ static int render_backward(const iron_render_train_desc* d, const float* pts, co
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(k_wn_back, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, P.dW[l], ly[l].out_dim, ly[l].in_dim,
                            ly[l].d_weight_v, ly[l].d_weight_g);
-        TR_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
+        IRON_TRAIN_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
     }
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -980,9 +972,9 @@ static int nerf_backward(const iron_nerf_train_desc* d, const float* pts, const 
     const int wv = ly[iV].out_dim, hD = ly[iA].in_dim;
     for (int l = 0; l < P.nl; ++l) {
         hipLaunchKernelGGL(k_wn_fold, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, ly[l].out_dim, ly[l].in_dim, P.Wt[l]);
-        TR_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
+        IRON_TRAIN_HIP(hipMemsetAsync(P.db[l], 0, sizeof(float) * ly[l].out_dim, st));
         if (n == 0 || (l == iA && !d_alpha) || ((l == iF || l == iV || l == iC) && !d_rgb))
-            TR_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
+            IRON_TRAIN_HIP(hipMemsetAsync(P.dW[l], 0, sizeof(float) * ly[l].out_dim * ly[l].in_dim, st));
     }
     for (int64_t p0 = 0; p0 < n; p0 += P.m_max) {
         const int m = (int)((n - p0) < P.m_max ? (n - p0) : P.m_max);
@@ -1009,7 +1001,7 @@ static int nerf_backward(const iron_nerf_train_desc* d, const float* pts, const 
             hipLaunchKernelGGL(k_relu_act, grid1((int64_t)m * wv), dim3(256), 0, st, P.ZV, ly[iV].bias, m, wv, 1.0f, P.AV, wv);
         }
         // ---- reverse
-        TR_HIP(hipMemsetAsync(P.dA, 0, sizeof(float) * (size_t)m * hD, st));  // dA = dL/dh_D
+        IRON_TRAIN_HIP(hipMemsetAsync(P.dA, 0, sizeof(float) * (size_t)m * hD, st));  // dA = dL/dh_D
         if (d_rgb) {
             const float* g = d_rgb + (size_t)p0 * 3;
             const int inv = ly[iV].in_dim;
@@ -1041,9 +1033,9 @@ static int nerf_backward(const iron_nerf_train_desc* d, const float* pts, const 
     for (int l = 0; l < P.nl; ++l) {
         hipLaunchKernelGGL(k_wn_back, dim3(ly[l].out_dim), dim3(64), 0, st, ly[l].weight_v, ly[l].weight_g, P.dW[l], ly[l].out_dim, ly[l].in_dim,
                            ly[l].d_weight_v, ly[l].d_weight_g);
-        TR_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
+        IRON_TRAIN_HIP(hipMemcpyAsync(ly[l].d_bias, P.db[l], sizeof(float) * ly[l].out_dim, hipMemcpyDeviceToDevice, st));
     }
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -1186,7 +1178,7 @@ extern "C" int iron_coloc_head_backward(int32_t kind, float light, float eta, fl
                                         float* d_roughness, void* stream) {
     if (n < 0 || kind < 0 || kind > 3) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (d_light) TR_HIP(hipMemsetAsync(d_light, 0, sizeof(float), st));
+    if (d_light) IRON_TRAIN_HIP(hipMemsetAsync(d_light, 0, sizeof(float), st));
     if (n == 0) return IRON_OK;
     if (!distance || !normal || !viewdir || !diffuse_albedo || !specular_albedo || (kind == 3 && !roughness)) return IRON_ERR_BAD_ARG;
     HeadBackArgs a;
@@ -1196,7 +1188,7 @@ extern "C" int iron_coloc_head_backward(int32_t kind, float light, float eta, fl
     a.d_rough = d_roughness;
     a.light = light; a.eta = eta; a.k = k; a.kind = kind; a.n = (int)n;
     hipLaunchKernelGGL(k_coloc_head_back, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -1215,7 +1207,7 @@ extern "C" int iron_nerf_backward(const iron_nerf_train_desc* desc, const float*
 extern "C" int iron_neus_composite_backward(const iron_neus_composite_args* fwd, const iron_neus_composite_grads* g, void* stream) {
     if (!fwd || !g || fwd->n < 0 || fwd->m < 1 || fwd->m > kNeusMax) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (g->d_inv_s) TR_HIP(hipMemsetAsync(g->d_inv_s, 0, sizeof(float), st));
+    if (g->d_inv_s) IRON_TRAIN_HIP(hipMemsetAsync(g->d_inv_s, 0, sizeof(float), st));
     if (fwd->n == 0) return IRON_OK;
     if (!fwd->dists || !fwd->pts || !fwd->dirs || !fwd->sdf || !fwd->grad || !fwd->color) return IRON_ERR_BAD_ARG;
     if (fwd->bg_density && (!fwd->bg_dists || !fwd->bg_color || fwd->mo < fwd->m || fwd->mo > kNeusMax)) return IRON_ERR_BAD_ARG;
@@ -1227,7 +1219,7 @@ extern "C" int iron_neus_composite_backward(const iron_neus_composite_args* fwd,
     a.d_sdf = g->d_sdf; a.d_grad = g->d_grad; a.d_sample_color = g->d_sample_color; a.d_inv_s = g->d_inv_s;
     a.d_bg_density = g->d_bg_density; a.d_bg_color = g->d_bg_color;
     hipLaunchKernelGGL(k_neus_composite_back, dim3((unsigned)((fwd->n + 63) / 64)), dim3(64), 0, st, a);
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -1237,7 +1229,7 @@ extern "C" int iron_composite_colocated_backward(float light, const float* dista
                                                  const iron_composite_grads_in* g, const iron_composite_grads_out* o, void* stream) {
     if (n < 0 || !p || !g || !o) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (o->d_light) TR_HIP(hipMemsetAsync(o->d_light, 0, sizeof(float), st));
+    if (o->d_light) IRON_TRAIN_HIP(hipMemsetAsync(o->d_light, 0, sizeof(float), st));
     if (n == 0) return IRON_OK;
     if ((!distance && !p->env_light) || !normal || !viewdir || !p->diffuse_albedo || !p->specular_albedo || !p->specular_roughness || !p->metallic_eta ||
         !p->metallic_k || !p->dielectric_eta || !tab_trans || !tab_diff)
@@ -1252,7 +1244,7 @@ extern "C" int iron_composite_colocated_backward(float light, const float* dista
     a.d_d_eta = o->d_dielectric_eta; a.d_env = o->d_env_light;
     a.light = light; a.n = (int)n;
     hipLaunchKernelGGL(k_composite_back, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -1261,12 +1253,12 @@ extern "C" int iron_composite_colocated_backward(float light, const float* dista
 extern "C" int iron_train_numeric_status(int32_t reset, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int v = 0;
-    TR_HIP(hipMemcpyFromSymbolAsync(&v, HIP_SYMBOL(g_gemm_range_flag), sizeof(int), 0, hipMemcpyDeviceToHost, st));
-    TR_HIP(hipStreamSynchronize(st));
+    IRON_TRAIN_HIP(hipMemcpyFromSymbolAsync(&v, HIP_SYMBOL(g_gemm_range_flag), sizeof(int), 0, hipMemcpyDeviceToHost, st));
+    IRON_TRAIN_HIP(hipStreamSynchronize(st));
     if (v && reset) {
         const int z = 0;
-        TR_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_gemm_range_flag), &z, sizeof(int), 0, hipMemcpyHostToDevice, st));
-        TR_HIP(hipStreamSynchronize(st));
+        IRON_TRAIN_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_gemm_range_flag), &z, sizeof(int), 0, hipMemcpyHostToDevice, st));
+        IRON_TRAIN_HIP(hipStreamSynchronize(st));
     }
     return v ? IRON_ERR_RANGE : IRON_OK;
 }
@@ -1295,7 +1287,7 @@ extern "C" int iron_train_gemm(int32_t op_a, int32_t op_b, int32_t m, int32_t n,
     if (op_a && !op_b) rc = gemm_dw(h, st, m, n, k, A, B, beta, C, partial);   // A stored [k,m] (ld = m), B [k,n] (ld = n), C [m,n] (ld = n)
     else rc = gemm_rm(h, op_a != 0, op_b != 0, m, n, k, A, lda, B, ldb, beta, C, ldc);
     if (rc != IRON_OK) return rc;
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
@@ -1332,12 +1324,12 @@ extern "C" int iron_ggx_colocated_backward(float light, const float* distance, c
                                            float* d_viewdir, float* d_diffuse_albedo, float* d_specular_albedo, float* d_roughness, void* stream) {
     if (n < 0) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (d_light) TR_HIP(hipMemsetAsync(d_light, 0, sizeof(float), st));
+    if (d_light) IRON_TRAIN_HIP(hipMemsetAsync(d_light, 0, sizeof(float), st));
     if (n == 0) return IRON_OK;
     if (!distance || !normal || !viewdir || !diffuse_albedo || !specular_albedo || !roughness || !tab_trans || !tab_diff) return IRON_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_ggx_back, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, light, distance, normal, viewdir, diffuse_albedo, specular_albedo,
                        roughness, tab_trans, tab_diff, (int)n, d_diffuse_rgb, d_specular_rgb, d_rgb, d_light, d_distance, d_normal, d_viewdir,
                        d_diffuse_albedo, d_specular_albedo, d_roughness);
-    TR_HIP(hipGetLastError());
+    IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }

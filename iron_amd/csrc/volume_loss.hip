@@ -1,9 +1,9 @@
 // The loss of the stage-1 training step (render_volume.py:458-496, and the statistics of :507-510) in one launch chain.  C ABI
 // in include/iron_train.h; Python side in iron_amd/image_losses.py (volume_losses) over iron_amd.autograd.VolumeLossFn.
 //
-//   k_vloss_partial   one workgroup per kVlSpan rays: per-ray values in fp32 as torch forms them, six fixed-order block sums
-//                     in fp64 -> one slot of the workspace
-//   k_vloss_final     one workgroup: the slots in a fixed order, then the scalars of the record and the backward's scales
+//   k_vloss_partial   one workgroup per kVlSpan rays: per-ray values in fp32 as torch forms them, six block sums in fp64 -> one
+//                     slot of the workspace (fixed_sum.h)
+//   k_vloss_final     one workgroup: the slots' totals (fixed_sum.h), then the scalars of the record and the backward's scales
 //   k_vloss_backward  one thread per ray: d color_fine, d weight_sum (and thread 0: d gradient_error)
 // No atomics anywhere, and the cut into workgroups is fixed by the batch size alone: forward and backward are bitwise reproducible.
 //
@@ -12,51 +12,20 @@
 // Scalars (fp64 from the fp64 sums, rounded once to fp32):  mask_sum = sum m + 1e-5;  color = sum |e| / mask_sum;
 // psnr = 20 log10(1 / sqrt(sum (c - t)^2 m / (3 mask_sum)));  mask_loss = sum bce / B;  loss = color + igr_weight gradient_error +
 // mask_weight mask_loss.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
 
-#include "../../include/iron_train.h"
+#include "fixed_sum.h"
+#include "train_common.h"
 
-namespace iron_train {
-extern thread_local int g_hip_error;
-}
+using namespace iron_train;
 
 namespace {
 
-using iron_train::g_hip_error;
-
-#define VL_HIP(expr)                   \
-    do {                               \
-        hipError_t _e = (expr);        \
-        if (_e != hipSuccess) {        \
-            g_hip_error = (int)_e;     \
-            return IRON_ERR_HIP;       \
-        }                              \
-    } while (0)
-
-constexpr int kThreads = 256;
 constexpr int kVlPerThread = 8;
 constexpr int kVlSpan = kThreads * kVlPerThread;   // rays per workgroup
 constexpr int kVlVals = 6;                         // sum |e|, sum sq, sum bce, sum cdf m, sum weight_max m, sum m
 constexpr float kClipLo = 1e-3f;                   // torch clamps a float tensor at the bounds rounded to float
 constexpr float kClipHi = (float)(1.0 - 1e-3);
-
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// fixed-order block sum of one double per thread; the result is valid in thread 0
-__device__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 __device__ __forceinline__ float ray_mask(const iron_volume_loss_args& a, int64_t i) {
     if (!(a.mask_weight > 0.f)) return 1.f;
@@ -86,10 +55,7 @@ __global__ __launch_bounds__(kThreads) void k_vloss_partial(iron_volume_loss_arg
         acc[4] += (double)(a.weight_max[i] * m);
         acc[5] += (double)m;
     }
-    for (int j = 0; j < kVlVals; ++j) {
-        const double s = block_sum(acc[j], red);
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * kVlVals + j] = s;
-    }
+    fixed_sum::store_slot<kThreads>(acc, part, red);
 }
 
 // state: [0] 1 / mask_sum, [1] mask_weight / B, [2] igr_weight
@@ -98,11 +64,7 @@ __global__ __launch_bounds__(kThreads) void k_vloss_final(iron_volume_loss_args 
                                                          double* __restrict__ state) {
     __shared__ double red[kThreads];
     double tot[kVlVals];
-    for (int j = 0; j < kVlVals; ++j) {
-        double s = 0.0;
-        for (int64_t b = threadIdx.x; b < nb; b += kThreads) s += part[(size_t)b * kVlVals + j];
-        tot[j] = block_sum(s, red);
-    }
+    fixed_sum::load_slots<kThreads>(part, nb, tot, red);
     if (threadIdx.x != 0) return;
     const double mask_sum = tot[5] + 1e-5;
     const double color = tot[0] / mask_sum;
@@ -166,21 +128,18 @@ extern "C" {
 
 size_t iron_volume_loss_workspace_bytes(int64_t b) {
     if (b < 0) return 0;
-    const int64_t nb = cdiv64(b, kVlSpan);
-    return sizeof(double) * kVlVals * (size_t)(nb > 0 ? nb : 1);
+    return slot_bytes(slot_count(b, kVlSpan), kVlVals);
 }
 
 int iron_volume_loss(const iron_volume_loss_args* a, float* loss, float* record, double* state, void* workspace,
                      size_t workspace_bytes, void* stream) {
     if (!vloss_args_ok(a) || !loss || !record || !state || !workspace) return IRON_ERR_BAD_ARG;
     if (workspace_bytes < iron_volume_loss_workspace_bytes(a->b)) return IRON_ERR_WORKSPACE;
-    const int64_t nb = cdiv64(a->b, kVlSpan);
-    if (nb > 0x7fffffff) return IRON_ERR_UNSUPPORTED;
+    const int64_t nb = slot_count(a->b, kVlSpan);
+    if (!grid_ok(nb)) return IRON_ERR_UNSUPPORTED;
     double* part = (double*)workspace;
-    hipLaunchKernelGGL(k_vloss_partial, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, *a, part);
-    VL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_vloss_final, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, *a, part, nb, loss, record, state);
-    VL_HIP(hipGetLastError());
+    IRON_TRAIN_LAUNCH(k_vloss_partial, (unsigned)nb, kThreads, (hipStream_t)stream, *a, part);
+    IRON_TRAIN_LAUNCH(k_vloss_final, 1, kThreads, (hipStream_t)stream, *a, part, nb, loss, record, state);
     return IRON_OK;
 }
 
@@ -188,10 +147,9 @@ int iron_volume_loss_backward(const iron_volume_loss_args* a, const double* stat
                               float* d_weight_sum, float* d_gradient_error, void* stream) {
     if (!vloss_args_ok(a) || !state) return IRON_ERR_BAD_ARG;
     const int64_t nb = cdiv64(a->b, kThreads);
-    if (nb > 0x7fffffff) return IRON_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_vloss_backward, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, *a, state, d_loss, d_color,
-                       d_weight_sum, d_gradient_error);
-    VL_HIP(hipGetLastError());
+    if (!grid_ok(nb)) return IRON_ERR_UNSUPPORTED;
+    IRON_TRAIN_LAUNCH(k_vloss_backward, (unsigned)nb, kThreads, (hipStream_t)stream, *a, state, d_loss, d_color, d_weight_sum,
+                      d_gradient_error);
     return IRON_OK;
 }
 
