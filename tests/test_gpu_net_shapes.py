@@ -19,6 +19,7 @@ from oracle import train_ref as T
 
 import _nets as N
 from _nets import _compare_param_grads
+from _shading_oracle import scene as _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -273,29 +274,6 @@ def test_nerf_refused_shapes(name):
 # ---- tracing and shading ---------------------------------------------------------------------------------------------------------
 FLIP_SDF = 5e-3      # a mask flip is allowed only on a ray that passes within this fp64 |sdf| of the surface (a grazing ray)
 MIN_HITS = 0.3       # hit fraction the generalised scenes keep (S1: ~0.34): a perturbation that lost the surface fails here
-
-
-def _scene(variant):
-    """S1 with every network generalise()d; "mat2_6": its diffuse / specular-albedo nets replaced by 2- and 6-layer nets."""
-    nets = scenes.build_networks("S1")
-    specs = dict(R.GGX_SPECS)
-    if variant == "mat2_6":
-        for key, depth in (("diffuse_albedo_network", 2), ("specular_albedo_network", 6)):
-            kw = dict(N.RENDER_FAMILIES["idr_0_4" if key.startswith("diffuse") else "nvd_6"], n_layers=depth)
-            torch.manual_seed(depth)
-            nets[key] = RenderingNetwork(**kw)
-            specs[key] = N.render_spec(kw)
-    for i, key in enumerate(sorted(specs) + ["sdf_network"]):
-        N.generalise(nets[key], 50 + i)
-    mt, md = _tables()
-    sc = R.Scene({k: v.detach().clone() for k, v in nets["sdf_network"].state_dict().items()}, R.SDFSpec(),
-                 {k: ({n: v.detach().clone() for n, v in nets[k].state_dict().items()}, specs[k]) for k in specs}, float(nets["point_light_network"]()), mt, md)
-    return nets, sc
-
-
-def _tables():
-    from iron_amd.renderer_ggx import load_mts_tables
-    return load_mts_tables()
 
 
 def _ray_min_abs_sdf(sd64, o, d, near, far, m=1024):
