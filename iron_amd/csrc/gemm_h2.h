@@ -373,7 +373,10 @@ __device__ __forceinline__ void softplus100(float z, float* a, float* s1, float*
 
 // The same on the hardware exp2 / log2 / rcp (1 ulp each), for the fused epilogues: there the activation runs at the row kernel's two
 // waves per SIMD, and expf / log1pf (~60 instructions per element) would cost more than the tile's MFMAs.  u = exp(-|100 z|) never
-// overflows; above the reference's threshold (100 z > 20) u < 2^-24, so 1 + u == 1 and (a, s1, s2) = (z, 1, 0) exactly as there.
+// overflows; above the reference's threshold (100 z > 20) u < 2^-24, so 1 + u == 1 and (a, s1) = (z, 1) exactly as there.  s2 is
+// NOT the reference's 0 there but 100 u: 2.1e-7 at the threshold, falling as exp(-100 z) until u underflows near 100 z = 88 -- under
+// 2^-22 of s2's peak (25), i.e. below the split product's own per-operand error (pinned column by column by the activation probe of
+// tests/test_gpu_backward_rows.py).
 __device__ __forceinline__ void softplus100_fast(float z, float* a, float* s1, float* s2) {
     const float u = __builtin_amdgcn_exp2f(fabsf(z) * -144.26950408889634f);
     const float w = 1.0f + u;

@@ -14,7 +14,9 @@ pytestmark = pytest.mark.gpu
 def test_unfused_backward_still_matches():
     env = dict(os.environ, IRON_TRAIN_FUSE="0")
     sel = "sdf_get_all_backward_vs_autograd or additive_over_points or eikonal or render_network_backward or g14_training"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_train.py"), "-x", "-q", "-m", "gpu", "-k", sel,
+    sel += " or test_sdf_rows or test_render_rows or activation_probe"   # tests/test_gpu_backward_rows.py: its small-n part
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_train.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_backward_rows.py"), "-x", "-q", "-m", "gpu", "-k", sel,
                         "-p", "no:cacheprovider"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert " passed" in r.stdout and "failed" not in r.stdout
