@@ -132,3 +132,164 @@ def test_install_as_models_resolves_the_drivers_import_line():
         for k in [k for k in sys.modules if k == "models" or k.startswith("models.")]:
             del sys.modules[k]
         sys.modules.update(saved)
+
+
+# ---- the per-pixel bound of tests/test_gpu_image_loss_pixels.py, checked on the CPU ------------------------------------------------
+def _dense_cases():
+    """Every dense case the GPU file judges per pixel: (name, case, tile)."""
+    out = []
+    for h, w in O.PYR_SIZES:
+        x, y = O.case_images(31, 2, 3, h, w)
+        out.append(("pyr %dx%d" % (h, w), dict(kind="pyr", x=x, y=y), O.PYR_TILE))
+    for h, w, win in O.SSIM_SHAPES + O.SSIM_PASS_THROUGH:
+        x, y = O.case_images(41, 1, 3, h, w)
+        out.append(("ssim %dx%d win %d" % (h, w, win), dict(kind="ssim", x=x, y=y, win=win), O.SSIM_TILE))
+        if (h, w, win) in O.SSIM_SHAPES:
+            out.append(("ssim %dx%d win %d masked" % (h, w, win), dict(kind="ssim", x=x, y=y, win=win, mask=O.det_mask(1, h, w)), O.SSIM_TILE))
+    return out
+
+
+def _grad64(fn, x, y):
+    x = x.double().requires_grad_(True)
+    y = y.double().requires_grad_(True)
+    loss = fn(x, y)
+    dx, dy = torch.autograd.grad(loss, (x, y))
+    return loss.detach().numpy(), dx.numpy(), dy.numpy()
+
+
+def test_fp32_oracle_meets_the_per_pixel_bound_at_margin_1_and_not_at_099():
+    """F is the fp32 restatement's own worst pixel: judged against itself it passes at margin 1 with its worst pixel exactly on
+    the bound, and fails at 0.99 -- the bound is one floor wide, not a figure with slack in it."""
+    n = 0
+    for name, case, tile in _dense_cases():
+        r64, r32, F = O.floors(case)
+        for k in ("dx", "dy"):
+            assert F[k] > 0, (name, k)
+            v = O.judge(r32[k], r64[k], F[k], 1.0, tile)
+            assert v.ok and v.ratio == 1.0, (name, k, v)
+            assert not O.judge(r32[k], r64[k], F[k], 0.99, tile).ok, (name, k)
+            assert O.judge(r64[k], r64[k], F[k], 0.0).ok
+            n += 1
+    assert n == 2 * (5 + 12 + 10)
+    # a non-finite value fails whatever the margin, and the report names the pixel and its seam
+    x, y = O.case_images(41, 1, 3, 43, 75)
+    r64, _, F = O.floors(dict(kind="ssim", x=x, y=y))
+    got = r64["dx"].copy()
+    got[0, 1, 16, 32] = np.nan
+    v = O.judge(got, r64["dx"], F["dx"], 1e30, O.SSIM_TILE)
+    assert not v.ok and v.index == (0, 1, 16, 32) and "row 0 of its 16-row tile, column 0 of its 32-column tile" in v.where, v
+
+
+def test_manual_pyramid_adjoint_is_the_autograd_gradient():
+    for h, w in O.PYR_SIZES:
+        x, y = O.case_images(31, 2, 3, h, w)
+        for scale in (1.0, -2.5):
+            _, dx, _ = _grad64(lambda a, b: scale * O.pyramid_l2(a, b), x, y)
+            g = O.pyramid_l2_grad(x.double(), y.double(), scale=scale).numpy()
+            assert np.abs(g - dx).max() <= 1e-13 * np.abs(dx).max(), (h, w)
+        per = O.pyramid_l2(x.double(), y.double(), per_image=True)
+        assert abs(float(per.sum()) - float(O.pyramid_l2(x.double(), y.double()))) <= 1e-15
+        assert abs(float(per[1]) - float(O.pyramid_l2(x[1:].double(), y[1:].double()))) <= 1e-15
+
+
+def test_wrong_pyramid_restatements_fail_the_bound_at_margin_4():
+    """Level divisors from the floor-pooled sizes, and a pooling adjoint that also feeds the dropped last row / column: each is
+    the restatement itself wherever no level is odd (16x16, 64x64) and fails margin 4 by orders of magnitude wherever one is."""
+    for h, w in O.PYR_SIZES:
+        x, y = O.case_images(31, 2, 3, h, w)
+        r64, _, F = O.floors(dict(kind="pyr", x=x, y=y))
+        _, dx, _ = _grad64(lambda a, b: O.pyramid_l2(a, b, divisors="floor"), x, y)
+        floor_div = O.judge(dx, r64["dx"], F["dx"], O.MARGIN, O.PYR_TILE)
+        clamp = O.judge(O.pyramid_l2_grad(x.double(), y.double(), adjoint="clamp").numpy(), r64["dx"], F["dx"], O.MARGIN, O.PYR_TILE)
+        odd = (h, w) not in ((16, 16), (64, 64))
+        assert floor_div.ok != odd and clamp.ok != odd, (h, w, floor_div, clamp)
+        if odd:
+            assert floor_div.ratio > 1e3 and clamp.ratio > 1e3, (h, w, floor_div, clamp)
+
+
+def test_wrong_mask_restatements_fail_the_bound_at_margin_4():
+    """An erosion that counts out-of-image pixels as zero loses the kept pixels near the border (loss and gradient fail); a border
+    band that counts 0 changes the loss alone.  win 1 has neither a band nor a window that leaves the image: both are exact there."""
+    for h, w, win in O.SSIM_SHAPES:
+        x, y = O.case_images(41, 1, 3, h, w)
+        m = O.det_mask(1, h, w)
+        r64, _, F = O.floors(dict(kind="ssim", x=x, y=y, win=win, mask=m))
+        for kw, grad_fails in ((dict(erode_pad=0.0), True), (dict(band_value=0.0), False)):
+            loss, dx, _ = _grad64(lambda a, b: O.ssim(a, b, m, win_size=win, **kw), x, y)
+            vl = O.judge(loss, r64["loss"], F["loss"], O.MARGIN)
+            vg = O.judge(dx, r64["dx"], F["dx"], O.MARGIN, O.SSIM_TILE)
+            if win == 1:
+                assert vl.ratio == 0.0 and vg.ratio == 0.0, (h, w, win, kw)
+                continue
+            assert not vl.ok and vl.ratio > 1e3, (h, w, win, kw, vl)
+            assert abs(float(loss) - float(r64["loss"])) > max(1e-6 * float(r64["loss"]), 1.5 * F["loss"])  # the GPU file's loss rule
+            assert vg.ok != grad_fails, (h, w, win, kw, vg)
+
+
+def _threshold_mask(h, w):
+    m = torch.ones(1, 1, h, w)
+    for (py, px), v in O.THRESHOLD_PIXELS.items():
+        m[0, 0, py, px] = v
+    return m
+
+
+def test_masked_cases_keep_and_drop_enough():
+    """Every masked case keeps at least a quarter of its valid map, at least one pixel of the border band (win 1 has no band)
+    and drops at least one pixel; a speckle mask under the largest window keeps nothing of the valid map, hence det_mask."""
+    for h, w, win in O.SSIM_SHAPES:
+        for m in [O.det_mask(1, h, w)] + ([_threshold_mask(h, w)] if (h, w, win) == (27, 43, 11) else []):
+            s = O.mask_stats(m, win)
+            assert s["valid_kept"] >= 0.25 and s["dropped"] >= 1, (h, w, win, s)
+            assert (s["band_kept"] >= 1) if win >= 3 else (s["band_kept"] == 0), (h, w, win, s)
+    speckle = torch.from_numpy((O._hash(36 * 52, 99) % np.uint64(25) != 0).reshape(1, 1, 36, 52))
+    assert O.mask_stats(speckle, 21)["valid_kept"] == 0.0
+    # only 0.5 and below, and NaN, are dropped: the oracle's kept set under the threshold mask
+    keep = O.keep_map(_threshold_mask(27, 43), 11)[0, 0]
+    gone = torch.zeros(27, 43, dtype=torch.bool)
+    for (py, px), v in O.THRESHOLD_PIXELS.items():
+        if not (v > 0.5):
+            gone[max(py - 5, 0):py + 6, max(px - 5, 0):px + 6] = True
+        else:
+            assert bool(keep[py, px]), (py, px, v)
+    assert torch.equal(~keep, gone) and int(gone.sum()) == 3 * 9 * 11
+
+
+def test_probe_masks_keep_exactly_one_valid_pixel():
+    n = 0
+    for h, w, win in O.SSIM_SHAPES:
+        pts = O.ssim_probe_points(h, w, win)
+        assert 8 <= len(pts) <= 15, (h, w, win, len(pts))
+        for q in pts:
+            m, keep, n_band = O.probe_mask(h, w, win, q)   # asserts the property
+            assert int(m.sum()) == win * win and int(keep.sum()) == n_band + 1
+            n += 1
+    _, keep, n_band = O.probe_mask(26, 42, 11, (0, 0))
+    assert int(keep.sum()) == 36 and n_band == 35 and bool(keep[:6, :6].all())   # the 6x6 corner
+    _, keep, n_band = O.probe_mask(43, 75, 11, (16, 32))
+    assert int(keep.sum()) == 1 and n_band == 0
+    assert n > 100
+
+
+def test_ssim_map_is_what_ssim_averages_and_probes_read_one_pixel_of_it():
+    x, y = O.case_images(41, 1, 3, 27, 43)
+    x, y = x.double(), y.double()
+    smap = O.ssim_map(x, y, 11)
+    assert smap.shape == (1, 1, 17, 33)
+    assert abs(float(1.0 - smap.mean()) - float(O.ssim(x, y))) <= 1e-15
+    for q in O.ssim_probe_points(27, 43, 11):
+        m, keep, n_band = O.probe_mask(27, 43, 11, q)
+        want = 1.0 - (n_band + float(smap[0, 0, q[0], q[1]])) / int(keep.sum())
+        assert abs(float(O.ssim(x, y, m)) - want) <= 1e-14, q
+
+
+def test_impulse_loss_depends_on_where_the_impulse_sits():
+    """The pyramid loss of one impulse varies with its position (zero padding and floor-dropped rows differ per level), so it is a
+    forward probe of the per-level border handling; the fp32 restatement stays within 1.5e-7 relative of the fp64 one."""
+    for h, w in O.PYR_SIZES:
+        pts = O.impulse_points(h, w)
+        assert 25 <= len(pts) <= 72
+        X = torch.cat([O.impulse(h, w, p)[0] for p in pts])
+        l64 = O.pyramid_l2(X.double(), torch.zeros_like(X).double(), per_image=True).numpy()
+        l32 = O.pyramid_l2(X, torch.zeros_like(X), per_image=True).double().numpy()
+        assert (l64.max() - l64.min()) / l64.min() > 0.02, (h, w)
+        assert (np.abs(l32 - l64) / l64).max() < 1.5e-7, (h, w)
