@@ -1023,6 +1023,40 @@ int iron_volume_frame_u8(const float* color, const float* gradients, const float
                          uint8_t* normal_frame, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multiresolution hash-grid encoding (the tcnn.Encoding of models/tcnn_fields.py: tiny-cuda-nn's published HashGrid with Linear
+ * interpolation, 3-D input, fp32 table), csrc/hashgrid.hip; the definition is csrc/hashgrid_common.h and DESIGN.md "Hash-grid
+ * encoding".  Level l: scale = exp2(l log2 per_level_scale) base_resolution - 1 (double, stored fp32), res = ceil(scale) + 1,
+ * size = min(roundup8(res^3), 2^log2_hashmap_size) entries of n_features_per_level floats, dense iff res^3 <= size; the flat
+ * table is the levels one after another, [n_params, F].
+ *   iron_hashgrid_layout   HOST only, no device needed.  Validates the descriptor (n_levels 1..32, F in {1, 2, 4, 8},
+ *                          log2_hashmap_size 1..24, base_resolution >= 1, per_level_scale >= 1, else IRON_ERR_BAD_ARG;
+ *                          IRON_ERR_RANGE when a level's scale reaches 2^22) and writes n_levels records to levels_out (may be
+ *                          NULL) and the number of table entries to *n_params_out (may be NULL).
+ *   iron_hashgrid_encode   x [n,3] (clamped to [0,1] per axis) -> y [n, L F], level-major within a row, and, when jac is not
+ *                          NULL, jac [n, L F, 3] = dy/dx (a column is zero on an axis where x lay outside [0,1]).  One thread per
+ *                          (point, level); the eight corners are summed in corner order in fp32, so a row does not depend on
+ *                          the other rows of the call.  `table` must hold n_params F floats.
+ * ------------------------------------------------------------------------------------------- */
+#define IRON_HASHGRID_MAX_LEVELS 32
+typedef struct iron_hashgrid_desc {
+    int32_t n_levels;
+    int32_t n_features_per_level;
+    int32_t log2_hashmap_size;
+    int32_t base_resolution;
+    double per_level_scale;
+} iron_hashgrid_desc;
+typedef struct iron_hashgrid_level {
+    float scale;
+    uint32_t res;
+    uint32_t size;    /* entries */
+    uint32_t dense;   /* 1: (c0 + c1 res + c2 res^2) mod size, 0: the xor hash mod size */
+    int64_t offset;   /* first entry of the level in the flat table */
+} iron_hashgrid_level;
+int iron_hashgrid_layout(const iron_hashgrid_desc* desc, iron_hashgrid_level* levels_out, int64_t* n_params_out);
+int iron_hashgrid_encode(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table, float* y, float* jac_or_null,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the
  * caller's stream around each compute kernel.  Off by default.  iron_profile_read blocks on the
  * recorded events, adds their elapsed milliseconds / launch counts into the caller's arrays

@@ -307,6 +307,30 @@ int iron_volume_loss(const iron_volume_loss_args* a, float* loss, float* record,
 int iron_volume_loss_backward(const iron_volume_loss_args* a, const double* state, const float* d_loss, float* d_color,
                               float* d_weight_sum, float* d_gradient_error, void* stream);
 
+/* Gradients of the hash-grid encoding (iron_hip.h, iron_hashgrid_* block), csrc/hashgrid_train.hip.  x [n,3], dy [n, L F],
+ * table and d_table [n_params, F], all fp32.
+ *   iron_hashgrid_backward           d_table[idx_o][l-th level, f] = sum over points and corners of wgt_o dy[l,f]  (may be NULL);
+ *                                    d_x [n,3] = sum_{l,f} dy[l,f] J[l,f,:]  (may be NULL; needs `table`, else it may be NULL).
+ *   iron_hashgrid_backward_backward  the backward of d_x as a function of (dy, table), for the gradient g [n,3] arriving at d_x:
+ *                                    d_dy[n,l,f] = sum_d J[l,f,d] g_d  (may be NULL), and the table term (may be NULL), which
+ *                                    scatters dy[l,f] sum_d g_d live_d scale_l dw_o,d to corner o.  The second derivative with
+ *                                    respect to x (the mixed terms of the trilinear form) is not built.
+ * d_table is WRITTEN whole: an entry no corner touches is +0.0 whatever the buffer held.  It is bitwise reproducible and bitwise
+ * invariant under a permutation of the points: contributions are rounded in fp64 to a multiple of a power-of-two unit and summed
+ * as 64-bit integers in `workspace`; the unit's exponent is iron_hashgrid_grad_unit_exp(bound, n) with bound = max |dy| (first
+ * order) or fl(fl(fl(3 max |g|) scale_l) max |dy|) (second order, per level), so that 8 n contributions stay inside 63 bits.  A
+ * non-finite dy (or g) makes every entry NaN.  The per-point outputs (d_x, d_dy) are fixed-order fp32 sums that do not depend on
+ * the other points.  The workspace is needed for d_table only; *_workspace_bytes returns 0 for a descriptor the layout refuses.
+ * IRON_ERR_WORKSPACE: workspace too small. */
+size_t iron_hashgrid_backward_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n);
+int iron_hashgrid_backward(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table_or_null, const float* dy,
+                           float* d_table_or_null, float* d_x_or_null, void* workspace, size_t workspace_bytes, void* stream);
+size_t iron_hashgrid_backward_backward_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n);
+int iron_hashgrid_backward_backward(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table, const float* dy,
+                                    const float* g, float* d_dy_or_null, float* d_table_or_null, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int iron_hashgrid_grad_unit_exp(float bound, int64_t n);   /* HOST: log2 of the fixed-point unit */
+
 /* Diagnostics: last hipError_t seen by this library on the calling thread (iron_train_last_blas_status: kept for ABI
  * stability, always 0: the library links no BLAS). */
 int iron_train_last_hip_error(void);

@@ -8,6 +8,7 @@ Module names mirror the reference's `models/` package for this path:
     iron_amd.embedder       <- models/embedder.py
     iron_amd.image_losses   <- models/image_losses.py
     iron_amd.export_mesh    <- models/export_mesh.py
+    iron_amd.tcnn_fields    <- models/tcnn_fields.py (TCNNSDF on iron_amd.hashgrid, the HIP hash-grid encoding; no tiny-cuda-nn)
     iron_amd.export_uv      <- models/export_uv.py (a Blender script: run as `python -m iron_amd.export_uv IN.obj OUT.obj`)
 `install_as_models()` registers them under those names for `render_surface.py`-style callers.
 """
@@ -41,7 +42,7 @@ def install_as_models() -> None:
             pkg.__path__ = []  # mark as package
             sys.modules["models"] = pkg
     for name in ("raytracer", "renderer_ggx", "rendering_func", "fields", "embedder", "renderer", "network_conf", "image_losses",
-                 "export_materials", "export_mesh"):
+                 "export_materials", "export_mesh", "tcnn_fields"):
         mod = importlib.import_module("iron_amd." + name)
         sys.modules["models." + name] = mod
         setattr(pkg, name, mod)

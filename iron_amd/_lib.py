@@ -126,6 +126,18 @@ class iron_neural_bounce(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("hit", "distance", "points", "normal", "diffuse_albedo", "specular_albedo", "specular_roughness")]
 
 
+class iron_hashgrid_desc(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("n_features_per_level", C.c_int32), ("log2_hashmap_size", C.c_int32),
+                ("base_resolution", C.c_int32), ("per_level_scale", C.c_double)]
+
+
+class iron_hashgrid_level(C.Structure):
+    _fields_ = [("scale", C.c_float), ("res", C.c_uint32), ("size", C.c_uint32), ("dense", C.c_uint32), ("offset", C.c_int64)]
+
+
+IRON_HASHGRID_MAX_LEVELS = 32
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -269,6 +281,8 @@ SYMBOLS = {
     "iron_volume_rays": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "iron_volume_rays_grid": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "iron_volume_frame_u8": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _P, _P, _P]),
+    "iron_hashgrid_layout": (C.c_int, [C.POINTER(iron_hashgrid_desc), C.POINTER(iron_hashgrid_level), C.POINTER(_I64)]),
+    "iron_hashgrid_encode": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),
@@ -375,6 +389,11 @@ TRAIN_SYMBOLS = {
     "iron_ssim_backward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, C.c_double, C.c_double, _I32, _P, _P,
                                      _SZ, _P, _SZ, _P, _P, _P]),
     "iron_gaussian_filter": (C.c_int, [_P, _I64, _I32, _I32, C.POINTER(C.c_float), _I32, _P, _P]),
+    "iron_hashgrid_backward_workspace_bytes": (_SZ, [C.POINTER(iron_hashgrid_desc), _I64]),
+    "iron_hashgrid_backward": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_hashgrid_backward_backward_workspace_bytes": (_SZ, [C.POINTER(iron_hashgrid_desc), _I64]),
+    "iron_hashgrid_backward_backward": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_hashgrid_grad_unit_exp": (C.c_int, [_F, _I64]),
 }
 
 _lock = threading.Lock()
