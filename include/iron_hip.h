@@ -1057,6 +1057,38 @@ int iron_hashgrid_encode(const iron_hashgrid_desc* desc, const float* x, int64_t
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fused inference evaluation of the hash-grid field (TCNNSDF of models/tcnn_fields.py: the encoding above and a bias-free MLP
+ * head, tiny-cuda-nn's FullyFusedMLP), csrc/hashgrid_field.hip; DESIGN.md §28.  One launch computes out [n, n_out] and, when
+ * grad is not NULL, grad [n, 3] = d out[:, 0] / dp; neither the features nor their Jacobian are written to memory.
+ *   head      layer 0: L F -> n_neurons, n_hidden_layers - 1 layers n_neurons -> n_neurons, last: n_neurons -> n_out; `activation`
+ *             between layers, none after the last.  Weights: the flat fp32 concatenation of the [out, in] row-major matrices.
+ *             Every pre-activation is one fp32 fma chain over the input index in ascending order, starting from zero.
+ *   shapes    L F <= 128, n_neurons in {16, 32, 64, 128}, n_hidden_layers 1..4, n_out 1..16, else IRON_ERR_RANGE; a descriptor
+ *             the encoding refuses returns the encoding's code; an unknown activation IRON_ERR_BAD_ARG.
+ *   iron_hashgrid_field_check       HOST only, no device needed: validates and writes the number of weights (may be NULL).
+ *   iron_hashgrid_field_pack_bytes  size of the packed blob (0 for a refused descriptor); `packed` must be 16-byte aligned.
+ *   iron_hashgrid_field_pack        weights -> MFMA fragment order, both orientations; once per weight version.
+ *   iron_hashgrid_field_eval        evaluates at x_d = fma(p_d, a_d, b_d) (map_a3 / map_b3: HOST pointers to 3 floats, NULL: a = 1 /
+ *                                   b = 0), x clamped to [0, 1] as the encoding does; grad is with respect to p (a_d times the
+ *                                   gradient at x) and exactly zero on an axis where x lay outside [0, 1].  A row's results do not
+ *                                   depend on the other rows, on n or on its position; n = 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+enum { IRON_FIELD_ACT_NONE = 0, IRON_FIELD_ACT_RELU = 1, IRON_FIELD_ACT_SOFTPLUS = 2 };
+typedef struct iron_hashgrid_field_desc {
+    iron_hashgrid_desc encoding;
+    int32_t n_neurons;
+    int32_t n_hidden_layers;
+    int32_t n_out;
+    int32_t activation;   /* IRON_FIELD_ACT_* */
+} iron_hashgrid_field_desc;
+int iron_hashgrid_field_check(const iron_hashgrid_field_desc* desc, int64_t* n_weights_out);
+size_t iron_hashgrid_field_pack_bytes(const iron_hashgrid_field_desc* desc);
+int iron_hashgrid_field_pack(const iron_hashgrid_field_desc* desc, const float* weights, void* packed, void* stream);
+int iron_hashgrid_field_eval(const iron_hashgrid_field_desc* desc, const float* p, int64_t n, const float* map_a3_or_null,
+                             const float* map_b3_or_null, const float* table, const void* packed, float* out, float* grad_or_null,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the
  * caller's stream around each compute kernel.  Off by default.  iron_profile_read blocks on the
  * recorded events, adds their elapsed milliseconds / launch counts into the caller's arrays

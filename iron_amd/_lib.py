@@ -138,6 +138,14 @@ class iron_hashgrid_level(C.Structure):
 IRON_HASHGRID_MAX_LEVELS = 32
 
 
+class iron_hashgrid_field_desc(C.Structure):
+    _fields_ = [("encoding", iron_hashgrid_desc), ("n_neurons", C.c_int32), ("n_hidden_layers", C.c_int32), ("n_out", C.c_int32),
+                ("activation", C.c_int32)]
+
+
+IRON_FIELD_ACT = {"None": 0, "ReLU": 1, "Softplus": 2}
+
+
 class iron_lpips_weights(C.Structure):
     _fields_ = [("conv_weight", C.c_void_p * 5), ("conv_bias", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
@@ -283,6 +291,10 @@ SYMBOLS = {
     "iron_volume_frame_u8": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _P, _P, _P]),
     "iron_hashgrid_layout": (C.c_int, [C.POINTER(iron_hashgrid_desc), C.POINTER(iron_hashgrid_level), C.POINTER(_I64)]),
     "iron_hashgrid_encode": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P]),
+    "iron_hashgrid_field_check": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), C.POINTER(_I64)]),
+    "iron_hashgrid_field_pack_bytes": (_SZ, [C.POINTER(iron_hashgrid_field_desc)]),
+    "iron_hashgrid_field_pack": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _P, _P]),
+    "iron_hashgrid_field_eval": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _I64, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _P, _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),

@@ -1,0 +1,480 @@
+// Fused inference evaluation of the hash-grid SDF field (include/iron_hip.h, iron_hashgrid_field_* block): the
+// encoding of hashgrid_common.h and the bias-free MLP head behind it in ONE launch, the value and on request d out[0] / dp.
+//
+//   k_hg_field<ACT, GRAD, CT, NT>   one wave64 per workgroup owns P = 32 CT points.  Every stage of the head lives in LDS as
+//                               [row k][P points] floats, so a k-step's B operand (rows 2s, 2s+1) is one ds_read per lane.
+//       encode    lane = point, the level loop inside the wave (its gathers stay within four neighbouring levels, two for
+//                 F >= 4); hg::walk, the rows loaded first, then y[f] = sum_o wgt[o] row_o[f] in corner order: the bits of
+//                 iron_hashgrid_encode.
+//       head      Z^T[out, point] = W[out, in] H^T[in, point] on v_mfma_f32_32x32x2_f32, A = a packed weight fragment (one
+//                 16-byte load per lane feeds 4 CT MFMAs), accumulator from zero: per output one fp32 fma chain over the input
+//                 index in ascending order.  The activation is applied on the accumulator, which is then written to the next
+//                 stage's rows.  The last layer's accumulator goes straight to `out`.
+//       gradient  (GRAD) the derivative of the activation is recovered from the stored activation itself (ReLU: h > 0;
+//                 Softplus: sigmoid(z) = -expm1(-h)), so the forward keeps nothing but the stages.  d_{m-1} = act'(h_{m-1}) W_m[0,:],
+//                 then per layer G = W_l^T d_l with the transposed fragments (a chain over the OUTPUT index, ascending),
+//                 d_{l-1} = act'(h_{l-1}) G in place, e = W_0^T d_0 into the feature rows.  The corner rows are gathered again,
+//                 J[l,f,d] is formed as k_hg_encode forms it and grad_d = fma(e[l,f], J[l,f,d], grad_d) in ascending (l, f).
+//   k_hg_field_pack             W (flat [out, in] row-major, layer after layer) -> fragment order, both orientations.
+//
+// Rows are independent: a point only ever touches its own LDS column, and padded rows / k-steps multiply exact zeros.
+#include "hashgrid_common.h"
+#include "host_util.h"
+#include "mlp_core.h"
+
+namespace iron {
+
+constexpr int kFieldMaxLayers = 5;    // 4 hidden + the output layer
+constexpr int kFieldMaxWidth = 128;   // L F and n_neurons
+constexpr int kFieldLdsTwoTiles = 64 * 1024;   // up to here a wave takes 64 points (two MFMA column tiles), above it 32
+constexpr int kFieldFragAhead = 4;             // weight fragments (16 bytes per lane each) in flight ahead of the MFMAs
+
+// What the kernels need of a validated descriptor.  Offsets into the packed blob count float4s.
+struct FieldPlan {
+    int32_t m, lf, neurons, n_out, act;
+    int32_t in[kFieldMaxLayers], out[kFieldMaxLayers], w_off[kFieldMaxLayers];      // layer j: dims and first weight in the flat array
+    int32_t kq[kFieldMaxLayers], tiles[kFieldMaxLayers], fwd_off[kFieldMaxLayers];   // forward: k quads (8 inputs each), output tiles
+    int32_t tq[kFieldMaxLayers], ttiles[kFieldMaxLayers], tr_off[kFieldMaxLayers];   // transposed (layers 0 .. m-1)
+    int32_t row0_off, total_f4;
+    int32_t n_weights;
+};
+
+static inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
+
+static int make_plan(const iron_hashgrid_field_desc* d, FieldPlan* pl) {
+    if (!d) return IRON_ERR_BAD_ARG;
+    const int rc = hg::layout(&d->encoding, nullptr, nullptr);
+    if (rc != IRON_OK) return rc;
+    if (d->activation < IRON_FIELD_ACT_NONE || d->activation > IRON_FIELD_ACT_SOFTPLUS) return IRON_ERR_BAD_ARG;
+    const int lf = d->encoding.n_levels * d->encoding.n_features_per_level, N = d->n_neurons;
+    if (lf > kFieldMaxWidth) return IRON_ERR_RANGE;
+    if (!(N == 16 || N == 32 || N == 64 || N == 128)) return IRON_ERR_RANGE;
+    if (d->n_hidden_layers < 1 || d->n_hidden_layers > kFieldMaxLayers - 1) return IRON_ERR_RANGE;
+    if (d->n_out < 1 || d->n_out > 16) return IRON_ERR_RANGE;
+    FieldPlan p = {};
+    p.m = d->n_hidden_layers; p.lf = lf; p.neurons = N; p.n_out = d->n_out; p.act = d->activation;
+    int off = 0, w = 0;
+    for (int j = 0; j <= p.m; ++j) {
+        p.in[j] = j == 0 ? lf : N;
+        p.out[j] = j == p.m ? d->n_out : N;
+        p.w_off[j] = w;
+        w += p.in[j] * p.out[j];
+        p.kq[j] = round_up(p.in[j], 8) / 8;
+        p.tiles[j] = round_up(p.out[j], 32) / 32;
+        p.fwd_off[j] = off;
+        off += p.tiles[j] * p.kq[j] * 64;
+    }
+    for (int j = 0; j < p.m; ++j) {
+        p.tq[j] = round_up(p.out[j], 8) / 8;
+        p.ttiles[j] = round_up(p.in[j], 32) / 32;
+        p.tr_off[j] = off;
+        off += p.ttiles[j] * p.tq[j] * 64;
+    }
+    p.row0_off = off;
+    off += round_up(N, 32) / 4;
+    p.total_f4 = off;
+    p.n_weights = w;
+    *pl = p;
+    return IRON_OK;
+}
+
+// stage buffers in LDS (float offsets for P points): value only, one buffer serves every stage in place; with the gradient every
+// stage 0 .. m keeps its own (the backward chain walks them in place)
+struct FieldLds {
+    int32_t buf[kFieldMaxLayers + 1];
+};
+static size_t lds_layout(const FieldPlan& p, bool grad, int P, FieldLds* out) {
+    const int r0 = round_up(p.lf, 32), rn = round_up(p.neurons, 32);
+    FieldLds L = {};
+    size_t rows;
+    if (grad) {
+        int o = 0;
+        for (int s = 0; s <= p.m; ++s) {
+            L.buf[s] = o * P;
+            o += s == 0 ? r0 : rn;
+        }
+        rows = (size_t)o;
+    } else {
+        rows = (size_t)(r0 > rn ? r0 : rn);          // every stage in the one buffer (offset 0)
+    }
+    if (out) *out = L;
+    return rows * P * sizeof(float);
+}
+
+template <int ACT>
+__device__ __forceinline__ float field_act(float z) {
+    if constexpr (ACT == IRON_FIELD_ACT_RELU) return fmaxf(z, 0.0f);
+    else if constexpr (ACT == IRON_FIELD_ACT_SOFTPLUS) return z > 20.0f ? z : log1pf(expf(z));   // nn.Softplus(): beta 1, threshold 20
+    else return z;
+}
+// act'(z) from h = act(z)
+template <int ACT>
+__device__ __forceinline__ float field_act_grad(float h) {
+    if constexpr (ACT == IRON_FIELD_ACT_RELU) return h > 0.0f ? 1.0f : 0.0f;
+    else if constexpr (ACT == IRON_FIELD_ACT_SOFTPLUS) return -expm1f(-h);
+    else return 1.0f;
+}
+
+// the row of accumulator register r in lane half h (C/D map of the 32x32 MFMAs)
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// The level loop of a wave, G levels at a time: the corner walks and the 8 G gathers of a group are issued first, then every level
+// is summed, in level order.  A wave has few other waves to hide its latency behind (LDS holds the stages of a handful), so the
+// gathers in flight have to come from the wave itself.  Per level the arithmetic is k_hg_encode's: y[f] = sum_o wgt[o] row_o[f]
+// in corner order -> rows l F .. l F + F - 1 of the stage, this lane's column.
+template <int F>
+__device__ __forceinline__ void field_encode(const hg::Levels& L, const float* xs, const float* __restrict__ table,
+                                             float* __restrict__ dst, int P) {
+    constexpr int G = F <= 2 ? 4 : 2;
+    for (int l0 = 0; l0 < L.n_levels; l0 += G) {
+        hg::Walk k[G];
+        float row[G][8][F];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (l0 + g < L.n_levels) {
+                const iron_hashgrid_level lv = L.lv[l0 + g];
+                hg::walk(lv, xs, &k[g]);
+                const float* base = table + lv.offset * F;
+#pragma unroll
+                for (int o = 0; o < 8; ++o) hg::load_row<F>(base + (int64_t)k[g].idx[o] * F, row[g][o]);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (l0 + g < L.n_levels) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int o = 0; o < 8; ++o) s = fmaf(k[g].wgt[o], row[g][o][f], s);
+                    dst[((l0 + g) * F + f) * P] = s;
+                }
+            }
+        }
+    }
+}
+
+// g[d] = fma(e[l,f], J[l,f,d], g[d]) in ascending (l, f), J as k_hg_encode forms it; the gathers grouped as above
+template <int F>
+__device__ __forceinline__ void field_grad(const hg::Levels& L, const float* xs, const float* __restrict__ table,
+                                           const float* __restrict__ e, int P, float* gr) {
+    constexpr int G = F <= 2 ? 4 : 2;
+    for (int l0 = 0; l0 < L.n_levels; l0 += G) {
+        hg::Walk k[G];
+        float row[G][8][F];
+        float scale[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (l0 + g < L.n_levels) {
+                const iron_hashgrid_level lv = L.lv[l0 + g];
+                hg::walk(lv, xs, &k[g]);
+                scale[g] = lv.scale;
+                const float* base = table + lv.offset * F;
+#pragma unroll
+                for (int o = 0; o < 8; ++o) hg::load_row<F>(base + (int64_t)k[g].idx[o] * F, row[g][o]);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (l0 + g < L.n_levels) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    const float ef = e[((l0 + g) * F + f) * P];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        float s = 0.0f;
+#pragma unroll
+                        for (int o = 0; o < 8; ++o) s = fmaf(k[g].dw[o][d], row[g][o][f], s);
+                        gr[d] = fmaf(ef, k[g].live[d] * (scale[g] * s), gr[d]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// acc[ct] = sum over k of frag[k][row of this lane] * in[k][point], k ascending: nq quads of four k-steps
+template <int CT>
+__device__ __forceinline__ void field_tile(const float4* __restrict__ frag, int nq, const float* __restrict__ in, int lane,
+                                           f32x16 (&acc)[CT]) {
+    constexpr int P = 32 * CT;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
+    const float* bp = in + (lane >> 5) * P + (lane & 31);
+    // the fragments come from L2: kFieldFragAhead of them are fetched while the previous ones feed the MFMAs (the order of the
+    // k-steps, and so every bit of the result, is that of the plain loop)
+    float4 ahead[kFieldFragAhead];
+#pragma unroll
+    for (int i = 0; i < kFieldFragAhead; ++i) ahead[i] = i < nq ? frag[i * 64 + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int q0 = 0; q0 < nq; q0 += kFieldFragAhead) {
+        float4 a[kFieldFragAhead];
+#pragma unroll
+        for (int i = 0; i < kFieldFragAhead; ++i) {
+            a[i] = ahead[i];
+            if (q0 + kFieldFragAhead + i < nq) ahead[i] = frag[(q0 + kFieldFragAhead + i) * 64 + lane];
+        }
+#pragma unroll
+        for (int i = 0; i < kFieldFragAhead; ++i) {
+            if (q0 + i < nq) {
+                const float* b = bp + (q0 + i) * 8 * P;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma32(a[i].x, b[32 * ct], acc[ct]);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma32(a[i].y, b[2 * P + 32 * ct], acc[ct]);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma32(a[i].z, b[4 * P + 32 * ct], acc[ct]);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma32(a[i].w, b[6 * P + 32 * ct], acc[ct]);
+            }
+        }
+    }
+}
+
+struct FieldMap {
+    float a[3], b[3];
+};
+
+// NT > 0 (value only): one LDS buffer serves every stage in place -- the NT output tiles of a hidden layer wait in registers until
+// the layer's last k-step has read its input -- which halves the LDS of a wave and doubles the waves a CU holds.
+template <int ACT, bool GRAD, int CT, int NT>
+__global__ __launch_bounds__(64) void k_hg_field(hg::Levels L, FieldPlan pl, FieldLds lo, const float* __restrict__ p, int64_t n,
+                                                 FieldMap map, const float* __restrict__ table, const float4* __restrict__ packed,
+                                                 float* __restrict__ out, float* __restrict__ grad) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int P = 32 * CT;
+    const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
+    const int64_t first = (int64_t)blockIdx.x * P;
+    const int64_t pt = first + lane;
+    const bool owner = lane < P;               // this lane encodes a point
+    const bool have = owner && pt < n;
+    float xs[3] = {0.0f, 0.0f, 0.0f};          // a column past n evaluates at the origin; nothing of it is written
+    if (have) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) xs[d] = fmaf(p[3 * pt + d], map.a[d], map.b[d]);
+    }
+    const int F = L.n_features;
+
+    // ---- encode: stage 0, rows l F + f; the rows between L F and the next multiple of 8 are zero (k-step padding) ----
+    float* s0 = lds + lo.buf[0];
+    if (owner) {
+        for (int k = pl.lf; k < pl.kq[0] * 8; ++k) s0[k * P + lane] = 0.0f;
+        switch (F) {
+            case 1: field_encode<1>(L, xs, table, s0 + lane, P); break;
+            case 2: field_encode<2>(L, xs, table, s0 + lane, P); break;
+            case 4: field_encode<4>(L, xs, table, s0 + lane, P); break;
+            default: field_encode<8>(L, xs, table, s0 + lane, P); break;
+        }
+    }
+
+    // ---- head ----
+    for (int j = 0; j <= pl.m; ++j) {
+        __syncthreads();
+        const float* in = lds + lo.buf[j];
+        const float4* w = packed + pl.fwd_off[j];
+        const int nq = pl.kq[j];
+        if (j < pl.m) {
+            float* o = lds + lo.buf[j + 1];
+            if constexpr (NT > 0) {
+                f32x16 acc[NT][CT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) field_tile<CT>(w + (size_t)t * nq * 64, nq, in, lane, acc[t]);
+                __syncthreads();
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            o[(32 * t + acc_row(r, half)) * P + 32 * ct + col] = field_act<ACT>(acc[t][ct][r]);
+            } else
+            for (int t = 0; t < pl.tiles[j]; ++t) {
+                f32x16 acc[CT];
+                field_tile<CT>(w + (size_t)t * nq * 64, nq, in, lane, acc);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[(32 * t + acc_row(r, half)) * P + 32 * ct + col] = field_act<ACT>(acc[ct][r]);
+            }
+        } else {
+            f32x16 acc[CT];
+            field_tile<CT>(w, nq, in, lane, acc);   // n_out <= 16: one tile
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const int64_t q = first + 32 * ct + col;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int o = acc_row(r, half);
+                    if (q < n && o < pl.n_out) out[q * pl.n_out + o] = acc[ct][r];
+                }
+            }
+        }
+    }
+
+    if constexpr (GRAD) {
+        // ---- d_{m-1} = act'(h_{m-1}) W_m[0, :] ----
+        __syncthreads();
+        {
+            const float* w0 = (const float*)(packed + pl.row0_off);
+            float* hb = lds + lo.buf[pl.m];
+            const int rows = pl.tq[pl.m - 1] * 8;
+            if (owner)
+                for (int k = 0; k < rows; ++k) hb[k * P + lane] = field_act_grad<ACT>(hb[k * P + lane]) * w0[k];
+        }
+        // ---- G = W_l^T d_l;  d_{l-1} = act'(h_{l-1}) G in place, e = G at l = 0 ----
+        for (int l = pl.m - 1; l >= 0; --l) {
+            __syncthreads();
+            const float* din = lds + lo.buf[l + 1];
+            float* o = lds + lo.buf[l];
+            const float4* w = packed + pl.tr_off[l];
+            const int nq = pl.tq[l];
+            for (int t = 0; t < pl.ttiles[l]; ++t) {
+                f32x16 acc[CT];
+                field_tile<CT>(w + (size_t)t * nq * 64, nq, din, lane, acc);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float* q = o + (32 * t + acc_row(r, half)) * P + 32 * ct + col;
+                        *q = l > 0 ? field_act_grad<ACT>(*q) * acc[ct][r] : acc[ct][r];
+                    }
+            }
+        }
+        // ---- grad_d = sum_{l,f} e[l,f] J[l,f,d], the corner rows gathered again ----
+        __syncthreads();
+        if (owner) {
+            float g[3] = {0.0f, 0.0f, 0.0f};
+            switch (F) {
+                case 1: field_grad<1>(L, xs, table, s0 + lane, P, g); break;
+                case 2: field_grad<2>(L, xs, table, s0 + lane, P, g); break;
+                case 4: field_grad<4>(L, xs, table, s0 + lane, P, g); break;
+                default: field_grad<8>(L, xs, table, s0 + lane, P, g); break;
+            }
+            if (have) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) grad[3 * pt + d] = map.a[d] * g[d];
+            }
+        }
+    }
+}
+
+// one thread per float4 of the blob
+__global__ __launch_bounds__(256) void k_hg_field_pack(FieldPlan pl, const float* __restrict__ w, float4* __restrict__ dst) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= pl.total_f4) return;
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (e >= pl.row0_off) {                       // W_m[0, k], zero past n_neurons
+        const int k0 = (e - pl.row0_off) * 4;
+        for (int c = 0; c < 4; ++c)
+            if (k0 + c < pl.in[pl.m]) v[c] = w[pl.w_off[pl.m] + k0 + c];
+    } else {
+        int j = 0;
+        bool tr = false;
+        if (e >= pl.tr_off[0]) {
+            tr = true;
+            while (j + 1 < pl.m && e >= pl.tr_off[j + 1]) ++j;
+        } else {
+            while (j < pl.m && e >= pl.fwd_off[j + 1]) ++j;
+        }
+        const int r = e - (tr ? pl.tr_off[j] : pl.fwd_off[j]);
+        const int nq = tr ? pl.tq[j] : pl.kq[j];
+        const int lane = r & 63, q = (r >> 6) % nq, t = (r >> 6) / nq;
+        const int i = 32 * t + (lane & 31), h = lane >> 5;
+        const float* wj = w + pl.w_off[j];
+        for (int c = 0; c < 4; ++c) {
+            const int k = 8 * q + 2 * c + h;
+            if (!tr) {
+                if (i < pl.out[j] && k < pl.in[j]) v[c] = wj[(size_t)i * pl.in[j] + k];       // lane row i = output, k = input
+            } else {
+                if (i < pl.in[j] && k < pl.out[j]) v[c] = wj[(size_t)k * pl.in[j] + i];       // lane row i = input, k = output
+            }
+        }
+    }
+    dst[e] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+template <int ACT, bool GRAD, int CT, int NT>
+static int field_launch(const hg::Levels& L, const FieldPlan& pl, const FieldLds& lo, size_t lds_bytes, const float* p, int64_t n,
+                        const FieldMap& map, const float* table, const float4* packed, float* out, float* grad, hipStream_t st) {
+    if (lds_bytes > 64 * 1024)
+        IRON_HIP_TRY(hipFuncSetAttribute((const void*)k_hg_field<ACT, GRAD, CT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const int64_t blocks = (n + 32 * CT - 1) / (32 * CT);
+    hipLaunchKernelGGL((k_hg_field<ACT, GRAD, CT, NT>), dim3((unsigned)blocks), dim3(64), lds_bytes, st, L, pl, lo, p, n, map, table, packed,
+                       out, grad);
+    IRON_HIP_TRY(hipGetLastError());
+    return IRON_OK;
+}
+
+template <int ACT>
+static int field_dispatch(const hg::Levels& L, const FieldPlan& pl, const float* p, int64_t n, const FieldMap& map, const float* table,
+                          const float4* packed, float* out, float* grad, hipStream_t st) {
+    FieldLds lo;
+    if (!grad) {   // value: 64 points per wave always fit (at most 128 rows of 256 bytes); the hidden layers' tiles in registers
+        const size_t bytes = lds_layout(pl, false, 64, &lo);
+        switch (pl.tiles[0]) {
+            case 1: return field_launch<ACT, false, 2, 1>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+            case 2: return field_launch<ACT, false, 2, 2>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+            default: return field_launch<ACT, false, 2, 4>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+        }
+    }
+    size_t bytes = lds_layout(pl, true, 64, &lo);
+    if (bytes <= (size_t)kFieldLdsTwoTiles) return field_launch<ACT, true, 2, 0>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+    bytes = lds_layout(pl, true, 32, &lo);
+    return field_launch<ACT, true, 1, 0>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+}
+
+}  // namespace iron
+
+using namespace iron;
+
+extern "C" int iron_hashgrid_field_check(const iron_hashgrid_field_desc* desc, int64_t* n_weights_out) {
+    FieldPlan pl;
+    const int rc = make_plan(desc, &pl);
+    if (rc != IRON_OK) return rc;
+    if (n_weights_out) *n_weights_out = pl.n_weights;
+    return IRON_OK;
+}
+
+extern "C" size_t iron_hashgrid_field_pack_bytes(const iron_hashgrid_field_desc* desc) {
+    FieldPlan pl;
+    if (make_plan(desc, &pl) != IRON_OK) return 0;
+    return (size_t)pl.total_f4 * sizeof(float4);
+}
+
+extern "C" int iron_hashgrid_field_pack(const iron_hashgrid_field_desc* desc, const float* weights, void* packed, void* stream) {
+    FieldPlan pl;
+    const int rc = make_plan(desc, &pl);
+    if (rc != IRON_OK) return rc;
+    if (!weights || !packed || ((uintptr_t)packed & 15)) return IRON_ERR_BAD_ARG;
+    IRON_LAUNCH(k_hg_field_pack, blocks_for(pl.total_f4, 256), 256, (hipStream_t)stream, pl, weights, (float4*)packed);
+    return IRON_OK;
+}
+
+extern "C" int iron_hashgrid_field_eval(const iron_hashgrid_field_desc* desc, const float* p, int64_t n, const float* map_a3_or_null,
+                                        const float* map_b3_or_null, const float* table, const void* packed, float* out,
+                                        float* grad_or_null, void* stream) {
+    FieldPlan pl;
+    int rc = make_plan(desc, &pl);
+    if (rc != IRON_OK) return rc;
+    hg::Levels L;
+    int64_t n_params = 0;
+    rc = hg::make_levels(&desc->encoding, &L, &n_params);
+    if (rc != IRON_OK) return rc;
+    if (n < 0) return IRON_ERR_BAD_ARG;
+    if (n == 0) return IRON_OK;
+    if (!p || !table || !packed || !out || ((uintptr_t)packed & 15)) return IRON_ERR_BAD_ARG;
+    if (n > (int64_t)0x7fffffff * 32) return IRON_ERR_RANGE;
+    FieldMap map;
+    for (int d = 0; d < 3; ++d) {
+        map.a[d] = map_a3_or_null ? map_a3_or_null[d] : 1.0f;
+        map.b[d] = map_b3_or_null ? map_b3_or_null[d] : 0.0f;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const float4* pk = (const float4*)packed;
+    switch (pl.act) {
+        case IRON_FIELD_ACT_RELU: return field_dispatch<IRON_FIELD_ACT_RELU>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
+        case IRON_FIELD_ACT_SOFTPLUS: return field_dispatch<IRON_FIELD_ACT_SOFTPLUS>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
+        default: return field_dispatch<IRON_FIELD_ACT_NONE>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
+    }
+}

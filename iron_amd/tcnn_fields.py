@@ -6,9 +6,13 @@ nn.Linear layers (tiny-cuda-nn's MLPs carry no biases) with the configured activ
 gradient / get_all keep the reference's shapes and detach rules (tcnn_fields.py:26-66).  Points are taken in the unit cube, as the
 reference hands them to tcnn (the encoding clamps to [0, 1]).
 
+Inference has a fused form beside it: `eval_fused` / `as_callable` evaluate the encoding and the head, and on request d sdf / dx, in
+one launch of csrc/hashgrid_field.hip (exact-fp32 MFMA head, no autograd); training keeps the plain head.
+
 `TCNNRendering` and `TCNNNeRF` are not built: the reference's forwards are empty or mis-shaped (tcnn_fields.py:201-249)."""
 from __future__ import annotations
 
+import ctypes as C
 import json
 
 import torch
@@ -71,6 +75,8 @@ class TCNNSDF(nn.Module):
                 layers.append(_ACTIVATIONS[net["activation"]]())
         self.sdf_network = nn.Sequential(*layers)
         self.model = nn.Sequential(self.sdf_encoding, self.sdf_network)
+        self._network_config = dict(net, n_out=n_outputs_dims)    # plain attributes: the fused evaluation's shape and its
+        self._fused_cache = None                                  # packed weights (key, blob); neither is part of state_dict()
 
     def forward(self, inputs):
         return self.model(inputs)
@@ -98,3 +104,94 @@ class TCNNSDF(nn.Module):
         if not is_training:
             out, grad = out.detach(), grad.detach()
         return out[..., :1], out[..., 1:], grad
+
+    # ---- fused inference (csrc/hashgrid_field.hip): encoding and head in one launch, no autograd ----
+    def _fused_desc(self):
+        """The C descriptor of the fused evaluation; a shape the kernel is not built for raises an IronError that names the key."""
+        net, enc = self._network_config, self.sdf_encoding
+        if net["n_neurons"] not in (16, 32, 64, 128):
+            raise _lib.IronError("TCNNSDF.eval_fused: n_neurons = %r is not built (16 / 32 / 64 / 128)" % (net["n_neurons"],))
+        if not 1 <= net["n_hidden_layers"] <= 4:
+            raise _lib.IronError("TCNNSDF.eval_fused: n_hidden_layers = %r is not built (1 .. 4)" % (net["n_hidden_layers"],))
+        if not 1 <= net["n_out"] <= 16:
+            raise _lib.IronError("TCNNSDF.eval_fused: n_outputs_dims = %r is not built (1 .. 16)" % (net["n_out"],))
+        if enc.n_output_dims > 128:
+            raise _lib.IronError("TCNNSDF.eval_fused: n_levels * n_features_per_level = %d is not built (at most 128)" % enc.n_output_dims)
+        d = _lib.iron_hashgrid_field_desc()
+        d.encoding = enc.desc
+        d.n_neurons, d.n_hidden_layers, d.n_out = net["n_neurons"], net["n_hidden_layers"], net["n_out"]
+        d.activation = _lib.IRON_FIELD_ACT[net["activation"]]
+        return d
+
+    def fused_supported(self) -> bool:
+        try:
+            self._fused_desc()
+        except _lib.IronError:
+            return False
+        return True
+
+    def _fused_packed(self, desc, device):
+        """The head's weights in MFMA fragment order, repacked when a parameter was replaced or written in place."""
+        lin = [m.weight for m in self.sdf_network if isinstance(m, nn.Linear)]
+        key = (device,) + tuple((w.data_ptr(), w._version) for w in lin)
+        if self._fused_cache is not None and self._fused_cache[0] == key:
+            return self._fused_cache[1]
+        lib = _lib.load()
+        n_weights = C.c_int64(0)
+        _lib.check(lib.iron_hashgrid_field_check(C.byref(desc), C.byref(n_weights)))
+        for w in lin:
+            if w.device != device or w.dtype != torch.float32:
+                raise _lib.IronError("TCNNSDF.eval_fused: the head's weights must be float32 on x's device")
+        flat = torch.cat([w.detach().reshape(-1) for w in lin])
+        if flat.numel() != n_weights.value:
+            raise _lib.IronError("TCNNSDF.eval_fused: the head holds %d weights, the descriptor needs %d" % (flat.numel(), n_weights.value))
+        packed = torch.empty(lib.iron_hashgrid_field_pack_bytes(C.byref(desc)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(lib.iron_hashgrid_field_pack(C.byref(desc), flat.data_ptr(), packed.data_ptr(), _lib.stream_ptr(device)))
+        self._fused_cache = (key, packed)
+        return packed
+
+    def eval_fused(self, x, gradient=False, scale=None, offset=None):
+        """out [..., n_out], or (out, d out[..., 0] / dx [..., 3]) with gradient=True, at scale * x + offset (per axis; None: x itself),
+        in one launch.  Inference only: runs under no_grad, the results carry no graph."""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.IronError("TCNNSDF.eval_fused: x must be a CUDA (ROCm) tensor: iron_amd has no CPU path")
+        if x.dtype != torch.float32:
+            raise _lib.IronError("TCNNSDF.eval_fused: x must be float32, got %s" % (x.dtype,))
+        if x.dim() < 1 or x.shape[-1] != 3:
+            raise _lib.IronError("TCNNSDF.eval_fused: x must end in 3 coordinates, got %s" % (tuple(x.shape),))
+        desc = self._fused_desc()
+        table = self.sdf_encoding.params
+        if table.device != x.device or table.dtype != torch.float32:
+            raise _lib.IronError("TCNNSDF.eval_fused: the table must be float32 on x's device; call .cuda() first")
+        a, b = _map3(scale, "scale"), _map3(offset, "offset")
+        with torch.no_grad():
+            flat = x.detach().reshape(-1, 3).contiguous()
+            n, n_out = flat.shape[0], desc.n_out
+            packed = self._fused_packed(desc, x.device)
+            out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
+            grad = torch.empty((n, 3), dtype=torch.float32, device=x.device) if gradient else None
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().iron_hashgrid_field_eval(C.byref(desc), flat.data_ptr(), n, a, b, table.detach().contiguous().data_ptr(),
+                                                                packed.data_ptr(), out.data_ptr(), _lib.ptr(grad), _lib.stream_ptr(x.device)))
+        out = out.reshape(*x.shape[:-1], n_out)
+        return (out, grad.reshape(x.shape)) if gradient else out
+
+    def as_callable(self, scale=None, offset=None):
+        """The signed distance (column 0 of eval_fused) at scale * x + offset as an SDFCallable: the form to hand to RayTracer.forward
+        and extract_fields_gpu, which work in the unit sphere while the field lives in the unit cube (scale = offset = 0.5)."""
+        from .raytracer import SDFCallable
+        self._fused_desc()
+        return SDFCallable(lambda x: self.eval_fused(x, scale=scale, offset=offset)[..., 0])
+
+
+def _map3(v, name):
+    """None, a number or three numbers -> None or a float[3] for the C ABI"""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        v = v.detach().cpu().tolist()
+    vals = [float(v)] * 3 if isinstance(v, (int, float)) else [float(c) for c in v]
+    if len(vals) != 3:
+        raise _lib.IronError("TCNNSDF.eval_fused: %s must be a number or three numbers, got %r" % (name, v))
+    return (C.c_float * 3)(*vals)
