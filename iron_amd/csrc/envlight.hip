@@ -14,13 +14,14 @@
 // a fixed order: reproducible); a direction is uniform in (u, v) inside its texel, so its solid-angle density is
 // P(texel) We He / (2 pi^2 sin theta).
 //
-// Integrator (k_shade_env): kEnvGroup lanes work one pixel; sample s of the pixel's n_light + n_brdf runs on lane s % kEnvGroup in
-// round s / kEnvGroup, every lane adds its rounds in order, and a fixed butterfly adds the lanes: a pixel's sums depend on nothing
-// but its own samples.  Random numbers: env_rand, a pure function of (seed, pixel index, sample, dimension).
+// Integrators: the estimator (vertex, sample draws, terms, pixel reduction) is written once, in the section of that name; a pixel's
+// sums depend on nothing but its own samples.  k_shade_env runs the direct estimator on the mesh.  Random numbers: env_rand, a pure
+// function of (seed, pixel index, sample, dimension).
 //
 // Interreflections (k_shade_env_indirect): the light that reaches a primary hit after at least one more surface, by
-// paths of a fixed largest length.  The same lane scheme with a path in a sample's place; the bounce rays walk bvh_closest_hit of
-// ray_walk.h (k_raycast's walk), the shadow rays bvh_any_hit, both on the one LDS stack in turn.  The direct term stays k_shade_env's.
+// paths of a fixed largest length; the bounce rays walk bvh_closest_hit of ray_walk.h (k_raycast's walk), the shadow rays
+// bvh_any_hit, both on the one LDS stack in turn.  The direct term stays k_shade_env's.  The k_nenv_* and k_npath_* kernels run the
+// same two estimators on the neural scene.
 #include "asset_common.h"
 #include "ggx_core.h"
 #include "pair_scan.h"
@@ -389,12 +390,202 @@ __device__ __forceinline__ bool dir_counts(float3 n, float3 ng, float ngv, float
     return dot3(n, w) > 0.0f && dot3(ng, w) * ngv > 0.0f && finite3(w);
 }
 
-// V(w) of the integrators: w counts and the shadow ray from x meets no face other than x's own
-__device__ __forceinline__ bool env_visible(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf, float3 x, float3 n,
-                                            float3 ng, float ngv, float3 w, float off, int32_t face, int32_t (*stack)[kBvQueryBlock],
-                                            int lane) {
-    if (!dir_counts(n, ng, ngv, w)) return false;
-    const float3 org = leave_origin(x, ng, dot3(ng, w), off);
+// ---- the estimator ----
+// What the four integrators below share, written once: the shading vertex, the two sample draws, the terms, the pixel reduction.
+// A scene supplies two things.  The origin of a ray that leaves a vertex: leave_origin along n_g on the mesh, offset_origin on the
+// neural scene, whose vertices carry the shading normal in the geometric normal's place.  And the answer to visibility and closest
+// hit: the mesh walks its BVH in place, the neural scene reads the sphere tracer's listed answer.  With -ffp-contract=off one
+// expression gives one result, so the scenes agree bit for bit where their inputs do.
+struct EnvVertex {
+    float3 pt, n, ng, v;  // point, shading normal, geometric normal, direction back to the viewer or along the path
+    float mat[7];         // diffuse albedo, specular albedo, roughness
+};
+
+__device__ __forceinline__ void vertex_clear(EnvVertex& x) {
+    x.pt = x.n = x.ng = x.v = make_float3(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) x.mat[c] = 0.0f;
+}
+
+__device__ __forceinline__ float vertex_alpha(const EnvVertex& x) { return fmaxf(x.mat[6], 0.0001f); }
+
+// BRDF . cos of the vertex for the light direction w
+__device__ __forceinline__ void vertex_brdf(const EnvVertex& x, float3 w, const float* __restrict__ tab_trans,
+                                            const float* __restrict__ tab_diff, PlasticOut& f) {
+    const float nn[3] = {x.n.x, x.n.y, x.n.z}, vv[3] = {x.v.x, x.v.y, x.v.z}, ww[3] = {w.x, w.y, w.z};
+    roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], tab_trans, tab_diff, f);
+}
+
+// the neural scene's ray origin: x + eps n, each product and sum rounded on its own
+__device__ __forceinline__ float3 offset_origin(float3 x, float3 n, float eps) {
+    const float ex = eps * n.x, ey = eps * n.y, ez = eps * n.z;
+    return make_float3(x.x + ex, x.y + ey, x.z + ez);
+}
+
+// Sample k of a vertex's direct light: an environment sample for k < n_light, else a BRDF sample; random dimensions 0, 1, 2 of
+// (seed, pixel, k).  As declared: no sample.
+struct DirectDraw {
+    float3 w = make_float3(0.f, 0.f, 0.f);  // the direction (zero: no sample)
+    float denom = 0.0f;                     // the balance heuristic's n_light p_light + n_brdf p_brdf
+    float L[3] = {0.f, 0.f, 0.f};           // the map's radiance along w
+    bool counts = false;                    // w is a sample, and one that dir_counts lets through
+};
+
+__device__ __forceinline__ void draw_direct(const EnvDev& env, uint32_t seed, uint32_t pixel, int32_t k, int32_t n_light, int32_t n_brdf,
+                                            const EnvVertex& x, DirectDraw& s) {
+    const float alpha = vertex_alpha(x);
+    float pl;
+    bool ok;
+    if (k < n_light) {
+        int r, c;
+        pl = env_sample(env, env_rand(seed, pixel, k, 0), env_rand(seed, pixel, k, 1), r, c, s.w);
+        const float* p = env.image + 3 * ((int64_t)r * env.We + c);
+        s.L[0] = p[0]; s.L[1] = p[1]; s.L[2] = p[2];
+        ok = true;
+    } else {
+        ok = brdf_sample(x.n, x.v, alpha, env_rand(seed, pixel, k, 0), env_rand(seed, pixel, k, 1), env_rand(seed, pixel, k, 2), s.w);
+        if (!ok) s.w = make_float3(0.f, 0.f, 0.f);
+        pl = env_eval(env, s.w, s.L);
+    }
+    const float pb = ok ? brdf_pdf(x.n, x.v, s.w, alpha) : 0.0f;
+    s.denom = (n_light > 0 ? (float)n_light * pl : 0.0f) + (n_brdf > 0 ? (float)n_brdf * pb : 0.0f);
+    s.counts = dir_counts(x.n, x.ng, dot3(x.ng, x.v), s.w);  // no sample: w is zero, which never counts
+}
+
+// The two samples of vertex j of path p (vertex 0 is the primary hit), random dimensions 8 (j + 1) + c of (seed, pixel, p):
+// c = 0, 1, 2 the BRDF sample that continues the path, c = 3, 4 the environment sample (vertices j >= 1: the primary's direct light
+// is the direct estimator's).  As declared: no sample.
+struct VertexDraw {
+    float3 wl = make_float3(0.f, 0.f, 0.f), wb = wl;         // light direction, bounce direction (zero: no sample)
+    float dl = 0.0f, db = 0.0f, pb = 0.0f;                   // the two denominators p_light + p_brdf, and p_brdf(w_b)
+    float Ll[3] = {0.f, 0.f, 0.f}, Lb[3] = {0.f, 0.f, 0.f};  // the map's radiance along the two
+    bool lcounts = false, bcounts = false;                   // the light / the bounce direction is a sample that dir_counts lets through
+};
+
+__device__ __forceinline__ void draw_vertex(const EnvDev& env, uint32_t seed, uint32_t pixel, int32_t p, int32_t j, const EnvVertex& x,
+                                            VertexDraw& s) {
+    const uint32_t dim = 8u * (uint32_t)(j + 1);
+    const float alpha = vertex_alpha(x), ngv = dot3(x.ng, x.v);
+    if (j >= 1) {
+        int r, c;
+        const float pl = env_sample(env, env_rand(seed, pixel, p, dim + 3u), env_rand(seed, pixel, p, dim + 4u), r, c, s.wl);
+        const float* L = env.image + 3 * ((int64_t)r * env.We + c);
+        s.Ll[0] = L[0]; s.Ll[1] = L[1]; s.Ll[2] = L[2];
+        s.dl = pl + brdf_pdf(x.n, x.v, s.wl, alpha);
+        s.lcounts = dir_counts(x.n, x.ng, ngv, s.wl);
+    }
+    const bool ok = brdf_sample(x.n, x.v, alpha, env_rand(seed, pixel, p, dim), env_rand(seed, pixel, p, dim + 1u),
+                                env_rand(seed, pixel, p, dim + 2u), s.wb);
+    if (!ok) s.wb = make_float3(0.f, 0.f, 0.f);
+    s.bcounts = ok && dir_counts(x.n, x.ng, ngv, s.wb);
+    if (s.bcounts) {
+        const float pl = env_eval(env, s.wb, s.Lb);
+        s.pb = brdf_pdf(x.n, x.v, s.wb, alpha);
+        s.db = pl + s.pb;
+    }
+}
+
+// the two lobes of a direct sample
+__device__ __forceinline__ void direct_terms(const float L[3], const PlasticOut& f, float denom, float cd[3], float cs[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        cd[c] = L[c] * f.diffuse[c] / denom;  // an infinite density (the map's poles) gives 0
+        cs[c] = L[c] * f.specular[c] / denom;
+    }
+}
+
+// what a path of throughput T gathers at a vertex from its environment sample ...
+__device__ __forceinline__ void light_term(const float T[3], const float L[3], const PlasticOut& f, float dl, float lt[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lt[c] = (T[c] * L[c]) * (f.diffuse[c] + f.specular[c]) / dl;  // an infinite density gives 0
+}
+
+// ... and through its BRDF sample when that escapes: the same estimator over the other denominator
+__device__ __forceinline__ void escape_term(const float T[3], const float L[3], const PlasticOut& f, float db, float et[3]) {
+    light_term(T, L, f, db, et);
+}
+
+// is y, met along w_b, the path's next vertex?  A surface met from behind is black, like a back-facing primary hit
+__device__ __forceinline__ bool path_goes_on(const EnvVertex& y, float3 wb, float pb) { return -dot3(y.ng, wb) > 0.0f && pb > 0.0f; }
+
+// the step to the next vertex: the primary's two lobe weights f_d / p_brdf and f_s / p_brdf stay apart (they multiply what the path
+// gathered when it ends); after it T, the throughput past the primary, takes (f_d + f_s) / p_brdf
+__device__ __forceinline__ void advance(int32_t j, const PlasticOut& f, float pb, float T[3], float bd[3], float bs[3]) {
+    if (j == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            bd[c] = f.diffuse[c] / pb;
+            bs[c] = f.specular[c] / pb;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T[c] = T[c] * (f.diffuse[c] + f.specular[c]) / pb;
+    }
+}
+
+__device__ __forceinline__ void add3(float acc[3], const float t[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += t[c];
+}
+
+// The pixel reduction: kEnvGroup lanes work one pixel, item k (a sample, a path) on lane k % kEnvGroup in round k / kEnvGroup;
+// every lane adds its rounds in order and a fixed butterfly adds the lanes.  The order is part of the contract.
+template <class Body>
+__device__ __forceinline__ void for_each_of_pixel(int32_t n, int sl, Body body) {
+    for (int32_t base = 0; base < n; base += kEnvGroup) {
+        const int32_t k = base + sl;
+        if (k >= n) break;  // the ragged tail of the last round
+        body(k);
+    }
+}
+
+__device__ __forceinline__ void group_sum16(float accd[3], float accs[3]) {
+#pragma unroll
+    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
+            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
+        }
+}
+
+__device__ __forceinline__ void store_direct_dump(const iron_env_dump& dump, int64_t at, const DirectDraw& q, bool vis, const float cd[3],
+                                                  const float cs[3]) {
+    st3(dump.dir, at, q.w.x, q.w.y, q.w.z);
+    if (dump.denom) dump.denom[at] = q.denom;
+    if (dump.vis) dump.vis[at] = vis ? 1 : 0;
+    st3(dump.contrib, at, cd[0] + cs[0], cd[1] + cs[1], cd[2] + cs[2]);
+}
+
+// what both scenes' path dumps record of vertex j (iron_env_path_dump, iron_neural_path_dump: the fields of the same name)
+template <class Dump>
+__device__ __forceinline__ void store_vertex_dump(const Dump& dump, int64_t at, const VertexDraw& q, float3 org, bool lvis, const float lt[3],
+                                                  const float et[3], const float tp[3]) {
+    st3(dump.bounce_dir, at, q.wb.x, q.wb.y, q.wb.z);
+    st3(dump.bounce_org, at, org.x, org.y, org.z);
+    st3(dump.light_dir, at, q.wl.x, q.wl.y, q.wl.z);
+    if (dump.light_vis) dump.light_vis[at] = lvis ? 1 : 0;
+    if (dump.denom_light) dump.denom_light[at] = q.dl;
+    if (dump.denom_brdf) dump.denom_brdf[at] = q.db;
+    st3(dump.light_term, at, lt[0], lt[1], lt[2]);
+    st3(dump.escape_term, at, et[0], et[1], et[2]);
+    st3(dump.throughput, at, tp[0], tp[1], tp[2]);
+}
+
+// ---- the mesh ----
+__device__ __forceinline__ void mesh_vertex(const iron_asset_mesh& m, const SurfHit& s, EnvVertex& x) {
+    x.pt = s.pt; x.n = s.nrm;
+    x.ng = asset_face_normal(m, s);
+    x.v = make_float3(-s.d.x, -s.d.y, -s.d.z);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) x.mat[c] = s.mat[c];
+}
+
+// V(w) for a direction that counts at x: the shadow ray from x meets no face other than x's own
+__device__ __forceinline__ bool mesh_unoccluded(const float4* __restrict__ nodes, const float4* __restrict__ tris, int64_t nf,
+                                                const EnvVertex& x, int32_t face, float3 w, float off, int32_t (*stack)[kBvQueryBlock],
+                                                int lane) {
+    const float3 org = leave_origin(x.pt, x.ng, dot3(x.ng, w), off);
     if (!ray_valid(org, w)) return false;
     RayPre r;
     ray_setup(org, w, r);
@@ -408,68 +599,31 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env(EnvShadeArgs a) {
     if (i >= a.n) return;  // a whole group leaves together
     SurfHit s;
     asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s);
+    EnvVertex x;
+    mesh_vertex(a.m, s, x);
     const int32_t N = a.n_light + a.n_brdf;
     const uint32_t pixel = a.pixel_idx ? (uint32_t)a.pixel_idx[i] : (uint32_t)i;
-    float3 ng = make_float3(0.f, 0.f, 0.f), v = ng;
-    float off = 0.0f, ngv = 0.0f, alpha = 0.0f;
-    if (s.hit) {
-        ng = asset_face_normal(a.m, s);
-        v = make_float3(-s.d.x, -s.d.y, -s.d.z);
-        ngv = dot3(ng, v);
-        off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
-        alpha = fmaxf(s.mat[6], 0.0001f);
-    }
-    const float nn[3] = {s.nrm.x, s.nrm.y, s.nrm.z}, vv[3] = {v.x, v.y, v.z};
+    const float off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
     float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
-    for (int32_t base = 0; base < N; base += kEnvGroup) {
-        const int32_t k = base + sl;
-        if (k >= N) break;  // the ragged tail of the last round
-        float3 w = make_float3(0.f, 0.f, 0.f);
-        float denom = 0.0f, cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
+    for_each_of_pixel(N, sl, [&](int32_t k) {
+        DirectDraw q;
+        float cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
         bool vis = false;
         if (s.hit) {
-            float L[3], pl;
-            bool ok;
-            if (k < a.n_light) {
-                int r, c;
-                pl = env_sample(a.env, env_rand(a.seed, pixel, k, 0), env_rand(a.seed, pixel, k, 1), r, c, w);
-                const float* p = a.env.image + 3 * ((int64_t)r * a.env.We + c);
-                L[0] = p[0]; L[1] = p[1]; L[2] = p[2];
-                ok = true;
-            } else {
-                ok = brdf_sample(s.nrm, v, alpha, env_rand(a.seed, pixel, k, 0), env_rand(a.seed, pixel, k, 1), env_rand(a.seed, pixel, k, 2), w);
-                if (!ok) w = make_float3(0.f, 0.f, 0.f);
-                pl = env_eval(a.env, w, L);
-            }
-            const float pb = ok ? brdf_pdf(s.nrm, v, w, alpha) : 0.0f;
-            denom = (a.n_light > 0 ? (float)a.n_light * pl : 0.0f) + (a.n_brdf > 0 ? (float)a.n_brdf * pb : 0.0f);
-            vis = ok && env_visible(a.nodes, a.tris, a.m.n_faces, s.pt, s.nrm, ng, ngv, w, off, (int32_t)s.face, stack, lane);
-            if (vis && denom > 0.0f) {
+            draw_direct(a.env, a.seed, pixel, k, a.n_light, a.n_brdf, x, q);
+            // the shadow ray is cast, and its answer dumped, whatever the denominator
+            vis = q.counts && mesh_unoccluded(a.nodes, a.tris, a.m.n_faces, x, (int32_t)s.face, q.w, off, stack, lane);
+            if (vis && q.denom > 0.0f) {
                 PlasticOut f;
-                const float ww[3] = {w.x, w.y, w.z};
-                roughplastic_point(nn, vv, ww, s.mat, s.mat + 3, s.mat[6], a.tab_trans, a.tab_diff, f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    cd[c] = L[c] * f.diffuse[c] / denom;  // an infinite density (the map's poles) gives 0
-                    cs[c] = L[c] * f.specular[c] / denom;
-                    accd[c] += cd[c];
-                    accs[c] += cs[c];
-                }
+                vertex_brdf(x, q.w, a.tab_trans, a.tab_diff, f);
+                direct_terms(q.L, f, q.denom, cd, cs);
+                add3(accd, cd);
+                add3(accs, cs);
             }
         }
-        const int64_t at = i * N + k;
-        st3(a.dump.dir, at, w.x, w.y, w.z);
-        if (a.dump.denom) a.dump.denom[at] = denom;
-        if (a.dump.vis) a.dump.vis[at] = vis ? 1 : 0;
-        st3(a.dump.contrib, at, cd[0] + cs[0], cd[1] + cs[1], cd[2] + cs[2]);
-    }
-#pragma unroll
-    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
-            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
-        }
+        store_direct_dump(a.dump, i * N + k, q, vis, cd, cs);
+    });
+    group_sum16(accd, accs);
     if (sl != 0) return;
     st3(a.o.color, i, accd[0] + accs[0], accd[1] + accs[1], accd[2] + accs[2]);
     st3(a.o.diffuse_color, i, accd[0], accd[1], accd[2]);
@@ -492,28 +646,9 @@ struct EnvPathArgs {
     float shadow_eps;
 };
 
-// what a path keeps of its current vertex
-struct PathVertex {
-    float3 pt, nrm, ng, v;  // point, shading normal, geometric normal, direction back along the path
-    float mat[7];
-    int32_t face;
-};
-
-__device__ __forceinline__ void path_vertex(const iron_asset_mesh& m, const SurfHit& s, PathVertex& x) {
-    x.pt = s.pt; x.nrm = s.nrm;
-    x.ng = asset_face_normal(m, s);
-    x.v = make_float3(-s.d.x, -s.d.y, -s.d.z);
-#pragma unroll
-    for (int c = 0; c < 7; ++c) x.mat[c] = s.mat[c];
-    x.face = (int32_t)s.face;
-}
-
-// Path p of a pixel runs on lane p % kEnvGroup in round p / kEnvGroup.  Vertex 0 is the primary hit; at vertex j the random numbers
-// are env_rand(seed, pixel, p, 8 (j + 1) + c): c = 0, 1, 2 the BRDF sample that continues the path, c = 3, 4 the environment sample
-// (vertices j >= 1: the primary's direct light is k_shade_env's).  T is the throughput past the primary, the product of
-// (f_d + f_s) / p_brdf over the vertices 1 .. j; the primary's own two lobe weights f_d / p_brdf and f_s / p_brdf stay apart and
-// multiply what the path gathered, C, when it ends.  Every vertex runs the same code, the last one included (its closest hit decides
-// between the escape term and nothing), so the first D' vertices of a path do not depend on max_depth.
+// A path in a sample's place in the pixel reduction; C is what the path gathered.  Every vertex runs the same code, the last one
+// included (its closest hit decides between the escape term and nothing), so the first D' vertices of a path do not depend on
+// max_depth.
 __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArgs a) {
     __shared__ int32_t stack[kBvStack][kBvQueryBlock];
     const int lane = threadIdx.x, sl = lane % kEnvGroup;
@@ -522,94 +657,61 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArg
     const uint32_t pixel = a.pixel_idx ? (uint32_t)a.pixel_idx[i] : (uint32_t)i;
     const float off = a.shadow_eps * bvh_diagonal(a.nodes, a.tris, a.m.n_faces);
     const int32_t D = a.max_depth;
-    PathVertex x0;
-    bool hit0;
-    {
-        SurfHit s;
-        asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s);
-        hit0 = s.hit;
-        path_vertex(a.m, s, x0);
-    }
+    SurfHit s0;
+    asset_surface(a.m, a.face_idx, a.t, a.ray_o, a.ray_d, a.bary, i, s0);
+    EnvVertex x0;
+    mesh_vertex(a.m, s0, x0);
     float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
-    for (int32_t base = 0; base < a.n_paths; base += kEnvGroup) {
-        const int32_t p = base + sl;
-        if (p >= a.n_paths) break;  // the ragged tail of the last round
-        PathVertex x = x0;
+    for_each_of_pixel(a.n_paths, sl, [&](int32_t p) {
+        EnvVertex x = x0;
+        int32_t face = (int32_t)s0.face;
         float T[3] = {1.f, 1.f, 1.f}, C[3] = {0.f, 0.f, 0.f}, bd[3] = {0.f, 0.f, 0.f}, bs[3] = {0.f, 0.f, 0.f};
-        bool alive = hit0;
+        bool alive = s0.hit;
         for (int32_t j = 0; j < D; ++j) {
-            float3 wl = make_float3(0.f, 0.f, 0.f), wb = wl, org = wl;
-            float dl = 0.0f, db = 0.0f, th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
+            VertexDraw q;
+            float3 org = make_float3(0.f, 0.f, 0.f);
+            float th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
             bool lvis = false;
             int32_t reached = -2;
             if (alive) {
                 alive = false;  // until the vertex hands the path on
-                const uint32_t dim = 8u * (uint32_t)(j + 1);
-                const float alpha = fmaxf(x.mat[6], 0.0001f), ngv = dot3(x.ng, x.v);
-                const float nn[3] = {x.nrm.x, x.nrm.y, x.nrm.z}, vv[3] = {x.v.x, x.v.y, x.v.z};
-                if (j >= 1) {  // the environment sample
-                    int r, c;
-                    const float pl = env_sample(a.env, env_rand(a.seed, pixel, p, dim + 3u), env_rand(a.seed, pixel, p, dim + 4u), r, c, wl);
-                    const float* L = a.env.image + 3 * ((int64_t)r * a.env.We + c);
-                    dl = pl + brdf_pdf(x.nrm, x.v, wl, alpha);
-                    lvis = env_visible(a.nodes, a.tris, a.m.n_faces, x.pt, x.nrm, x.ng, ngv, wl, off, x.face, stack, lane);
-                    if (lvis && dl > 0.0f) {
-                        PlasticOut f;
-                        const float ww[3] = {wl.x, wl.y, wl.z};
-                        roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
-#pragma unroll
-                        for (int c3 = 0; c3 < 3; ++c3) {
-                            lt[c3] = (T[c3] * L[c3]) * (f.diffuse[c3] + f.specular[c3]) / dl;  // an infinite density gives 0
-                            C[c3] += lt[c3];
-                        }
-                    }
+                draw_vertex(a.env, a.seed, pixel, p, j, x, q);
+                lvis = q.lcounts && mesh_unoccluded(a.nodes, a.tris, a.m.n_faces, x, face, q.wl, off, stack, lane);
+                if (lvis && q.dl > 0.0f) {
+                    PlasticOut f;
+                    vertex_brdf(x, q.wl, a.tab_trans, a.tab_diff, f);
+                    light_term(T, q.Ll, f, q.dl, lt);
+                    add3(C, lt);
                 }
-                // the BRDF sample and its ray
-                const bool ok = brdf_sample(x.nrm, x.v, alpha, env_rand(a.seed, pixel, p, dim), env_rand(a.seed, pixel, p, dim + 1u),
-                                            env_rand(a.seed, pixel, p, dim + 2u), wb);
-                if (!ok) wb = make_float3(0.f, 0.f, 0.f);
-                if (ok && dir_counts(x.nrm, x.ng, ngv, wb)) {
-                    float L[3];
-                    const float pl = env_eval(a.env, wb, L), pb = brdf_pdf(x.nrm, x.v, wb, alpha);
-                    db = pl + pb;
-                    org = leave_origin(x.pt, x.ng, dot3(x.ng, wb), off);
-                    if (ray_valid(org, wb)) {
+                if (q.bcounts) {
+                    org = leave_origin(x.pt, x.ng, dot3(x.ng, q.wb), off);
+                    if (ray_valid(org, q.wb)) {
                         RayPre r;
-                        ray_setup(org, wb, r);
+                        ray_setup(org, q.wb, r);
                         RayHit h = ray_hit_none(kInfF);
-                        bvh_closest_hit(a.nodes, a.tris, a.m.n_faces, r, 0.0f, x.face, stack, lane, h);
+                        bvh_closest_hit(a.nodes, a.tris, a.m.n_faces, r, 0.0f, face, stack, lane, h);
                         const bool hit = h.face != kNoFace;
-                        if (hit) refine_bary(a.tris, org, wb, h);
+                        if (hit) refine_bary(a.tris, org, q.wb, h);
                         reached = hit ? h.face : -1;
                         th = hit ? h.t : kInfF;
                         PlasticOut f;
-                        const float ww[3] = {wb.x, wb.y, wb.z};
-                        roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+                        vertex_brdf(x, q.wb, a.tab_trans, a.tab_diff, f);
                         if (!hit) {
-                            if (j >= 1 && db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
-#pragma unroll
-                                for (int c = 0; c < 3; ++c) {
-                                    et[c] = (T[c] * L[c]) * (f.diffuse[c] + f.specular[c]) / db;
-                                    C[c] += et[c];
-                                }
+                            if (j >= 1 && q.db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
+                                escape_term(T, q.Lb, f, q.db, et);
+                                add3(C, et);
                             }
                         } else {
                             SurfHit s;
-                            asset_surface_at(a.m, h.face, h.t, org, wb, h.b1, h.b2, s);
-                            const float3 ng2 = asset_face_normal(a.m, s);
-                            // a face met from behind is black, like a back-facing primary hit
-                            if (s.hit && -dot3(ng2, wb) > 0.0f && pb > 0.0f) {
+                            asset_surface_at(a.m, h.face, h.t, org, q.wb, h.b1, h.b2, s);
+                            EnvVertex y;
+                            mesh_vertex(a.m, s, y);
+                            if (s.hit && path_goes_on(y, q.wb, q.pb)) {
+                                advance(j, f, q.pb, T, bd, bs);
 #pragma unroll
-                                for (int c = 0; c < 3; ++c) {
-                                    if (j == 0) {
-                                        bd[c] = f.diffuse[c] / pb;
-                                        bs[c] = f.specular[c] / pb;
-                                    } else {
-                                        T[c] = T[c] * (f.diffuse[c] + f.specular[c]) / pb;
-                                    }
-                                    tp[c] = T[c];
-                                }
-                                path_vertex(a.m, s, x);
+                                for (int c = 0; c < 3; ++c) tp[c] = T[c];
+                                x = y;
+                                face = (int32_t)s.face;
                                 alive = true;
                             }
                         }
@@ -617,17 +719,9 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArg
                 }
             }
             const int64_t at = ((int64_t)i * a.n_paths + p) * D + j;
-            st3(a.dump.bounce_dir, at, wb.x, wb.y, wb.z);
-            st3(a.dump.bounce_org, at, org.x, org.y, org.z);
+            store_vertex_dump(a.dump, at, q, org, lvis, lt, et, tp);
             if (a.dump.face) a.dump.face[at] = reached;
             if (a.dump.t) a.dump.t[at] = th;
-            st3(a.dump.light_dir, at, wl.x, wl.y, wl.z);
-            if (a.dump.light_vis) a.dump.light_vis[at] = lvis ? 1 : 0;
-            if (a.dump.denom_light) a.dump.denom_light[at] = dl;
-            if (a.dump.denom_brdf) a.dump.denom_brdf[at] = db;
-            st3(a.dump.light_term, at, lt[0], lt[1], lt[2]);
-            st3(a.dump.escape_term, at, et[0], et[1], et[2]);
-            st3(a.dump.throughput, at, tp[0], tp[1], tp[2]);
         }
         st3(a.dump.lobe_diffuse, (int64_t)i * a.n_paths + p, bd[0], bd[1], bd[2]);
         st3(a.dump.lobe_specular, (int64_t)i * a.n_paths + p, bs[0], bs[1], bs[2]);
@@ -636,14 +730,8 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArg
             accd[c] += bd[c] * C[c];
             accs[c] += bs[c] * C[c];
         }
-    }
-#pragma unroll
-    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
-            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
-        }
+    });
+    group_sum16(accd, accs);
     if (sl != 0) return;
     const float np = (float)a.n_paths;
     st3(a.indirect_diffuse, i, accd[0] / np, accd[1] / np, accd[2] / np);
@@ -651,17 +739,16 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_shade_env_indirect(EnvPathArg
 }
 
 // ---- the neural scene ----
-// The direct integrator of k_shade_env on a G-buffer of the neural scene (iron_amd/neural_relight.py), its shadow rays answered
-// by the sphere tracer (iron_trace_occluded) instead of a BVH walk, in three steps on one stream:
-//   k_nenv_emit     sample k of pixel i on lane k % kEnvGroup of the pixel's group, as in k_shade_env; the direction of every
-//                   sample goes to a dense [pixels, N, 3] array and a 0/1 flag -- the sample counts and its denominator is > 0 -- to
-//                   level 0 of a pair_scan; k_nenv_compact then lists the flagged samples' rays in ascending (pixel, sample) order;
+// The direct estimator on a G-buffer of the neural scene (iron_amd/neural_relight.py), its shadow rays answered by the sphere
+// tracer (iron_trace_occluded) instead of a BVH walk, in three steps on one stream:
+//   k_nenv_emit     draws every sample of the pixel reduction; its direction goes to a dense [pixels, N, 3] array and a 0/1 flag
+//                   -- the sample counts and its denominator is > 0 -- to level 0 of a pair_scan; k_nenv_compact then lists the
+//                   flagged samples' rays in ascending (pixel, sample) order;
 //   (the caller)    intersect_sphere and iron_trace_occluded on the list;
 //   k_nenv_scatter  the answers back to a [pixels, N] byte array of visibilities, and k_nenv_resolve draws every sample again
-//                   from the hash (nenv_sample: the one function both kernels run) and adds the visible ones' terms in k_shade_env's
-//                   order.
-// There is no geometric normal: the shading normal stands in dir_counts's second place, so a sample counts when n.w > 0, n.v > 0
-// and w is finite.  A block of pixels [p0, p0 + nb) is worked per call; nothing a pixel gets depends on the block it is in.
+//                   from the hash and adds the visible ones' terms.
+// There is no geometric normal: a vertex carries the shading normal in its place, so a sample counts when n.w > 0, n.v > 0 and w is
+// finite.  A block of pixels [p0, p0 + nb) is worked per call; nothing a pixel gets depends on the block it is in.
 struct NeuralEnvArgs {
     iron_neural_gbuffer g;
     iron_env_dump dump;
@@ -692,75 +779,42 @@ inline NeuralEnvLayout nenv_layout(int64_t n_samples) {
     return L;
 }
 
-struct NeuralPixel {
-    bool hit;
-    float3 x, n, v;
-    float nv, alpha, mat[7];
-    uint32_t pixel;
-};
-
-__device__ __forceinline__ void nenv_pixel(const iron_neural_gbuffer& g, int64_t i, NeuralPixel& px) {
-    px.hit = g.hit[i] != 0;
-    px.x = px.n = px.v = make_float3(0.f, 0.f, 0.f);
-    px.nv = px.alpha = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) px.mat[c] = 0.0f;
-    px.pixel = g.pixel_idx ? (uint32_t)g.pixel_idx[i] : (uint32_t)i;
-    if (!px.hit) return;
-    px.x = ld3(g.points, i);
-    px.n = ld3(g.normal, i);
+// pixel i of the G-buffer as a vertex (zeros on a miss); true on a hit
+__device__ __forceinline__ bool gbuffer_vertex(const iron_neural_gbuffer& g, int64_t i, EnvVertex& x) {
+    vertex_clear(x);
+    if (g.hit[i] == 0) return false;
+    x.pt = ld3(g.points, i);
+    x.n = x.ng = ld3(g.normal, i);
     const float3 d = ld3(g.ray_d, i);
-    px.v = make_float3(-d.x, -d.y, -d.z);
-    px.nv = dot3(px.n, px.v);
+    x.v = make_float3(-d.x, -d.y, -d.z);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { px.mat[c] = g.diffuse_albedo[3 * i + c]; px.mat[3 + c] = g.specular_albedo[3 * i + c]; }
-    px.mat[6] = g.specular_roughness[i];
-    px.alpha = fmaxf(px.mat[6], 0.0001f);
+    for (int c = 0; c < 3; ++c) { x.mat[c] = g.diffuse_albedo[3 * i + c]; x.mat[3 + c] = g.specular_albedo[3 * i + c]; }
+    x.mat[6] = g.specular_roughness[i];
+    return true;
 }
 
-// sample k of a hit pixel, as k_shade_env draws it: the direction (zero: no sample), the balance heuristic's denominator, the
-// map's radiance along it; true when the sample counts
-__device__ __forceinline__ bool nenv_sample(const NeuralEnvArgs& a, const NeuralPixel& px, int32_t k, float3& w, float& denom, float L[3]) {
-    float pl;
-    bool ok;
-    if (k < a.n_light) {
-        int r, c;
-        pl = env_sample(a.env, env_rand(a.seed, px.pixel, k, 0), env_rand(a.seed, px.pixel, k, 1), r, c, w);
-        const float* p = a.env.image + 3 * ((int64_t)r * a.env.We + c);
-        L[0] = p[0]; L[1] = p[1]; L[2] = p[2];
-        ok = true;
-    } else {
-        ok = brdf_sample(px.n, px.v, px.alpha, env_rand(a.seed, px.pixel, k, 0), env_rand(a.seed, px.pixel, k, 1), env_rand(a.seed, px.pixel, k, 2), w);
-        if (!ok) w = make_float3(0.f, 0.f, 0.f);
-        pl = env_eval(a.env, w, L);
-    }
-    const float pb = ok ? brdf_pdf(px.n, px.v, w, px.alpha) : 0.0f;
-    denom = (a.n_light > 0 ? (float)a.n_light * pl : 0.0f) + (a.n_brdf > 0 ? (float)a.n_brdf * pb : 0.0f);
-    return ok && dir_counts(px.n, px.n, px.nv, w);
+__device__ __forceinline__ uint32_t gbuffer_pixel(const iron_neural_gbuffer& g, int64_t i) {
+    return g.pixel_idx ? (uint32_t)g.pixel_idx[i] : (uint32_t)i;
 }
 
 __global__ __launch_bounds__(kBvQueryBlock) void k_nenv_emit(NeuralEnvArgs a) {
     const int lane = threadIdx.x, sl = lane % kEnvGroup;
     const int64_t j = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;   // the pixel's place in the block
     if (j >= a.nb) return;
-    NeuralPixel px;
-    nenv_pixel(a.g, a.p0 + j, px);
+    EnvVertex x;
+    const bool hit = gbuffer_vertex(a.g, a.p0 + j, x);
+    const uint32_t pixel = gbuffer_pixel(a.g, a.p0 + j);
     const int32_t N = a.n_light + a.n_brdf;
-    for (int32_t base = 0; base < N; base += kEnvGroup) {
-        const int32_t k = base + sl;
-        if (k >= N) break;
-        float3 w = make_float3(0.f, 0.f, 0.f);
-        float denom = 0.0f, L[3];
-        bool cast = false;
-        if (px.hit) cast = nenv_sample(a, px, k, w, denom, L) && denom > 0.0f;
+    for_each_of_pixel(N, sl, [&](int32_t k) {
+        DirectDraw q;
+        if (hit) draw_direct(a.env, a.seed, pixel, k, a.n_light, a.n_brdf, x, q);
         const int64_t at = j * N + k;
-        st3(a.dir, at, w.x, w.y, w.z);
-        a.flags[at] = Pair64{cast ? 1 : 0, 0};
-    }
+        st3(a.dir, at, q.w.x, q.w.y, q.w.z);
+        a.flags[at] = Pair64{q.counts && q.denom > 0.0f ? 1 : 0, 0};
+    });
 }
 
-// the flagged samples' shadow rays, in the order of their flags: origin x + shadow_eps n (each product and sum rounded on its
-// own: -ffp-contract=off), direction w.  count[0] = their number.
+// the flagged samples' shadow rays, in the order of their flags: origin offset_origin, direction w.  count[0] = their number.
 __global__ __launch_bounds__(256) void k_nenv_compact(NeuralEnvArgs a, const Pair64* __restrict__ prefix, const Pair64* __restrict__ total,
                                                       int64_t capacity, float* __restrict__ ray_o, float* __restrict__ ray_d,
                                                       int32_t* __restrict__ sample_idx, int64_t* __restrict__ count) {
@@ -771,9 +825,8 @@ __global__ __launch_bounds__(256) void k_nenv_compact(NeuralEnvArgs a, const Pai
     const int64_t pos = prefix[at].a, next = at + 1 < M ? prefix[at + 1].a : total[0].a;
     if (next == pos || pos >= capacity) return;   // not flagged (the capacity holds every sample: the second test never fires)
     const int64_t i = a.p0 + at / N;
-    const float3 x = ld3(a.g.points, i), n = ld3(a.g.normal, i), w = ld3(a.dir, at);
-    const float ex = a.shadow_eps * n.x, ey = a.shadow_eps * n.y, ez = a.shadow_eps * n.z;
-    st3(ray_o, pos, x.x + ex, x.y + ey, x.z + ez);
+    const float3 org = offset_origin(ld3(a.g.points, i), ld3(a.g.normal, i), a.shadow_eps), w = ld3(a.dir, at);
+    st3(ray_o, pos, org.x, org.y, org.z);
     st3(ray_d, pos, w.x, w.y, w.z);
     sample_idx[pos] = (int32_t)at;
 }
@@ -791,47 +844,29 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_nenv_resolve(NeuralEnvArgs a)
     const int64_t j = (int64_t)blockIdx.x * kEnvPixels + lane / kEnvGroup;
     if (j >= a.nb) return;  // a whole group leaves together
     const int64_t i = a.p0 + j;
-    NeuralPixel px;
-    nenv_pixel(a.g, i, px);
+    EnvVertex x;
+    const bool hit = gbuffer_vertex(a.g, i, x);
+    const uint32_t pixel = gbuffer_pixel(a.g, i);
     const int32_t N = a.n_light + a.n_brdf;
-    const float nn[3] = {px.n.x, px.n.y, px.n.z}, vv[3] = {px.v.x, px.v.y, px.v.z};
     float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
-    for (int32_t base = 0; base < N; base += kEnvGroup) {
-        const int32_t k = base + sl;
-        if (k >= N) break;  // the ragged tail of the last round
-        float3 w = make_float3(0.f, 0.f, 0.f);
-        float denom = 0.0f, cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
+    for_each_of_pixel(N, sl, [&](int32_t k) {
+        DirectDraw q;
+        float cd[3] = {0.f, 0.f, 0.f}, cs[3] = {0.f, 0.f, 0.f};
         bool vis = false;
-        if (px.hit) {
-            float L[3];
-            const bool counts = nenv_sample(a, px, k, w, denom, L);
-            vis = counts && denom > 0.0f && a.vis[j * N + k] != 0;
+        if (hit) {
+            draw_direct(a.env, a.seed, pixel, k, a.n_light, a.n_brdf, x, q);
+            vis = q.counts && q.denom > 0.0f && a.vis[j * N + k] != 0;  // a listed sample that the tracer found unoccluded
             if (vis) {
                 PlasticOut f;
-                const float ww[3] = {w.x, w.y, w.z};
-                roughplastic_point(nn, vv, ww, px.mat, px.mat + 3, px.mat[6], a.tab_trans, a.tab_diff, f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    cd[c] = L[c] * f.diffuse[c] / denom;  // an infinite density (the map's poles) gives 0
-                    cs[c] = L[c] * f.specular[c] / denom;
-                    accd[c] += cd[c];
-                    accs[c] += cs[c];
-                }
+                vertex_brdf(x, q.w, a.tab_trans, a.tab_diff, f);
+                direct_terms(q.L, f, q.denom, cd, cs);
+                add3(accd, cd);
+                add3(accs, cs);
             }
         }
-        const int64_t at = i * N + k;
-        st3(a.dump.dir, at, w.x, w.y, w.z);
-        if (a.dump.denom) a.dump.denom[at] = denom;
-        if (a.dump.vis) a.dump.vis[at] = vis ? 1 : 0;
-        st3(a.dump.contrib, at, cd[0] + cs[0], cd[1] + cs[1], cd[2] + cs[2]);
-    }
-#pragma unroll
-    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
-            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
-        }
+        store_direct_dump(a.dump, i * N + k, q, vis, cd, cs);
+    });
+    group_sum16(accd, accs);
     if (sl != 0) return;
     st3(a.color, i, accd[0] + accs[0], accd[1] + accs[1], accd[2] + accs[2]);
     st3(a.diffuse_color, i, accd[0], accd[1], accd[2]);
@@ -839,24 +874,21 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_nenv_resolve(NeuralEnvArgs a)
 }
 
 // ---- interreflections on the neural scene ----
-// k_shade_env_indirect's paths on the neural scene, as a wavefront over depth: a path's closest hit is the sphere tracer's, which
-// is a call of its own, so a path's state lives in a workspace between two tracer calls.  Per block of pixels [p0, p0 + nb), slot
+// The path estimator on the neural scene, as a wavefront over depth: a path's closest hit is the sphere tracer's, which is a call
+// of its own, so a path's state lives in a workspace between two tracer calls.  Per block of pixels [p0, p0 + nb), slot
 // s = (pixel - p0) n_paths + path, on one stream:
 //   k_npath_begin    the state of every slot from the G-buffer: alive, the vertex (x, n, v, the seven material channels), T = 1,
 //                    C = b_d = b_s = 0;
-//   k_npath_emit     depth j: per alive slot the two samples of npath_sample (the one function emit and resolve run); their
-//                    directions to the workspace, the two flags -- the light sample counts with dl > 0; the BRDF sample counts and
-//                    its ray is valid -- to level 0 of one pair_scan (Pair64 carries both); k_npath_compact then lists the shadow
-//                    rays and the bounce rays (origin x + shadow_eps n, direction, slot) in ascending slot order;
+//   k_npath_emit     depth j: per alive slot the two samples of draw_vertex; their directions to the workspace, the two flags --
+//                    the light sample counts with dl > 0; the BRDF sample counts and its ray is valid -- to level 0 of one
+//                    pair_scan (Pair64 carries both); k_npath_compact then lists the shadow rays and the bounce rays (origin
+//                    offset_origin for both, direction, slot) in ascending slot order;
 //   (the caller)     intersect_sphere with occluded on the shadow list, with forward(chunk = 1) and the surface record on the
 //                    bounce list;
 //   k_npath_resolve  depth j: draws both samples again, adds the visible light term and the escape term to C, forms the next vertex
 //                    and T (b_d, b_s at j = 0) or ends the path, writes the dumps.  A slot finds its rays' answers through the
 //                    scan's prefixes, which stay in the workspace;
-//   k_npath_finish   the pixel's sums of b_d C and b_s C in k_shade_env_indirect's order: path p on lane p % 16 in round p / 16, the
-//                    butterfly, one division by n_paths.
-// Vertex, samples, random numbers, terms and their order are k_shade_env_indirect's with the shading normal in the geometric
-// normal's place (dir_counts(n, n, n.v, w)) and both rays leaving x + shadow_eps n.
+//   k_npath_finish   the pixel's sums of b_d C and b_s C by the pixel reduction, one division by n_paths.
 constexpr int kPathState = 28;  // floats per slot: x 0-2, n 3-5, v 6-8, material 9-15, T 16-18, C 19-21, b_d 22-24, b_s 25-27
 constexpr int kPathBlock = 256;
 
@@ -898,88 +930,36 @@ struct NeuralPathArgs {
     float *indirect_diffuse, *indirect_specular;  // finish
 };
 
-// what a slot keeps of its vertex
-struct NeuralVertex {
-    float3 x, n, v;
-    float mat[7];
-};
-
 __device__ __forceinline__ float3 npath_ld3(const float* __restrict__ state, int64_t cap, int f, int64_t s) {
     return make_float3(state[(int64_t)f * cap + s], state[(int64_t)(f + 1) * cap + s], state[(int64_t)(f + 2) * cap + s]);
 }
 __device__ __forceinline__ void npath_st3(float* __restrict__ state, int64_t cap, int f, int64_t s, float a, float b, float c) {
     state[(int64_t)f * cap + s] = a; state[(int64_t)(f + 1) * cap + s] = b; state[(int64_t)(f + 2) * cap + s] = c;
 }
-__device__ __forceinline__ void npath_load_vertex(const float* __restrict__ state, int64_t cap, int64_t s, NeuralVertex& x) {
-    x.x = npath_ld3(state, cap, 0, s); x.n = npath_ld3(state, cap, 3, s); x.v = npath_ld3(state, cap, 6, s);
+__device__ __forceinline__ void npath_load_vertex(const float* __restrict__ state, int64_t cap, int64_t s, EnvVertex& x) {
+    x.pt = npath_ld3(state, cap, 0, s); x.n = x.ng = npath_ld3(state, cap, 3, s); x.v = npath_ld3(state, cap, 6, s);
 #pragma unroll
     for (int c = 0; c < 7; ++c) x.mat[c] = state[(int64_t)(9 + c) * cap + s];
 }
-__device__ __forceinline__ void npath_store_vertex(float* __restrict__ state, int64_t cap, int64_t s, const NeuralVertex& x) {
-    npath_st3(state, cap, 0, s, x.x.x, x.x.y, x.x.z);
+__device__ __forceinline__ void npath_store_vertex(float* __restrict__ state, int64_t cap, int64_t s, const EnvVertex& x) {
+    npath_st3(state, cap, 0, s, x.pt.x, x.pt.y, x.pt.z);
     npath_st3(state, cap, 3, s, x.n.x, x.n.y, x.n.z);
     npath_st3(state, cap, 6, s, x.v.x, x.v.y, x.v.z);
 #pragma unroll
     for (int c = 0; c < 7; ++c) state[(int64_t)(9 + c) * cap + s] = x.mat[c];
 }
 
-// the two samples of vertex j of path p, as k_shade_env_indirect draws them
-struct PathSample {
-    float3 wl, wb, org;     // light direction, bounce direction (zero: no sample), the origin of both rays
-    float dl, db, pb;       // the two denominators, p_brdf(w_b)
-    float Ll[3], Lb[3];     // the map's radiance along the two
-    bool lcast, bcast;      // a shadow ray / a bounce ray is cast
-};
-
-__device__ __forceinline__ void npath_sample(const EnvDev& env, uint32_t seed, uint32_t pixel, int32_t p, int32_t j, const NeuralVertex& x,
-                                             float shadow_eps, PathSample& s) {
-    const uint32_t dim = 8u * (uint32_t)(j + 1);
-    const float alpha = fmaxf(x.mat[6], 0.0001f), nv = dot3(x.n, x.v);
-    s.wl = s.wb = make_float3(0.f, 0.f, 0.f);
-    s.dl = s.db = s.pb = 0.0f;
-    s.lcast = s.bcast = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s.Ll[c] = s.Lb[c] = 0.0f;
-    const float ex = shadow_eps * x.n.x, ey = shadow_eps * x.n.y, ez = shadow_eps * x.n.z;  // each product and sum rounded on its own
-    s.org = make_float3(x.x.x + ex, x.x.y + ey, x.x.z + ez);
-    if (j >= 1) {  // the environment sample
-        int r, c;
-        const float pl = env_sample(env, env_rand(seed, pixel, p, dim + 3u), env_rand(seed, pixel, p, dim + 4u), r, c, s.wl);
-        const float* L = env.image + 3 * ((int64_t)r * env.We + c);
-        s.Ll[0] = L[0]; s.Ll[1] = L[1]; s.Ll[2] = L[2];
-        s.dl = pl + brdf_pdf(x.n, x.v, s.wl, alpha);
-        s.lcast = dir_counts(x.n, x.n, nv, s.wl) && s.dl > 0.0f;
-    }
-    const bool ok = brdf_sample(x.n, x.v, alpha, env_rand(seed, pixel, p, dim), env_rand(seed, pixel, p, dim + 1u),
-                                env_rand(seed, pixel, p, dim + 2u), s.wb);
-    if (!ok) s.wb = make_float3(0.f, 0.f, 0.f);
-    if (ok && dir_counts(x.n, x.n, nv, s.wb)) {
-        const float pl = env_eval(env, s.wb, s.Lb);
-        s.pb = brdf_pdf(x.n, x.v, s.wb, alpha);
-        s.db = pl + s.pb;
-        s.bcast = ray_valid(s.org, s.wb);
-    }
-}
-
-__device__ __forceinline__ uint32_t npath_pixel(const iron_neural_gbuffer& g, int64_t i) {
-    return g.pixel_idx ? (uint32_t)g.pixel_idx[i] : (uint32_t)i;
-}
-
 __global__ __launch_bounds__(kPathBlock) void k_npath_begin(NeuralPathArgs a) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= a.nb * a.n_paths) return;
-    NeuralPixel px;
-    nenv_pixel(a.g, a.p0 + s / a.n_paths, px);
-    NeuralVertex x;
-    x.x = px.x; x.n = px.n; x.v = px.v;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) x.mat[c] = px.mat[c];
+    EnvVertex x;
+    const bool hit = gbuffer_vertex(a.g, a.p0 + s / a.n_paths, x);
     npath_store_vertex(a.state, a.capacity, s, x);
     npath_st3(a.state, a.capacity, 16, s, 1.f, 1.f, 1.f);
     npath_st3(a.state, a.capacity, 19, s, 0.f, 0.f, 0.f);
     npath_st3(a.state, a.capacity, 22, s, 0.f, 0.f, 0.f);
     npath_st3(a.state, a.capacity, 25, s, 0.f, 0.f, 0.f);
-    a.alive[s] = px.hit ? 1 : 0;
+    a.alive[s] = hit ? 1 : 0;
 }
 
 // counts[2] += the alive slots (one atomic per wave: integer, so the order does not matter)
@@ -987,19 +967,20 @@ __global__ __launch_bounds__(kPathBlock) void k_npath_emit(NeuralPathArgs a, uns
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool in = s < a.nb * a.n_paths;
     const bool alive = in && a.alive[s] != 0;
-    PathSample q;
-    q.wl = q.wb = make_float3(0.f, 0.f, 0.f);
-    q.lcast = q.bcast = false;
+    VertexDraw q;
+    bool lcast = false, bcast = false;  // a shadow ray / a bounce ray is cast
     if (alive) {
-        NeuralVertex x;
+        EnvVertex x;
         npath_load_vertex(a.state, a.capacity, s, x);
-        npath_sample(a.env, a.seed, npath_pixel(a.g, a.p0 + s / a.n_paths), (int32_t)(s % a.n_paths), a.depth, x, a.shadow_eps, q);
+        draw_vertex(a.env, a.seed, gbuffer_pixel(a.g, a.p0 + s / a.n_paths), (int32_t)(s % a.n_paths), a.depth, x, q);
+        lcast = q.lcounts && q.dl > 0.0f;
+        bcast = q.bcounts && ray_valid(offset_origin(x.pt, x.n, a.shadow_eps), q.wb);
     }
     if (in) {
         float* d = a.dir + 6 * s;
         d[0] = q.wl.x; d[1] = q.wl.y; d[2] = q.wl.z; d[3] = q.wb.x; d[4] = q.wb.y; d[5] = q.wb.z;
-        a.flags[s] = Pair64{q.lcast ? 1 : 0, q.bcast ? 1 : 0};
-        a.cast[s] = (uint8_t)((q.lcast ? 1 : 0) | (q.bcast ? 2 : 0));
+        a.flags[s] = Pair64{lcast ? 1 : 0, bcast ? 1 : 0};
+        a.cast[s] = (uint8_t)((lcast ? 1 : 0) | (bcast ? 2 : 0));
     }
     const unsigned long long wave = __ballot(alive);
     if ((threadIdx.x & (warpSize - 1)) == 0 && wave != 0) atomicAdd(counts + 2, (unsigned long long)__popcll(wave));
@@ -1015,17 +996,16 @@ __global__ __launch_bounds__(kPathBlock) void k_npath_compact(NeuralPathArgs a, 
     if (s >= a.nb * a.n_paths) return;
     const uint8_t cast = a.cast[s];
     if (cast == 0) return;
-    const float3 x = npath_ld3(a.state, a.capacity, 0, s), n = npath_ld3(a.state, a.capacity, 3, s);
-    const float ex = a.shadow_eps * n.x, ey = a.shadow_eps * n.y, ez = a.shadow_eps * n.z;
+    const float3 org = offset_origin(npath_ld3(a.state, a.capacity, 0, s), npath_ld3(a.state, a.capacity, 3, s), a.shadow_eps);
     const float* d = a.dir + 6 * s;
     const Pair64 at = prefix[s];
     if ((cast & 1) && at.a < a.capacity) {
-        st3(shadow_o, at.a, x.x + ex, x.y + ey, x.z + ez);
+        st3(shadow_o, at.a, org.x, org.y, org.z);
         st3(shadow_d, at.a, d[0], d[1], d[2]);
         shadow_idx[at.a] = (int32_t)s;
     }
     if ((cast & 2) && at.b < a.capacity) {
-        st3(bounce_o, at.b, x.x + ex, x.y + ey, x.z + ez);
+        st3(bounce_o, at.b, org.x, org.y, org.z);
         st3(bounce_d, at.b, d[3], d[4], d[5]);
         bounce_idx[at.b] = (int32_t)s;
     }
@@ -1037,77 +1017,61 @@ __global__ __launch_bounds__(kPathBlock) void k_npath_resolve(NeuralPathArgs a) 
     const int64_t i = a.p0 + s / a.n_paths;
     const int32_t p = (int32_t)(s % a.n_paths), j = a.depth;
     const int64_t cap = a.capacity;
-    float3 wl = make_float3(0.f, 0.f, 0.f), wb = wl, org = wl;
-    float dl = 0.0f, db = 0.0f, th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
-    float rx[3] = {0.f, 0.f, 0.f}, rn[3] = {0.f, 0.f, 0.f}, rkd[3] = {0.f, 0.f, 0.f}, rks[3] = {0.f, 0.f, 0.f}, rr = 0.0f;
+    VertexDraw q;
+    EnvVertex y;  // the surface the bounce ray met
+    vertex_clear(y);
+    float3 org = make_float3(0.f, 0.f, 0.f);
+    float th = 0.0f, lt[3] = {0.f, 0.f, 0.f}, et[3] = {0.f, 0.f, 0.f}, tp[3] = {0.f, 0.f, 0.f};
     bool lvis = false;
     int32_t reached = -2;
     if (a.alive[s] != 0) {
         bool alive = false;  // until the vertex hands the path on
-        NeuralVertex x;
+        EnvVertex x;
         npath_load_vertex(a.state, cap, s, x);
-        float3 T = npath_ld3(a.state, cap, 16, s), Cs = npath_ld3(a.state, cap, 19, s);
-        float Tv[3] = {T.x, T.y, T.z}, C[3] = {Cs.x, Cs.y, Cs.z};
-        PathSample q;
-        npath_sample(a.env, a.seed, npath_pixel(a.g, i), p, j, x, a.shadow_eps, q);
-        wl = q.wl; wb = q.wb; dl = q.dl; db = q.db;
+        const float3 Ts = npath_ld3(a.state, cap, 16, s), Cs = npath_ld3(a.state, cap, 19, s);
+        float T[3] = {Ts.x, Ts.y, Ts.z}, C[3] = {Cs.x, Cs.y, Cs.z};
+        draw_vertex(a.env, a.seed, gbuffer_pixel(a.g, i), p, j, x, q);
         const uint8_t cast = a.cast[s];
         const Pair64 at = a.flags[s];
-        const float nn[3] = {x.n.x, x.n.y, x.n.z}, vv[3] = {x.v.x, x.v.y, x.v.z};
         if ((cast & 1) && at.a < a.n_shadow) {  // the environment sample: listed means it counts and dl > 0
             lvis = a.occluded[at.a] == 0;
             if (lvis) {
                 PlasticOut f;
-                const float ww[3] = {wl.x, wl.y, wl.z};
-                roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    lt[c] = (Tv[c] * q.Ll[c]) * (f.diffuse[c] + f.specular[c]) / dl;  // an infinite density gives 0
-                    C[c] += lt[c];
-                }
+                vertex_brdf(x, q.wl, a.tab_trans, a.tab_diff, f);
+                light_term(T, q.Ll, f, q.dl, lt);
+                add3(C, lt);
             }
         }
         if ((cast & 2) && at.b < a.n_bounce) {  // the BRDF sample and its ray
-            org = q.org;
+            org = offset_origin(x.pt, x.n, a.shadow_eps);
             const bool hit = a.bounce_hit[at.b] != 0;
             reached = hit ? 1 : -1;
             th = hit ? a.bounce_dist[at.b] : kInfF;
             PlasticOut f;
-            const float ww[3] = {wb.x, wb.y, wb.z};
-            roughplastic_point(nn, vv, ww, x.mat, x.mat + 3, x.mat[6], a.tab_trans, a.tab_diff, f);
+            vertex_brdf(x, q.wb, a.tab_trans, a.tab_diff, f);
             if (!hit) {
-                if (j >= 1 && db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        et[c] = (Tv[c] * q.Lb[c]) * (f.diffuse[c] + f.specular[c]) / db;
-                        C[c] += et[c];
-                    }
+                if (j >= 1 && q.db > 0.0f) {  // the environment through the BRDF sample; the primary's is direct light
+                    escape_term(T, q.Lb, f, q.db, et);
+                    add3(C, et);
                 }
             } else {
-                const float3 x2 = ld3(a.bounce_points, at.b), n2 = ld3(a.bounce_normal, at.b);
-                rx[0] = x2.x; rx[1] = x2.y; rx[2] = x2.z; rn[0] = n2.x; rn[1] = n2.y; rn[2] = n2.z;
+                y.pt = ld3(a.bounce_points, at.b);
+                y.n = y.ng = ld3(a.bounce_normal, at.b);
+                y.v = make_float3(-q.wb.x, -q.wb.y, -q.wb.z);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { rkd[c] = a.bounce_kd[3 * at.b + c]; rks[c] = a.bounce_ks[3 * at.b + c]; }
-                rr = a.bounce_rough[at.b];
-                // a surface met from behind is black, like a back-facing primary hit
-                if (-dot3(n2, wb) > 0.0f && q.pb > 0.0f) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        if (j == 0) {
-                            a.state[(int64_t)(22 + c) * cap + s] = f.diffuse[c] / q.pb;
-                            a.state[(int64_t)(25 + c) * cap + s] = f.specular[c] / q.pb;
-                        } else {
-                            Tv[c] = Tv[c] * (f.diffuse[c] + f.specular[c]) / q.pb;
-                        }
-                        tp[c] = Tv[c];
+                for (int c = 0; c < 3; ++c) { y.mat[c] = a.bounce_kd[3 * at.b + c]; y.mat[3 + c] = a.bounce_ks[3 * at.b + c]; }
+                y.mat[6] = a.bounce_rough[at.b];
+                if (path_goes_on(y, q.wb, q.pb)) {
+                    float bd[3] = {0.f, 0.f, 0.f}, bs[3] = {0.f, 0.f, 0.f};
+                    advance(j, f, q.pb, T, bd, bs);
+                    if (j == 0) {
+                        npath_st3(a.state, cap, 22, s, bd[0], bd[1], bd[2]);
+                        npath_st3(a.state, cap, 25, s, bs[0], bs[1], bs[2]);
                     }
-                    NeuralVertex y;
-                    y.x = x2; y.n = n2; y.v = make_float3(-wb.x, -wb.y, -wb.z);
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) { y.mat[c] = rkd[c]; y.mat[3 + c] = rks[c]; }
-                    y.mat[6] = rr;
+                    for (int c = 0; c < 3; ++c) tp[c] = T[c];
                     npath_store_vertex(a.state, cap, s, y);
-                    npath_st3(a.state, cap, 16, s, Tv[0], Tv[1], Tv[2]);
+                    npath_st3(a.state, cap, 16, s, T[0], T[1], T[2]);
                     alive = true;
                 }
             }
@@ -1116,22 +1080,14 @@ __global__ __launch_bounds__(kPathBlock) void k_npath_resolve(NeuralPathArgs a) 
         a.alive[s] = alive ? 1 : 0;
     }
     const int64_t at = ((int64_t)i * a.n_paths + p) * a.max_depth + j;
-    st3(a.dump.bounce_dir, at, wb.x, wb.y, wb.z);
-    st3(a.dump.bounce_org, at, org.x, org.y, org.z);
+    store_vertex_dump(a.dump, at, q, org, lvis, lt, et, tp);
     if (a.dump.reached) a.dump.reached[at] = reached;
     if (a.dump.distance) a.dump.distance[at] = th;
-    st3(a.dump.vertex_points, at, rx[0], rx[1], rx[2]);
-    st3(a.dump.vertex_normal, at, rn[0], rn[1], rn[2]);
-    st3(a.dump.vertex_diffuse_albedo, at, rkd[0], rkd[1], rkd[2]);
-    st3(a.dump.vertex_specular_albedo, at, rks[0], rks[1], rks[2]);
-    if (a.dump.vertex_roughness) a.dump.vertex_roughness[at] = rr;
-    st3(a.dump.light_dir, at, wl.x, wl.y, wl.z);
-    if (a.dump.light_vis) a.dump.light_vis[at] = lvis ? 1 : 0;
-    if (a.dump.denom_light) a.dump.denom_light[at] = dl;
-    if (a.dump.denom_brdf) a.dump.denom_brdf[at] = db;
-    st3(a.dump.light_term, at, lt[0], lt[1], lt[2]);
-    st3(a.dump.escape_term, at, et[0], et[1], et[2]);
-    st3(a.dump.throughput, at, tp[0], tp[1], tp[2]);
+    st3(a.dump.vertex_points, at, y.pt.x, y.pt.y, y.pt.z);
+    st3(a.dump.vertex_normal, at, y.n.x, y.n.y, y.n.z);
+    st3(a.dump.vertex_diffuse_albedo, at, y.mat[0], y.mat[1], y.mat[2]);
+    st3(a.dump.vertex_specular_albedo, at, y.mat[3], y.mat[4], y.mat[5]);
+    if (a.dump.vertex_roughness) a.dump.vertex_roughness[at] = y.mat[6];
 }
 
 __global__ __launch_bounds__(kBvQueryBlock) void k_npath_finish(NeuralPathArgs a) {
@@ -1140,9 +1096,7 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_npath_finish(NeuralPathArgs a
     if (k >= a.nb) return;  // a whole group leaves together
     const int64_t i = a.p0 + k, cap = a.capacity;
     float accd[3] = {0.f, 0.f, 0.f}, accs[3] = {0.f, 0.f, 0.f};
-    for (int32_t base = 0; base < a.n_paths; base += kEnvGroup) {
-        const int32_t p = base + sl;
-        if (p >= a.n_paths) break;  // the ragged tail of the last round
+    for_each_of_pixel(a.n_paths, sl, [&](int32_t p) {
         const int64_t s = k * a.n_paths + p;
         const float3 C = npath_ld3(a.state, cap, 19, s), bd = npath_ld3(a.state, cap, 22, s), bs = npath_ld3(a.state, cap, 25, s);
         const float Cv[3] = {C.x, C.y, C.z}, bdv[3] = {bd.x, bd.y, bd.z}, bsv[3] = {bs.x, bs.y, bs.z};
@@ -1154,14 +1108,8 @@ __global__ __launch_bounds__(kBvQueryBlock) void k_npath_finish(NeuralPathArgs a
             accd[c] += bdv[c] * Cv[c];
             accs[c] += bsv[c] * Cv[c];
         }
-    }
-#pragma unroll
-    for (int m = kEnvGroup / 2; m > 0; m >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            accd[c] += __shfl_xor(accd[c], m, kEnvGroup);
-            accs[c] += __shfl_xor(accs[c], m, kEnvGroup);
-        }
+    });
+    group_sum16(accd, accs);
     if (sl != 0) return;
     const float np = (float)a.n_paths;
     st3(a.indirect_diffuse, i, accd[0] / np, accd[1] / np, accd[2] / np);
@@ -1180,6 +1128,16 @@ static bool env_dev(const iron_envmap* env, EnvDev& E) {
     for (int k = 0; k < 9; ++k) E.R[k] = env->to_world[k];
     return true;
 }
+
+static bool asset_mesh_ok(const iron_asset_mesh* mesh) {
+    if (!mesh) return false;
+    if (mesh->n_faces <= 0 || mesh->n_faces >= 0x7fffffffLL || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
+        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
+        return false;
+    return mesh->verts && mesh->faces && mesh->uvs && mesh->face_uvs && mesh->material;
+}
+
+static bool shadow_eps_ok(float e) { return e >= 0.0f && e < kInfF; }  // NaN fails
 
 }  // namespace iron
 
@@ -1258,12 +1216,8 @@ extern "C" int iron_asset_shade_env(const iron_asset_mesh* mesh, const void* bvh
                                     const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays, int32_t n_light,
                                     int32_t n_brdf, uint32_t seed, float shadow_eps, const iron_asset_out* out, const iron_env_dump* dump,
                                     void* stream) {
-    if (!mesh || !out || !bvh_workspace || n_rays < 0 || n_light < 0 || n_brdf < 0 || (int64_t)n_light + n_brdf > (1 << 20)) return IRON_ERR_BAD_ARG;
-    if (mesh->n_faces <= 0 || mesh->n_faces >= 0x7fffffffLL || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
-        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
-        return IRON_ERR_BAD_ARG;
-    if (!mesh->verts || !mesh->faces || !mesh->uvs || !mesh->face_uvs || !mesh->material || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
-    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    if (!out || !bvh_workspace || n_rays < 0 || n_light < 0 || n_brdf < 0 || (int64_t)n_light + n_brdf > (1 << 20)) return IRON_ERR_BAD_ARG;
+    if (!asset_mesh_ok(mesh) || !tab_trans || !tab_diff_trans || !shadow_eps_ok(shadow_eps)) return IRON_ERR_BAD_ARG;
     EnvShadeArgs a;
     if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
     if (n_rays == 0) return IRON_OK;
@@ -1283,12 +1237,8 @@ extern "C" int iron_asset_shade_env_indirect(const iron_asset_mesh* mesh, const 
                                              const int32_t* face_idx, const float* bary, const int32_t* pixel_idx, int64_t n_rays,
                                              int32_t n_paths, int32_t max_depth, uint32_t seed, float shadow_eps, float* indirect_diffuse,
                                              float* indirect_specular, const iron_env_path_dump* dump, void* stream) {
-    if (!mesh || !bvh_workspace || n_rays < 0 || n_paths < 1 || n_paths > (1 << 16) || max_depth < 2 || max_depth > 8) return IRON_ERR_BAD_ARG;
-    if (mesh->n_faces <= 0 || mesh->n_faces >= 0x7fffffffLL || mesh->n_verts <= 0 || mesh->n_uvs <= 0 || mesh->tex_h <= 0 || mesh->tex_w <= 0 ||
-        (int64_t)mesh->tex_h * mesh->tex_w > (1 << 24))
-        return IRON_ERR_BAD_ARG;
-    if (!mesh->verts || !mesh->faces || !mesh->uvs || !mesh->face_uvs || !mesh->material || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
-    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    if (!bvh_workspace || n_rays < 0 || n_paths < 1 || n_paths > (1 << 16) || max_depth < 2 || max_depth > 8) return IRON_ERR_BAD_ARG;
+    if (!asset_mesh_ok(mesh) || !tab_trans || !tab_diff_trans || !shadow_eps_ok(shadow_eps)) return IRON_ERR_BAD_ARG;
     EnvPathArgs a;
     if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
     if (n_rays == 0) return IRON_OK;
@@ -1340,8 +1290,7 @@ extern "C" int iron_neural_env_emit(const iron_neural_gbuffer* g, const iron_env
     NeuralEnvLayout L;
     const int rc = nenv_args(g, env, p0, nb, n_light, n_brdf, capacity, workspace, workspace_bytes, a, L);
     if (rc != IRON_OK) return rc;
-    if (!ray_o || !ray_d || !sample_idx || !count) return IRON_ERR_BAD_ARG;
-    if (!(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    if (!ray_o || !ray_d || !sample_idx || !count || !shadow_eps_ok(shadow_eps)) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t M = nb * ((int64_t)n_light + n_brdf);
     a.seed = seed; a.shadow_eps = shadow_eps;
@@ -1424,7 +1373,7 @@ extern "C" int iron_neural_path_emit(const iron_neural_gbuffer* g, const iron_en
     NeuralPathArgs a;
     const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
     if (rc != IRON_OK) return rc;
-    if (depth < 0 || depth >= max_depth || !(shadow_eps >= 0.0f) || !(shadow_eps < kInfF)) return IRON_ERR_BAD_ARG;
+    if (depth < 0 || depth >= max_depth || !shadow_eps_ok(shadow_eps)) return IRON_ERR_BAD_ARG;
     if (!shadow_o || !shadow_d || !shadow_idx || !bounce_o || !bounce_d || !bounce_idx || !counts) return IRON_ERR_BAD_ARG;
     if (!env_dev(env, a.env)) return IRON_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1452,7 +1401,7 @@ extern "C" int iron_neural_path_resolve(const iron_neural_gbuffer* g, const iron
     const int rc = npath_args(g, p0, nb, n_paths, max_depth, capacity, workspace, workspace_bytes, a);
     if (rc != IRON_OK) return rc;
     const int64_t M = nb * n_paths;
-    if (depth < 0 || depth >= max_depth || !(shadow_eps >= 0.0f) || !(shadow_eps < kInfF) || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
+    if (depth < 0 || depth >= max_depth || !shadow_eps_ok(shadow_eps) || !tab_trans || !tab_diff_trans) return IRON_ERR_BAD_ARG;
     if (n_shadow < 0 || n_shadow > M || n_bounce < 0 || n_bounce > M || (n_shadow > 0 && !occluded)) return IRON_ERR_BAD_ARG;
     if (n_bounce > 0 && (!bounce || !bounce->hit || !bounce->distance || !bounce->points || !bounce->normal || !bounce->diffuse_albedo ||
                          !bounce->specular_albedo || !bounce->specular_roughness))
