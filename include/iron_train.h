@@ -321,7 +321,16 @@ int iron_volume_loss_backward(const iron_volume_loss_args* a, const double* stat
  * order) or fl(fl(fl(3 max |g|) scale_l) max |dy|) (second order, per level), so that 8 n contributions stay inside 63 bits.  A
  * non-finite dy (or g) makes every entry NaN.  The per-point outputs (d_x, d_dy) are fixed-order fp32 sums that do not depend on
  * the other points.  The workspace is needed for d_table only; *_workspace_bytes returns 0 for a descriptor the layout refuses.
- * IRON_ERR_WORKSPACE: workspace too small. */
+ * IRON_ERR_WORKSPACE: workspace too small.
+ *   iron_hashgrid_backward_pair      d_table of iron_hashgrid_backward(dy1) plus d_table of iron_hashgrid_backward_backward(dy2, g)
+ *                                    in ONE pass over the corners: per (corner, feature) the contribution wgt_o dy1[l,f] +
+ *                                    c_o dy2[l,f] (c_o = sum_d g_d live_d scale_l dw_o,d, the second-order coefficient bit for
+ *                                    bit) is formed in fp64, rounded once to the unit and added with one integer atomic, where
+ *                                    the two calls round and add twice.  The unit's exponent per level is
+ *                                    iron_hashgrid_grad_unit_exp(fl(max |dy1| + fl(fl(fl(3 max |g|) scale_l) max |dy2|)), n): the
+ *                                    sum of the two bounds above.  d_table and the workspace are required; written whole, bitwise
+ *                                    reproducible and permutation invariant as above; a non-finite dy1, dy2 or g makes every entry
+ *                                    NaN; n = 0 writes zeros.  `table` is not read and may be NULL. */
 size_t iron_hashgrid_backward_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n);
 int iron_hashgrid_backward(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table_or_null, const float* dy,
                            float* d_table_or_null, float* d_x_or_null, void* workspace, size_t workspace_bytes, void* stream);
@@ -329,7 +338,41 @@ size_t iron_hashgrid_backward_backward_workspace_bytes(const iron_hashgrid_desc*
 int iron_hashgrid_backward_backward(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table, const float* dy,
                                     const float* g, float* d_dy_or_null, float* d_table_or_null, void* workspace,
                                     size_t workspace_bytes, void* stream);
+size_t iron_hashgrid_backward_pair_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n);
+int iron_hashgrid_backward_pair(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table_or_null,
+                                const float* dy1, const float* dy2, const float* g, float* d_table, void* workspace,
+                                size_t workspace_bytes, void* stream);
 int iron_hashgrid_grad_unit_exp(float bound, int64_t n);   /* HOST: log2 of the fixed-point unit */
+
+/* Fused training backward of the hash-grid field (iron_hip.h, iron_hashgrid_field_* block), csrc/hashgrid_field_train.hip;
+ * definition and orders: DESIGN.md §29.  The forward of a training step IS iron_hashgrid_field_eval (out [n, n_out] and, when asked,
+ * g [n, 3] = d out[:,0] / dp); nothing is kept but p.  For the adjoints d_out [n, n_out] and d_g [n, 3] (either may be NULL: zero)
+ *   iron_hashgrid_field_backward   recomputes the forward per tile of points and writes
+ *       d_weights [n_weights] fp32, flat in iron_hashgrid_field_pack's weight order: the first-order term sum_n delta_l h_{l-1}^T plus
+ *                   the second-order (eikonal) term sum_n d_l hdot_{l-1}^T;
+ *       d_table [n_params, F] (may be NULL): iron_hashgrid_backward_pair(x = a p + b, dy1 = ybar, dy2 = e, g = a d_g on live axes);
+ *       ybar, e [n, L F] (may be NULL): the adjoint of the features and the chain vector W_0^T d_0, per point.
+ *     No gradient reaches p.  ybar and e of a point depend on that point alone.  d_weights is bitwise reproducible: the points are
+ *     cut into slots of iron_hashgrid_field_train_slot(n) consecutive points (HOST; a function of n alone), a slot's sum is an fp32
+ *     accumulation over its points in ascending order (per pair of points the first-order product, then the second-order one), and
+ *     the slots are added in fp64 in a fixed order and rounded to fp32 once.  n = 0: IRON_OK, d_weights and d_table zeros.
+ *   iron_hashgrid_field_train_check   HOST.  IRON_OK for a shape the backward is built for: whatever iron_hashgrid_field_check
+ *     accepts with n_neurons <= 64 whose stages fit the 160 KiB of LDS at 32 points: with r(v) = v rounded up to 32, the stages take
+ *     3 r(n_neurons) rows per hidden layer (4 with Softplus) plus 2 r(L F) + 32 rows, of 4 (P + 1) bytes each at P points per tile
+ *     (132 bytes at P = 32, the size the check uses; 260 at P = 64, taken where it fits).  IRON_ERR_RANGE otherwise (n_neurons = 128
+ *     always).
+ *   iron_hashgrid_field_train_pack    `packed` is iron_hashgrid_field_pack's blob, unchanged; `train_packed` holds the transposed
+ *     fragments of the output layer, which the adjoint chain needs and the inference blob lacks.  Repack both when a weight changes.
+ * workspace: 256-byte aligned, *_workspace_bytes(desc, n) bytes (0 for a refused descriptor); IRON_ERR_WORKSPACE if too small. */
+int iron_hashgrid_field_train_check(const iron_hashgrid_field_desc* desc);
+int64_t iron_hashgrid_field_train_slot(int64_t n);
+size_t iron_hashgrid_field_train_pack_bytes(const iron_hashgrid_field_desc* desc);
+int iron_hashgrid_field_train_pack(const iron_hashgrid_field_desc* desc, const float* weights, void* train_packed, void* stream);
+size_t iron_hashgrid_field_backward_workspace_bytes(const iron_hashgrid_field_desc* desc, int64_t n);
+int iron_hashgrid_field_backward(const iron_hashgrid_field_desc* desc, const float* p, int64_t n, const float* map_a3_or_null,
+                                 const float* map_b3_or_null, const float* table, const void* packed, const void* train_packed,
+                                 const float* d_out_or_null, const float* d_g_or_null, float* d_weights, float* d_table_or_null,
+                                 float* ybar_out_or_null, float* e_out_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostics: last hipError_t seen by this library on the calling thread (iron_train_last_blas_status: kept for ABI
  * stability, always 0: the library links no BLAS). */

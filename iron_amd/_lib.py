@@ -405,7 +405,16 @@ TRAIN_SYMBOLS = {
     "iron_hashgrid_backward": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "iron_hashgrid_backward_backward_workspace_bytes": (_SZ, [C.POINTER(iron_hashgrid_desc), _I64]),
     "iron_hashgrid_backward_backward": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_hashgrid_backward_pair_workspace_bytes": (_SZ, [C.POINTER(iron_hashgrid_desc), _I64]),
+    "iron_hashgrid_backward_pair": (C.c_int, [C.POINTER(iron_hashgrid_desc), _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "iron_hashgrid_grad_unit_exp": (C.c_int, [_F, _I64]),
+    "iron_hashgrid_field_train_check": (C.c_int, [C.POINTER(iron_hashgrid_field_desc)]),
+    "iron_hashgrid_field_train_slot": (_I64, [_I64]),
+    "iron_hashgrid_field_train_pack_bytes": (_SZ, [C.POINTER(iron_hashgrid_field_desc)]),
+    "iron_hashgrid_field_train_pack": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _P, _P]),
+    "iron_hashgrid_field_backward_workspace_bytes": (_SZ, [C.POINTER(iron_hashgrid_field_desc), _I64]),
+    "iron_hashgrid_field_backward": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _I64, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _P,
+                                               _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lock = threading.Lock()

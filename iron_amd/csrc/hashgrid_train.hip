@@ -13,6 +13,9 @@
 //                     first order:   acc[idx_o][f] += round(wgt_o dy[f] / unit)
 //                     second order:  c_o = sum_d (g_d live_d scale) dw[o][d];  acc[idx_o][f] += round(c_o dy[f] / unit);
 //                                    d_dy[f] = sum_o c_o table[idx_o][f]   (= sum_d J[f][d] g_d)
+//   k_hg_scatter_pair<F>
+//                     both orders in one pass: acc[idx_o][f] += round((wgt_o dy1[f] + c_o dy2[f]) / unit), c_o from (g, dy2's
+//                     level) as above; one rounding and one atomic per (corner, feature) where the two calls spend two
 //   k_hg_dx<F>        one thread per point, levels in order: d_x[d] = sum_l sum_f dy[l,f] J[l,f,d], one fp32 chain per axis
 //   k_hg_convert<F>   acc -> fp32, every entry of d_table written (+0.0 where nothing landed); NaN everywhere when max |dy| (or
 //                     max |g|) is not finite
@@ -213,6 +216,92 @@ static int hg_backward(const hg::Levels& L, int64_t n_params, const float* x, in
     return IRON_OK;
 }
 
+// ---- both orders in one pass (iron_hashgrid_backward_pair): one rounding and one atomic per (corner, feature) ----
+struct HgPairHead {        // first 256 bytes of the workspace
+    uint32_t max_dy1, max_dy2, max_g;
+};
+
+__device__ __forceinline__ bool hg_pair_finite(const HgPairHead& h) {
+    return hg_finite_bits(h.max_dy1) && hg_finite_bits(h.max_dy2) && hg_finite_bits(h.max_g);
+}
+
+// one contribution is wgt_o dy1 + c_o dy2: the first-order bound plus the second-order bound of the level
+__device__ __forceinline__ int hg_pair_unit_exp(const HgPairHead& h, const iron_hashgrid_level& lv, int64_t n) {
+    const float first = __uint_as_float(h.max_dy1);
+    const float second = ((3.0f * __uint_as_float(h.max_g)) * lv.scale) * __uint_as_float(h.max_dy2);
+    return hg::grad_unit_exp(first + second, n);
+}
+
+template <int F>
+__global__ __launch_bounds__(kHgBlock) void k_hg_scatter_pair(hg::Levels L, const float* __restrict__ x, int64_t n,
+                                                              const float* __restrict__ dy1, const float* __restrict__ dy2,
+                                                              const float* __restrict__ g, const HgPairHead* __restrict__ head,
+                                                              unsigned long long* __restrict__ acc) {
+    const int64_t p = (int64_t)blockIdx.x * kHgBlock + threadIdx.x;
+    if (p >= n) return;
+    const iron_hashgrid_level lv = L.lv[blockIdx.y];
+    const HgPairHead h = *head;
+    if (!hg_pair_finite(h)) return;
+    const double inv_unit = ldexp(1.0, -hg_pair_unit_exp(h, lv, n));
+    const float xs[3] = {x[3 * p], x[3 * p + 1], x[3 * p + 2]};
+    hg::Walk k;
+    hg::walk(lv, xs, &k);
+    const int64_t col = p * ((int64_t)L.n_levels * F) + (int64_t)blockIdx.y * F;
+    float v1[F], v2[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        v1[f] = dy1[col + f];
+        v2[f] = dy2[col + f];
+    }
+    float gs[3];                                  // the coefficient of k_hg_scatter<F, true>, bit for bit
+#pragma unroll
+    for (int d = 0; d < 3; ++d) gs[d] = (g[3 * p + d] * k.live[d]) * lv.scale;
+    unsigned long long* a = acc + lv.offset * F;
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        const float coef = fmaf(gs[2], k.dw[o][2], fmaf(gs[1], k.dw[o][1], gs[0] * k.dw[o][0]));
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            // both products are exact in fp64; their sum is rounded there once (2^-53) and then to the unit
+            const double t = fma((double)k.wgt[o], (double)v1[f], (double)coef * (double)v2[f]);
+            const long long q = __double2ll_rn(t * inv_unit);
+            if (q != 0) atomicAdd(a + (int64_t)k.idx[o] * F + f, (unsigned long long)q);
+        }
+    }
+}
+
+template <int F>
+__global__ __launch_bounds__(kHgBlock) void k_hg_convert_pair(hg::Levels L, const HgPairHead* __restrict__ head, int64_t n,
+                                                              const long long* __restrict__ acc, float* __restrict__ d_table) {
+    const iron_hashgrid_level lv = L.lv[blockIdx.y];
+    const int64_t i = (int64_t)blockIdx.x * kHgBlock + threadIdx.x;
+    if (i >= (int64_t)lv.size * F) return;
+    const HgPairHead h = *head;
+    const int64_t at = lv.offset * F + i;
+    d_table[at] = hg_pair_finite(h) ? (float)ldexp((double)acc[at], hg_pair_unit_exp(h, lv, n)) : __builtin_nanf("");
+}
+
+template <int F>
+static int hg_table_grad_pair(const hg::Levels& L, int64_t n_params, const float* x, int64_t n, const float* dy1, const float* dy2,
+                              const float* g, float* d_table, void* ws, hipStream_t st) {
+    const HgLayout w = hg_ws_layout(n_params, F);
+    HgPairHead* head = ws_ptr<HgPairHead>(ws, w.head_off);
+    long long* acc = ws_ptr<long long>(ws, w.acc_off);
+    const int64_t width = (int64_t)L.n_levels * F;
+    IRON_TRAIN_HIP(hipMemsetAsync(head, 0, sizeof(HgPairHead), st));
+    IRON_TRAIN_HIP(hipMemsetAsync(acc, 0, sizeof(int64_t) * (size_t)n_params * F, st));
+    IRON_TRAIN_LAUNCH(k_hg_absmax, hg_max_blocks(n * width), kHgBlock, st, dy1, n * width, &head->max_dy1);
+    IRON_TRAIN_LAUNCH(k_hg_absmax, hg_max_blocks(n * width), kHgBlock, st, dy2, n * width, &head->max_dy2);
+    IRON_TRAIN_LAUNCH(k_hg_absmax, hg_max_blocks(n * 3), kHgBlock, st, g, n * 3, &head->max_g);
+    const dim3 grid(blocks_for(n, kHgBlock), (unsigned)L.n_levels);
+    IRON_TRAIN_LAUNCH(k_hg_scatter_pair<F>, grid, kHgBlock, st, L, x, n, dy1, dy2, g, (const HgPairHead*)head, (unsigned long long*)acc);
+    uint32_t top = 0;
+    for (int l = 0; l < L.n_levels; ++l) top = L.lv[l].size > top ? L.lv[l].size : top;
+    const dim3 cgrid(blocks_for((int64_t)top * F, kHgBlock), (unsigned)L.n_levels);
+    IRON_TRAIN_LAUNCH(k_hg_convert_pair<F>, cgrid, kHgBlock, st, L, (const HgPairHead*)head, n, (const long long*)acc, d_table);
+    return IRON_OK;
+}
+
 static size_t hg_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n) {
     hg::Levels L;
     int64_t n_params = 0;
@@ -257,6 +346,36 @@ extern "C" int iron_hashgrid_backward(const iron_hashgrid_desc* desc, const floa
         case 2: return hg_backward<2>(L, n_params, x, n, table_or_null, dy, d_table_or_null, d_x_or_null, workspace, st);
         case 4: return hg_backward<4>(L, n_params, x, n, table_or_null, dy, d_table_or_null, d_x_or_null, workspace, st);
         default: return hg_backward<8>(L, n_params, x, n, table_or_null, dy, d_table_or_null, d_x_or_null, workspace, st);
+    }
+}
+
+extern "C" size_t iron_hashgrid_backward_pair_workspace_bytes(const iron_hashgrid_desc* desc, int64_t n) {
+    return hg_workspace_bytes(desc, n);
+}
+
+extern "C" int iron_hashgrid_backward_pair(const iron_hashgrid_desc* desc, const float* x, int64_t n, const float* table_or_null,
+                                           const float* dy1, const float* dy2, const float* g, float* d_table, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    (void)table_or_null;   // the table term of either order does not read the table
+    hg::Levels L;
+    int64_t n_params = 0;
+    const int rc = hg::make_levels(desc, &L, &n_params);
+    if (rc != IRON_OK) return rc;
+    if (n < 0 || !d_table || !workspace) return IRON_ERR_BAD_ARG;
+    if (n > (int64_t)0x7fffffff * kHgBlock / (3 * L.n_levels * L.n_features)) return IRON_ERR_RANGE;
+    const int F = L.n_features;
+    hipStream_t st = (hipStream_t)stream;
+    if (workspace_bytes < hg_ws_layout(n_params, F).bytes) return IRON_ERR_WORKSPACE;
+    if (n == 0) {
+        IRON_TRAIN_HIP(hipMemsetAsync(d_table, 0, sizeof(float) * (size_t)n_params * F, st));
+        return IRON_OK;
+    }
+    if (!x || !dy1 || !dy2 || !g) return IRON_ERR_BAD_ARG;
+    switch (F) {
+        case 1: return hg_table_grad_pair<1>(L, n_params, x, n, dy1, dy2, g, d_table, workspace, st);
+        case 2: return hg_table_grad_pair<2>(L, n_params, x, n, dy1, dy2, g, d_table, workspace, st);
+        case 4: return hg_table_grad_pair<4>(L, n_params, x, n, dy1, dy2, g, d_table, workspace, st);
+        default: return hg_table_grad_pair<8>(L, n_params, x, n, dy1, dy2, g, d_table, workspace, st);
     }
 }
 

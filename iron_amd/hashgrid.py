@@ -167,6 +167,25 @@ def backward_backward(desc, n_params, x, table, dy, g, want_dy=True, want_table=
     return d_dy, d_table
 
 
+def backward_pair(desc, n_params, x, table, dy1, dy2, g, d_table_out=None):
+    """d_table [n_params, F] of iron_hashgrid_backward_pair: backward(dy1)'s table term plus backward_backward(dy2, g)'s, each
+    (corner, feature) rounded and added once."""
+    x, table = _check_inputs(x, table, desc, n_params)
+    dy1, dy2, g = _lib.require_cuda_f32(dy1, "dy1"), _lib.require_cuda_f32(dy2, "dy2"), _lib.require_cuda_f32(g, "g")
+    n, F = x.shape[0], desc.n_features_per_level
+    if dy1.numel() != n * desc.n_levels * F or dy2.numel() != n * desc.n_levels * F or g.numel() != n * 3:
+        raise _lib.IronError("hash-grid encoding: dy1 and dy2 must be [n, %d] and g [n, 3]" % (desc.n_levels * F))
+    lib = _lib.load_train()
+    d_table = _table_out(d_table_out, n_params, F, x.device)
+    with torch.cuda.device(x.device):
+        nbytes = lib.iron_hashgrid_backward_pair_workspace_bytes(C.byref(desc), n)
+        ws = _lib.workspace(nbytes, x.device, "hashgrid")
+        _lib.check_train(lib.iron_hashgrid_backward_pair(C.byref(desc), x.data_ptr(), n, table.data_ptr(), dy1.data_ptr(), dy2.data_ptr(),
+                                                         g.data_ptr(), d_table.data_ptr(), _lib.ptr(ws), nbytes,
+                                                         _lib.stream_ptr(x.device)))
+    return d_table
+
+
 class _InputGradFn(torch.autograd.Function):
     """d_x = sum_{l,f} dy[l,f] J[l,f,:] as a function of (dy, table); x is a constant here (its second derivative is not built)."""
 

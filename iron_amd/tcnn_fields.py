@@ -7,7 +7,10 @@ gradient / get_all keep the reference's shapes and detach rules (tcnn_fields.py:
 reference hands them to tcnn (the encoding clamps to [0, 1]).
 
 Inference has a fused form beside it: `eval_fused` / `as_callable` evaluate the encoding and the head, and on request d sdf / dx, in
-one launch of csrc/hashgrid_field.hip (exact-fp32 MFMA head, no autograd); training keeps the plain head.
+one launch of csrc/hashgrid_field.hip (exact-fp32 MFMA head, no autograd, DESIGN.md §28).  Training keeps the plain head by default;
+with `field.fused_training = True` forward / sdf / sdf_hidden_appearance / gradient / get_all run through one autograd function whose
+forward is that launch and whose backward is csrc/hashgrid_field_train.hip: first- and second-order (eikonal)
+gradients of the table and the head in closed form, no autograd graph through the head and no gradient with respect to x.
 
 `TCNNRendering` and `TCNNNeRF` are not built: the reference's forwards are empty or mis-shaped (tcnn_fields.py:201-249)."""
 from __future__ import annotations
@@ -59,6 +62,70 @@ def read_config(conf_path) -> dict:
     return {"encoding": parse_encoding_config(config["encoding"]), "network": parse_network_config(config["network"])}
 
 
+def field_backward(desc, p, table, packed, train_packed, d_out, d_g, scale=None, offset=None, want_table=True, want_rows=False):
+    """iron_hashgrid_field_backward (csrc/hashgrid_field_train.hip) for the adjoints d_out [n, n_out] and d_g [n, 3] of
+    the fused evaluation's two results (either may be None: zero) -> (d_weights [n_weights], flat in the pack's weight order,
+    d_table [n_params, F] or None, ybar [n, L F] or None, e [n, L F] or None)."""
+    lib, libt = _lib.load(), _lib.load_train()
+    p, table = _lib.require_cuda_f32(p, "x"), _lib.require_cuda_f32(table, "params")
+    n, lf = p.shape[0], desc.encoding.n_levels * desc.encoding.n_features_per_level
+    if d_out is not None:
+        d_out = _lib.require_cuda_f32(d_out, "d_out")
+        if d_out.numel() != n * desc.n_out:
+            raise _lib.IronError("TCNNSDF: d_out must be [n, %d]" % desc.n_out)
+    if d_g is not None:
+        d_g = _lib.require_cuda_f32(d_g, "d_g")
+        if d_g.numel() != n * 3:
+            raise _lib.IronError("TCNNSDF: d_g must be [n, 3]")
+    n_weights = C.c_int64(0)
+    _lib.check(lib.iron_hashgrid_field_check(C.byref(desc), C.byref(n_weights)))
+    d_weights = torch.empty(n_weights.value, dtype=torch.float32, device=p.device)
+    d_table = torch.empty_like(table) if want_table else None
+    ybar = torch.empty((n, lf), dtype=torch.float32, device=p.device) if want_rows else None
+    e = torch.empty((n, lf), dtype=torch.float32, device=p.device) if want_rows else None
+    with torch.cuda.device(p.device):
+        nbytes = libt.iron_hashgrid_field_backward_workspace_bytes(C.byref(desc), n)
+        ws = _lib.workspace(nbytes, p.device, "hashfield_train")
+        _lib.check_train(libt.iron_hashgrid_field_backward(
+            C.byref(desc), p.data_ptr(), n, _map3(scale, "scale"), _map3(offset, "offset"), table.data_ptr(), packed.data_ptr(),
+            train_packed.data_ptr(), _lib.ptr(d_out), _lib.ptr(d_g), d_weights.data_ptr(), _lib.ptr(d_table), _lib.ptr(ybar), _lib.ptr(e),
+            ws.data_ptr(), nbytes, _lib.stream_ptr(p.device)))
+    return d_weights, d_table, ybar, e
+
+
+class _FieldFn(torch.autograd.Function):
+    """(out, d out[:, 0] / dx) of the fused evaluation as a function of (table, the head's weights); x is a constant: no gradient
+    reaches it (the second derivative of the trilinear form is not built).  The forward keeps nothing but x and the
+    two packed blobs; the backward recomputes it (csrc/hashgrid_field_train.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, table, field, want_grad, *weights):
+        desc = field._fused_desc()
+        packed, train_packed = field._fused_packed(desc, x.device), field._train_packed(desc, x.device)
+        n = x.shape[0]
+        out = torch.empty((n, desc.n_out), dtype=torch.float32, device=x.device)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=x.device) if want_grad else None
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().iron_hashgrid_field_eval(C.byref(desc), x.data_ptr(), n, None, None, table.data_ptr(), packed.data_ptr(),
+                                                            out.data_ptr(), _lib.ptr(grad), _lib.stream_ptr(x.device)))
+        ctx.desc, ctx.packed, ctx.train_packed, ctx.shapes = desc, packed, train_packed, [w.shape for w in weights]
+        ctx.save_for_backward(x, table)
+        ctx.set_materialize_grads(False)
+        return (out, grad) if want_grad else out
+
+    @staticmethod
+    def backward(ctx, d_out, d_g=None):
+        if torch.is_grad_enabled():
+            raise _lib.IronError("TCNNSDF.fused_training: a second backward through the fused gradient (create_graph=True) is not "
+                                 "built; the plain path (fused_training = False) differentiates twice")
+        x, table = ctx.saved_tensors
+        d_weights, d_table, _, _ = field_backward(ctx.desc, x, table, ctx.packed, ctx.train_packed, d_out, d_g,
+                                                  want_table=ctx.needs_input_grad[1])
+        parts = torch.split(d_weights, [s.numel() for s in ctx.shapes])
+        grads = [g.view(s) if need else None for g, s, need in zip(parts, ctx.shapes, ctx.needs_input_grad[4:])]
+        return (None, d_table.view_as(table) if d_table is not None else None, None, None, *grads)
+
+
 class TCNNSDF(nn.Module):
     def __init__(self, conf_path, n_inputs_dims=3, n_outputs_dims=1, geometric_init=True, weight_norm=True, inside_outside=False):
         super().__init__()
@@ -77,8 +144,12 @@ class TCNNSDF(nn.Module):
         self.model = nn.Sequential(self.sdf_encoding, self.sdf_network)
         self._network_config = dict(net, n_out=n_outputs_dims)    # plain attributes: the fused evaluation's shape and its
         self._fused_cache = None                                  # packed weights (key, blob); neither is part of state_dict()
+        self._train_cache = None                                  # the training blob, keyed the same way
+        self.fused_training = False                               # True: training runs through _FieldFn
 
     def forward(self, inputs):
+        if self.fused_training:
+            return self._fused_apply(inputs, False)
         return self.model(inputs)
 
     def sdf(self, x):
@@ -91,6 +162,9 @@ class TCNNSDF(nn.Module):
         """(forward(x), d sdf / dx); x becomes a leaf that requires grad, in place, as in the reference.  `attached` keeps the
         gradient differentiable with respect to the table and the head (the reference's create_graph)."""
         x.requires_grad_(True)
+        if self.fused_training:
+            out, grad = self._fused_apply(x, True)
+            return out, (grad if attached else grad.detach())
         out = self.forward(x)
         (grad,) = torch.autograd.grad(out[..., :1].sum(), x, create_graph=attached)
         return out, grad
@@ -129,6 +203,60 @@ class TCNNSDF(nn.Module):
         except _lib.IronError:
             return False
         return True
+
+    def fused_training_supported(self) -> bool:
+        """Whether fused_training = True can run this shape (iron_hashgrid_field_train_check; host only)."""
+        try:
+            self._train_desc()
+        except _lib.IronError:
+            return False
+        return True
+
+    def _train_desc(self):
+        desc = self._fused_desc()
+        rc = _lib.load_train().iron_hashgrid_field_train_check(C.byref(desc))
+        if rc == _lib.IRON_ERR_RANGE:
+            raise _lib.IronError("TCNNSDF.fused_training: n_neurons = %r with %d hidden layers on %d features is not built (16 / 32 / 64, "
+                                 "and the stages of 32 points must fit the 160 KiB of LDS)"
+                                 % (self._network_config["n_neurons"], self._network_config["n_hidden_layers"], self.sdf_encoding.n_output_dims))
+        _lib.check_train(rc)
+        return desc
+
+    def _fused_apply(self, x, want_grad):
+        """forward (and d sdf / dx) through _FieldFn: differentiable with respect to the table and the head, not to x"""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.IronError("TCNNSDF.fused_training: x must be a CUDA (ROCm) tensor: iron_amd has no CPU path")
+        if x.dtype != torch.float32:
+            raise _lib.IronError("TCNNSDF.fused_training: x must be float32, got %s" % (x.dtype,))
+        if x.dim() < 1 or x.shape[-1] != 3:
+            raise _lib.IronError("TCNNSDF.fused_training: x must end in 3 coordinates, got %s" % (tuple(x.shape),))
+        if x.grad_fn is not None and torch.is_grad_enabled():
+            raise _lib.IronError("TCNNSDF.fused_training: x is the result of a differentiable computation, and no gradient reaches x "
+                                 "here, so its term would silently be missing; evaluate at a leaf (x.detach())")
+        self._train_desc()
+        table = self.sdf_encoding.params
+        if table.device != x.device or table.dtype != torch.float32:
+            raise _lib.IronError("TCNNSDF.fused_training: the table must be float32 on x's device; call .cuda() first")
+        lin = [m.weight for m in self.sdf_network if isinstance(m, nn.Linear)]
+        res = _FieldFn.apply(x.detach().reshape(-1, 3).contiguous(), table, self, want_grad, *lin)
+        n_out = self._network_config["n_out"]
+        if want_grad:
+            return res[0].reshape(*x.shape[:-1], n_out), res[1].reshape(x.shape)
+        return res.reshape(*x.shape[:-1], n_out)
+
+    def _train_packed(self, desc, device):
+        """The transposed fragments of the output layer (the adjoint chain's), repacked with the inference blob's key."""
+        lin = [m.weight for m in self.sdf_network if isinstance(m, nn.Linear)]
+        key = (device,) + tuple((w.data_ptr(), w._version) for w in lin)
+        if self._train_cache is not None and self._train_cache[0] == key:
+            return self._train_cache[1]
+        lib = _lib.load_train()
+        flat = torch.cat([w.detach().reshape(-1) for w in lin])
+        blob = torch.empty(lib.iron_hashgrid_field_train_pack_bytes(C.byref(desc)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check_train(lib.iron_hashgrid_field_train_pack(C.byref(desc), flat.data_ptr(), blob.data_ptr(), _lib.stream_ptr(device)))
+        self._train_cache = (key, blob)
+        return blob
 
     def _fused_packed(self, desc, device):
         """The head's weights in MFMA fragment order, repacked when a parameter was replaced or written in place."""
