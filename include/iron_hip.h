@@ -1089,6 +1089,42 @@ int iron_hashgrid_field_eval(const iron_hashgrid_field_desc* desc, const float* 
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Device-resident sphere tracer of the hash-grid field (csrc/hashgrid_trace.hip).  RayTracer.forward on the field
+ * above with the field evaluated inside the tracing kernels: a fixed launch sequence, every count left on the device.  All entries
+ * ENQUEUE ONLY: no device-to-host copy, no stream synchronise.  conv / points / sdf_out / dist are, bit for bit and NaN payloads
+ * included, what the callable tracer (iron_trace_any_*) computes when its values come from column 0 of iron_hashgrid_field_eval
+ * with the same map; `chunk` couples rays [k chunk, (k+1) chunk) through the bisection count exactly as there.
+ *   desc, map_a3 / map_b3 (HOST, may be NULL), table, packed     as for iron_hashgrid_field_eval
+ *   p                 iron_trace_params; n_steps 2 .. 4096 else IRON_ERR_RANGE, as is a shape iron_hashgrid_field_check refuses
+ *   lin_steps         n_steps floats = torch.linspace(0, 1, n_steps), DEVICE
+ *   n                 0 .. INT_MAX - 1 (else IRON_ERR_BAD_ARG); n = 0 launches nothing.  Null pointers and a workspace smaller
+ *                     than iron_hashgrid_trace_workspace_bytes(n, p) (0 for an n out of range): IRON_ERR_BAD_ARG
+ *   stats             NULL or 8 int64 words on the DEVICE, which the caller zeroes and the entries add to:
+ *                     [0] lane evaluations issued (64 per wave evaluation)   [1] evaluations that belonged to a live ray
+ *                     [2] sampled rays   [3] bisected rays   [4] the sum over chunks of the bisection count T
+ *                     [5] incomplete: a bracket was still open after 256 iterations (a NaN inside an open bracket); the chunk
+ *                         stopped there and its results are not the reference's (which would not end)   [6], [7] reserved
+ *   iron_hashgrid_trace_occluded   the same `conv` alone: final once the sampler has found, or not found, a first negative sample
+ *   iron_hashgrid_trace_stage      the three reference stages on their own, arguments as for iron_trace_stage (stage 0 sphere
+ *                                  tracing, 1 ray_sampler with its bisection on the intervals given, 2 rootfind of the brackets
+ *                                  given); the bisection count is global to the call
+ * ------------------------------------------------------------------------------------------- */
+size_t iron_hashgrid_trace_workspace_bytes(int64_t n, const iron_trace_params* p);
+int iron_hashgrid_trace(const iron_hashgrid_field_desc* desc, const iron_trace_params* p, const float* map_a3, const float* map_b3,
+                        const float* table, const void* packed, const float* lin_steps, const float* ray_o, const float* ray_d,
+                        const float* near, const float* far, const uint8_t* work, int64_t n, uint8_t* conv, float* points, float* sdf_out,
+                        float* dist, int64_t* stats_or_null, void* workspace, size_t workspace_bytes, void* stream);
+int iron_hashgrid_trace_occluded(const iron_hashgrid_field_desc* desc, const iron_trace_params* p, const float* map_a3, const float* map_b3,
+                                 const float* table, const void* packed, const float* lin_steps, const float* ray_o, const float* ray_d,
+                                 const float* near, const float* far, const uint8_t* work, int64_t n, uint8_t* occluded,
+                                 int64_t* stats_or_null, void* workspace, size_t workspace_bytes, void* stream);
+int iron_hashgrid_trace_stage(int32_t stage, const iron_hashgrid_field_desc* desc, const iron_trace_params* p, const float* map_a3,
+                              const float* map_b3, const float* table, const void* packed, const float* lin_steps, const float* ray_o,
+                              const float* ray_d, const float* in0, const float* in1, const float* in2, const float* in3,
+                              const uint8_t* work, int64_t n, uint8_t* mask_out, uint8_t* unfinished_out, float* points, float* sdf_out,
+                              float* dist, int64_t* stats_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart): per-kernel device time from hipEvents recorded on the
  * caller's stream around each compute kernel.  Off by default.  iron_profile_read blocks on the
  * recorded events, adds their elapsed milliseconds / launch counts into the caller's arrays

@@ -152,6 +152,8 @@ class iron_lpips_weights(C.Structure):
 
 TRACE_STATS_FIELDS = ("n_evals", "n_sphere_conv", "n_sampler", "n_bisect", "n_conv", "n_evals_ref", "n_evals_sphere",
                       "reserved")
+# iron_hashgrid_trace*: eight int64 words on the device
+HASHGRID_TRACE_STATS_FIELDS = ("n_evals_issued", "n_evals", "n_sampler", "n_bisect", "n_bisect_iters", "incomplete", "reserved0", "reserved1")
 PROF_KINDS = ("sphere", "sampler", "bisect_a", "bisect_b", "sdf_grad", "material", "ggx", "sdf_forward")
 
 # every symbol include/iron_hip.h declares: name -> (restype, argtypes)
@@ -295,6 +297,13 @@ SYMBOLS = {
     "iron_hashgrid_field_pack_bytes": (_SZ, [C.POINTER(iron_hashgrid_field_desc)]),
     "iron_hashgrid_field_pack": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _P, _P]),
     "iron_hashgrid_field_eval": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), _P, _I64, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _P, _P]),
+    "iron_hashgrid_trace_workspace_bytes": (_SZ, [_I64, C.POINTER(iron_trace_params)]),
+    "iron_hashgrid_trace": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), C.POINTER(iron_trace_params), C.POINTER(_F), C.POINTER(_F), _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "iron_hashgrid_trace_occluded": (C.c_int, [C.POINTER(iron_hashgrid_field_desc), C.POINTER(iron_trace_params), C.POINTER(_F), C.POINTER(_F),
+                                               _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "iron_hashgrid_trace_stage": (C.c_int, [_I32, C.POINTER(iron_hashgrid_field_desc), C.POINTER(iron_trace_params), C.POINTER(_F),
+                                            C.POINTER(_F), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "iron_profile_enable": (C.c_int, [_I32]),
     "iron_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
     "iron_shade_workspace_bytes": (_SZ, [_I64]),

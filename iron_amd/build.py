@@ -19,9 +19,9 @@ LIB_TRAIN = os.path.join(CSRC, "libiron_train.so")  # backward passes (include/i
 OBJ_DIR = os.path.join(CSRC, "build")
 MANIFEST = os.path.join(OBJ_DIR, "manifest.json")  # which flag set every translation unit was compiled with (bench.py echoes it)
 
-SOURCES = ["pack.hip", "pack_h2.hip", "sdf_forward.hip", "h2_kernels.hip", "w16.hip", "pointwise.hip", "trace.hip", "trace_any.hip", "shade.hip", "getall_rev.hip", "envelope.hip", "nerf.hip", "neus.hip", "profile.hip", "pair_scan.hip", "mcubes.hip", "texbake.hip", "meshdist.hip", "meshrender.hip", "envlight.hip", "uvunwrap.hip", "imgmetrics.hip", "volume.hip", "hashgrid.hip", "hashgrid_field.hip"]
+SOURCES = ["pack.hip", "pack_h2.hip", "sdf_forward.hip", "h2_kernels.hip", "w16.hip", "pointwise.hip", "trace.hip", "trace_any.hip", "shade.hip", "getall_rev.hip", "envelope.hip", "nerf.hip", "neus.hip", "profile.hip", "pair_scan.hip", "mcubes.hip", "texbake.hip", "meshdist.hip", "meshrender.hip", "envlight.hip", "uvunwrap.hip", "imgmetrics.hip", "volume.hip", "hashgrid.hip", "hashgrid_field.hip", "hashgrid_trace.hip"]
 TRAIN_SOURCES = ["train.hip", "losses.hip", "optim.hip", "volume_loss.hip", "hashgrid_train.hip", "hashgrid_field_train.hip"]
-HEADERS = [os.path.join("..", "..", "include", "iron_train.h"), "gemm_h2.h", "lds_dma.h", "iron_common.h", "mlp_core.h", "mlp_h2.h", "mlp_h2_rev.h", "shade_args.h", "h2_setup.h", "pack_common.h", "ggx_core.h", "mc_table.h", "host_util.h", "ws_layout.h", "fixed_sum.h", "train_common.h", "pair_scan.h", "mesh_common.h", "bvh_common.h", "ray_core.h", "ray_walk.h", "asset_common.h", "hashgrid_common.h", "hashgrid_field_common.h", os.path.join("..", "..", "include", "iron_hip.h")]
+HEADERS = [os.path.join("..", "..", "include", "iron_train.h"), "gemm_h2.h", "lds_dma.h", "iron_common.h", "mlp_core.h", "mlp_h2.h", "mlp_h2_rev.h", "shade_args.h", "h2_setup.h", "pack_common.h", "ggx_core.h", "mc_table.h", "host_util.h", "ws_layout.h", "fixed_sum.h", "train_common.h", "pair_scan.h", "mesh_common.h", "bvh_common.h", "ray_core.h", "ray_walk.h", "asset_common.h", "hashgrid_common.h", "hashgrid_field_common.h", "trace_ray.h", os.path.join("..", "..", "include", "iron_hip.h")]
 
 BASE_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -24,7 +24,8 @@
 namespace iron {
 
 // NT > 0 (value only): one LDS buffer serves every stage in place -- the NT output tiles of a hidden layer wait in registers until
-// the layer's last k-step has read its input -- which halves the LDS of a wave and doubles the waves a CU holds.
+// the layer's last k-step has read its input -- which halves the LDS of a wave and doubles the waves a CU holds.  That form is
+// field_value_acc (hashgrid_field_common.h), which the device tracer (hashgrid_trace.hip) calls too.
 template <int ACT, bool GRAD, int CT, int NT>
 __global__ __launch_bounds__(64) void k_hg_field(hg::Levels L, FieldPlan pl, FieldLds lo, const float* __restrict__ p, int64_t n,
                                                  FieldMap map, const float* __restrict__ table, const float4* __restrict__ packed,
@@ -40,6 +41,20 @@ __global__ __launch_bounds__(64) void k_hg_field(hg::Levels L, FieldPlan pl, Fie
     if (have) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) xs[d] = fmaf(p[3 * pt + d], map.a[d], map.b[d]);
+    }
+    if constexpr (NT > 0) {   // value only: the shared value path (field_value_acc), then every output row of the last accumulator
+        f32x16 acc[CT];
+        field_value_acc<ACT, CT, NT>(L, pl, lds, xs, owner, table, packed, lane, acc);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            const int64_t q = first + 32 * ct + col;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = acc_row(r, half);
+                if (q < n && o < pl.n_out) out[q * pl.n_out + o] = acc[ct][r];
+            }
+        }
+        return;
     }
     const int F = L.n_features;
 
@@ -63,19 +78,6 @@ __global__ __launch_bounds__(64) void k_hg_field(hg::Levels L, FieldPlan pl, Fie
         const int nq = pl.kq[j];
         if (j < pl.m) {
             float* o = lds + lo.buf[j + 1];
-            if constexpr (NT > 0) {
-                f32x16 acc[NT][CT];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) field_tile<CT>(w + (size_t)t * nq * 64, nq, in, lane, acc[t]);
-                __syncthreads();
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            o[(32 * t + acc_row(r, half)) * P + 32 * ct + col] = field_act<ACT>(acc[t][ct][r]);
-            } else
             for (int t = 0; t < pl.tiles[j]; ++t) {
                 f32x16 acc[CT];
                 field_tile<CT>(w + (size_t)t * nq * 64, nq, in, lane, acc);

@@ -221,4 +221,56 @@ struct FieldMap {
     float a[3], b[3];
 };
 
+// The value path of one wave64 on P = 32 CT points: lane `lane` < P encodes the point xs (already mapped into the
+// unit cube) into stage 0, the hidden layers run in the one LDS buffer `lds` (lds_layout(pl, false, P) bytes) with their NT output
+// tiles waiting in registers until the layer's last k-step has read its input, and the last layer's accumulator comes back in
+// `acc`: row acc_row(r, lane >> 5) of point 32 ct + (lane & 31) in acc[ct][r].  Every lane of the wave must call it (MFMAs and
+// barriers).  k_hg_field's value form and the device tracer (hashgrid_trace.hip) are both this function, so they agree bit for bit.
+template <int ACT, int CT, int NT>
+__device__ __forceinline__ void field_value_acc(const hg::Levels& L, const FieldPlan& pl, float* __restrict__ lds, const float* xs, bool owner,
+                                                const float* __restrict__ table, const float4* __restrict__ packed, int lane,
+                                                f32x16 (&acc)[CT]) {
+    constexpr int P = 32 * CT;
+    const int half = lane >> 5, col = lane & 31;
+    // ---- encode: stage 0, rows l F + f; the rows between L F and the next multiple of 8 are zero (k-step padding) ----
+    if (owner) {
+        for (int k = pl.lf; k < pl.kq[0] * 8; ++k) lds[k * P + lane] = 0.0f;
+        switch (L.n_features) {
+            case 1: field_encode<1>(L, xs, table, lds + lane, P); break;
+            case 2: field_encode<2>(L, xs, table, lds + lane, P); break;
+            case 4: field_encode<4>(L, xs, table, lds + lane, P); break;
+            default: field_encode<8>(L, xs, table, lds + lane, P); break;
+        }
+    }
+    // ---- head ----
+    for (int j = 0; j < pl.m; ++j) {
+        __syncthreads();
+        const float4* w = packed + pl.fwd_off[j];
+        const int nq = pl.kq[j];
+        f32x16 hid[NT][CT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) field_tile<CT>(w + (size_t)t * nq * 64, nq, lds, lane, hid[t]);
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) lds[(32 * t + acc_row(r, half)) * P + 32 * ct + col] = field_act<ACT>(hid[t][ct][r]);
+    }
+    __syncthreads();
+    field_tile<CT>(packed + pl.fwd_off[pl.m], pl.kq[pl.m], lds, lane, acc);   // n_out <= 16: one tile
+}
+
+// Output 0 of the 64 points of a wave (CT = 2), handed back to the point's own lane: row 0 sits in accumulator register 0 of the
+// lower lane half, point 32 ct + col in acc[ct] of lane col.
+template <int ACT, int NT>
+__device__ __forceinline__ float field_value(const hg::Levels& L, const FieldPlan& pl, float* __restrict__ lds, const float* xs,
+                                             const float* __restrict__ table, const float4* __restrict__ packed, int lane) {
+    f32x16 acc[2];
+    field_value_acc<ACT, 2, NT>(L, pl, lds, xs, true, table, packed, lane, acc);
+    const float upper = __shfl(acc[1][0], lane & 31, 64);
+    return lane < 32 ? acc[0][0] : upper;
+}
+
 }  // namespace iron

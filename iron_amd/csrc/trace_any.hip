@@ -6,6 +6,7 @@
 // rounding per product and sum (-ffp-contract=off), and the comparisons are the reference's own so that NaN and zero fall where
 // torch puts them.  Compaction is pair_scan over 0/1 flags: ascending ray index, bitwise deterministic.
 #include "pair_scan.h"
+#include "trace_ray.h"
 
 #include <limits.h>
 
@@ -67,11 +68,9 @@ bool open_ws(Ws& w, int64_t n, void* workspace, size_t workspace_bytes) {
 
 __device__ __forceinline__ int64_t gid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
-// p = o + d * t, component by component
-__device__ __forceinline__ void ray_point(const float* __restrict__ o, const float* __restrict__ d, int64_t ray, float t, float* __restrict__ out) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = o[ray * 3 + c] + d[ray * 3 + c] * t;
-}
+// the per-ray formulas (trace_ray.h), shared with the hash-grid field's device tracer
+using ray::ray_point;
+using ray::sample_z;
 
 __global__ __launch_bounds__(kBlk) void k_any_start(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ near,
                                                     int64_t n, float* __restrict__ points, float* __restrict__ dist) {
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(kBlk) void k_any_sphere_flag(const float* __restric
     const float s = values[k];
     sdf[ray] = s;
     const bool before = list_in ? unf[ray] != 0 : work[ray] != 0;
-    const bool u = before && (fabsf(s) > thr) && (dist[ray] < far[ray]);
+    const bool u = ray::still_unfinished(before, s, thr, dist[ray], far[ray]);
     unf[ray] = u ? 1 : 0;
     flags[k] = Pair64{u ? 1 : 0, 0};
 }
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(kBlk) void k_any_sphere_emit(const int32_t* __restr
             dist[ray] = dist[ray] + s;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float p = points[ray * 3 + c] + d[ray * 3 + c] * s;
+                const float p = ray::advance(points[ray * 3 + c], d[ray * 3 + c], s);
                 points[ray * 3 + c] = p;
                 pts_out[pos * 3 + c] = p;
             }
@@ -131,7 +130,7 @@ __global__ __launch_bounds__(kBlk) void k_any_sphere_finish(const uint8_t* __res
     const int64_t i = gid();
     if (i >= n) return;
     const bool u = unf[i] != 0;
-    conv[i] = (work[i] != 0 && !u && (fabsf(sdf[i]) <= thr) && (dist[i] < far[i])) ? 1 : 0;
+    conv[i] = ray::sphere_converged(work[i] != 0, u, sdf[i], thr, dist[i], far[i]) ? 1 : 0;
     if (unf_out) unf_out[i] = u ? 1 : 0;
 }
 
@@ -142,14 +141,8 @@ __global__ __launch_bounds__(kBlk) void k_any_interval(const int32_t* __restrict
     const int64_t k = gid();
     if (k >= m) return;
     const int64_t ray = list[k];
-    const float pos = sdf[ray] > 0.0f ? 1.0f : 0.0f;
-    const float neg = 1.0f - pos;
-    const float t = dist[ray];
-    smin[k] = pos * t + neg * near[ray];
-    smax[k] = pos * far[ray] + neg * t;
+    ray::sampler_interval(sdf[ray], dist[ray], near[ray], far[ray], smin + k, smax + k);
 }
-
-__device__ __forceinline__ float sample_z(float lo, float hi, float lin) { return lo + lin * (hi - lo); }
 
 // raytracer.py:144-150 for the rays [k0, k0 + nk) of the list: point q of the batch is sample q % n_steps of ray k0 + q / n_steps
 __global__ __launch_bounds__(kBlk) void k_any_sampler_points(const int32_t* __restrict__ list, int64_t k0, int64_t nk, int n_steps,
@@ -208,8 +201,8 @@ struct Bisect {
 __device__ __forceinline__ void bisect_open(const Bisect& B, int64_t b, int64_t ray, float dlo, float dhi, float flo, float fhi,
                                             const float* __restrict__ o, const float* __restrict__ d, float* __restrict__ pts_out,
                                             int64_t* __restrict__ words) {
-    const bool w = (flo > 0.0f) && (fhi < 0.0f);
-    const float mid = (dlo + dhi) / 2.0f;
+    const bool w = ray::bracket_open(flo, fhi);
+    const float mid = ray::bracket_mid(dlo, dhi);
     B.ray[b] = (int32_t)ray;
     B.dlo[b] = dlo; B.dhi[b] = dhi; B.flo[b] = flo; B.fhi[b] = fhi; B.dmid[b] = mid;
     B.work[b] = w ? 1 : 0;
@@ -254,12 +247,12 @@ __global__ __launch_bounds__(kBlk) void k_any_bisect_step(const float* __restric
     if (b >= nb) return;
     const float fm = values[b];
     const float mid0 = B.dmid[b];
-    float dlo = B.dlo[b], dhi = B.dhi[b];
-    if (fm > 0.0f) { dlo = mid0; B.dlo[b] = mid0; B.flo[b] = fm; }
-    if (fm <= 0.0f) { dhi = mid0; B.dhi[b] = mid0; B.fhi[b] = fm; }
-    const float mid = (dlo + dhi) / 2.0f;
+    float dlo = B.dlo[b], dhi = B.dhi[b], flo = B.flo[b], fhi = B.fhi[b];
+    ray::bracket_update(fm, mid0, &dlo, &dhi, &flo, &fhi);
+    B.dlo[b] = dlo; B.dhi[b] = dhi; B.flo[b] = flo; B.fhi[b] = fhi;
+    const float mid = ray::bracket_mid(dlo, dhi);
     B.dmid[b] = mid;
-    const bool w = B.work[b] != 0 && ((dhi - dlo) > two_thr);
+    const bool w = B.work[b] != 0 && ray::bracket_wide(dlo, dhi, two_thr);
     B.work[b] = w ? 1 : 0;
     ray_point(o, d, B.ray[b], mid, pts_out + b * 3);
     if (w) words[1] = 1;

@@ -22,7 +22,7 @@ import torch
 
 from . import _args, _lib
 from .mesh_render import _mts_tables, check_path_args, subpixel_uvs
-from .raytracer import SDFCallable, SDFHandle, intersect_sphere, raytrace_pixels, render_normal_and_color
+from .raytracer import HashFieldSDF, SDFCallable, SDFHandle, intersect_sphere, raytrace_pixels, render_normal_and_color
 
 WHAT = "neural relight"
 GBUFFER = ("convergent_mask", "points", "normal", "ray_d", "diffuse_albedo", "specular_albedo", "specular_roughness")
@@ -41,8 +41,8 @@ PATH_STAGES = ("path_emit", "path_shadow", "path_bounce", "path_surface", "path_
 
 
 def _as_sdf(sdf):
-    """What RayTracer.occluded takes: an SDFNetwork is wrapped in its handle; SDFHandle and SDFCallable pass."""
-    if isinstance(sdf, (SDFHandle, SDFCallable)):
+    """What RayTracer.occluded takes: an SDFNetwork is wrapped in its handle; SDFHandle, SDFCallable and HashFieldSDF pass."""
+    if isinstance(sdf, (SDFHandle, SDFCallable, HashFieldSDF)):
         return sdf
     if hasattr(sdf, "hip_net"):
         return SDFHandle(sdf)
@@ -94,7 +94,8 @@ def relight_results(results, sdf, raytracer, envmap, n_light=64, n_brdf=64, seed
     cut to the unit sphere by intersect_sphere, is not raytracer.occluded(sdf, ...); a ray that misses the sphere is visible.
     shadow_eps (default 1e-3 = 20 x the tracer's sdf_threshold) is a parameter, not a measurement.
 
-    `sdf`: an SDFNetwork, an SDFHandle or an SDFCallable.  Pixels are worked in blocks of max_shadow_rays // (n_light + n_brdf),
+    `sdf`: an SDFNetwork, an SDFHandle or an SDFCallable; a HashFieldSDF (TCNNSDF.as_traced) is taken by occluded / forward(chunk=1)
+    like any handle and, as an SDFCallable does, needs a surface_fn above max_depth 1.  Pixels are worked in blocks of max_shadow_rays // (n_light + n_brdf),
     which bounds the memory (about 170 bytes per shadow ray) and changes no bit of the result.  Every block waits once for the host
     to read the number of its shadow rays, the size of the tracer's call.
     -> {"color", "diffuse_color", "specular_color"} [..., 3], color = diffuse_color + specular_color, zeros on a miss; dump=True adds
@@ -245,8 +246,9 @@ def _surface(sdf, surface_fn, color_network_dict):
                 full[k] = torch.zeros((points.shape[0],) + want[1:], dtype=torch.float32, device=dev).index_copy_(0, at, v.contiguous())
             return full
         return from_fn
-    if isinstance(sdf, SDFCallable):
-        raise _lib.IronError("%s: interreflections on an SDFCallable need a surface_fn" % WHAT)
+    if isinstance(sdf, (SDFCallable, HashFieldSDF)):
+        raise _lib.IronError("%s: interreflections on %s need a surface_fn"
+                             % (WHAT, "an SDFCallable" if isinstance(sdf, SDFCallable) else "a HashFieldSDF"))
     net = sdf.sdf_network if isinstance(sdf, SDFHandle) else sdf
     if not hasattr(net, "hip_net") or not hasattr(net, "get_all"):
         raise _lib.IronError("%s: interreflections need an iron_amd SDFNetwork (or its handle), or a surface_fn" % WHAT)

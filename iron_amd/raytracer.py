@@ -13,6 +13,8 @@ render_edge_pixels :665-729), and is_training=True (reparam_po
 attached to the parameters through the differentiable HIP operators of iron_amd.autograd).
 An SDF the library cannot evaluate itself is traced through SDFCallable(fn): the reference's evaluation schedule with fn supplying
 the values, the per-ray bookkeeping between two calls in csrc/trace_any.hip.
+A hash-grid field (TCNNSDF.as_traced() -> HashFieldSDF) is traced with the field evaluated inside the tracer's kernels
+(csrc/hashgrid_trace.hip): the callable path's bits without its host round trips.
 There is no CPU path: tensors must be CUDA (ROCm) fp32.
 """
 from __future__ import annotations
@@ -56,6 +58,51 @@ class SDFCallable:
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return self.fn(x)
+
+
+class HashFieldSDF:
+    """The hash-grid field `TCNNSDF` at scale * x + offset as an SDF the tracer evaluates INSIDE its own kernels
+    (csrc/hashgrid_trace.hip); made by TCNNSDF.as_traced().  RayTracer.forward / occluded / sphere_tracing /
+    ray_sampler / rootfind enqueue a fixed launch sequence for it and read nothing back (unless collect_stats=True); the results are,
+    bit for bit, those of the same call on field.as_callable(scale, offset).  Holds the field itself, not a copy: the table is read
+    in place and the head is repacked when a weight changed.  Calling the handle evaluates the field (column 0 of eval_fused).  The
+    multi-rank form (phase_begin / forward_phased) does not take one."""
+
+    def __init__(self, field, scale=None, offset=None):
+        from .tcnn_fields import TCNNSDF, _map3
+        if not isinstance(field, TCNNSDF):
+            raise _lib.IronError("HashFieldSDF needs a TCNNSDF, got %s" % type(field).__name__)
+        field._fused_desc()   # an unsupported head shape is refused here, by name
+        self.field = field
+        self.scale, self.offset = scale, offset
+        self._a, self._b = _map3(scale, "scale"), _map3(offset, "offset")
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        return self.field.eval_fused(x, scale=self.scale, offset=self.offset)[..., 0]
+
+    def field_args(self, device):
+        """(desc, map a, map b, table, packed) for the iron_hashgrid_trace* entries; the tensors must be kept alive over the call."""
+        desc = self.field._fused_desc()
+        table = self.field.sdf_encoding.params
+        if table.device != device or table.dtype != torch.float32:
+            raise _lib.IronError("HashFieldSDF: the table must be float32 on the rays' device; call .cuda() first")
+        return desc, self._a, self._b, table.detach().contiguous(), self.field._fused_packed(desc, device)
+
+
+_lin_cache = {}
+
+
+def _linspace_steps_cached(n_steps: int, device) -> torch.Tensor:
+    """_linspace_steps, uploaded once per (n_steps, device): the device tracer's calls copy nothing from the host"""
+    key = (int(n_steps), device)
+    if key not in _lin_cache:
+        _lin_cache[key] = _linspace_steps(n_steps, device)
+    return _lin_cache[key]
+
+
+def _check_hashfield_stats(stats) -> None:
+    if stats.get("incomplete", 0):   # the callable tracer's own error, for the same cause
+        raise _lib.IronError("the bisection does not close: the sdf callable returns NaN inside an open bracket, or a bracket is not finite")
 
 
 class _AnyTrace:
@@ -242,6 +289,8 @@ class RayTracer(nn.Module):
         o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         if isinstance(sdf, SDFCallable):
             return self._forward_callable(sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats)
+        if isinstance(sdf, HashFieldSDF):
+            return self._forward_hashfield(sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, False)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
         near = _lib.require_cuda_f32(min_dis, "min_dis").reshape(-1)
@@ -285,6 +334,8 @@ class RayTracer(nn.Module):
             work_mask = torch.ones(n, dtype=torch.bool, device=dev)
         if isinstance(sdf, SDFCallable):
             return self.forward(sdf, o, ray_d, min_dis, max_dis, work_mask, collect_stats=collect_stats)["convergent_mask"]
+        if isinstance(sdf, HashFieldSDF):
+            return self._forward_hashfield(sdf, o, ray_d, min_dis, max_dis, work_mask, 0, collect_stats, True)
         net = _resolve_sdf_network(sdf, dev)
         d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
         work = self._work_arg(work_mask, n)
@@ -355,6 +406,85 @@ class RayTracer(nn.Module):
             self.last_stats = stats
         return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
 
+    # ---- a hash-grid field (HashFieldSDF): the same reference call with the field evaluated inside the kernels of
+    # csrc/hashgrid_trace.hip; a fixed launch sequence, nothing read back unless the stats are asked for
+    def _hashfield_params(self, chunk):
+        if not 2 <= int(self.n_steps) <= 4096:
+            raise _lib.IronError("the hash-grid tracer takes n_steps in 2 .. 4096, got %r" % (self.n_steps,))
+        if int(self.sphere_tracing_iters) < 0:
+            raise _lib.IronError("sphere_tracing_iters must not be negative, got %r" % (self.sphere_tracing_iters,))
+        return self._params(0 if chunk is None else max(int(chunk), 0))
+
+    def _hashfield_stats_out(self, stats, check):
+        """the eight device words -> last_stats (one read-back), and the `incomplete` word -> the callable tracer's IronError"""
+        words = dict(zip(_lib.HASHGRID_TRACE_STATS_FIELDS, stats.cpu().tolist()))
+        self.last_stats = {k: v for k, v in words.items() if not k.startswith("reserved")}
+        if check:
+            _check_hashfield_stats(self.last_stats)
+
+    def _forward_hashfield(self, sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, mask_only):
+        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
+        n, dev = o.shape[0], o.device
+        work = self._work_arg(work_mask, n)
+        prm = self._hashfield_params(chunk)
+        conv = torch.empty(n, dtype=torch.bool, device=dev)
+        if not mask_only:
+            points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            sdf_out = torch.empty(n, dtype=torch.float32, device=dev)
+            dist = torch.empty(n, dtype=torch.float32, device=dev)
+        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
+        if n > 0:
+            lib = _lib.load()
+            desc, map_a, map_b, table, packed = sdf.field_args(dev)
+            ws_bytes = lib.iron_hashgrid_trace_workspace_bytes(n, C.byref(prm))
+            if ws_bytes == 0:
+                raise _lib.IronError("the hash-grid tracer takes fewer than 2^31 - 1 rays per call")
+            lin = _linspace_steps_cached(self.n_steps, dev)
+            with torch.cuda.device(dev):
+                ws = _lib.workspace(ws_bytes, dev, "hashfield_trace")
+                head = (C.byref(desc), C.byref(prm), map_a, map_b, table.data_ptr(), packed.data_ptr(), lin.data_ptr(), o.data_ptr(),
+                        d.data_ptr(), near.data_ptr(), far.data_ptr(), work.data_ptr(), n, conv.data_ptr())
+                tail = (_lib.ptr(stats), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+                if mask_only:
+                    _lib.check(lib.iron_hashgrid_trace_occluded(*head, *tail))
+                else:
+                    _lib.check(lib.iron_hashgrid_trace(*head, points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(), *tail))
+        if collect_stats:
+            self._hashfield_stats_out(stats, True)
+        if mask_only:
+            return conv
+        return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
+
+    def _stage_hashfield(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
+        """The reference's stage methods on a HashFieldSDF.  They are the debugging surface, not the frame's path: each reads the
+        stats words back once, so that a bisection that does not close raises here as it does on the callable."""
+        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        args = self._ray_args(o, ray_d, *[t for t in (in0, in1, in2, in3) if t is not None])
+        d, ins = args[0], list(args[1:]) + [None, None]
+        n, dev = o.shape[0], o.device
+        work = self._work_arg(work_mask, n) if work_mask is not None else None
+        prm = self._hashfield_params(0)
+        mask = torch.zeros(n, dtype=torch.bool, device=dev)
+        unfinished = torch.zeros(n, dtype=torch.bool, device=dev)
+        points = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        sdf_out = torch.zeros(n, dtype=torch.float32, device=dev)
+        dist = torch.zeros(n, dtype=torch.float32, device=dev)
+        if n > 0:
+            lib = _lib.load()
+            desc, map_a, map_b, table, packed = sdf.field_args(dev)
+            ws_bytes = lib.iron_hashgrid_trace_workspace_bytes(n, C.byref(prm))
+            lin = _linspace_steps_cached(self.n_steps, dev)
+            stats = torch.zeros(8, dtype=torch.int64, device=dev)
+            with torch.cuda.device(dev):
+                ws = _lib.workspace(ws_bytes, dev, "hashfield_trace")
+                _lib.check(lib.iron_hashgrid_trace_stage(stage, C.byref(desc), C.byref(prm), map_a, map_b, table.data_ptr(), packed.data_ptr(),
+                                                         lin.data_ptr(), o.data_ptr(), d.data_ptr(), _lib.ptr(ins[0]), _lib.ptr(ins[1]),
+                                                         _lib.ptr(ins[2]), _lib.ptr(ins[3]), _lib.ptr(work), n, mask.data_ptr(),
+                                                         unfinished.data_ptr(), points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(),
+                                                         stats.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
+            self._hashfield_stats_out(stats, True)
+        return mask, unfinished, points, sdf_out, dist
+
     def _stage_callable(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
         o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         args = self._ray_args(o, ray_d, *[t for t in (in0, in1, in2, in3) if t is not None])
@@ -389,7 +519,9 @@ class RayTracer(nn.Module):
     def _stage(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
         if isinstance(sdf, SDFCallable):
             return self._stage_callable(stage, sdf, ray_o, ray_d, in0, in1, in2, in3, work_mask)
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        if isinstance(sdf, HashFieldSDF):
+            return self._stage_hashfield(stage, sdf, ray_o, ray_d, in0, in1, in2, in3, work_mask)
+        o =_lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
         ins = [None if t is None else _lib.require_cuda_f32(t, "argument").reshape(-1) for t in (in0, in1, in2, in3)]
@@ -447,7 +579,9 @@ class RayTracer(nn.Module):
         state["chunk_iters"] (int32 [n_chunks], device) is the table to reduce in place."""
         if isinstance(sdf, SDFCallable):
             raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take an SDFCallable: call forward() per rank")
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+        if isinstance(sdf, HashFieldSDF):
+            raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take a HashFieldSDF: call forward() per rank")
+        o =_lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
         net = _resolve_sdf_network(sdf, o.device)
         d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
         near = _lib.require_cuda_f32(min_dis, "min_dis").reshape(-1)
@@ -664,7 +798,9 @@ def raytrace_pixels(sdf_network, raytracer, uv, camera, mask=None, max_num_rays=
         mask = torch.ones_like(uv[..., 0]).bool()
     dots_sh = list(uv.shape[:-1])
     ray_o, ray_d, ray_d_norm = camera.get_rays(uv)
-    if hasattr(sdf_network, "hip_net"):
+    if isinstance(sdf_network, HashFieldSDF):   # TCNNSDF.as_traced(): the hash-grid field's device tracer, passed through
+        sdf = sdf_network
+    elif hasattr(sdf_network, "hip_net"):
         sdf = SDFHandle(sdf_network)
     else:  # a foreign network: traced through its own forward, as the reference does (raytracer.py:375)
         sdf = SDFCallable(lambda x: sdf_network(x)[..., 0])

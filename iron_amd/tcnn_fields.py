@@ -312,6 +312,14 @@ class TCNNSDF(nn.Module):
         self._fused_desc()
         return SDFCallable(lambda x: self.eval_fused(x, scale=scale, offset=offset)[..., 0])
 
+    def as_traced(self, scale=None, offset=None):
+        """The same signed distance as a HashFieldSDF handle: RayTracer.forward / occluded / the stage methods and raytrace_pixels
+        trace it with the field evaluated inside the tracer's own kernels (csrc/hashgrid_trace.hip), bit for bit the
+        results of as_callable(scale, offset) without its host round trips.  The handle holds this field, not a copy: an optimiser
+        step is seen by the next trace."""
+        from .raytracer import HashFieldSDF
+        return HashFieldSDF(self, scale, offset)
+
 
 def _map3(v, name):
     """None, a number or three numbers -> None or a float[3] for the C ABI"""
