@@ -184,33 +184,29 @@ __global__ __launch_bounds__(256) void k_hg_field_pack(FieldPlan pl, const float
 }
 
 template <int ACT, bool GRAD, int CT, int NT>
-static int field_launch(const hg::Levels& L, const FieldPlan& pl, const FieldLds& lo, size_t lds_bytes, const float* p, int64_t n,
-                        const FieldMap& map, const float* table, const float4* packed, float* out, float* grad, hipStream_t st) {
+static int field_launch(const FieldBinding& F, const FieldLds& lo, size_t lds_bytes, const float* p, int64_t n, float* out, float* grad,
+                        hipStream_t st) {
     if (lds_bytes > 64 * 1024)
         IRON_HIP_TRY(hipFuncSetAttribute((const void*)k_hg_field<ACT, GRAD, CT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     const int64_t blocks = (n + 32 * CT - 1) / (32 * CT);
-    hipLaunchKernelGGL((k_hg_field<ACT, GRAD, CT, NT>), dim3((unsigned)blocks), dim3(64), lds_bytes, st, L, pl, lo, p, n, map, table, packed,
-                       out, grad);
+    hipLaunchKernelGGL((k_hg_field<ACT, GRAD, CT, NT>), dim3((unsigned)blocks), dim3(64), lds_bytes, st, F.L, F.pl, lo, p, n, F.map, F.table,
+                       F.packed, out, grad);
     IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
 }
 
-template <int ACT>
-static int field_dispatch(const hg::Levels& L, const FieldPlan& pl, const float* p, int64_t n, const FieldMap& map, const float* table,
-                          const float4* packed, float* out, float* grad, hipStream_t st) {
+static int field_dispatch(const FieldBinding& F, const float* p, int64_t n, float* out, float* grad, hipStream_t st) {
     FieldLds lo;
     if (!grad) {   // value: 64 points per wave always fit (at most 128 rows of 256 bytes); the hidden layers' tiles in registers
-        const size_t bytes = lds_layout(pl, false, 64, &lo);
-        switch (pl.tiles[0]) {
-            case 1: return field_launch<ACT, false, 2, 1>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
-            case 2: return field_launch<ACT, false, 2, 2>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
-            default: return field_launch<ACT, false, 2, 4>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
-        }
+        const size_t bytes = lds_layout(F.pl, false, 64, &lo);
+        return with_value_path(F.pl, [&](auto act, auto nt) { return field_launch<act(), false, 2, nt()>(F, lo, bytes, p, n, out, grad, st); });
     }
-    size_t bytes = lds_layout(pl, true, 64, &lo);
-    if (bytes <= (size_t)kFieldLdsTwoTiles) return field_launch<ACT, true, 2, 0>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
-    bytes = lds_layout(pl, true, 32, &lo);
-    return field_launch<ACT, true, 1, 0>(L, pl, lo, bytes, p, n, map, table, packed, out, grad, st);
+    return with_act(F.pl, [&](auto act) {
+        size_t bytes = lds_layout(F.pl, true, 64, &lo);
+        if (bytes <= (size_t)kFieldLdsTwoTiles) return field_launch<act(), true, 2, 0>(F, lo, bytes, p, n, out, grad, st);
+        bytes = lds_layout(F.pl, true, 32, &lo);
+        return field_launch<act(), true, 1, 0>(F, lo, bytes, p, n, out, grad, st);
+    });
 }
 
 }  // namespace iron
@@ -243,27 +239,14 @@ extern "C" int iron_hashgrid_field_pack(const iron_hashgrid_field_desc* desc, co
 extern "C" int iron_hashgrid_field_eval(const iron_hashgrid_field_desc* desc, const float* p, int64_t n, const float* map_a3_or_null,
                                         const float* map_b3_or_null, const float* table, const void* packed, float* out,
                                         float* grad_or_null, void* stream) {
-    FieldPlan pl;
-    int rc = make_plan(desc, &pl);
-    if (rc != IRON_OK) return rc;
-    hg::Levels L;
-    int64_t n_params = 0;
-    rc = hg::make_levels(&desc->encoding, &L, &n_params);
+    FieldBinding F;
+    int rc = field_open(desc, &F);
     if (rc != IRON_OK) return rc;
     if (n < 0) return IRON_ERR_BAD_ARG;
     if (n == 0) return IRON_OK;
-    if (!p || !table || !packed || !out || ((uintptr_t)packed & 15)) return IRON_ERR_BAD_ARG;
-    if (n > (int64_t)0x7fffffff * 32) return IRON_ERR_RANGE;
-    FieldMap map;
-    for (int d = 0; d < 3; ++d) {
-        map.a[d] = map_a3_or_null ? map_a3_or_null[d] : 1.0f;
-        map.b[d] = map_b3_or_null ? map_b3_or_null[d] : 0.0f;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const float4* pk = (const float4*)packed;
-    switch (pl.act) {
-        case IRON_FIELD_ACT_RELU: return field_dispatch<IRON_FIELD_ACT_RELU>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
-        case IRON_FIELD_ACT_SOFTPLUS: return field_dispatch<IRON_FIELD_ACT_SOFTPLUS>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
-        default: return field_dispatch<IRON_FIELD_ACT_NONE>(L, pl, p, n, map, table, pk, out, grad_or_null, st);
-    }
+    if (!p || !out) return IRON_ERR_BAD_ARG;
+    rc = field_bind(&F, map_a3_or_null, map_b3_or_null, table, packed);
+    if (rc != IRON_OK) return rc;
+    if (n > (int64_t)0x7fffffff * 32) return IRON_ERR_RANGE;   // behind the pointers: a null one is a bad argument whatever n is
+    return field_dispatch(F, p, n, out, grad_or_null, (hipStream_t)stream);
 }

@@ -6,6 +6,8 @@
 #include "hashgrid_common.h"
 #include "mlp_core.h"
 
+#include <type_traits>
+
 namespace iron {
 
 constexpr int kFieldMaxLayers = 5;    // 4 hidden + the output layer
@@ -83,6 +85,64 @@ static inline size_t lds_layout(const FieldPlan& p, bool grad, int P, FieldLds* 
     }
     if (out) *out = L;
     return rows * P * sizeof(float);
+}
+
+// x -> a x + b per axis, from the caller's coordinates into the unit cube of the encoding
+struct FieldMap {
+    float a[3], b[3];
+};
+
+// What a launch needs of a field: the levels and the plan of its descriptor, the map, the table and the packed head.  The entries
+// of hashgrid_field.hip, hashgrid_field_train.hip and hashgrid_trace.hip fill one with the two helpers below; the tracer's kernels
+// take it as their first argument.
+struct FieldBinding {
+    hg::Levels L;
+    FieldPlan pl;
+    FieldMap map;
+    const float* table;
+    const float4* packed;
+};
+
+// levels and plan of a descriptor: BAD_ARG for a null or malformed one, RANGE for a shape the kernels are not built for
+static inline int field_open(const iron_hashgrid_field_desc* d, FieldBinding* F, int64_t* n_params = nullptr) {
+    const int rc = make_plan(d, &F->pl);
+    if (rc != IRON_OK) return rc;
+    return hg::make_levels(&d->encoding, &F->L, n_params);
+}
+
+// map (a null half is the identity's), table and packed head: BAD_ARG unless both are there and the head is 16-byte aligned
+static inline int field_bind(FieldBinding* F, const float* map_a3_or_null, const float* map_b3_or_null, const float* table, const void* packed) {
+    if (!table || !packed || ((uintptr_t)packed & 15)) return IRON_ERR_BAD_ARG;
+    for (int d = 0; d < 3; ++d) {
+        F->map.a[d] = map_a3_or_null ? map_a3_or_null[d] : 1.0f;
+        F->map.b[d] = map_b3_or_null ? map_b3_or_null[d] : 0.0f;
+    }
+    F->table = table;
+    F->packed = (const float4*)packed;
+    return IRON_OK;
+}
+
+// fn(integral_constant<int, ACT>) for the activation of a validated plan
+template <class Fn>
+static inline int with_act(const FieldPlan& pl, Fn&& fn) {
+    switch (pl.act) {
+        case IRON_FIELD_ACT_RELU: return fn(std::integral_constant<int, IRON_FIELD_ACT_RELU>{});
+        case IRON_FIELD_ACT_SOFTPLUS: return fn(std::integral_constant<int, IRON_FIELD_ACT_SOFTPLUS>{});
+        default: return fn(std::integral_constant<int, IRON_FIELD_ACT_NONE>{});
+    }
+}
+
+// fn(integral_constant ACT, integral_constant NT) for the <ACT, NT> instance of the value path (field_value_acc) that serves a
+// plan: NT is the number of 32-row output tiles of a hidden layer, 1, 2 or 4 for the 16 / 32, 64 and 128 neurons make_plan accepts
+template <class Fn>
+static inline int with_value_path(const FieldPlan& pl, Fn&& fn) {
+    return with_act(pl, [&](auto act) {
+        switch (pl.tiles[0]) {
+            case 1: return fn(act, std::integral_constant<int, 1>{});
+            case 2: return fn(act, std::integral_constant<int, 2>{});
+            default: return fn(act, std::integral_constant<int, 4>{});
+        }
+    });
 }
 
 template <int ACT>
@@ -216,10 +276,6 @@ __device__ __forceinline__ void field_tile(const float4* __restrict__ frag, int 
         }
     }
 }
-
-struct FieldMap {
-    float a[3], b[3];
-};
 
 // The value path of one wave64 on P = 32 CT points: lane `lane` < P encodes the point xs (already mapped into the
 // unit cube) into stage 0, the hidden layers run in the one LDS buffer `lds` (lds_layout(pl, false, P) bytes) with their NT output

@@ -367,36 +367,37 @@ static TrainWs train_ws_layout(const iron_hashgrid_field_desc* d, const FieldPla
     return w;
 }
 
-// the plan of a shape the backward is built for: IRON_ERR_RANGE for 128 neurons and for stages that do not fit the LDS of a CU
-static int make_train(const iron_hashgrid_field_desc* d, FieldPlan* pl, TrainPlan* tp) {
-    const int rc = make_plan(d, pl);
-    if (rc != IRON_OK) return rc;
-    if (pl->neurons > 64) return IRON_ERR_RANGE;
-    if (train_lds_layout(*pl, 32, nullptr) > (size_t)kTrainLdsMax) return IRON_ERR_RANGE;
-    *tp = make_train_plan(*pl);
+// the training plan of a shape the backward is built for: IRON_ERR_RANGE for 128 neurons and for stages that do not fit the LDS of a CU
+static int train_plan(const FieldPlan& pl, TrainPlan* tp) {
+    if (pl.neurons > 64) return IRON_ERR_RANGE;
+    if (train_lds_layout(pl, 32, nullptr) > (size_t)kTrainLdsMax) return IRON_ERR_RANGE;
+    *tp = make_train_plan(pl);
     return IRON_OK;
 }
 
+static int make_train(const iron_hashgrid_field_desc* d, FieldPlan* pl, TrainPlan* tp) {
+    const int rc = make_plan(d, pl);
+    return rc != IRON_OK ? rc : train_plan(*pl, tp);
+}
+
 template <int ACT, int CT>
-static int train_launch(const hg::Levels& L, const FieldPlan& pl, const TrainPlan& tp, const TrainLds& lo, size_t lds_bytes,
-                        const FieldMap& map, const TrainArgs& a, hipStream_t st) {
+static int train_launch(const FieldBinding& F, const TrainPlan& tp, const TrainLds& lo, size_t lds_bytes, const TrainArgs& a, hipStream_t st) {
     if (lds_bytes > 64 * 1024)
         IRON_TRAIN_HIP(hipFuncSetAttribute((const void*)k_hg_field_bwd<ACT, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL((k_hg_field_bwd<ACT, CT>), dim3((unsigned)a.slots), dim3(64), lds_bytes, st, L, pl, tp, lo, map, a);
+    hipLaunchKernelGGL((k_hg_field_bwd<ACT, CT>), dim3((unsigned)a.slots), dim3(64), lds_bytes, st, F.L, F.pl, tp, lo, F.map, a);
     IRON_TRAIN_HIP(hipGetLastError());
     return IRON_OK;
 }
 
 template <int ACT>
-static int train_dispatch(const hg::Levels& L, const FieldPlan& pl, const TrainPlan& tp, const FieldMap& map, const TrainArgs& a,
-                          hipStream_t st) {
+static int train_dispatch(const FieldBinding& F, const TrainPlan& tp, const TrainArgs& a, hipStream_t st) {
     // 64 points per tile where their stages fit; the accumulator tiles beside them in LDS where those fit too
     TrainLds lo;
-    const int P = train_lds_layout(pl, 64, nullptr) <= (size_t)kTrainLdsMax ? 64 : 32;
-    size_t bytes = train_lds_layout(pl, P, &lo, tp.n_tiles);
-    if (bytes > (size_t)kTrainLdsMax) bytes = train_lds_layout(pl, P, &lo);
-    if (P == 64) return train_launch<ACT, 2>(L, pl, tp, lo, bytes, map, a, st);
-    return train_launch<ACT, 1>(L, pl, tp, lo, bytes, map, a, st);
+    const int P = train_lds_layout(F.pl, 64, nullptr) <= (size_t)kTrainLdsMax ? 64 : 32;
+    size_t bytes = train_lds_layout(F.pl, P, &lo, tp.n_tiles);
+    if (bytes > (size_t)kTrainLdsMax) bytes = train_lds_layout(F.pl, P, &lo);
+    if (P == 64) return train_launch<ACT, 2>(F, tp, lo, bytes, a, st);
+    return train_launch<ACT, 1>(F, tp, lo, bytes, a, st);
 }
 
 }  // namespace iron_train
@@ -440,33 +441,29 @@ extern "C" int iron_hashgrid_field_backward(const iron_hashgrid_field_desc* desc
                                             const void* train_packed, const float* d_out_or_null, const float* d_g_or_null,
                                             float* d_weights, float* d_table_or_null, float* ybar_out_or_null, float* e_out_or_null,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-    FieldPlan pl;
+    FieldBinding F;
     TrainPlan tp;
-    int rc = make_train(desc, &pl, &tp);
-    if (rc != IRON_OK) return rc;
-    hg::Levels L;
     int64_t n_params = 0;
-    rc = hg::make_levels(&desc->encoding, &L, &n_params);
+    int rc = field_open(desc, &F, &n_params);
+    if (rc == IRON_OK) rc = train_plan(F.pl, &tp);
     if (rc != IRON_OK) return rc;
+    const FieldPlan& pl = F.pl;
     if (n < 0 || !d_weights) return IRON_ERR_BAD_ARG;
     if (n > (int64_t)0x7fffffff * 32) return IRON_ERR_RANGE;   // iron_hashgrid_field_eval's limit; the scatter checks its own
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         IRON_TRAIN_HIP(hipMemsetAsync(d_weights, 0, sizeof(float) * (size_t)pl.n_weights, st));
-        if (d_table_or_null) IRON_TRAIN_HIP(hipMemsetAsync(d_table_or_null, 0, sizeof(float) * (size_t)n_params * L.n_features, st));
+        if (d_table_or_null) IRON_TRAIN_HIP(hipMemsetAsync(d_table_or_null, 0, sizeof(float) * (size_t)n_params * F.L.n_features, st));
         return IRON_OK;
     }
-    if (!p || !table || !packed || !train_packed || !workspace) return IRON_ERR_BAD_ARG;
-    if (((uintptr_t)packed & 15) || ((uintptr_t)train_packed & 15) || ((uintptr_t)workspace & 255)) return IRON_ERR_BAD_ARG;
+    if (!p || !train_packed || !workspace) return IRON_ERR_BAD_ARG;
+    rc = field_bind(&F, map_a3_or_null, map_b3_or_null, table, packed);
+    if (rc != IRON_OK) return rc;
+    if (((uintptr_t)train_packed & 15) || ((uintptr_t)workspace & 255)) return IRON_ERR_BAD_ARG;
     const TrainWs w = train_ws_layout(desc, pl, tp, n);
     if (workspace_bytes < w.bytes) return IRON_ERR_WORKSPACE;
-    FieldMap map;
-    for (int d = 0; d < 3; ++d) {
-        map.a[d] = map_a3_or_null ? map_a3_or_null[d] : 1.0f;
-        map.b[d] = map_b3_or_null ? map_b3_or_null[d] : 0.0f;
-    }
     TrainArgs a{};
-    a.p = p; a.table = table; a.packed = (const float4*)packed; a.tpacked = (const float4*)train_packed;
+    a.p = p; a.table = F.table; a.packed = F.packed; a.tpacked = (const float4*)train_packed;
     a.d_out = d_out_or_null; a.d_g = d_g_or_null;
     a.ybar = ybar_out_or_null ? ybar_out_or_null : ws_ptr<float>(workspace, w.ybar);
     a.e = e_out_or_null ? e_out_or_null : ws_ptr<float>(workspace, w.e);
@@ -476,11 +473,7 @@ extern "C" int iron_hashgrid_field_backward(const iron_hashgrid_field_desc* desc
     a.part = ws_ptr<double>(workspace, w.part);
     a.n = n; a.slot_points = train_slot_points(n);
     a.slots = (int32_t)cdiv64(n, a.slot_points);
-    switch (pl.act) {
-        case IRON_FIELD_ACT_RELU: rc = train_dispatch<IRON_FIELD_ACT_RELU>(L, pl, tp, map, a, st); break;
-        case IRON_FIELD_ACT_SOFTPLUS: rc = train_dispatch<IRON_FIELD_ACT_SOFTPLUS>(L, pl, tp, map, a, st); break;
-        default: rc = train_dispatch<IRON_FIELD_ACT_NONE>(L, pl, tp, map, a, st); break;
-    }
+    rc = with_act(pl, [&](auto act) { return train_dispatch<act()>(F, tp, a, st); });
     if (rc != IRON_OK) return rc;
     IRON_TRAIN_LAUNCH(k_hg_field_wsum, (unsigned)pl.n_weights, 64, st, (const double*)a.part, (int64_t)a.slots, d_weights);
     if (!d_table_or_null) return IRON_OK;

@@ -31,14 +31,6 @@ constexpr int kBisectCap = 256;   // fp32 brackets halve to nothing long before;
 enum { ST_ISSUED = 0, ST_LIVE = 1, ST_SAMPLER = 2, ST_BISECT = 3, ST_ITERS = 4, ST_INCOMPLETE = 5 };
 enum { W_UNFINISHED = 0, W_BRACKETS = 1 };
 
-struct FieldArgs {
-    hg::Levels L;
-    FieldPlan pl;
-    FieldMap map;
-    const float* table;
-    const float4* packed;
-};
-
 struct RayArgs {
     const float *o, *d;
     int64_t n;
@@ -110,7 +102,7 @@ __device__ __forceinline__ int wave_max(int v) {
 // the field at the 64 points of the wave, each lane its own; `live` lanes count as evaluations that belonged to a ray.  The barrier
 // behind the value keeps the next evaluation's encode from overwriting rows the last layer is still reading.
 template <int ACT, int NT>
-__device__ __forceinline__ float eval_at(const FieldArgs& F, float* lds, const float* p, bool live, int lane, int64_t& issued, int64_t& lived) {
+__device__ __forceinline__ float eval_at(const FieldBinding& F, float* lds, const float* p, bool live, int lane, int64_t& issued, int64_t& lived) {
     float xs[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) xs[c] = fmaf(p[c], F.map.a[c], F.map.b[c]);
@@ -135,7 +127,7 @@ struct SphereArgs {
 };
 
 template <int ACT, int NT>
-__global__ __launch_bounds__(64) void k_hgt_sphere(FieldArgs F, RayArgs R, SphereArgs A) {
+__global__ __launch_bounds__(64) void k_hgt_sphere(FieldBinding F, RayArgs R, SphereArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * 64 + lane;
@@ -225,7 +217,7 @@ struct SamplerArgs {
 };
 
 template <int ACT, int NT>
-__global__ __launch_bounds__(64) void k_hgt_sampler(FieldArgs F, RayArgs R, SamplerArgs A) {
+__global__ __launch_bounds__(64) void k_hgt_sampler(FieldBinding F, RayArgs R, SamplerArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     const int64_t m = A.words[W_UNFINISHED];
@@ -333,7 +325,7 @@ __device__ __forceinline__ int64_t chunk_of(int64_t ray, int64_t chunk) { return
 
 // a bracket's own iterations: while it is open and wider than 2 thr
 template <int ACT, int NT>
-__global__ __launch_bounds__(64) void k_hgt_bisect_a(FieldArgs F, RayArgs R, BisectArgs A) {
+__global__ __launch_bounds__(64) void k_hgt_bisect_a(FieldBinding F, RayArgs R, BisectArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     const int64_t nb = A.words[W_BRACKETS];
@@ -383,7 +375,7 @@ __global__ __launch_bounds__(64) void k_hgt_bisect_a(FieldArgs F, RayArgs R, Bis
 
 // from a bracket's own count to its chunk's: every slot moves, open or not (raytracer.py:205-217); then the final mid point
 template <int ACT, int NT>
-__global__ __launch_bounds__(64) void k_hgt_bisect_b(FieldArgs F, RayArgs R, BisectArgs A) {
+__global__ __launch_bounds__(64) void k_hgt_bisect_b(FieldBinding F, RayArgs R, BisectArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     const int64_t nb = A.words[W_BRACKETS];
@@ -427,27 +419,9 @@ __global__ __launch_bounds__(64) void k_hgt_bisect_b(FieldArgs F, RayArgs R, Bis
     }
 }
 
-// K<ACT, NT> for the descriptor's activation and the tile count of its hidden layers, one wave64 per workgroup
-#define HGT_LAUNCH(K, field, grid, lds_bytes, st, ...)                                                                              \
-    do {                                                                                                                            \
-        const int _nt = (field).pl.tiles[0] >= 3 ? 4 : (field).pl.tiles[0];                                                         \
-        switch ((field).pl.act * 8 + _nt) {                                                                                         \
-            case IRON_FIELD_ACT_NONE * 8 + 1: hipLaunchKernelGGL((K<IRON_FIELD_ACT_NONE, 1>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_NONE * 8 + 2: hipLaunchKernelGGL((K<IRON_FIELD_ACT_NONE, 2>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_NONE * 8 + 4: hipLaunchKernelGGL((K<IRON_FIELD_ACT_NONE, 4>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_RELU * 8 + 1: hipLaunchKernelGGL((K<IRON_FIELD_ACT_RELU, 1>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_RELU * 8 + 2: hipLaunchKernelGGL((K<IRON_FIELD_ACT_RELU, 2>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_RELU * 8 + 4: hipLaunchKernelGGL((K<IRON_FIELD_ACT_RELU, 4>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_SOFTPLUS * 8 + 1: hipLaunchKernelGGL((K<IRON_FIELD_ACT_SOFTPLUS, 1>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            case IRON_FIELD_ACT_SOFTPLUS * 8 + 2: hipLaunchKernelGGL((K<IRON_FIELD_ACT_SOFTPLUS, 2>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((K<IRON_FIELD_ACT_SOFTPLUS, 4>), dim3(grid), dim3(64), lds_bytes, st, __VA_ARGS__); break;   \
-        }                                                                                                                           \
-        IRON_HIP_TRY(hipGetLastError());                                                                                            \
-    } while (0)
-
 // one call's validated arguments
 struct Call {
-    FieldArgs F;
+    FieldBinding F;
     size_t lds_bytes;
     iron_trace_params prm;
     int64_t n;
@@ -455,35 +429,40 @@ struct Call {
     hipStream_t st;
 };
 
+#define HGT_TRY(expr)                  \
+    do {                               \
+        const int _rc = (expr);        \
+        if (_rc != IRON_OK) return _rc; \
+    } while (0)
+
 // The house order of the checks: null descriptor / parameters -> BAD_ARG, a refused shape or n_steps -> RANGE, n -> BAD_ARG.
 // *go is set when there is work to enqueue (n > 0); the pointer checks of the entry follow.
 int open_call(Call& c, const iron_hashgrid_field_desc* desc, const iron_trace_params* p, const float* map_a3, const float* map_b3, const float* table,
               const void* packed, int64_t n, void* workspace, size_t workspace_bytes, void* stream, bool* go) {
     *go = false;
     if (!desc || !p) return IRON_ERR_BAD_ARG;
-    int rc = make_plan(desc, &c.F.pl);
-    if (rc != IRON_OK) return rc;
-    int64_t n_params = 0;
-    rc = hg::make_levels(&desc->encoding, &c.F.L, &n_params);
-    if (rc != IRON_OK) return rc;
+    HGT_TRY(field_open(desc, &c.F));
     if (p->n_steps < 2 || p->n_steps > 4096) return IRON_ERR_RANGE;
     if (p->sphere_tracing_iters < 0 || !(p->sdf_threshold >= 0.0f)) return IRON_ERR_BAD_ARG;
     if (n < 0 || n > (int64_t)INT_MAX - 1) return IRON_ERR_BAD_ARG;
     if (n == 0) return IRON_OK;
-    if (!table || !packed || ((uintptr_t)packed & 15) || !workspace) return IRON_ERR_BAD_ARG;
+    HGT_TRY(field_bind(&c.F, map_a3, map_b3, table, packed));
+    if (!workspace) return IRON_ERR_BAD_ARG;
     c.prm = *p;
     c.n = n;
     c.ws = open_ws(n, p->chunk, workspace);
     if (workspace_bytes < c.ws.L.total) return IRON_ERR_BAD_ARG;
-    for (int d = 0; d < 3; ++d) {
-        c.F.map.a[d] = map_a3 ? map_a3[d] : 1.0f;
-        c.F.map.b[d] = map_b3 ? map_b3[d] : 0.0f;
-    }
-    c.F.table = table;
-    c.F.packed = (const float4*)packed;
     c.lds_bytes = lds_layout(c.F.pl, false, 64, nullptr);
     c.st = (hipStream_t)stream;
     *go = true;
+    return IRON_OK;
+}
+
+// K<ACT, NT>, one wave64 per workgroup, `grid` of them on the call's stream with the LDS of the value path
+template <class A>
+int launch_wave(void (*k)(FieldBinding, RayArgs, A), unsigned grid, const Call& c, const RayArgs& R, const A& a) {
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64), c.lds_bytes, c.st, c.F, R, a);
+    IRON_HIP_TRY(hipGetLastError());
     return IRON_OK;
 }
 
@@ -499,7 +478,7 @@ int run_sphere(const Call& c, const RayArgs& R, const float* near, const float* 
     SphereArgs A{near, far, work, c.prm.sdf_threshold, c.prm.sphere_tracing_iters, conv, points, sdf, dist, w.unf(), unf_out, w.flags(), stats};
     {
         ProfScope ps(IRON_PROF_SPHERE, c.st);
-        HGT_LAUNCH(k_hgt_sphere, c.F, blocks_for(c.n, 64), c.lds_bytes, c.st, c.F, R, A);
+        HGT_TRY(with_value_path(c.F.pl, [&](auto act, auto nt) { return launch_wave(k_hgt_sphere<act(), nt()>, blocks_for(c.n, 64), c, R, A); }));
     }
     const int rc = pair_scan(w.S, w.base, c.st);
     if (rc != IRON_OK) return rc;
@@ -517,7 +496,7 @@ int run_sampler(const Call& c, const RayArgs& R, const float* near, const float*
     const int64_t cap = (int64_t)cu_total() * 8;
     {
         ProfScope ps(IRON_PROF_SAMPLER, c.st);
-        HGT_LAUNCH(k_hgt_sampler, c.F, (unsigned)(c.n < cap ? c.n : cap), c.lds_bytes, c.st, c.F, R, A);
+        HGT_TRY(with_value_path(c.F.pl, [&](auto act, auto nt) { return launch_wave(k_hgt_sampler<act(), nt()>, (unsigned)(c.n < cap ? c.n : cap), c, R, A); }));
     }
     const int rc = pair_scan(w.S, w.base, c.st);
     if (rc != IRON_OK) return rc;
@@ -532,18 +511,12 @@ int run_bisect(const Call& c, const RayArgs& R, int64_t chunk, uint8_t* conv, fl
     BisectArgs A{w.words(), brackets_of(w), w.i32(w.L.iters), chunk, 2.0f * c.prm.sdf_threshold, conv, points, sdf, dist, stats};
     {
         ProfScope ps(IRON_PROF_BISECT_A, c.st);
-        HGT_LAUNCH(k_hgt_bisect_a, c.F, blocks_for(c.n, 64), c.lds_bytes, c.st, c.F, R, A);
+        HGT_TRY(with_value_path(c.F.pl, [&](auto act, auto nt) { return launch_wave(k_hgt_bisect_a<act(), nt()>, blocks_for(c.n, 64), c, R, A); }));
     }
     ProfScope ps(IRON_PROF_BISECT_B, c.st);
-    HGT_LAUNCH(k_hgt_bisect_b, c.F, blocks_for(c.n, 64), c.lds_bytes, c.st, c.F, R, A);
+    HGT_TRY(with_value_path(c.F.pl, [&](auto act, auto nt) { return launch_wave(k_hgt_bisect_b<act(), nt()>, blocks_for(c.n, 64), c, R, A); }));
     return IRON_OK;
 }
-
-#define HGT_TRY(expr)                  \
-    do {                               \
-        const int _rc = (expr);        \
-        if (_rc != IRON_OK) return _rc; \
-    } while (0)
 
 }  // namespace
 }  // namespace iron

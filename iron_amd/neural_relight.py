@@ -22,7 +22,7 @@ import torch
 
 from . import _args, _lib
 from .mesh_render import _mts_tables, check_path_args, subpixel_uvs
-from .raytracer import HashFieldSDF, SDFCallable, SDFHandle, intersect_sphere, raytrace_pixels, render_normal_and_color
+from .raytracer import HashFieldSDF, SDFCallable, SDFHandle, as_traceable, intersect_sphere, raytrace_pixels, render_normal_and_color
 
 WHAT = "neural relight"
 GBUFFER = ("convergent_mask", "points", "normal", "ray_d", "diffuse_albedo", "specular_albedo", "specular_roughness")
@@ -42,10 +42,9 @@ PATH_STAGES = ("path_emit", "path_shadow", "path_bounce", "path_surface", "path_
 
 def _as_sdf(sdf):
     """What RayTracer.occluded takes: an SDFNetwork is wrapped in its handle; SDFHandle, SDFCallable and HashFieldSDF pass."""
-    if isinstance(sdf, (SDFHandle, SDFCallable, HashFieldSDF)):
-        return sdf
-    if hasattr(sdf, "hip_net"):
-        return SDFHandle(sdf)
+    handle = as_traceable(sdf)
+    if handle is not None:
+        return handle
     raise _lib.IronError("%s: sdf must be an iron_amd SDFNetwork, an SDFHandle or an SDFCallable, got %s" % (WHAT, type(sdf).__name__))
 
 

@@ -30,6 +30,7 @@ import torch.nn as nn
 from . import _lib
 
 VERBOSE_MODE = False
+RESULT_KEYS = ("convergent_mask", "points", "sdf", "distance")   # of RayTracer.forward's dictionary, in the order of the outputs
 
 
 class SDFHandle:
@@ -89,20 +90,71 @@ class HashFieldSDF:
         return desc, self._a, self._b, table.detach().contiguous(), self.field._fused_packed(desc, device)
 
 
+def as_traceable(sdf):
+    """What RayTracer takes for `sdf`: a HashFieldSDF, an SDFHandle or an SDFCallable passes, an iron_amd SDFNetwork (anything with
+    `hip_net`) is wrapped in its handle.  None for anything else: the caller decides what a foreign object becomes."""
+    if isinstance(sdf, (HashFieldSDF, SDFHandle, SDFCallable)):
+        return sdf
+    return SDFHandle(sdf) if hasattr(sdf, "hip_net") else None
+
+
 _lin_cache = {}
 
 
+def _linspace_steps(n_steps: int, device) -> torch.Tensor:
+    # torch.linspace(0, 1, n_steps).float() exactly as raytracer.py:144-146 builds it; a fresh upload (tests restate the sampler with it)
+    return torch.linspace(0, 1, steps=n_steps).float().to(device)
+
+
 def _linspace_steps_cached(n_steps: int, device) -> torch.Tensor:
-    """_linspace_steps, uploaded once per (n_steps, device): the device tracer's calls copy nothing from the host"""
+    """_linspace_steps, uploaded once per (n_steps, device): the one source of the sample steps for every arm, so that no tracer
+    call copies anything from the host"""
     key = (int(n_steps), device)
     if key not in _lin_cache:
         _lin_cache[key] = _linspace_steps(n_steps, device)
     return _lin_cache[key]
 
 
-def _check_hashfield_stats(stats) -> None:
-    if stats.get("incomplete", 0):   # the callable tracer's own error, for the same cause
-        raise _lib.IronError("the bisection does not close: the sdf callable returns NaN inside an open bracket, or a bracket is not finite")
+def _per_ray(t, name, dtype, like):
+    """work_mask (bool) / ray_index (int64) -> [n], contiguous, beside the rays `like`"""
+    if t.dtype != dtype or not t.is_cuda:
+        raise _lib.IronError("%s must be a CUDA %s tensor" % (name, "bool" if dtype == torch.bool else "int64"))
+    t = t.reshape(-1).contiguous()
+    if t.shape[0] != like.shape[0] or t.device != like.device:
+        raise _lib.IronError("%s must have one entry per ray" % name)
+    return t
+
+
+def _ray_call(ray_o, ray_d, scalars, work_mask=None, ray_index=None):
+    """The arguments of one tracer call, normalised for every public entry -> (o, d, scalars, work, index): ray_o and ray_d [n, 3],
+    every per-ray scalar [n], all CUDA fp32; work_mask bool [n] and ray_index int64 [n], CUDA (None stays None: what that means is
+    the entry's); everything contiguous, one entry per ray, on one device.  [n, 1] scalars, masks of any shape with n elements and
+    non-contiguous tensors are taken.  The C entries read n entries from every array and can check none of this."""
+    o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
+    d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
+    rest = [_lib.require_cuda_f32(t, "argument").reshape(-1) for t in scalars]
+    for t in [d] + rest:
+        if t.shape[0] != o.shape[0] or t.device != o.device:
+            raise _lib.IronError("the ray arguments must have one entry per ray, on one device")
+    work = None if work_mask is None else _per_ray(work_mask, "work_mask", torch.bool, o)
+    index = None if ray_index is None else _per_ray(ray_index, "ray_index", torch.int64, o)
+    return o, d, rest, work, index
+
+
+def _outputs(alloc, n, dev, mask_only=False):
+    """(mask, points, sdf, distance) of a call on n rays from torch.empty or torch.zeros; mask_only: the three behind it are None"""
+    mask = alloc(n, dtype=torch.bool, device=dev)
+    if mask_only:
+        return mask, None, None, None
+    return (mask, alloc((n, 3), dtype=torch.float32, device=dev), alloc(n, dtype=torch.float32, device=dev),
+            alloc(n, dtype=torch.float32, device=dev))
+
+
+def _ray_workspace(ws_bytes, n, dev, tag):
+    """the call-scoped workspace of a tracer whose *_workspace_bytes answers 0 for a ray count it does not take"""
+    if n > 0 and ws_bytes == 0:
+        raise _lib.IronError("the tracer takes fewer than 2^31 - 1 rays per call; pass fewer rays (the callable tracer: chunk=)")
+    return _lib.workspace(ws_bytes, dev, tag)
 
 
 class _AnyTrace:
@@ -121,9 +173,7 @@ class _AnyTrace:
         self.lib = _lib.load()
         self.st = _lib.stream_ptr(self.dev)
         self.ws_bytes = self.lib.iron_trace_any_workspace_bytes(self.n)
-        if self.n > 0 and self.ws_bytes == 0:
-            raise _lib.IronError("the callable tracer takes fewer than 2^31 - 1 rays per call; pass chunk=")
-        self.ws = _lib.workspace(self.ws_bytes, self.dev, "trace_any")
+        self.ws = _ray_workspace(self.ws_bytes, self.n, self.dev, "trace_any")
         self.wsp = self.ws.data_ptr()
         self.buf = torch.empty((max(self.n, 1), 3), dtype=torch.float32, device=self.dev)   # the next batch of the list stages
         self.words = (C.c_int64 * 2)()
@@ -251,16 +301,234 @@ def _resolve_sdf_network(sdf, device):
     return net
 
 
-def _linspace_steps(n_steps: int, device) -> torch.Tensor:
-    # torch.linspace(0, 1, n_steps).float() exactly as raytracer.py:144-146 builds it
-    return torch.linspace(0, 1, steps=n_steps).float().to(device)
+class _Arm:
+    """One kind of SDF behind RayTracer.  RayTracer normalises the arguments (_ray_call), allocates the outputs (_outputs) and turns
+    the stats words into last_stats; an arm makes its tracer's launches between the two, and its callers do not know which it is:
+        trace(tr, o, d, near, far, work, chunk, out, collect_stats)   forward() / occluded() into out = (mask, points, sdf, distance);
+                                                                      points None: the mask alone (an arm with mask_only)
+        stage(tr, stage, o, d, ins, work, out, unfinished)            sphere_tracing / ray_sampler / rootfind = stage 0 / 1 / 2
+        phase_begin(tr, ...) -> state, phase_finish(state)            the multi-rank pair, where the arm has it
+    trace and stage return the call's stats words (a device tensor, or host counters) or None.  stats_fields names the words (None:
+    not reported) and check(stats) raises on words that void the result."""
+    stats_fields = ()
+    mask_only = True    # occluded() has a shortened form that writes the mask alone
+    phased = None       # what phase_begin calls the arm when it refuses it
+
+    @staticmethod
+    def check(stats) -> None:
+        pass
+
+    def phase_begin(self, *args):
+        raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take %s: call forward() per rank" % self.phased)
 
 
-def _check_stats(stats) -> None:
-    """`reserved` counts k_sampler workgroups that gave up polling their work queue (csrc/trace.hip): never, unless the queue protocol
-    is broken -- then the trace is incomplete and must not pass as a result."""
-    if stats.get("reserved", 0):
-        raise _lib.IronError("k_sampler left its work queue by the poll bound (%d workgroups): the trace is incomplete" % stats["reserved"])
+class _NetworkArm(_Arm):
+    """An SDFNetwork on the fused kernels of csrc/trace.hip: one iron_trace* call per operation."""
+    stats_fields = _lib.TRACE_STATS_FIELDS
+
+    def __init__(self, net):
+        self.net = net
+
+    @staticmethod
+    def check(stats) -> None:
+        """`reserved` counts k_sampler workgroups that gave up polling their work queue (csrc/trace.hip): never, unless the queue
+        protocol is broken -- then the trace is incomplete and must not pass as a result."""
+        if stats.get("reserved", 0):
+            raise _lib.IronError("k_sampler left its work queue by the poll bound (%d workgroups): the trace is incomplete" % stats["reserved"])
+
+    def trace(self, tr, o, d, near, far, work, chunk, out, collect_stats):
+        conv, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        if points is None and n == 0:
+            return None
+        lib = _lib.load()
+        prm = tr._params(chunk)
+        ws_bytes = (lib.iron_trace_workspace_bytes if points is not None else lib.iron_trace_occluded_workspace_bytes)(n, C.byref(prm))
+        ws = _lib.workspace(ws_bytes, dev, "trace")
+        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
+        lin = _linspace_steps_cached(tr.n_steps, dev)
+        head = (self.net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(), near.data_ptr(), far.data_ptr(),
+                work.data_ptr(), n, conv.data_ptr())
+        tail = (_lib.ptr(stats), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        with torch.cuda.device(dev):
+            if points is None:
+                _lib.check(lib.iron_trace_occluded(*head, *tail))
+            else:
+                _lib.check(lib.iron_trace(*head, points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(), *tail))
+        return stats
+
+    def stage(self, tr, stage, o, d, ins, work, out, unfinished):
+        """one iron_trace_stage call, i.e. the same persistent kernels forward() chains"""
+        mask, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        if n > 0:
+            lib = _lib.load()
+            prm = tr._params(0)
+            ws_bytes = lib.iron_trace_workspace_bytes(n, C.byref(prm))
+            ws = _lib.workspace(ws_bytes, dev, "trace")
+            lin = _linspace_steps_cached(tr.n_steps, dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.iron_trace_stage(stage, self.net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(),
+                                                _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]), _lib.ptr(ins[3]), _lib.ptr(work), n,
+                                                mask.data_ptr(), unfinished.data_ptr(), points.data_ptr(), sdf_out.data_ptr(),
+                                                dist.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
+        return None
+
+    def phase_begin(self, tr, o, d, near, far, work, idx, n_chunks, chunk, collect_stats):
+        n, dev = o.shape[0], o.device
+        out = _outputs(torch.empty, n, dev)
+        chunk_iters = torch.zeros(int(n_chunks), dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        prm = tr._params(chunk)
+        ws_bytes = lib.iron_trace_workspace_bytes(n, C.byref(prm))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # the state outlives the call: not the call-scoped workspace
+        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
+        lin = _linspace_steps_cached(tr.n_steps, dev)
+        args = (self.net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(), near.data_ptr(),
+                far.data_ptr(), work.data_ptr(), idx.data_ptr(), n, chunk_iters.data_ptr(), int(n_chunks),
+                *[t.data_ptr() for t in out], _lib.ptr(stats), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        state = {"args": args, "keep": (prm, lin, o, d, near, far, work, idx, ws), "n": n, "device": dev, "arm": self,
+                 "out": dict(zip(RESULT_KEYS, out)), "chunk_iters": chunk_iters, "stats": stats}
+        if n > 0:
+            with torch.cuda.device(dev):
+                _lib.check(lib.iron_trace_phase(0, *args))
+        return state
+
+    def phase_finish(self, state):
+        if state["n"] > 0:
+            with torch.cuda.device(state["device"]):
+                _lib.check(_lib.load().iron_trace_phase(1, *state["args"]))
+
+
+class _CallableArm(_Arm):
+    """An opaque callable (SDFCallable): the same reference call, its evaluations made by the caller's function and everything between
+    them by the kernels of csrc/trace_any.hip (_AnyTrace)."""
+    stats_fields = ("n_evals", "n_calls", "n_sampler", "n_bisect", "n_bisect_iters")   # counted on the host
+    mask_only = False   # occluded() is forward()'s mask: that form is not shortened
+    phased = "an SDFCallable"
+
+    def __init__(self, sdf):
+        self.sdf = sdf
+
+    def trace(self, tr, o, d, near, far, work, chunk, out, collect_stats):
+        conv, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        stats = dict.fromkeys(self.stats_fields, 0) if collect_stats else None
+        lin = _linspace_steps_cached(tr.n_steps, dev)
+        step = n if chunk is None or int(chunk) <= 0 else int(chunk)
+        with torch.cuda.device(dev):
+            for a in range(0, n, max(step, 1)):   # each chunk is a reference call of its own; slices of dim 0 stay contiguous
+                b = min(n, a + step)
+                run = _AnyTrace(tr, self.sdf, o[a:b], d[a:b], stats)
+                c_near, c_far, c_work = near[a:b], far[a:b], work[a:b]
+                c_conv, c_points, c_sdf, c_dist = conv[a:b], points[a:b], sdf_out[a:b], dist[a:b]
+                sel, m = run.sphere(c_near, c_far, c_work, c_points, c_sdf, c_dist)
+                run.sphere_finish(c_far, c_work, c_sdf, c_dist, c_conv)
+                if m > 0:
+                    _, nb, it = run.sampler(sel, m, c_near, c_far, lin, c_conv, c_points, c_sdf, c_dist)
+                    if stats is not None:
+                        stats["n_sampler"] += m
+                        stats["n_bisect"] += nb
+                        stats["n_bisect_iters"] += it
+        return list(stats.values()) if collect_stats else None
+
+    def stage(self, tr, stage, o, d, ins, work, out, unfinished):
+        mask, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        if n > 0:
+            with torch.cuda.device(dev):
+                run = _AnyTrace(tr, self.sdf, o, d, None)
+                if stage == 0:
+                    run.sphere(ins[0], ins[1], work, points, sdf_out, dist)
+                    run.sphere_finish(ins[1], work, sdf_out, dist, mask, unfinished)
+                elif stage == 1:
+                    run.sampler(-1, n, ins[0], ins[1], _linspace_steps_cached(tr.n_steps, dev), mask, points, sdf_out, dist)
+                    # the gather clears the rootless rays and the finish raises the bracketed ones: `mask` started as zeros
+                else:
+                    _lib.check(run.lib.iron_trace_any_bisect_load(ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(),
+                                                                  o.data_ptr(), d.data_ptr(), n, run.buf.data_ptr(), run.buf.shape[0],
+                                                                  run.wsp, run.ws_bytes, run.st))
+                    _, wide = run.read()
+                    run.bisect(n, wide, None, points, sdf_out, dist)
+        return None
+
+
+class _HashFieldArm(_Arm):
+    """A hash-grid field (HashFieldSDF): the same reference call with the field evaluated inside the kernels of
+    csrc/hashgrid_trace.hip; a fixed launch sequence, nothing read back unless the stats are asked for."""
+    stats_fields = tuple(None if k.startswith("reserved") else k for k in _lib.HASHGRID_TRACE_STATS_FIELDS)
+    phased = "a HashFieldSDF"
+
+    def __init__(self, sdf):
+        self.sdf = sdf
+
+    @staticmethod
+    def check(stats) -> None:
+        if stats.get("incomplete", 0):   # the callable tracer's own error, for the same cause
+            raise _lib.IronError("the bisection does not close: the sdf callable returns NaN inside an open bracket, or a bracket is not finite")
+
+    @staticmethod
+    def _params(tr, chunk):
+        if not 2 <= int(tr.n_steps) <= 4096:
+            raise _lib.IronError("the hash-grid tracer takes n_steps in 2 .. 4096, got %r" % (tr.n_steps,))
+        if int(tr.sphere_tracing_iters) < 0:
+            raise _lib.IronError("sphere_tracing_iters must not be negative, got %r" % (tr.sphere_tracing_iters,))
+        return tr._params(0 if chunk is None else max(int(chunk), 0))
+
+    def _bind(self, lib, tr, prm, n, dev):
+        """-> (the field and parameter arguments every iron_hashgrid_trace* entry begins with, the workspace and stream ones it ends
+        with, what must stay alive over the call)"""
+        desc, map_a, map_b, table, packed = self.sdf.field_args(dev)
+        ws_bytes = lib.iron_hashgrid_trace_workspace_bytes(n, C.byref(prm))
+        ws = _ray_workspace(ws_bytes, n, dev, "hashfield_trace")
+        lin = _linspace_steps_cached(tr.n_steps, dev)
+        return ((C.byref(desc), C.byref(prm), map_a, map_b, table.data_ptr(), packed.data_ptr(), lin.data_ptr()),
+                (ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)), (desc, table, packed))
+
+    def trace(self, tr, o, d, near, far, work, chunk, out, collect_stats):
+        conv, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        prm = self._params(tr, chunk)
+        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
+        if n > 0:
+            lib = _lib.load()
+            with torch.cuda.device(dev):
+                field, tail, keep = self._bind(lib, tr, prm, n, dev)
+                rays = (o.data_ptr(), d.data_ptr(), near.data_ptr(), far.data_ptr(), work.data_ptr(), n, conv.data_ptr())
+                if points is None:
+                    _lib.check(lib.iron_hashgrid_trace_occluded(*field, *rays, _lib.ptr(stats), *tail))
+                else:
+                    _lib.check(lib.iron_hashgrid_trace(*field, *rays, points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(),
+                                                       _lib.ptr(stats), *tail))
+        return stats
+
+    def stage(self, tr, stage, o, d, ins, work, out, unfinished):
+        """The stage methods are the debugging surface, not the frame's path: each reads the stats words back once, so that a
+        bisection that does not close raises here as it does on the callable."""
+        mask, points, sdf_out, dist = out
+        n, dev = o.shape[0], o.device
+        prm = self._params(tr, 0)
+        if n == 0:
+            return None
+        lib = _lib.load()
+        stats = torch.zeros(8, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            field, tail, keep = self._bind(lib, tr, prm, n, dev)
+            _lib.check(lib.iron_hashgrid_trace_stage(stage, *field, o.data_ptr(), d.data_ptr(), _lib.ptr(ins[0]), _lib.ptr(ins[1]),
+                                                     _lib.ptr(ins[2]), _lib.ptr(ins[3]), _lib.ptr(work), n, mask.data_ptr(),
+                                                     unfinished.data_ptr(), points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(),
+                                                     stats.data_ptr(), *tail))
+        return stats
+
+
+def _arm_of(sdf, device) -> _Arm:
+    """The arm that serves `sdf`: the one place that asks what kind of SDF it is.  Anything but the two marked kinds must resolve to
+    an SDFNetwork (_resolve_sdf_network and its probe) or is refused there."""
+    if isinstance(sdf, SDFCallable):
+        return _CallableArm(sdf)
+    if isinstance(sdf, HashFieldSDF):
+        return _HashFieldArm(sdf)
+    return _NetworkArm(_resolve_sdf_network(sdf, device))
 
 
 class RayTracer(nn.Module):
@@ -280,45 +548,34 @@ class RayTracer(nn.Module):
         p.chunk = int(chunk)
         return p
 
+    def _stats_out(self, words, fields, check) -> None:
+        """a call's stats words (None: it collected none) under the arm's field names -> last_stats (for a device tensor the one
+        read-back), then the arm's check of them"""
+        if words is None:
+            return
+        values = words.cpu().tolist() if torch.is_tensor(words) else words
+        self.last_stats = {k: v for k, v in zip(fields, values) if k is not None}
+        check(self.last_stats)
+
+    def _trace(self, sdf, ray_o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, mask_only):
+        o, d, (near, far), work, _ = _ray_call(ray_o, ray_d, (min_dis, max_dis), work_mask)
+        n, dev = o.shape[0], o.device
+        if work is None:
+            if not mask_only:
+                raise _lib.IronError("work_mask must be a CUDA bool tensor")
+            work = torch.ones(n, dtype=torch.bool, device=dev)
+        arm = _arm_of(sdf, dev)
+        out = _outputs(torch.empty, n, dev, mask_only and arm.mask_only)
+        self._stats_out(arm.trace(self, o, d, near, far, work, chunk, out, collect_stats), arm.stats_fields, arm.check)
+        return out[0] if mask_only else dict(zip(RESULT_KEYS, out))
+
     @torch.no_grad()
     def forward(self, sdf, ray_o, ray_d, min_dis, max_dis, work_mask, chunk: int = 0, collect_stats: bool = False):
         """One reference call = sphere_tracing + ray_sampler + rootfind on n rays (raytracer.py:45-103).
 
         `chunk` (extension): rays [k*chunk,(k+1)*chunk) are treated as separate reference calls
         (they share the bisection iteration count, raytracer.py:204-217); 0 = the whole batch."""
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        if isinstance(sdf, SDFCallable):
-            return self._forward_callable(sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats)
-        if isinstance(sdf, HashFieldSDF):
-            return self._forward_hashfield(sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, False)
-        net = _resolve_sdf_network(sdf, o.device)
-        d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
-        near = _lib.require_cuda_f32(min_dis, "min_dis").reshape(-1)
-        far = _lib.require_cuda_f32(max_dis, "max_dis").reshape(-1)
-        if work_mask.dtype != torch.bool or not work_mask.is_cuda:
-            raise _lib.IronError("work_mask must be a CUDA bool tensor")
-        work = work_mask.reshape(-1).contiguous()
-        n = o.shape[0]
-        dev = o.device
-        conv = torch.empty(n, dtype=torch.bool, device=dev)
-        points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        sdf_out = torch.empty(n, dtype=torch.float32, device=dev)
-        dist = torch.empty(n, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        prm = self._params(chunk)
-        ws_bytes = lib.iron_trace_workspace_bytes(n, C.byref(prm))
-        ws = _lib.workspace(ws_bytes, dev, "trace")
-        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
-        lin = _linspace_steps(self.n_steps, dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.iron_trace(net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(),
-                                      near.data_ptr(), far.data_ptr(), work.data_ptr(), n, conv.data_ptr(),
-                                      points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(), _lib.ptr(stats),
-                                      ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
-        if collect_stats:
-            self.last_stats = dict(zip(_lib.TRACE_STATS_FIELDS, stats.cpu().tolist()))
-            _check_stats(self.last_stats)
-        return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
+        return self._trace(sdf, ray_o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, False)
 
     @torch.no_grad()
     def occluded(self, sdf, ray_o, ray_d, min_dis, max_dis, work_mask=None, collect_stats: bool = False):
@@ -328,226 +585,18 @@ class RayTracer(nn.Module):
         found, a first negative sample (raytracer.py:162-167), so no ray is bisected and no point, sdf or distance is returned.
         An SDFCallable is traced by forward() itself and its mask returned: that form is not shortened.  work_mask None: every ray.
         Bare callables and CPU tensors are refused as forward() refuses them."""
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        n, dev = o.shape[0], o.device
-        if work_mask is None:
-            work_mask = torch.ones(n, dtype=torch.bool, device=dev)
-        if isinstance(sdf, SDFCallable):
-            return self.forward(sdf, o, ray_d, min_dis, max_dis, work_mask, collect_stats=collect_stats)["convergent_mask"]
-        if isinstance(sdf, HashFieldSDF):
-            return self._forward_hashfield(sdf, o, ray_d, min_dis, max_dis, work_mask, 0, collect_stats, True)
-        net = _resolve_sdf_network(sdf, dev)
-        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
-        work = self._work_arg(work_mask, n)
-        occ = torch.empty(n, dtype=torch.bool, device=dev)
-        if n == 0:
-            return occ
-        lib = _lib.load()
-        prm = self._params(0)
-        ws_bytes = lib.iron_trace_occluded_workspace_bytes(n, C.byref(prm))
-        ws = _lib.workspace(ws_bytes, dev, "trace")
-        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
-        lin = _linspace_steps(self.n_steps, dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.iron_trace_occluded(net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(),
-                                               near.data_ptr(), far.data_ptr(), work.data_ptr(), n, occ.data_ptr(), _lib.ptr(stats),
-                                               ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
-        if collect_stats:
-            self.last_stats = dict(zip(_lib.TRACE_STATS_FIELDS, stats.cpu().tolist()))
-            _check_stats(self.last_stats)
-        return occ
-
-    # ---- an opaque callable (SDFCallable): the same reference call, its evaluations made by the caller's function and everything
-    # between them by the kernels of csrc/trace_any.hip
-    @staticmethod
-    def _ray_args(o, ray_d, *scalars):
-        d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
-        rest = [_lib.require_cuda_f32(t, "argument").reshape(-1) for t in scalars]
-        for t in [d] + rest:
-            if t.shape[0] != o.shape[0] or t.device != o.device:
-                raise _lib.IronError("the ray arguments must have one entry per ray, on one device")
-        return [d] + rest
-
-    @staticmethod
-    def _work_arg(work_mask, n):
-        if work_mask.dtype != torch.bool or not work_mask.is_cuda:
-            raise _lib.IronError("work_mask must be a CUDA bool tensor")
-        work = work_mask.reshape(-1).contiguous()
-        if work.shape[0] != n:
-            raise _lib.IronError("work_mask must have one entry per ray")
-        return work
-
-    def _forward_callable(self, sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats):
-        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
-        n, dev = o.shape[0], o.device
-        work = self._work_arg(work_mask, n)
-        conv = torch.empty(n, dtype=torch.bool, device=dev)
-        points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        sdf_out = torch.empty(n, dtype=torch.float32, device=dev)
-        dist = torch.empty(n, dtype=torch.float32, device=dev)
-        stats = {"n_evals": 0, "n_calls": 0, "n_sampler": 0, "n_bisect": 0, "n_bisect_iters": 0} if collect_stats else None
-        lin = _linspace_steps(self.n_steps, dev)
-        step = n if chunk is None or int(chunk) <= 0 else int(chunk)
-        with torch.cuda.device(dev):
-            for a in range(0, n, max(step, 1)):   # each chunk is a reference call of its own; slices of dim 0 stay contiguous
-                b = min(n, a + step)
-                run = _AnyTrace(self, sdf, o[a:b], d[a:b], stats)
-                c_near, c_far, c_work = near[a:b], far[a:b], work[a:b]
-                c_conv, c_points, c_sdf, c_dist = conv[a:b], points[a:b], sdf_out[a:b], dist[a:b]
-                sel, m = run.sphere(c_near, c_far, c_work, c_points, c_sdf, c_dist)
-                run.sphere_finish(c_far, c_work, c_sdf, c_dist, c_conv)
-                if m > 0:
-                    _, nb, it = run.sampler(sel, m, c_near, c_far, lin, c_conv, c_points, c_sdf, c_dist)
-                    if stats is not None:
-                        stats["n_sampler"] += m
-                        stats["n_bisect"] += nb
-                        stats["n_bisect_iters"] += it
-        if collect_stats:
-            self.last_stats = stats
-        return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
-
-    # ---- a hash-grid field (HashFieldSDF): the same reference call with the field evaluated inside the kernels of
-    # csrc/hashgrid_trace.hip; a fixed launch sequence, nothing read back unless the stats are asked for
-    def _hashfield_params(self, chunk):
-        if not 2 <= int(self.n_steps) <= 4096:
-            raise _lib.IronError("the hash-grid tracer takes n_steps in 2 .. 4096, got %r" % (self.n_steps,))
-        if int(self.sphere_tracing_iters) < 0:
-            raise _lib.IronError("sphere_tracing_iters must not be negative, got %r" % (self.sphere_tracing_iters,))
-        return self._params(0 if chunk is None else max(int(chunk), 0))
-
-    def _hashfield_stats_out(self, stats, check):
-        """the eight device words -> last_stats (one read-back), and the `incomplete` word -> the callable tracer's IronError"""
-        words = dict(zip(_lib.HASHGRID_TRACE_STATS_FIELDS, stats.cpu().tolist()))
-        self.last_stats = {k: v for k, v in words.items() if not k.startswith("reserved")}
-        if check:
-            _check_hashfield_stats(self.last_stats)
-
-    def _forward_hashfield(self, sdf, o, ray_d, min_dis, max_dis, work_mask, chunk, collect_stats, mask_only):
-        d, near, far = self._ray_args(o, ray_d, min_dis, max_dis)
-        n, dev = o.shape[0], o.device
-        work = self._work_arg(work_mask, n)
-        prm = self._hashfield_params(chunk)
-        conv = torch.empty(n, dtype=torch.bool, device=dev)
-        if not mask_only:
-            points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            sdf_out = torch.empty(n, dtype=torch.float32, device=dev)
-            dist = torch.empty(n, dtype=torch.float32, device=dev)
-        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
-        if n > 0:
-            lib = _lib.load()
-            desc, map_a, map_b, table, packed = sdf.field_args(dev)
-            ws_bytes = lib.iron_hashgrid_trace_workspace_bytes(n, C.byref(prm))
-            if ws_bytes == 0:
-                raise _lib.IronError("the hash-grid tracer takes fewer than 2^31 - 1 rays per call")
-            lin = _linspace_steps_cached(self.n_steps, dev)
-            with torch.cuda.device(dev):
-                ws = _lib.workspace(ws_bytes, dev, "hashfield_trace")
-                head = (C.byref(desc), C.byref(prm), map_a, map_b, table.data_ptr(), packed.data_ptr(), lin.data_ptr(), o.data_ptr(),
-                        d.data_ptr(), near.data_ptr(), far.data_ptr(), work.data_ptr(), n, conv.data_ptr())
-                tail = (_lib.ptr(stats), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-                if mask_only:
-                    _lib.check(lib.iron_hashgrid_trace_occluded(*head, *tail))
-                else:
-                    _lib.check(lib.iron_hashgrid_trace(*head, points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(), *tail))
-        if collect_stats:
-            self._hashfield_stats_out(stats, True)
-        if mask_only:
-            return conv
-        return {"convergent_mask": conv, "points": points, "sdf": sdf_out, "distance": dist}
-
-    def _stage_hashfield(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
-        """The reference's stage methods on a HashFieldSDF.  They are the debugging surface, not the frame's path: each reads the
-        stats words back once, so that a bisection that does not close raises here as it does on the callable."""
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        args = self._ray_args(o, ray_d, *[t for t in (in0, in1, in2, in3) if t is not None])
-        d, ins = args[0], list(args[1:]) + [None, None]
-        n, dev = o.shape[0], o.device
-        work = self._work_arg(work_mask, n) if work_mask is not None else None
-        prm = self._hashfield_params(0)
-        mask = torch.zeros(n, dtype=torch.bool, device=dev)
-        unfinished = torch.zeros(n, dtype=torch.bool, device=dev)
-        points = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        sdf_out = torch.zeros(n, dtype=torch.float32, device=dev)
-        dist = torch.zeros(n, dtype=torch.float32, device=dev)
-        if n > 0:
-            lib = _lib.load()
-            desc, map_a, map_b, table, packed = sdf.field_args(dev)
-            ws_bytes = lib.iron_hashgrid_trace_workspace_bytes(n, C.byref(prm))
-            lin = _linspace_steps_cached(self.n_steps, dev)
-            stats = torch.zeros(8, dtype=torch.int64, device=dev)
-            with torch.cuda.device(dev):
-                ws = _lib.workspace(ws_bytes, dev, "hashfield_trace")
-                _lib.check(lib.iron_hashgrid_trace_stage(stage, C.byref(desc), C.byref(prm), map_a, map_b, table.data_ptr(), packed.data_ptr(),
-                                                         lin.data_ptr(), o.data_ptr(), d.data_ptr(), _lib.ptr(ins[0]), _lib.ptr(ins[1]),
-                                                         _lib.ptr(ins[2]), _lib.ptr(ins[3]), _lib.ptr(work), n, mask.data_ptr(),
-                                                         unfinished.data_ptr(), points.data_ptr(), sdf_out.data_ptr(), dist.data_ptr(),
-                                                         stats.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
-            self._hashfield_stats_out(stats, True)
-        return mask, unfinished, points, sdf_out, dist
-
-    def _stage_callable(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
-        o = _lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        args = self._ray_args(o, ray_d, *[t for t in (in0, in1, in2, in3) if t is not None])
-        d, ins = args[0], args[1:]
-        n, dev = o.shape[0], o.device
-        mask = torch.zeros(n, dtype=torch.bool, device=dev)
-        unfinished = torch.zeros(n, dtype=torch.bool, device=dev)
-        points = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        sdf_out = torch.zeros(n, dtype=torch.float32, device=dev)
-        dist = torch.zeros(n, dtype=torch.float32, device=dev)
-        if n > 0:
-            with torch.cuda.device(dev):
-                run = _AnyTrace(self, sdf, o, d, None)
-                if stage == 0:
-                    work = self._work_arg(work_mask, n)
-                    run.sphere(ins[0], ins[1], work, points, sdf_out, dist)
-                    run.sphere_finish(ins[1], work, sdf_out, dist, mask, unfinished)
-                elif stage == 1:
-                    run.sampler(-1, n, ins[0], ins[1], _linspace_steps(self.n_steps, dev), mask, points, sdf_out, dist)
-                    # the gather clears the rootless rays and the finish raises the bracketed ones: `mask` started as zeros
-                else:
-                    _lib.check(run.lib.iron_trace_any_bisect_load(ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(),
-                                                                  o.data_ptr(), d.data_ptr(), n, run.buf.data_ptr(), run.buf.shape[0],
-                                                                  run.wsp, run.ws_bytes, run.st))
-                    _, wide = run.read()
-                    run.bisect(n, wide, None, points, sdf_out, dist)
-        return mask, unfinished, points, sdf_out, dist
-
+        return self._trace(sdf, ray_o, ray_d, min_dis, max_dis, work_mask, 0, collect_stats, True)
 
     # ---- the three stages as the reference exposes them (raytracer.py:105-220; tests/test_raytracer.py drives forward(), the
-    # methods are public API of the class): each is one iron_trace_stage call, i.e. the same persistent kernels forward() chains
+    # methods are public API of the class)
     def _stage(self, stage, sdf, ray_o, ray_d, in0, in1, in2=None, in3=None, work_mask=None):
-        if isinstance(sdf, SDFCallable):
-            return self._stage_callable(stage, sdf, ray_o, ray_d, in0, in1, in2, in3, work_mask)
-        if isinstance(sdf, HashFieldSDF):
-            return self._stage_hashfield(stage, sdf, ray_o, ray_d, in0, in1, in2, in3, work_mask)
-        o =_lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        net = _resolve_sdf_network(sdf, o.device)
-        d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
-        ins = [None if t is None else _lib.require_cuda_f32(t, "argument").reshape(-1) for t in (in0, in1, in2, in3)]
+        o, d, ins, work, _ = _ray_call(ray_o, ray_d, [t for t in (in0, in1, in2, in3) if t is not None], work_mask)
         n, dev = o.shape[0], o.device
-        work = None
-        if work_mask is not None:
-            if work_mask.dtype != torch.bool or not work_mask.is_cuda:
-                raise _lib.IronError("work_mask must be a CUDA bool tensor")
-            work = work_mask.reshape(-1).contiguous()
-        mask = torch.zeros(n, dtype=torch.bool, device=dev)
+        arm = _arm_of(sdf, dev)
+        out = _outputs(torch.zeros, n, dev)   # zeros: what a stage leaves unwritten, and the callable arm's sampler relies on `mask` starting so
         unfinished = torch.zeros(n, dtype=torch.bool, device=dev)
-        points = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        sdf_out = torch.zeros(n, dtype=torch.float32, device=dev)
-        dist = torch.zeros(n, dtype=torch.float32, device=dev)
-        if n > 0:
-            lib = _lib.load()
-            prm = self._params(0)
-            ws_bytes = lib.iron_trace_workspace_bytes(n, C.byref(prm))
-            ws = _lib.workspace(ws_bytes, dev, "trace")
-            lin = _linspace_steps(self.n_steps, dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.iron_trace_stage(stage, net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(),
-                                                _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]), _lib.ptr(ins[3]), _lib.ptr(work), n,
-                                                mask.data_ptr(), unfinished.data_ptr(), points.data_ptr(), sdf_out.data_ptr(),
-                                                dist.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
-        return mask, unfinished, points, sdf_out, dist
+        self._stats_out(arm.stage(self, stage, o, d, ins + [None] * (4 - len(ins)), work, out, unfinished), arm.stats_fields, arm.check)
+        return (out[0], unfinished) + out[1:]
 
     @torch.no_grad()
     def sphere_tracing(self, sdf, ray_o, ray_d, min_dis, max_dis, work_mask):
@@ -577,53 +626,16 @@ class RayTracer(nn.Module):
         (raytracer.py:204-217) has to be MAX-reduced over the ranks before the second half runs.  `ray_index` [n] int64 =
         position of each ray in the whole job (chunk id = ray_index // chunk).  Returns the state phase_finish() takes;
         state["chunk_iters"] (int32 [n_chunks], device) is the table to reduce in place."""
-        if isinstance(sdf, SDFCallable):
-            raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take an SDFCallable: call forward() per rank")
-        if isinstance(sdf, HashFieldSDF):
-            raise _lib.IronError("the multi-rank form (phase_begin / forward_phased) does not take a HashFieldSDF: call forward() per rank")
-        o =_lib.require_cuda_f32(ray_o, "ray_o").reshape(-1, 3)
-        net = _resolve_sdf_network(sdf, o.device)
-        d = _lib.require_cuda_f32(ray_d, "ray_d").reshape(-1, 3)
-        near = _lib.require_cuda_f32(min_dis, "min_dis").reshape(-1)
-        far = _lib.require_cuda_f32(max_dis, "max_dis").reshape(-1)
-        work = work_mask.reshape(-1).contiguous()
-        idx = ray_index.reshape(-1).contiguous()
-        if idx.dtype != torch.int64 or not idx.is_cuda:
-            raise _lib.IronError("ray_index must be a CUDA int64 tensor")
-        n = o.shape[0]
-        dev = o.device
-        out = {"convergent_mask": torch.empty(n, dtype=torch.bool, device=dev),
-               "points": torch.empty((n, 3), dtype=torch.float32, device=dev),
-               "sdf": torch.empty(n, dtype=torch.float32, device=dev),
-               "distance": torch.empty(n, dtype=torch.float32, device=dev)}
-        chunk_iters = torch.zeros(int(n_chunks), dtype=torch.int32, device=dev)
-        lib = _lib.load()
-        prm = self._params(chunk)
-        ws_bytes = lib.iron_trace_workspace_bytes(n, C.byref(prm))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        stats = torch.zeros(8, dtype=torch.int64, device=dev) if collect_stats else None
-        lin = _linspace_steps(self.n_steps, dev)
-        args = (net.hip_net().handle, C.byref(prm), lin.data_ptr(), o.data_ptr(), d.data_ptr(), near.data_ptr(),
-                far.data_ptr(), work.data_ptr(), idx.data_ptr(), n, chunk_iters.data_ptr(), int(n_chunks),
-                out["convergent_mask"].data_ptr(), out["points"].data_ptr(), out["sdf"].data_ptr(), out["distance"].data_ptr(),
-                _lib.ptr(stats), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        state = {"args": args, "keep": (prm, lin, o, d, near, far, work, idx, ws), "n": n, "device": dev, "out": out,
-                 "chunk_iters": chunk_iters, "stats": stats}
-        if n > 0:
-            with torch.cuda.device(dev):
-                _lib.check(lib.iron_trace_phase(0, *args))
-        return state
+        o, d, (near, far), work, idx = _ray_call(ray_o, ray_d, (min_dis, max_dis), work_mask, ray_index)
+        return _arm_of(sdf, o.device).phase_begin(self, o, d, near, far, work, idx, n_chunks, chunk, collect_stats)
 
     @torch.no_grad()
     def phase_finish(self, state):
         """Second half: every bracketed ray runs up to its chunk's (reduced) iteration count, then the final mid-point
         evaluation (iron_trace_phase 1).  Returns the result dict of forward()."""
-        if state["n"] > 0:
-            with torch.cuda.device(state["device"]):
-                _lib.check(_lib.load().iron_trace_phase(1, *state["args"]))
-        if state["stats"] is not None:
-            self.last_stats = dict(zip(_lib.TRACE_STATS_FIELDS, state["stats"].cpu().tolist()))
-            _check_stats(self.last_stats)
+        arm = state["arm"]
+        arm.phase_finish(state)
+        self._stats_out(state["stats"], arm.stats_fields, arm.check)
         return state["out"]
 
     @torch.no_grad()
@@ -798,11 +810,8 @@ def raytrace_pixels(sdf_network, raytracer, uv, camera, mask=None, max_num_rays=
         mask = torch.ones_like(uv[..., 0]).bool()
     dots_sh = list(uv.shape[:-1])
     ray_o, ray_d, ray_d_norm = camera.get_rays(uv)
-    if isinstance(sdf_network, HashFieldSDF):   # TCNNSDF.as_traced(): the hash-grid field's device tracer, passed through
-        sdf = sdf_network
-    elif hasattr(sdf_network, "hip_net"):
-        sdf = SDFHandle(sdf_network)
-    else:  # a foreign network: traced through its own forward, as the reference does (raytracer.py:375)
+    sdf = as_traceable(sdf_network)   # TCNNSDF.as_traced() and the other handles pass through
+    if sdf is None:  # a foreign network: traced through its own forward, as the reference does (raytracer.py:375)
         sdf = SDFCallable(lambda x: sdf_network(x)[..., 0])
     o, d = ray_o.reshape(-1, 3), ray_d.reshape(-1, 3)
     hit, near, far = intersect_sphere(o, d, r=1.0)
