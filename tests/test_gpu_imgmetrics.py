@@ -6,7 +6,8 @@ Where the bounds come from.  uint8 path: the window sums are exact integers, so 
 mean separate the kernel from the oracle fed the same integers: 1e-12 on SSIM, 1e-9 dB on PSNR.  Against the oracle fed the
 reference's float32(k / 255) the allowance is twice that oracle's own distance from the integer-fed one (plus the 1e-12 above),
 computed here.  fp32 path: twice the distance between a float32 and a float64 run of the oracle on the same input, floor 1e-6.
-LPIPS per layer: rel-L2 5e-7, the contract tests/test_gpu_gemm.py holds the split-fp16 product to.  LPIPS end to end:
+LPIPS per layer: rel-L2 5e-7, the contract tests/test_gpu_gemm.py holds the split-fp16 product to, and on the two small images
+the per-element C_CONV eps32 S of tests/test_gpu_imgmetrics_kernels.py (the constant comes from the oracle's emulation).  LPIPS end to end:
 max(4 e32, 1e-6) relative, e32 the error of the oracle's own float32 CPU run against its float64 run (4 = the ratio between the
 split's 22-bit operands and fp32's 24 bits); every figure is printed before it is asserted."""
 import os
@@ -145,20 +146,32 @@ def weights():
 
 @pytest.mark.parametrize("idx", range(7))
 def test_lpips_per_layer(idx):
-    """Each convolution, fed what the device computed before it, against the fp64 oracle on that same input."""
+    """Each convolution, fed what the device computed before it, against the fp64 oracle on that same input.  On the two small
+    images every output element is also held to the per-element contract C_CONV eps32 S of tests/test_gpu_imgmetrics_kernels.py,
+    where a few wrong border outputs cannot hide in the norm; conv1's input there is the device's own fp32 prepare
+    (O.prepare_reference, which test_prepare_bitwise pins bit for bit)."""
     name, pred, _ = lpips_cases()[idx]
     (cw, cb, _), lp = weights()
     taps = [t.cpu().double()[None] for t in lp.features(cu(pred))]
     x = O.lpips_input(f32(pred), torch.float64)   # the device forms float(k) / 255, 2 x - 1 and the scaling layer in fp32
+    per_element = name in ("31x31", "64x48")
+    x_dev = torch.from_numpy(O.prepare_reference(pred)).double().permute(2, 0, 1)[None]
     for l in range(5):
         want = O.conv_relu(x, l, cw, cb)
         assert taps[l].shape == want.shape, (taps[l].shape, want.shape)
         rel = float(torch.linalg.norm(taps[l] - want) / torch.linalg.norm(want))
         print("%s conv%d %s: rel-L2 %.3e" % (name, l + 1, tuple(want.shape[1:]), rel))
         assert rel <= 5e-7, (name, l, rel)
+        if per_element:
+            _, _, k, s, p = O.ALEX_LAYERS[l]
+            ref, S = O.conv_reference(x_dev.permute(0, 2, 3, 1), cw[l].permute(0, 2, 3, 1), cb[l], k, s, p)
+            ratio = O.conv_ratio(taps[l].permute(0, 2, 3, 1), ref, S)
+            print("%s conv%d: worst |got - ref| / (eps32 S) = %.3f (C_CONV %.2f)" % (name, l + 1, ratio, O.C_CONV))
+            assert ratio <= O.C_CONV, (name, l, ratio)
         x = taps[l]
         if O.POOL_AFTER[l]:
             x = torch.nn.functional.max_pool2d(x, 3, 2)
+        x_dev = x
 
 
 @pytest.mark.parametrize("idx", range(7))

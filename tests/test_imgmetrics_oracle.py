@@ -80,6 +80,79 @@ def test_oracle_lpips_symmetric_and_naive_convolution():
         O.lpips_features(a[:30, :30], w[0], w[1])             # 30 x 30: the second pool has nothing to pool
 
 
+# ---- the per-operator references (tests/test_gpu_imgmetrics_kernels.py) ----------------------------------------------------------
+def test_conv_emulation_sets_c_conv():
+    """C_CONV is twice what the numpy model of the kernel's split-fp16 arithmetic leaves against the fp64 reference on CONV_CASES:
+    a constant that went stale (new cases, a changed model) fails here, on the CPU, before any kernel is asked."""
+    worst = 0.0
+    for i, case in enumerate(O.CONV_CASES):
+        x, w, b = O.conv_case(i)
+        want, S = O.conv_reference(x, w, b, *case[5:])
+        got = O.conv_split_emulation(x, w, b, *case[5:])
+        assert got.dtype == np.float32 and got.shape == tuple(want.shape)
+        r = O.conv_ratio(got, want, S)
+        y32 = torch.relu(torch.nn.functional.conv2d(torch.from_numpy(x).permute(0, 3, 1, 2), torch.from_numpy(w).permute(0, 3, 1, 2),
+                                                    torch.from_numpy(b), stride=case[6], padding=case[7])).permute(0, 2, 3, 1)
+        print("%s K %d: emulation %.3f eps S, torch fp32 %.3f eps S, zeros %.2f" % (case, case[3] * case[5] ** 2, r, O.conv_ratio(y32, want, S),
+                                                                               float((want == 0).double().mean())))
+        worst = max(worst, r)
+    print("emulation's worst ratio %.3f, C_CONV %.3f" % (worst, O.C_CONV))
+    assert worst <= O.C_CONV / 2
+    assert worst >= O.C_CONV / 4
+
+
+@pytest.mark.parametrize("idx", [0, len(O.CONV_CASES) - 1])
+def test_conv_reference_against_loops(idx):
+    """conv_reference's layout conventions (NHWC, [Cout, ky, kx, Cin], zero padding, stride) from the definition, by explicit loops
+    with exact sums, on the first three outputs along every axis."""
+    import math
+    B, H, W, Cin, Cout, ks, stride, pad = O.CONV_CASES[idx]
+    x, w, b = O.conv_case(idx)
+    want, S = O.conv_reference(x, w, b, ks, stride, pad)
+    assert tuple(want.shape) == (B, (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1, Cout)
+    xd, wd = x.astype(np.float64), w.astype(np.float64)
+    for oy in range(min(3, want.shape[1])):
+        for ox in range(min(3, want.shape[2])):
+            for o in range(min(3, Cout)):
+                terms, mags = [float(b[o])], [abs(float(b[o]))]
+                for ky in range(ks):
+                    for kx in range(ks):
+                        iy, ix = oy * stride - pad + ky, ox * stride - pad + kx
+                        if 0 <= iy < H and 0 <= ix < W:
+                            for c in range(Cin):
+                                terms.append(xd[0, iy, ix, c] * wd[o, ky, kx, c])   # exact: two fp32 factors
+                                mags.append(abs(terms[-1]))
+                assert abs(float(want[0, oy, ox, o]) - max(math.fsum(terms), 0.0)) <= 1e-13, (oy, ox, o)
+                assert abs(float(S[0, oy, ox, o]) - math.fsum(mags)) <= 1e-13 * math.fsum(mags), (oy, ox, o)
+
+
+def test_ssim_map_direct_agrees_with_ssim_map():
+    p = photo()[200:248, 100:164].astype(np.float64) / 255.           # 64 wide, 48 high
+    q = O.partners(np.ascontiguousarray(photo()[200:248, 100:164]), seed=4)["noise"].astype(np.float64) / 255.
+    for ch in range(3):
+        a, b = np.ascontiguousarray(p[:, :, ch]), np.ascontiguousarray(q[:, :, ch])
+        direct = O.ssim_map_direct(a, b)
+        assert direct.shape == (38, 54)
+        assert np.abs(direct - O.ssim_map(a, b)).max() <= 1e-12
+
+
+def test_tap_reference_is_the_layer_term():
+    rng = np.random.default_rng(6)
+    for (h, w, c), signed in (((3, 5, 128), False), ((33, 32, 64), False), ((7, 9, 320), True)):
+        feat = np.maximum(rng.standard_normal((2, h * w, c)), 0.0).astype(np.float32)
+        feat[:, 0] = 0.0
+        feat[0, 1] = 0.0
+        lin = (rng.standard_normal(c) if signed else rng.uniform(0.0, 2.0, c)).astype(np.float32)
+        d, partials, Sd = O.tap_reference(feat, lin)
+        assert d.shape == (h * w,) and partials.shape == (1024,) and Sd.shape == (1024,)
+        assert d[0] == 0.0 and np.all(partials[h * w:] == 0.0) and np.all(Sd >= np.abs(partials))
+        maps = [torch.from_numpy(feat[i].astype(np.float64)).reshape(1, h, w, c).permute(0, 3, 1, 2) for i in range(2)]
+        want = float(O.lpips_layer_term(maps[0], maps[1], torch.from_numpy(lin)).item())
+        assert abs(partials.sum() / (h * w) - want) <= 1e-13, (h, w, c)
+        if h * w > 1024:   # wave 5 takes pixels 5 and 1029, in that order
+            assert partials[5] == d[5] + d[1029] and partials[32] == d[32]
+
+
 # ---- host side of the modules -----------------------------------------------------------------------------------------------------
 def test_format_metrics_is_the_references_text():
     from iron_amd.eval_image_folder import format_metrics
